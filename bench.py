@@ -20,7 +20,15 @@ contiguously over the ranks (disn_amd/parallel.py: no data-path collective), ONE
 slices (RCCL over xGMI), marching cubes of image b on rank b % N.  N = 1: one image (config 3);
 N > 1: eight images (config 4).  value = grid points evaluated per second, whole job.
 
-Besides the contract line's fields the JSON carries
+A plain run does only what the headline figure needs: set-up, warm-up, the K timed steps, --dump-outputs if given,
+the JSON line.  --dump-outputs DIR writes what the timed path returned in its last step as DIR/<name>.npy (float32 /
+float64, 64 MB at most: a fixed, seeded sample of anything larger); the inputs depend on the arguments only, so two
+builds run with the same arguments can be compared output for output.
+
+With --full (off by default) the run also checks and measures what follows; the JSON then carries, besides the
+contract line's fields,
+  max_abs_diff_of_a_repeated_job (config) -- jobs submitted again after the timed region agree with their first run;
+  phases_rank0 / roofline / all_gather (--workload grid) -- one extra instrumented step, phase by phase;
   roofline      -- the dominant kernel family (the 13 convolutions of one submitted call: conv_h2w.hip / conv_h2.hip,
                    two-term f16 split on the f16 MFMA pipes), duration of the launch chain measured with events on the
                    launch stream.  ONE convention for every MFMA roofline of the line: `achieved` / `frac` = EXECUTED
@@ -43,6 +51,7 @@ import argparse
 import json
 import os
 import sys
+import tempfile
 import time
 
 import numpy as np
@@ -74,6 +83,26 @@ def ev_time_ms(fn, reps, torch):
     return s.elapsed_time(e) / reps
 
 
+DUMP_CAP_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: arrays (name -> host array) as path/<name>.npy; float64 stays float64, everything else becomes
+    float32 (integers float64: exact).  Each array gets an equal share of DUMP_CAP_BYTES; a larger one is cut to a fixed,
+    seeded sample along its longest axis (the same indices from run to run for the same shape)."""
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_CAP_BYTES // max(1, len(arrays)) - 1024          # (room for the .npy header)
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        a = a.astype(np.float64 if a.dtype == np.float64 or a.dtype.kind in "iub" else np.float32)
+        if a.nbytes > share:
+            ax = int(np.argmax(a.shape))
+            keep = max(1, share // (a.nbytes // a.shape[ax]))
+            idx = np.sort(np.random.default_rng(0).choice(a.shape[ax], size=keep, replace=False))
+            a = np.take(a, idx, axis=ax)
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
+
+
 def train_feed(torch, dev, B, seed):
     g = torch.Generator(device=dev).manual_seed(seed)
     feed = {"imgs": torch.rand((B, 137, 137, 3), device=dev, generator=g),
@@ -103,7 +132,7 @@ def train_bench(args, torch, dist, dev, world, rank, launched):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        _, losses, _ = tr.step(feed)
+        pred, losses, _ = tr.step(feed)
     torch.cuda.synchronize()
     if launched:
         dist.barrier()
@@ -113,6 +142,9 @@ def train_bench(args, torch, dist, dev, world, rank, launched):
         t = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"pred_sdf": pred.float().cpu().numpy(),
+                                         **{"loss_" + k: np.float64(float(v)) for k, v in losses.items()}})
     loss = float(losses["overall_loss"])
     assert np.isfinite(loss)
     tr.close()
@@ -198,7 +230,49 @@ def grid_bench(args, torch, dist, dev, world, rank, launched, shared_gpu, backen
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     assert bool(torch.isfinite(full).all())
-    # ---- one instrumented step: where the time goes (synchronised phases; not part of the timed region) ----
+    if args.dump_outputs and rank == 0:
+        # this rank's grids (all_to_all: the images it meshes) and the first mesh it made
+        out = {"sdf": full.cpu().numpy()}
+        if meshes:
+            out.update({"mesh_vertices": meshes[0][0].cpu().numpy(), "mesh_faces": meshes[0][1].cpu().numpy()})
+        dump_outputs(args.dump_outputs, out)
+    line = {
+        "metric": "dense-grid SDF points/sec, end to end (encode + %d^3 grid + RCCL gather + marching cubes)" % (R + 1),
+        "value": B * total * args.steps / dt, "unit": "points/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": 1000.0 * dt / args.steps, "higher_is_better": True,
+        "scaling": "strong" if args.grid_images else ("weak" if world == 1 else "strong"),
+        "vs_baseline": None,
+        "dtype": "f32 results (products: two-term f16 split on v_mfma_f32_32x32x16_f16, ~22-bit operands, fp32 accumulate; "
+                 "gather / projection / grid points / marching cubes: fp32 / fp64 as the reference)",
+        "data": "synthetic",
+        "config": {"workload": "BASELINE config %s: %d image(s) x %d^3 dense grid, query chunks sharded over %d "
+                               "rank(s), one %s, marching cubes; img_feat_twostream, fp32, random-init "
+                               "(xavier) weights, nothing cached between steps" % (
+                                   "3" if world == 1 else "4", B, R + 1, world, args.exchange),
+                   "images": B, "grid_points_per_image": total, "seconds_per_step": dt / args.steps,
+                   "seconds_per_image": dt / args.steps / B,
+                   "point_mlp": "layer-by-layer GEMMs (three-term bf16)" if args.unfused else
+                                "fused kernels (two-term fp16, activations in registers)",
+                   "parallelism": "contiguous flat-index slices x%d, redundant encode, one %s (%s)%s" % (
+                       world, args.exchange, backend if launched else "none: single process",
+                       "; ranks SHARE GPUs (plumbing run, not a scaling measurement)" if shared_gpu else "")},
+        "mesh": {"vertices": int(sum(m[0].shape[0] for m in meshes)), "triangles": int(sum(m[1].shape[0] for m in meshes)),
+                 "images_meshed_on_rank0": len(mine)},
+    }
+    if args.full:
+        line.update(grid_phases(args, torch, dist, dev, world, rank, launched, backend, eng, imgs, tms, params, mine, full))
+    return line
+
+
+def grid_phases(args, torch, dist, dev, world, rank, launched, backend, eng, imgs, tms, params, mine, full):
+    """--full: one instrumented step of the grid workload, where the time goes (synchronised phases; not part of the
+    timed region)"""
+    from disn_amd import isosurface as iso
+    from disn_amd import parallel
+    B, R = imgs.shape[0], args.grid_res
+    total = (R + 1) ** 3
+    a2a = args.exchange == "all_to_all"
+
     def timed(fn):
         torch.cuda.synchronize()
         a = time.perf_counter()
@@ -237,29 +311,7 @@ def grid_bench(args, torch, dist, dev, world, rank, launched, shared_gpu, backen
     flop_pt = MLP_FLOP_PER_PT - 2 * 1472 * 512           # executed: local fold2/conv1 folded into the map
     peak = PEAK_FP32_MFMA_TFLOPS if args.unfused else PEAK_F16X2_TFLOPS
     mlp_tf = pts_rank * flop_pt / t_grid / 1e12
-    value = B * total * args.steps / dt
-    nv = int(sum(m[0].shape[0] for m in meshes))
-    nf = int(sum(m[1].shape[0] for m in meshes))
     return {
-        "metric": "dense-grid SDF points/sec, end to end (encode + %d^3 grid + RCCL gather + marching cubes)" % (R + 1),
-        "value": value, "unit": "points/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": 1000.0 * dt / args.steps, "higher_is_better": True,
-        "scaling": "strong" if args.grid_images else ("weak" if world == 1 else "strong"),
-        "vs_baseline": None,
-        "dtype": "f32 results (products: two-term f16 split on v_mfma_f32_32x32x16_f16, ~22-bit operands, fp32 accumulate; "
-                 "gather / projection / grid points / marching cubes: fp32 / fp64 as the reference)",
-        "data": "synthetic",
-        "config": {"workload": "BASELINE config %s: %d image(s) x %d^3 dense grid, query chunks sharded over %d "
-                               "rank(s), one %s, marching cubes; img_feat_twostream, fp32, random-init "
-                               "(xavier) weights, nothing cached between steps" % (
-                                   "3" if world == 1 else "4", B, R + 1, world, args.exchange),
-                   "images": B, "grid_points_per_image": total, "seconds_per_step": dt / args.steps,
-                   "seconds_per_image": dt / args.steps / B,
-                   "point_mlp": "layer-by-layer GEMMs (three-term bf16)" if args.unfused else
-                                "fused kernels (two-term fp16, activations in registers)",
-                   "parallelism": "contiguous flat-index slices x%d, redundant encode, one %s (%s)%s" % (
-                       world, args.exchange, backend if launched else "none: single process",
-                       "; ranks SHARE GPUs (plumbing run, not a scaling measurement)" if shared_gpu else "")},
         "phases_rank0": {"encode_s": t_enc, "fold_local_s": t_fold, "grid_slice_s": t_grid,
                          "all_gather_s": t_gather, "marching_cubes_s": t_mc,
                          "note": "one extra step with a host sync between phases (their sum exceeds the "
@@ -275,7 +327,6 @@ def grid_bench(args, torch, dist, dev, world, rank, launched, shared_gpu, backen
             "exchange": args.exchange,
             "bytes_received_per_rank": int(world * (len(mine) if a2a else B) * pad * 4), "seconds": t_gather,
             "GB_per_s": world * (len(mine) if a2a else B) * pad * 4 / t_gather / 1e9, "backend": backend},
-        "mesh": {"vertices": nv, "triangles": nf, "images_meshed_on_rank0": len(mine)},
     }
 
 
@@ -353,7 +404,12 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=None, help="timed steps (default: 300 query, 5 grid, 50 train)")
     ap.add_argument("--warmup", type=int, default=None, help="untimed warm-up steps (default: 20 query, 1 grid, 5 train)")
-    ap.add_argument("--no-extras", action="store_true", help="skip roofline / grid / cpu legs")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline figure: the repeated-job check, the roofline / grid / train / cpu legs "
+                         "(--workload query) and the instrumented phase step (--workload grid)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip roofline / grid / cpu legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned in its last step as DIR/<name>.npy")
     ap.add_argument("--in-flight", type=int, default=2,
                     help="--workload query: independent submissions in flight on this GPU (disn_amd.engine.StepPipeline: "
                          "one HIP stream + host thread per context); 1 = one at a time")
@@ -537,17 +593,19 @@ def main():
               " ".join("%d[%s]:%.2f" % (i, g, (t - t0) * 1e3) for i, g, t in sorted(pipe.trace, key=lambda x: x[2])) +
               " | done %.2f" % (dt * 1e3), file=sys.stderr)
     out = outs[0]
-    # Repeated-job check (with --steps <= the pool size no job repeats INSIDE the timed region): after the
-    # timed region the first jobs are submitted again, untimed, shifted by one position -- another slot of another
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"pred_sdf": outs[-1].cpu().numpy()})      # [1, 2048]: the last timed step
+    # Repeated-job check (--full; ADVICE r3: with --steps <= the pool size no job repeats INSIDE the timed region): after
+    # the timed region the first jobs are submitted again, untimed, shifted by one position -- another slot of another
     # call, possibly the other form of the convolutions when the call is shorter than four images -- and must give the
-    # same prediction up to fp32 summation order.  null = nothing was repeated.
-    n_rep = min(len(outs) - 1, POOL - 1, 2 * SB)
+    # same prediction up to fp32 summation order.  null = nothing was repeated (or no --full).
+    n_rep = min(len(outs) - 1, POOL - 1, 2 * SB) if args.full else 0
     rep_diff = None
     if n_rep >= 1:
         again = pipe.run([pool[i + 1] for i in range(n_rep)])
         torch.cuda.synchronize()
         rep_diff = max(float((again[i] - outs[i + 1]).abs().max()) for i in range(n_rep))
-    in_region = [float((outs[k] - outs[k - POOL]).abs().max()) for k in range(POOL, len(outs))]
+    in_region = [float((outs[k] - outs[k - POOL]).abs().max()) for k in range(POOL, len(outs))] if args.full else []
     if in_region:
         rep_diff = max([rep_diff or 0.0] + in_region)
     assert rep_diff is None or rep_diff <= 1e-5, "a repeated step disagrees with its first run: %g" % rep_diff
@@ -573,7 +631,7 @@ def main():
                    "images_per_step_per_gpu": 1, "points_per_step_per_gpu": N_POINTS,
                    "steps_per_call": SB, "calls_in_flight": S, "spinup_s": args.spinup_s,
                    "distinct_jobs": POOL, "max_abs_diff_of_a_repeated_job": rep_diff,
-                   "repeated_jobs_checked": max(0, n_rep) + max(0, len(outs) - POOL),
+                   "repeated_jobs_checked": max(0, n_rep) + len(in_region),
                    "untimed_warmup_note": "before the timed region: %.2f s of rehearsal steps (clock ramp, allocator pools; "
                                           "--spinup-s), the garbage collector parked, %.2f s of rehearsal steps again (the "
                                           "collection idles the GPU and its clocks drop; --reramp-s), then max(--warmup, %d) "
@@ -594,7 +652,7 @@ def main():
 
     if rank == 0:
         print("[bench] main line: %.4g points/s, %.4f ms/step" % (value, line["ms_per_step"]), file=sys.stderr)
-    if rank == 0 and world == 1 and not args.no_extras:   # roofline / cpu legs: N=1 only (bench contract)
+    if rank == 0 and world == 1 and args.full and not args.no_extras:   # roofline / cpu legs: N=1 only (bench contract)
         pmc = {}   # profiles/pmc_traffic.json (read in the roofline leg; the gather legs quote it too)
         # ---- one step at a time (the latency of a step; the main line overlaps S independent steps) ----------
         try:
@@ -877,9 +935,10 @@ def main():
             verts, faces = iso.marching_cubes(full, [-1, -1, -1, 1, 1, 1], 256, 0.0)
             torch.cuda.synchronize()
             t2 = time.perf_counter() - t0
-            t0 = time.perf_counter()
-            iso.write_obj("/tmp/disn_bench_mesh.obj", verts, faces)
-            t3 = time.perf_counter() - t0
+            with tempfile.TemporaryDirectory() as td_:
+                t0 = time.perf_counter()
+                iso.write_obj(os.path.join(td_, "mesh.obj"), verts, faces)
+                t3 = time.perf_counter() - t0
             line["grid256_mesh"] = {"seconds": t2, "vertices": int(verts.shape[0]), "triangles": int(faces.shape[0]),
                                     "obj_write_seconds": t3,
                                     "includes": "encode + 257^3 SDF + marching cubes on one GPU (random-init weights: "

@@ -205,6 +205,27 @@ def test_bench_and_entry_contract_static():
     assert "def build(" in ent and "def smoke(" in ent
 
 
+def test_bench_dump_outputs_types_cap_and_fixed_sample(tmp_path):
+    """bench.py --dump-outputs: float32 / float64 files only, 64 MB at most in all, a larger output cut to the same
+    seeded sample every time"""
+    import bench
+    big = (np.arange(1, 4, dtype=np.float32)[:, None] * (np.arange(257 ** 3) % 4099).astype(np.float32))   # 204 MB
+    arrays = {"sdf": big, "faces": np.arange(30, dtype=np.int32).reshape(10, 3), "loss": np.float64(0.25),
+              "small": np.ones((1, 2048), np.float16)}
+    for k in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / k), arrays)
+    got = {f[:-4]: np.load(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")}
+    assert sorted(got) == sorted(arrays)
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= bench.DUMP_CAP_BYTES
+    assert all(v.dtype in (np.float32, np.float64) for v in got.values())
+    assert got["faces"].dtype == np.float64 and np.array_equal(got["faces"], arrays["faces"])
+    assert got["loss"] == 0.25 and got["small"].shape == (1, 2048)
+    s = got["sdf"]
+    assert s.shape[0] == 3 and 0 < s.shape[1] < big.shape[1]
+    assert np.array_equal(s[2], 3 * s[0]) and len(np.unique(s[0])) > 4000     # the same columns of every row
+    assert np.array_equal(s, np.load(tmp_path / "b" / "sdf.npy"))
+
+
 def test_product_library_has_no_tuning_knobs():
     """no environment variable is read and no knob is exported by the product library:
     the knobs of csrc/tuning.hpp exist only in `build.py --tuning` builds"""

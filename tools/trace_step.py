@@ -1,7 +1,7 @@
 """Print the launch sequence of the LAST step out of a rocprofv3 kernel trace csv.
 usage: python tools/trace_step.py <kernel_trace.csv> <first-kernel-substring> [out.txt|-] [nth-from-end]
 The step is taken to start at the last launch whose name contains the substring (nth-from-end = 2: the step before the
-last one, printed up to the start of the last -- bench.py's final call is the 15-image repeated-job check)."""
+last one, printed up to the start of the last -- the final call of bench.py --full is the 15-image repeated-job check)."""
 import csv
 import re
 import sys
