@@ -170,6 +170,12 @@ SIGNATURES = {
     "disn_mc_count": (I, [P, I, F, P, P, Z, P]),
     "disn_mc_emit": (I, [P, C.POINTER(C.c_double * 6), I, F, P, P, P, Z, P]),
     "disn_write_obj": (I, [C.c_char_p, P, L, P, L]),
+    "disn_read_obj_verts": (L, [C.c_char_p, P, L]),
+    "disn_metrics_workspace_bytes": (Z, [I, I, I]),
+    "disn_nn_distance": (I, [P, P, I, I, I, P, P, P, P, P, Z, P]),
+    "disn_approx_match": (I, [P, P, I, I, I, P, P, Z, P]),
+    "disn_match_cost": (I, [P, P, P, I, I, I, P, P, Z, P]),
+    "disn_emd": (I, [P, P, I, I, I, P, P, Z, P]),
     "disn_grid_points": (I, [C.POINTER(C.c_double * 6), I, L, L, P, P]),
     "disn_query_grid_workspace_bytes": (Z, [L]),
     "disn_query_grid": (I, [C.POINTER(MlpWeights), P, P, P, C.POINTER(C.c_double * 6), I, L, L, F, P,

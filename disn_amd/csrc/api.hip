@@ -1496,6 +1496,53 @@ int disn_mc_emit(const float* sdf, const double* sdf_params_host, int R, float i
   return 0;
 }
 
+// ---- evaluation metrics (metrics.hip) ----
+size_t disn_metrics_workspace_bytes(int b, int n, int m) {
+  return (b < 1 || n < 1 || m < 1) ? 0 : metrics_ws_bytes(b, n, m);
+}
+
+static int metrics_shape(int b, int n, int m) {
+  if (b < 1 || n < 1 || m < 1) return DISN_E_ARG;
+  if (b > 65535) return DISN_E_SHAPE;  // one grid row per pair
+  return 0;
+}
+
+int disn_nn_distance(const float* xyz1, const float* xyz2, int b, int n, int m, float* dist1, int32_t* idx1,
+                     float* dist2, int32_t* idx2, void* ws, size_t ws_bytes, void* stream) {
+  if (!xyz1 || !xyz2 || !dist1 || !idx1 || !dist2 || !idx2 || !ws) return DISN_E_ARG;
+  if (int rc = metrics_shape(b, n, m)) return rc;
+  if (ws_bytes < metrics_ws_bytes(b, n, m)) return DISN_E_WS;
+  DISN_TRY(nn_distance_launch(xyz1, xyz2, b, n, m, dist1, idx1, dist2, idx2, ws, (hipStream_t)stream));
+  return 0;
+}
+
+int disn_approx_match(const float* xyz1, const float* xyz2, int b, int n, int m, float* match, void* ws,
+                      size_t ws_bytes, void* stream) {
+  if (!xyz1 || !xyz2 || !match || !ws) return DISN_E_ARG;
+  if (int rc = metrics_shape(b, n, m)) return rc;
+  if (ws_bytes < metrics_ws_bytes(b, n, m)) return DISN_E_WS;
+  DISN_TRY(approx_match_launch(xyz1, xyz2, b, n, m, match, ws, (hipStream_t)stream));
+  return 0;
+}
+
+int disn_match_cost(const float* xyz1, const float* xyz2, const float* match, int b, int n, int m, float* cost,
+                    void* ws, size_t ws_bytes, void* stream) {
+  if (!xyz1 || !xyz2 || !match || !cost || !ws) return DISN_E_ARG;
+  if (int rc = metrics_shape(b, n, m)) return rc;
+  if (ws_bytes < metrics_ws_bytes(b, n, m)) return DISN_E_WS;
+  DISN_TRY(match_cost_launch(xyz1, xyz2, match, b, n, m, cost, ws, (hipStream_t)stream));
+  return 0;
+}
+
+int disn_emd(const float* xyz1, const float* xyz2, int b, int n, int m, float* cost, void* ws, size_t ws_bytes,
+             void* stream) {
+  if (!xyz1 || !xyz2 || !cost || !ws) return DISN_E_ARG;
+  if (int rc = metrics_shape(b, n, m)) return rc;
+  if (ws_bytes < metrics_ws_bytes(b, n, m)) return DISN_E_WS;
+  DISN_TRY(emd_launch(xyz1, xyz2, b, n, m, cost, ws, (hipStream_t)stream));
+  return 0;
+}
+
 }  // extern "C"
 
 #ifdef DISN_TUNING

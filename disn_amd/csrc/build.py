@@ -38,6 +38,7 @@ SOURCES = {
     "dense_h2w.hip": [],
     "elementwise.hip": ["-ffp-contract=off"],
     "marching_cubes.hip": ["-ffp-contract=off"],
+    "metrics.hip": ["-ffp-contract=off"],       # nn_distance bit-identical to a float32 restatement
     "api.hip": [],
     "host_util.cpp": ["-msse4.2"],
 }

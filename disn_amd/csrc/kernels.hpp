@@ -254,6 +254,17 @@ hipError_t mc_count_launch(const float* vol, int R, float iso, unsigned long lon
 hipError_t mc_emit_launch(const float* vol, const GridSpec& g, float iso, float* verts, int* faces,
                           void* ws, hipStream_t st);
 
+// ---- metrics.hip (compiled with -ffp-contract=off): evaluation metrics, one workspace for every entry ----
+size_t metrics_ws_bytes(int b, int n, int m);
+hipError_t nn_distance_launch(const float* xyz1, const float* xyz2, int b, int n, int m, float* dist1, int* idx1,
+                              float* dist2, int* idx2, void* ws, hipStream_t st);
+hipError_t approx_match_launch(const float* xyz1, const float* xyz2, int b, int n, int m, float* match, void* ws,
+                               hipStream_t st);
+hipError_t emd_launch(const float* xyz1, const float* xyz2, int b, int n, int m, float* cost, void* ws,
+                      hipStream_t st);
+hipError_t match_cost_launch(const float* xyz1, const float* xyz2, const float* match, int b, int n, int m,
+                             float* cost, void* ws, hipStream_t st);
+
 // ---- mlp_fused.hip: both point MLPs as one persistent kernel per stream, activations in registers ----
 size_t mlp_fused_image_bytes();
 size_t mlp_fused_feat_image_bytes();

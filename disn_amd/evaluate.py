@@ -1,0 +1,229 @@
+"""Scoring of reconstructed meshes: the reference's ``test/test_cd_emd.py`` (Chamfer distance and approximate
+EMD, ``cd_emd_all`` / ``cd_emd_cat``) and ``test/test_f_score.py`` (``cal_f_score_all_cat`` / ``f_score_cat``),
+on ``disn_amd.metrics`` instead of the TF1 + CUDA custom ops.
+
+    python -m disn_amd.evaluate cd_emd  --cal_dir OBJS --gt_dir GT --test_lst_dir LSTS [--category all]
+    python -m disn_amd.evaluate f_score --cal_dir OBJS --gt_dir GT --test_lst_dir LSTS [--truethreshold 2.5]
+
+Layout, as the reference reads it:
+  predictions  <cal_dir>/<cat_id>/<cat_id>_<obj_id>_<view>.obj    (what ``isosurface.create_obj`` writes)
+  ground truth <gt_dir>/<cat_id>/<obj_id>/isosurf.obj
+  object lists <test_lst_dir>/<cat_id>_test.lst
+  F-score point files (optional; sample_save_*_pnt of test_cd_emd.py):
+               <gt_dir>/<cat_id>/<obj_id>/pnt_<N>.txt and <cal_dir>/pnt_<N>_<cat_id>/pnt_<obj_id>_<view>.txt
+Only the reference's ``batch_size == view_num`` path is mirrored: its other branch (test_cd_emd.py:259-280)
+stacks the ground truth with ``verts_batch[b]`` for b = 0, i.e. compares the ground truth with itself.
+Point sampling draws from ``numpy.random.Generator(seed)``, the view choice from ``random.Random(seed)``.
+"""
+from __future__ import annotations
+
+import argparse
+import os
+import random
+import sys
+from typing import Dict, List, Optional
+
+import numpy as np
+
+CATS_ALL = {
+    "watercraft": "04530566", "rifle": "04090263", "display": "03211117", "lamp": "03636649",
+    "speaker": "03691459", "chair": "03001627", "bench": "02828884", "cabinet": "02933112",
+    "car": "02958343", "airplane": "02691156", "sofa": "04256520", "table": "04379243", "phone": "04401088",
+}
+CATS_CLEAN = {"cabinet": "02933112", "display": "03211117", "speaker": "03691459", "rifle": "04090263",
+              "watercraft": "04530566"}
+
+
+def categories(category: str) -> Dict[str, str]:
+    """--category: "all", "clean" or one category name (test_cd_emd.py / test_f_score.py __main__)"""
+    if category == "all":
+        return dict(CATS_ALL)
+    if category == "clean":
+        return dict(CATS_CLEAN)
+    if category not in CATS_ALL:
+        raise ValueError("unknown category %r (all, clean or one of %s)" % (category, ", ".join(sorted(CATS_ALL))))
+    return {category: CATS_ALL[category]}
+
+
+def build_file_dict(dir: str) -> Dict[str, List[str]]:
+    """object id -> prediction files of a category directory: field 1 of the file name split on '_'
+    (test_cd_emd.py:126-136); lists sorted, so that a seed picks the same views on any file system"""
+    d: Dict[str, List[str]] = {}
+    for fn in sorted(os.listdir(dir)):
+        full = os.path.join(dir, fn)
+        if os.path.isfile(full):
+            d.setdefault(fn.split("_")[1], []).append(full)
+    return d
+
+
+def read_list(test_lst_f: str) -> List[str]:
+    with open(test_lst_f) as f:
+        objs = [l.rstrip("\r\n") for l in f]
+    objs = [o for o in objs if o]
+    if not objs:
+        raise ValueError("%s lists no object" % test_lst_f)
+    return objs
+
+
+def _predictions(pred_dict, obj_id: str, cat_id: str, pred_dir: str) -> List[str]:
+    if obj_id not in pred_dict:
+        raise FileNotFoundError("no prediction for object %s of category %s in %s" % (obj_id, cat_id, pred_dir))
+    return pred_dict[obj_id]
+
+
+def _mesh_points(path: str, n: int, rng: np.random.Generator):
+    from . import isosurface, metrics
+    return metrics.sample_vertices(isosurface.read_obj_verts(path), n, rng)
+
+
+def cd_emd_cat(cat_id: str, cat_nm: str, pred_dir: str, gt_dir: str, test_lst_f: str, view_num: int = 24,
+               num_sample_points: int = 2048, rng: Optional[np.random.Generator] = None,
+               pyrng: Optional[random.Random] = None, out=None) -> dict:
+    """Chamfer (x1000) and EMD (x0.01) of every listed object over ``view_num`` sampled views
+    (test_cd_emd.py:220-282) -> {"objects": {obj_id: {...}}, "avg_cf", "avg_emd"}"""
+    import torch
+
+    from . import metrics
+    rng = rng if rng is not None else np.random.default_rng(0)
+    pyrng = pyrng if pyrng is not None else random.Random(0)
+    out = out or sys.stdout
+    pred_dict = build_file_dict(pred_dir)
+    objs = read_list(test_lst_f)
+    for obj_id in objs:
+        _predictions(pred_dict, obj_id, cat_id, pred_dir)
+    res: Dict[str, dict] = {}
+    sum_cf = sum_em = 0.0
+    for count, obj_id in enumerate(objs, 1):
+        src_path = os.path.join(gt_dir, obj_id, "isosurf.obj")
+        preds = _predictions(pred_dict, obj_id, cat_id, pred_dir)
+        if len(preds) < view_num:
+            raise ValueError("object %s of category %s has %d predictions, --view_num is %d"
+                             % (obj_id, cat_id, len(preds), view_num))
+        gt = _mesh_points(src_path, num_sample_points, rng)
+        views = pyrng.sample(preds, view_num)
+        pred = torch.stack([_mesh_points(p, num_sample_points, rng) for p in views])
+        cf = metrics.chamfer_views(pred, gt)
+        em = metrics.emd_views(pred, gt)
+        avg_cf, min_cf, arg_cf = metrics.view_stats(cf)
+        avg_em, min_em, arg_em = metrics.view_stats(em)
+        sum_cf += avg_cf
+        sum_em += avg_em
+        res[obj_id] = {"avg_cf": avg_cf, "min_cf": min_cf, "arg_cf": arg_cf, "avg_emd": avg_em,
+                       "min_emd": min_em, "arg_emd": arg_em, "views": views,
+                       "cf_views": cf.cpu().numpy(), "emd_views": em.cpu().numpy()}
+        print("%d  %s avg cf:%s, min_cf:%s, arg_cf view:%d, avg emd:%s, min_emd:%s, arg_em view:%d"
+              % (count, src_path, avg_cf, min_cf, arg_cf, avg_em, min_em, arg_em), file=out)
+    summary = {"cat_nm": cat_nm, "cat_id": cat_id, "objects": res, "avg_cf": sum_cf / len(objs),
+               "avg_emd": sum_em / len(objs)}
+    print("cat_nm:%s, cat_id:%s, avg_cf:%s, avg_emd:%s" % (cat_nm, cat_id, summary["avg_cf"], summary["avg_emd"]),
+          file=out)
+    return summary
+
+
+def cd_emd_all(cats: Dict[str, str], pred_dir: str, gt_dir: str, test_lst_dir: str, seed: int = 0,
+               out=None, **kw) -> Dict[str, dict]:
+    out = out or sys.stdout
+    rng, pyrng = np.random.default_rng(seed), random.Random(seed)
+    res = {}
+    for cat_nm, cat_id in cats.items():
+        res[cat_id] = cd_emd_cat(cat_id, cat_nm, os.path.join(pred_dir, cat_id), os.path.join(gt_dir, cat_id),
+                                 os.path.join(test_lst_dir, cat_id + "_test.lst"), rng=rng, pyrng=pyrng, out=out,
+                                 **kw)
+    print("done!", file=out)
+    return res
+
+
+def f_score_cat(cat_id: str, cat_nm: str, pred_dir: str, gt_dir: str, test_lst_f: str, thresholds,
+                num_sample_points: int = 2048, rng: Optional[np.random.Generator] = None, out=None) -> dict:
+    """precision / recall of every listed object, pooled over all its predicted views (test_f_score.py:183-243)
+    -> {"objects": {obj_id: {"precision", "recall", "points"}}, "precision", "recall", "count"}.  The reference's
+    point files are scored when all of an object's exist; otherwise its points are sampled from the meshes."""
+    import torch
+
+    from . import metrics
+    rng = rng if rng is not None else np.random.default_rng(0)
+    out = out or sys.stdout
+    pred_dict = build_file_dict(pred_dir)
+    objs = read_list(test_lst_f)
+    for obj_id in objs:
+        _predictions(pred_dict, obj_id, cat_id, pred_dir)
+    pnt_dir = os.path.join(os.path.dirname(pred_dir), "pnt_%d_%s" % (num_sample_points, cat_id))
+    res: Dict[str, dict] = {}
+    pre_sum = rec_sum = 0.0
+    for obj_id in objs:
+        preds = _predictions(pred_dict, obj_id, cat_id, pred_dir)
+        gt_pnt = os.path.join(gt_dir, obj_id, "pnt_%d.txt" % num_sample_points)
+        pred_pnts = [os.path.join(pnt_dir, "pnt_%s_%s.txt" % (obj_id, p[-6:-4])) for p in preds]
+        if os.path.exists(gt_pnt) and all(os.path.exists(p) for p in pred_pnts):
+            source = "files"
+            gt = metrics.load_points(gt_pnt)
+            pred = torch.stack([metrics.load_points(p) for p in pred_pnts])
+        else:
+            source = "meshes"
+            gt = _mesh_points(os.path.join(gt_dir, obj_id, "isosurf.obj"), num_sample_points, rng)
+            pred = torch.stack([_mesh_points(p, num_sample_points, rng) for p in preds])
+        pre, rec = metrics.precision_recall(pred, gt, thresholds)
+        pre_sum = pre_sum + pre
+        rec_sum = rec_sum + rec
+        res[obj_id] = {"precision": pre, "recall": rec, "points": source}
+        print("cat_id %s, obj_id %s: precision %s, recall %s" % (cat_id, obj_id, pre, rec), file=out)
+    summary = {"cat_nm": cat_nm, "cat_id": cat_id, "objects": res, "precision": pre_sum / len(objs),
+               "recall": rec_sum / len(objs), "count": len(objs)}
+    print("%s, %s, precision_avg %s, recal_avg%s, count %d"
+          % (cat_nm, cat_id, summary["precision"], summary["recall"], len(objs)), file=out)
+    return summary
+
+
+def cal_f_score_all_cat(cats: Dict[str, str], pred_dir: str, gt_dir: str, test_lst_dir: str,
+                        truethreshold: float = 2.5, num_sample_points: int = 2048, seed: int = 0,
+                        out=None) -> dict:
+    """category averages weighted by object count, then F = 2PR/(P+R) (test_f_score.py:159-181)"""
+    from . import metrics
+    out = out or sys.stdout
+    thresholds = metrics.f_score_thresholds(truethreshold)
+    rng = np.random.default_rng(seed)
+    per = {}
+    for cat_nm, cat_id in cats.items():
+        per[cat_id] = f_score_cat(cat_id, cat_nm, os.path.join(pred_dir, cat_id), os.path.join(gt_dir, cat_id),
+                                  os.path.join(test_lst_dir, cat_id + "_test.lst"), thresholds,
+                                  num_sample_points=num_sample_points, rng=rng, out=out)
+    print("done!", file=out)
+    counts = [c["count"] for c in per.values()]
+    pre = metrics.weighted_category_average([c["precision"] for c in per.values()], counts)
+    rec = metrics.weighted_category_average([c["recall"] for c in per.values()], counts)
+    f = metrics.f_score(pre, rec)
+    print("pre_w_avg %s, rec_w_avg %s, f_score %s" % (pre, rec, f), file=out)
+    return {"categories": per, "thresholds": thresholds, "precision": pre, "recall": rec, "f_score": f}
+
+
+def parser() -> argparse.ArgumentParser:
+    p = argparse.ArgumentParser(prog="python -m disn_amd.evaluate",
+                                description="Chamfer / EMD / F-score of reconstructed meshes (test_cd_emd.py, "
+                                            "test_f_score.py)")
+    sub = p.add_subparsers(dest="command", required=True)
+    for name, hlp in (("cd_emd", "Chamfer distance and approximate EMD per object and category"),
+                      ("f_score", "precision, recall and F-score at six distance thresholds")):
+        s = sub.add_parser(name, help=hlp)
+        s.add_argument("--cal_dir", required=True, help="directory of the predicted meshes (<cat_id>/*.obj)")
+        s.add_argument("--gt_dir", required=True, help="ground-truth meshes (<cat_id>/<obj_id>/isosurf.obj)")
+        s.add_argument("--test_lst_dir", required=True, help="object lists (<cat_id>_test.lst)")
+        s.add_argument("--category", default="all", help="all, clean or one category name [default: all]")
+        s.add_argument("--view_num", type=int, default=24, help="views per object [default: 24]")
+        s.add_argument("--num_sample_points", type=int, default=2048, help="points per mesh [default: 2048]")
+        s.add_argument("--truethreshold", type=float, default=2.5, help="F-score side length [default: 2.5]")
+        s.add_argument("--seed", type=int, default=0, help="seed of the point and view sampling [default: 0]")
+    return p
+
+
+def main(argv=None) -> dict:
+    a = parser().parse_args(argv)
+    cats = categories(a.category)
+    if a.command == "cd_emd":
+        return cd_emd_all(cats, a.cal_dir, a.gt_dir, a.test_lst_dir, seed=a.seed, view_num=a.view_num,
+                          num_sample_points=a.num_sample_points)
+    return cal_f_score_all_cat(cats, a.cal_dir, a.gt_dir, a.test_lst_dir, truethreshold=a.truethreshold,
+                               num_sample_points=a.num_sample_points, seed=a.seed)
+
+
+if __name__ == "__main__":
+    main()

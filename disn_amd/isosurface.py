@@ -70,6 +70,21 @@ def read_obj(path: str):
     return np.asarray(vs, np.float32).reshape(-1, 3), np.asarray(fs, np.int32).reshape(-1, 3)
 
 
+def read_obj_verts(path: str) -> np.ndarray:
+    """the vertices of a Wavefront .obj as float32 [nv, 3], in file order (native reader, disn_read_obj_verts:
+    what the evaluation driver loads; ``read_obj`` is the full Python reader)"""
+    h = lib()
+    nv = h.disn_read_obj_verts(path.encode(), None, 0)
+    if nv < 0:
+        raise OSError("cannot read vertices of %s" % path)
+    v = np.empty((nv, 3), np.float32)
+    if nv:
+        got = h.disn_read_obj_verts(path.encode(), v.ctypes.data, nv)
+        if got != nv:
+            raise OSError("%s changed while it was read" % path)
+    return v
+
+
 def create_obj(pred_sdf_val, sdf_params, dir, cat_id, obj_nm, view_id, i, res: Optional[int] = None) -> str:
     """test/create_sdf.py:305-317 -- same arguments (``i`` is the iso value), same output path;
     ``pred_sdf_val`` may be a device tensor (preferred) or a numpy array of (res+1)^3 values."""

@@ -559,6 +559,37 @@ int disn_mc_emit(const float* sdf, const double* sdf_params_host, int R, float i
                  int32_t* faces, void* ws, size_t ws_bytes, void* stream);
 
 /* ---------------------------------------------------------------------- *
+ * Evaluation metrics: the two custom ops behind the paper's CD / EMD /     *
+ * F-score tables (models/tf_ops/nn_distance, models/tf_ops/approxmatch;    *
+ * used by test/test_cd_emd.py and test/test_f_score.py).  Point clouds     *
+ * are xyz1 [b,n,3] and xyz2 [b,m,3] float32; b <= 65535 (else DISN_E_SHAPE)*
+ * All five entries share one workspace size,                               *
+ * disn_metrics_workspace_bytes(b, n, m) (0 for a non-positive size).       *
+ *   disn_nn_distance  -> dist1 [b,n] = min_l |xyz2[l] - xyz1[k]|^2 and     *
+ *                        idx1 [b,n] the lowest l attaining it; dist2/idx2  *
+ *                        [b,m] the other direction.  d2 = (dx*dx + dy*dy)  *
+ *                        + dz*dz in fp32, no contraction (bit-exact).      *
+ *   disn_approx_match -> match [b,m,n]: the approximate transport plan     *
+ *                        (GPU schedule of the reference op, 10 levels).    *
+ *                        NOTE: b*m*n floats -- 403 MB at 24 x 2048 x 2048. *
+ *   disn_match_cost   -> cost [b] = sum_{k,l} |xyz2[l] - xyz1[k]| *        *
+ *                        match[l][k] (fixed-order reduction).              *
+ *   disn_emd          -> cost [b] = disn_match_cost(disn_approx_match())   *
+ *                        fused: no match buffer.                           *
+ * A pair's result never depends on b or on its place in the batch, and     *
+ * every entry is deterministic (no float atomics).                         *
+ * ---------------------------------------------------------------------- */
+size_t disn_metrics_workspace_bytes(int b, int n, int m);
+int disn_nn_distance(const float* xyz1, const float* xyz2, int b, int n, int m, float* dist1, int32_t* idx1,
+                     float* dist2, int32_t* idx2, void* ws, size_t ws_bytes, void* stream);
+int disn_approx_match(const float* xyz1, const float* xyz2, int b, int n, int m, float* match, void* ws,
+                      size_t ws_bytes, void* stream);
+int disn_match_cost(const float* xyz1, const float* xyz2, const float* match, int b, int n, int m, float* cost,
+                    void* ws, size_t ws_bytes, void* stream);
+int disn_emd(const float* xyz1, const float* xyz2, int b, int n, int m, float* cost, void* ws, size_t ws_bytes,
+             void* stream);
+
+/* ---------------------------------------------------------------------- *
  * Training step (BASELINE config 5): what ONE                *
  * sess.run([train_op, losses...]) of train/train_sdf.py:371-387 executes.  *
  * Every variable of the graph (train/train_sdf.py:266-268 minimises over   *
@@ -735,6 +766,11 @@ int disn_scale_channels(const float* in, int64_t rows, int C, const float* scale
  * reference's output artefact (test/create_sdf.py:311).  Returns 0, or DISN_E_ARG on I/O error. */
 int disn_write_obj(const char* path, const float* verts_host, int64_t nv, const int32_t* faces_host,
                    int64_t nf);
+
+/* Host utility: the vertices ("v x y z" lines) of a Wavefront .obj, in file order, into verts_host [cap,3]
+ * (NULL / cap 0: count only).  Returns the number of vertices in the file (only the first cap are written),
+ * or DISN_E_ARG on an I/O or parse error.  Faces and every other line are skipped. */
+int64_t disn_read_obj_verts(const char* path, float* verts_host, int64_t cap);
 
 /* Host utility (no device work): CRC-32C of a HOST buffer, continuing from `crc` (0 to start);
  * the checksum of TensorFlow's table blocks and tensor-bundle entries, used by the
