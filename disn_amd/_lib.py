@@ -25,7 +25,8 @@ class DisnLibraryError(RuntimeError):
 
 class DisnError(RuntimeError):
     def __init__(self, fn: str, status: int):
-        kind = {-1: "invalid argument", -2: "unsupported shape", -3: "workspace too small"}.get(
+        kind = {-1: "invalid argument", -2: "unsupported shape", -3: "workspace too small",
+                -4: "did not converge"}.get(
             status, "hipError_t %d" % status if status > 0 else "error")
         super().__init__("%s failed: %s (status %d)" % (fn, kind, status))
         self.status = status
@@ -171,6 +172,13 @@ SIGNATURES = {
     "disn_mc_emit": (I, [P, C.POINTER(C.c_double * 6), I, F, P, P, P, Z, P]),
     "disn_write_obj": (I, [C.c_char_p, P, L, P, L]),
     "disn_read_obj_verts": (L, [C.c_char_p, P, L]),
+    "disn_read_obj_mesh": (I, [C.c_char_p, P, L, P, L, P]),
+    "disn_mesh_bvh_bytes": (Z, [L]),
+    "disn_mesh_bvh_build": (I, [P, L, P, L, P, Z]),
+    "disn_mesh_udf_points": (I, [P, L, P, L, I, P, P]),
+    "disn_mesh_udf_grid": (I, [P, L, P, P, P, I, I, I, I, P, P]),
+    "disn_mesh_sign_workspace_bytes": (Z, [I, I, I]),
+    "disn_mesh_sign": (I, [P, L, P, P, P, I, I, I, P, F, I, F, P, P, P, Z, P]),
     "disn_metrics_workspace_bytes": (Z, [I, I, I]),
     "disn_nn_distance": (I, [P, P, I, I, I, P, P, P, P, P, Z, P]),
     "disn_approx_match": (I, [P, P, I, I, I, P, P, Z, P]),

@@ -3,6 +3,7 @@
 #include "../../include/disn_amd.h"
 
 #include "kernels.hpp"
+#include "mesh_bvh.hpp"
 #include "tuning.hpp"
 
 #include <new>
@@ -1541,6 +1542,46 @@ int disn_emd(const float* xyz1, const float* xyz2, int b, int n, int m, float* c
   if (ws_bytes < metrics_ws_bytes(b, n, m)) return DISN_E_WS;
   DISN_TRY(emd_launch(xyz1, xyz2, b, n, m, cost, ws, (hipStream_t)stream));
   return 0;
+}
+
+// ---- mesh-to-SDF preprocessing (mesh_sdf.hip; host parts in mesh_host.cpp) ----
+static int mesh_grid_shape(int nx, int ny, int nz) {
+  if (nx < 2 || ny < 2 || nz < 2) return DISN_E_ARG;
+  if ((int64_t)nx * ny * nz > INT32_MAX) return DISN_E_SHAPE;  // int32 component labels
+  return 0;
+}
+
+int disn_mesh_udf_points(const void* bvh, int64_t nf, const float* points, int64_t n, int brute, float* dist,
+                         void* stream) {
+  if (!bvh || !points || !dist || nf < 1 || n < 1) return DISN_E_ARG;
+  if (nf > kBvhMaxTris || n > (int64_t)UINT32_MAX * 256) return DISN_E_SHAPE;
+  DISN_TRY(mesh_udf_points_launch(bvh, nf, points, n, brute, dist, (hipStream_t)stream));
+  return 0;
+}
+
+int disn_mesh_udf_grid(const void* bvh, int64_t nf, const float* xs, const float* ys, const float* zs, int nx, int ny,
+                       int nz, int brute, float* dist, void* stream) {
+  if (!bvh || !xs || !ys || !zs || !dist || nf < 1) return DISN_E_ARG;
+  if (int rc = mesh_grid_shape(nx, ny, nz)) return rc;
+  if (nf > kBvhMaxTris) return DISN_E_SHAPE;
+  DISN_TRY(mesh_udf_grid_launch(bvh, nf, xs, ys, zs, nx, ny, nz, brute, dist, (hipStream_t)stream));
+  return 0;
+}
+
+size_t disn_mesh_sign_workspace_bytes(int nx, int ny, int nz) {
+  return mesh_grid_shape(nx, ny, nz) ? 0 : mesh_sign_ws_bytes((int64_t)nx * ny * nz);
+}
+
+int disn_mesh_sign(const void* bvh, int64_t nf, const float* xs, const float* ys, const float* zs, int nx, int ny,
+                   int nz, const float* u, float tau, int steps, float offset, float* sdf, uint8_t* outside, void* ws,
+                   size_t ws_bytes, void* stream) {
+  if (!bvh || !xs || !ys || !zs || !u || !sdf || !ws || nf < 1 || steps < 0) return DISN_E_ARG;
+  if (!(tau > 0.0f) || !(offset == offset)) return DISN_E_ARG;
+  if (int rc = mesh_grid_shape(nx, ny, nz)) return rc;
+  if (nf > kBvhMaxTris) return DISN_E_SHAPE;
+  if (ws_bytes < mesh_sign_ws_bytes((int64_t)nx * ny * nz)) return DISN_E_WS;
+  return mesh_sign_launch(bvh, nf, xs, ys, zs, nx, ny, nz, u, tau, steps, offset, sdf, outside, ws,
+                          (hipStream_t)stream);
 }
 
 }  // extern "C"

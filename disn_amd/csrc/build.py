@@ -39,11 +39,13 @@ SOURCES = {
     "elementwise.hip": ["-ffp-contract=off"],
     "marching_cubes.hip": ["-ffp-contract=off"],
     "metrics.hip": ["-ffp-contract=off"],       # nn_distance bit-identical to a float32 restatement
+    "mesh_sdf.hip": ["-ffp-contract=off"],      # distances and crossings bit-identical to their restatements
     "api.hip": [],
     "host_util.cpp": ["-msse4.2"],
+    "mesh_host.cpp": [],
 }
 COMMON = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
-HEADERS = ["kernels.hpp", "tuning.hpp", "h2_common.hpp", "mc_tables.h", os.path.join(ROOT, "include", "disn_amd.h")]
+HEADERS = ["kernels.hpp", "tuning.hpp", "h2_common.hpp", "mc_tables.h", "mesh_bvh.hpp", os.path.join(ROOT, "include", "disn_amd.h")]
 
 
 def _digest(paths, extra=""):

@@ -265,6 +265,17 @@ hipError_t emd_launch(const float* xyz1, const float* xyz2, int b, int n, int m,
 hipError_t match_cost_launch(const float* xyz1, const float* xyz2, const float* match, int b, int n, int m,
                              float* cost, void* ws, hipStream_t st);
 
+// ---- mesh_sdf.hip (compiled with -ffp-contract=off): mesh-to-SDF preprocessing; BVH image: mesh_bvh.hpp ----
+size_t mesh_sign_ws_bytes(int64_t N);
+hipError_t mesh_udf_points_launch(const void* bvh, int64_t nf, const float* pts, int64_t n, int brute, float* dist,
+                                  hipStream_t st);
+hipError_t mesh_udf_grid_launch(const void* bvh, int64_t nf, const float* xs, const float* ys, const float* zs,
+                                int nx, int ny, int nz, int brute, float* dist, hipStream_t st);
+// 0, a hipError_t, or DISN_E_CONVERGE; synchronises `st` once per labelling round
+int mesh_sign_launch(const void* bvh, int64_t nf, const float* xs, const float* ys, const float* zs, int nx, int ny,
+                     int nz, const float* u, float tau, int steps, float offset, float* sdf, unsigned char* outside,
+                     void* ws, hipStream_t st);
+
 // ---- mlp_fused.hip: both point MLPs as one persistent kernel per stream, activations in registers ----
 size_t mlp_fused_image_bytes();
 size_t mlp_fused_feat_image_bytes();

@@ -36,6 +36,7 @@ extern "C" {
 #define DISN_E_ARG (-1)   /* null pointer / non-positive size */
 #define DISN_E_SHAPE (-2) /* unsupported shape (channel multiple, image size ...) */
 #define DISN_E_WS (-3)    /* workspace too small */
+#define DISN_E_CONVERGE (-4) /* an iteration with a fixed cap did not converge (disn_mesh_sign) */
 
 /* ABI version of this header; disn_abi_version() returns the library's. */
 #define DISN_ABI_VERSION 10
@@ -771,6 +772,45 @@ int disn_write_obj(const char* path, const float* verts_host, int64_t nv, const 
  * (NULL / cap 0: count only).  Returns the number of vertices in the file (only the first cap are written),
  * or DISN_E_ARG on an I/O or parse error.  Faces and every other line are skipped. */
 int64_t disn_read_obj_verts(const char* path, float* verts_host, int64_t cap);
+
+/* ---------------------------------------------------------------------- *
+ * Mesh-to-SDF preprocessing (preprocessing/create_point_sdf_grid.py of the *
+ * reference; its computeDistanceField binary restated).                    *
+ *   disn_read_obj_mesh  (host) Wavefront .obj -> verts_host [vcap,3] f32,  *
+ *       faces_host [fcap,3] i32 0-based; "f" tokens v, v/vt, v//vn,        *
+ *       v/vt/vn, negative = relative; polygons fan-triangulated in file    *
+ *       order (0,t,t+1).  counts[0] = vertices, counts[1] = triangles in   *
+ *       the file (only the first vcap / fcap are written; NULL / 0: count  *
+ *       only).  DISN_E_ARG on an I/O error, a malformed record or an       *
+ *       out-of-range index.                                                *
+ *   disn_mesh_bvh_bytes / disn_mesh_bvh_build  (host) deterministic BVH of *
+ *       nf triangles into a HOST buffer (private format); copy the buffer  *
+ *       to the device as it is and pass it with the same nf below.         *
+ *   disn_mesh_udf_points  dist[n] = min over triangles of |p - T| for the  *
+ *       points [n,3] (fp32, bit-identical to the brute = 1 loop).          *
+ *   disn_mesh_udf_grid  the same at the nodes (xs[ix], ys[iy], zs[iz]),    *
+ *       dist[(iz*ny + iy)*nx + ix] (the .dist order, x fastest).           *
+ *   disn_mesh_sign  sdf = (outside ? u : -u) - offset on that grid, u from *
+ *       disn_mesh_udf_grid; outside = far flood of {u >= tau} from the box *
+ *       boundary, then `steps` band-flood steps through grid edges that    *
+ *       cross no triangle.  outside [N] uint8 optional (NULL).  Syncs the  *
+ *       stream once per labelling round; DISN_E_CONVERGE if the far flood  *
+ *       has not converged in 4096 rounds.                                  *
+ * Every device entry is deterministic.                                     *
+ * ---------------------------------------------------------------------- */
+int disn_read_obj_mesh(const char* path, float* verts_host, int64_t vcap, int32_t* faces_host, int64_t fcap,
+                       int64_t* counts);
+size_t disn_mesh_bvh_bytes(int64_t nf);
+int disn_mesh_bvh_build(const float* verts_host, int64_t nv, const int32_t* faces_host, int64_t nf, void* bvh_host,
+                        size_t bvh_bytes);
+int disn_mesh_udf_points(const void* bvh, int64_t nf, const float* points, int64_t n, int brute, float* dist,
+                         void* stream);
+int disn_mesh_udf_grid(const void* bvh, int64_t nf, const float* xs, const float* ys, const float* zs, int nx, int ny,
+                       int nz, int brute, float* dist, void* stream);
+size_t disn_mesh_sign_workspace_bytes(int nx, int ny, int nz);
+int disn_mesh_sign(const void* bvh, int64_t nf, const float* xs, const float* ys, const float* zs, int nx, int ny,
+                   int nz, const float* u, float tau, int steps, float offset, float* sdf, uint8_t* outside, void* ws,
+                   size_t ws_bytes, void* stream);
 
 /* Host utility (no device work): CRC-32C of a HOST buffer, continuing from `crc` (0 to start);
  * the checksum of TensorFlow's table blocks and tensor-bundle entries, used by the
