@@ -77,6 +77,13 @@ class ParamLayout(C.Structure):  # disn_param_layout_t
     _fields_ = [("offset", C.c_int64 * NUM_VARS), ("count", C.c_int64 * NUM_VARS), ("total", C.c_int64)]
 
 
+CAM_NUM_VARS = 50
+
+
+class CamParamLayout(C.Structure):  # disn_cam_param_layout_t
+    _fields_ = [("offset", C.c_int64 * CAM_NUM_VARS), ("count", C.c_int64 * CAM_NUM_VARS), ("total", C.c_int64)]
+
+
 # name -> (restype, argtypes); every symbol declared in include/disn_amd.h
 I, Z, P, F, L = C.c_int, C.c_size_t, C.c_void_p, C.c_float, C.c_int64
 SIGNATURES = {
@@ -156,6 +163,12 @@ SIGNATURES = {
     "disn_conv3x3_bf16": (I, [P, I, I, I, I, P, P, I, I, I, P, P, Z, P]),
     "disn_cam_head": (I, [C.POINTER(CamWeights), P, C.POINTER(C.c_float * 9), I, P, P, P, P, P]),
     "disn_param_layout": (I, [C.POINTER(ParamLayout)]),
+    "disn_cam_param_layout": (I, [C.POINTER(CamParamLayout)]),
+    "disn_cam_train_workspace_bytes": (Z, [I, I]),
+    "disn_cam_train_step": (I, [P, P, P, P, P, P, P, C.POINTER(C.c_float * 9), I, I, F, I, I, P, P, P, P, Z, P]),
+    "disn_cam_loss_backward_workspace_bytes": (Z, [I, I]),
+    "disn_cam_loss_backward": (I, [C.POINTER(CamWeights), P, C.POINTER(C.c_float * 9), P, P, P, I, I, I, P, P, P,
+                                   P, P, P, P, Z, P]),
     "disn_train_workspace_bytes": (Z, [I, I]),
     "disn_train_step": (I, [P, P, P, P, P, P, P, P, I, I, F, F, F, I, P, P, P, P, Z, P]),
     "disn_adam_update": (I, [P, P, P, P, L, F, F, F, F, F, P]),

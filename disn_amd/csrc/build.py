@@ -30,6 +30,7 @@ SOURCES = {
     "backward_img.hip": ["-munsafe-fp-atomics", "-ffp-contract=off"],  # same lerp weights as the forward
     "train.hip": [],
     "cam_head.hip": [],
+    "cam_train.hip": ["-ffp-contract=off"],    # fixed-order camera losses and head gradients
     "mlp_small.hip": [],
     "mlp_fused.hip": [],
     "conv_h2.hip": ["-mllvm", "-pragma-unroll-threshold=1000000"],

@@ -3,15 +3,14 @@
 // the SDF path.  0.9 M MACs and 2.9 MB of weights per image: one workgroup per image runs the three
 // towers layer by layer through LDS (thread = output column, weight rows read coalesced), thread 0
 // finishes with the 6-D -> rotation Gram-Schmidt (models/posenet.py:22-36).  Launch-latency bound.
+// `save` (optional, training): per image h1 [704], h2 [352] and the 10 raw tower outputs, CAM_SAVE_STRIDE floats
+// apart -- extra stores only, the arithmetic (and so every output bit) is the same with or without them.
 #include "../../include/disn_amd.h"
 
 #include "kernels.hpp"
 
 namespace disn {
 
-struct CamK {
-  float k[9];
-};
 
 __device__ __forceinline__ void cam_normalize(float* v) {
   float mag = sqrtf(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
@@ -30,7 +29,8 @@ __global__ __launch_bounds__(256) void cam_head_kernel(const disn_cam_weights_t 
                                                        float* __restrict__ rotation,
                                                        float* __restrict__ translation,
                                                        float* __restrict__ RT,
-                                                       float* __restrict__ trans_mat) {
+                                                       float* __restrict__ trans_mat,
+                                                       float* __restrict__ save) {
   __shared__ float emb[1024], h1[704], h2[352], o3[10];
   const int b = blockIdx.x, tid = threadIdx.x;
   for (int k = tid; k < 1024; k += 256) emb[k] = embedding[(size_t)b * 1024 + k];
@@ -46,6 +46,7 @@ __global__ __launch_bounds__(256) void cam_head_kernel(const disn_cam_weights_t 
     float acc = 0.f;
     for (int k = 0; k < 1024; ++k) acc += emb[k] * W[(size_t)k * ld + c];
     h1[n] = fmaxf(acc + bias[c], 0.f);
+    if (save) save[(size_t)b * CAM_SAVE_STRIDE + n] = h1[n];
   }
   __syncthreads();
   // layer 2: 64 -> 32, 512 -> 256, 128 -> 64, ReLU
@@ -58,6 +59,7 @@ __global__ __launch_bounds__(256) void cam_head_kernel(const disn_cam_weights_t 
     float acc = 0.f;
     for (int k = 0; k < kin; ++k) acc += x[k] * W[(size_t)k * ld + c];
     h2[n] = fmaxf(acc + bias[c], 0.f);
+    if (save) save[(size_t)b * CAM_SAVE_STRIDE + CAM_SAVE_H2 + n] = h2[n];
   }
   __syncthreads();
   // layer 3 (linear): 32 -> 1, 256 -> 6, 64 -> 3
@@ -70,6 +72,7 @@ __global__ __launch_bounds__(256) void cam_head_kernel(const disn_cam_weights_t 
     float acc = 0.f;
     for (int k = 0; k < kin; ++k) acc += x[k] * W[(size_t)k * ld + c];
     o3[tid] = acc + bias[c];
+    if (save) save[(size_t)b * CAM_SAVE_STRIDE + CAM_SAVE_O3 + tid] = o3[tid];
   }
   __syncthreads();
   if (tid == 0) {
@@ -98,6 +101,21 @@ __global__ __launch_bounds__(256) void cam_head_kernel(const disn_cam_weights_t 
   }
 }
 
+hipError_t cam_head_launch(const disn_cam_weights_t& w, const float* embedding, const CamK& K, int B,
+                           float* rotation, float* translation, float* RT, float* trans_mat, float* save,
+                           hipStream_t st) {
+  hipLaunchKernelGGL(cam_head_kernel, dim3(B), dim3(256), 0, st, w, embedding, K, rotation, translation, RT,
+                     trans_mat, save);
+  return hipGetLastError();
+}
+
+CamK cam_k(const float* K_host) {
+  CamK K;
+  const float kd[9] = {149.84375f, 0.f, 68.5f, 0.f, 149.84375f, 68.5f, 0.f, 0.f, 1.f};  // model_cam.py:28
+  for (int i = 0; i < 9; ++i) K.k[i] = K_host ? K_host[i] : kd[i];
+  return K;
+}
+
 }  // namespace disn
 
 extern "C" int disn_cam_head(const disn_cam_weights_t* w, const float* embedding, const float* K_host,
@@ -107,11 +125,7 @@ extern "C" int disn_cam_head(const disn_cam_weights_t* w, const float* embedding
   const float* const* p = reinterpret_cast<const float* const*>(w);
   for (size_t i = 0; i < sizeof(disn_cam_weights_t) / sizeof(const float*); ++i)
     if (!p[i]) return DISN_E_ARG;
-  disn::CamK K;
-  const float kd[9] = {149.84375f, 0.f, 68.5f, 0.f, 149.84375f, 68.5f, 0.f, 0.f, 1.f};  // model_cam.py:28
-  for (int i = 0; i < 9; ++i) K.k[i] = K_host ? K_host[i] : kd[i];
-  hipLaunchKernelGGL(disn::cam_head_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, *w, embedding, K,
-                     rotation, translation, RT, trans_mat);
-  const hipError_t e = hipGetLastError();
+  const hipError_t e = disn::cam_head_launch(*w, embedding, disn::cam_k(K_host), B, rotation, translation, RT,
+                                             trans_mat, nullptr, (hipStream_t)stream);
   return e == hipSuccess ? 0 : (int)e;
 }

@@ -5,6 +5,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "../../include/disn_amd.h"
+
 // disn_ctx_t of include/disn_amd.h: the auxiliary stream and the fork/join events of one caller stream
 struct disn_ctx {
   hipStream_t aux;
@@ -416,5 +418,33 @@ hipError_t pt_embed_launch(const float* pts, int64_t M, const float* g_w1, const
 hipError_t final_dot_launch(const float* g5, const float* l5, int64_t M, const float* g_w6,
                             const float* g_b6, const float* l_w6, const float* l_b6, float* sdf,
                             float* sdf_g, float* sdf_l, float out_div, hipStream_t st);
+
+// ---- cam_head.hip / cam_train.hip ----------------------------------------------
+struct CamK {
+  float k[9];
+};
+CamK cam_k(const float* K_host);  // NULL: the reference's constant (model_cam.py:28)
+// saved activations of one image (training): h1 [704] | h2 [352] | the 10 raw tower outputs; the gradient buffer of
+// the head backward has the same layout (pre-activation gradients dh1, dh2, d(o3))
+enum { CAM_SAVE_H2 = 704, CAM_SAVE_O3 = 1056, CAM_SAVE_STRIDE = 1088 };
+hipError_t cam_head_launch(const disn_cam_weights_t& w, const float* embedding, const CamK& K, int B,
+                           float* rotation, float* translation, float* RT, float* trans_mat, float* save,
+                           hipStream_t st);
+// scratch floats of cam_loss_launch
+size_t cam_loss_ws_floats(int B, int N);
+// losses[7] = {rotpc, rot2d, rotmatrix, rot2d_dist, rot3d_dist, regularization (*reg, 0 when NULL), overall};
+// dists [2][B] per-image rot2d_dist_all / rot3d_dist_all; dRT [B,12] = d(overall - regularization)/d(pred_RT)
+hipError_t cam_loss_launch(const float* pred_RT, const float* pred_T, const float* pts, const float* RT,
+                           const float* T, const CamK& K, int B, int N, int loss_mode, const float* reg,
+                           float* losses, float* dists, float* dRT, float* ws, hipStream_t st);
+// dRT -> dsave (pre-activation gradients of every head layer, CAM_SAVE_STRIDE per image) and demb [B,1024]
+hipError_t cam_head_bwd_launch(const disn_cam_weights_t& w, const float* save, const float* dRT, int B,
+                               float* dsave, float* demb, hipStream_t st);
+// the 18 weight / bias gradients (disn_cam_weights_t order), summed over the batch in image order
+struct CamGrads {
+  float* p[18];
+};
+hipError_t cam_head_wgrad_launch(const float* emb, const float* save, const float* dsave, int B, const CamGrads& g,
+                                 hipStream_t st);
 
 }  // namespace disn

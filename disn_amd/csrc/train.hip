@@ -244,9 +244,9 @@ struct TrainWs {
   size_t total;
 };
 
-size_t train_gemm_ws(int B, long M) {
+// forward + backward-data GEMM shapes (rows, N, K) of the convolution stack
+size_t conv_gemm_ws(int B) {
   size_t m = 0;
-  // forward + backward-data GEMM shapes (rows, N, K)
   for (int i = 0; i < 13; ++i) {
     const ConvL& L = kConv[i];
     const int rows = B * L.hw * L.hw;
@@ -257,6 +257,11 @@ size_t train_gemm_ws(int B, long M) {
       m = max_sz(m, gemm_bf16_ws_bytes(rows, L.cin, 9 * L.cout));
     }
   }
+  return m;
+}
+
+size_t train_gemm_ws(int B, long M) {
+  size_t m = conv_gemm_ws(B);
   const int shapes[9][2] = {{256, 64}, {512, 256}, {512, 512}, {512, 1984}, {256, 512},
                             {64, 256}, {512, 256}, {1472, 512}, {256, 512}};
   for (auto& s : shapes) {
@@ -329,6 +334,90 @@ TrainWs train_layout(void* ws, int B, int N) {
   t.bw = bwd_layout(b, (size_t)9 * 512 * 512, M, train_gemm_ws(B, M), red);
   t.total = (b.off + 255) & ~size_t(255);
   return t;
+}
+
+// ---- the camera network's step (cam_est/model_cam.py, cam_est/train_sdf_cam.py) ----------------
+// variables 0..31: the VGG of disn_param_layout at the same offsets; 32..49: cameraprediction/<scale|ortho6d|
+// translation>/fc{1,2,3}/{weights,biases} (disn_cam_weights_t order)
+void build_cam_layout(disn_cam_param_layout_t* L) {
+  disn_param_layout_t S;
+  build_layout(&S);
+  for (int i = 0; i < V_G; ++i) {
+    L->offset[i] = S.offset[i];
+    L->count[i] = S.count[i];
+  }
+  int64_t off = S.offset[V_G];
+  const int dims[3][4] = {{1024, 64, 32, 1}, {1024, 512, 256, 6}, {1024, 128, 64, 3}};
+  int idx = V_G;
+  for (int t = 0; t < 3; ++t)
+    for (int l = 0; l < 3; ++l)
+      for (int isb = 0; isb < 2; ++isb) {
+        const int64_t count = isb ? dims[t][l + 1] : (int64_t)dims[t][l] * dims[t][l + 1];
+        L->offset[idx] = off;
+        L->count[idx++] = count;
+        off += (count + 63) & ~int64_t(63);
+      }
+  L->total = off;
+}
+
+struct CamTrainWs {
+  float *conv_p[13], *conv_bT[13], *conv_h2img[13], *conv_h2bT[13];
+  float *resized, *act[13], *pooled[13], *h6, *h7, *emb;
+  float *demb, *dz7, *dz6, *dpool5, *gA, *gB, *col, *fc_ws, *sumsq_ws, *red_aux;
+  float *amax, *amax_bwd, *wmax;
+  float *rot, *trans, *pred_RT, *save, *dsave, *dRT, *loss_ws;
+  BwdWs bw;
+  size_t total;
+};
+
+CamTrainWs cam_train_layout(void* ws, int B, int N) {
+  Bump b(ws);
+  CamTrainWs t;
+  for (int i = 0; i < 13; ++i) t.conv_p[i] = b.take((size_t)conv_kpad(kConv[i].cin) * kConv[i].cout * 3 / 2);
+  t.conv_bT[0] = t.conv_h2img[0] = t.conv_h2bT[0] = nullptr;
+  for (int i = 1; i < 13; ++i) {
+    t.conv_bT[i] = b.take((size_t)9 * kConv[i].cin * kConv[i].cout * 3 / 2);
+    t.conv_h2img[i] = b.take(conv_h2_image_bytes(kConv[i].cin, kConv[i].cout) / sizeof(float) + 1);
+    t.conv_h2bT[i] = b.take(conv_h2_image_bytes(kConv[i].cout, kConv[i].cin) / sizeof(float) + 1);
+  }
+  t.resized = b.take((size_t)B * 224 * 224 * 3);
+  for (int i = 0; i < 13; ++i) {
+    const ConvL& L = kConv[i];
+    t.act[i] = b.take((size_t)B * L.hw * L.hw * L.cout);
+    t.pooled[i] = L.pool ? b.take((size_t)B * (L.hw / 2) * (L.hw / 2) * L.cout) : nullptr;
+  }
+  t.h6 = b.take((size_t)B * 4096); t.h7 = b.take((size_t)B * 4096);
+  t.emb = b.take((size_t)B * DISN_EMBED_DIM); t.demb = b.take((size_t)B * DISN_EMBED_DIM);
+  t.dz7 = b.take((size_t)B * 4096); t.dz6 = b.take((size_t)B * 4096);
+  t.dpool5 = b.take((size_t)B * 25088);
+  t.gA = b.take((size_t)B * 224 * 224 * 64); t.gB = b.take((size_t)B * 224 * 224 * 64);
+  t.col = b.take((size_t)B * 224 * 224 * 64);
+  size_t fws = gemv_ws_bytes(B, 25088, 4096);
+  fws = max_sz(fws, gemv_ws_bytes(B, 4096, 4096));
+  fws = max_sz(fws, gemv_ws_bytes(B, 4096, DISN_EMBED_DIM));
+  t.fc_ws = b.take(fws / sizeof(float) + 1);
+  t.sumsq_ws = b.take(32 * 256);
+  t.red_aux = b.take(colsum_ws_bytes(B, 4096) / sizeof(float) + 1);
+  t.amax = b.take((size_t)27 * B * 64);
+  t.amax_bwd = t.amax + (size_t)14 * B * 64;
+  t.wmax = b.take(16);
+  t.rot = b.take((size_t)B * 9); t.trans = b.take((size_t)B * 3); t.pred_RT = b.take((size_t)B * 12);
+  t.save = b.take((size_t)B * CAM_SAVE_STRIDE); t.dsave = b.take((size_t)B * CAM_SAVE_STRIDE);
+  t.dRT = b.take((size_t)B * 12);
+  t.loss_ws = b.take(cam_loss_ws_floats(B, N));
+  size_t red = colsum_ws_bytes(B, 4096);
+  for (int i = 0; i < 13; ++i)
+    red = max_sz(red, colsum_ws_bytes((long)B * kConv[i].hw * kConv[i].hw, kConv[i].cout));
+  t.bw = bwd_layout(b, (size_t)9 * 512 * 512, (long)B * 224 * 224, conv_gemm_ws(B), red);
+  t.total = (b.off + 255) & ~size_t(255);
+  return t;
+}
+
+disn_cam_weights_t cam_weights_at(const float* base, const disn_cam_param_layout_t& L) {
+  disn_cam_weights_t w;
+  const float** p = reinterpret_cast<const float**>(&w);
+  for (int j = 0; j < 18; ++j) p[j] = base + L.offset[V_G + j];
+  return w;
 }
 
 }  // namespace
@@ -692,6 +781,157 @@ int disn_train_step(disn_ctx_t* ctx, const float* params, float* grads, const fl
       // t.col ([B,224,224,64] floats, free until conv1_1) is the row-pass scratch (<= B*56*137*256)
       DISN_TRY(resize_bwd_launch(t.dmap, B, c.hw, c.hw, c.cout, DISN_IMG_H, DISN_IMG_W, DISN_FEAT_DIM,
                                  kTapOff[c.tap], dy, 1, t.col, st));
+    } else {
+      dy = const_cast<float*>(dcur);
+    }
+    const long rows = (long)B * c.hw * c.hw;
+    float* amax_i = h2fwd && i > 0 ? t.amax_bwd + (size_t)i * B * 64 : nullptr;
+    bool amax_ready = false;
+    DISN_TRY(relu_bwd_colsum_launch(dy, t.act[i], rows, c.cout, 1, G(2 * i + 1), s.red_ws, st, amax_i,
+                                    (long)c.hw * c.hw, &amax_ready));
+    const float* xin = i == 0 ? t.resized : (kConv[i - 1].pool ? t.pooled[i - 1] : t.act[i - 1]);
+    float* dx = nullptr;
+    if (i > 0) {
+      dx = bufs[which];
+      if (dx == dy) dx = bufs[which ^ 1];
+    }
+    DISN_RC(conv_bwd(xin, B, c.hw, c.hw, c.cin, P(2 * i), dy, c.cout, wd, dx, G(2 * i), t.col, s, st,
+                     t.conv_bT[i], h2fwd && i > 0 ? t.conv_h2bT[i] : nullptr, amax_i,
+                     h2fwd && i > 0 ? t.amax + (size_t)B * 64 * i : nullptr, amax_ready));
+    if (dx) {
+      which = (dx == bufs[0]) ? 1 : 0;
+      dcur = dx;
+    }
+  }
+  return 0;
+}
+
+// ---- the camera network's step ------------------------------------------------------
+int disn_cam_param_layout(disn_cam_param_layout_t* out) {
+  if (!out) return DISN_E_ARG;
+  build_cam_layout(out);
+  return 0;
+}
+
+size_t disn_cam_train_workspace_bytes(int B, int N) {
+  if (B <= 0 || N <= 0 || B > 256) return 0;
+  return cam_train_layout(nullptr, B, N).total;
+}
+
+int disn_cam_train_step(disn_ctx_t* ctx, const float* params, float* grads, const float* img, const float* pts,
+                        const float* RT, const float* trans_mat, const float* K_host, int B, int N, float wd,
+                        int loss_mode, int compute_bf16, float* pred_trans_mat, float* losses, float* dists,
+                        void* ws, size_t ws_bytes, void* stream) {
+  if (!params || !grads || !img || !pts || !RT || !trans_mat || !pred_trans_mat || !losses || !dists || !ws ||
+      B <= 0 || N <= 0 || loss_mode < 0 || loss_mode > 3)
+    return DISN_E_ARG;
+  if (B > 256) return DISN_E_SHAPE;
+  const CamTrainWs t = cam_train_layout(ws, B, N);
+  if (ws_bytes < t.total) return DISN_E_WS;
+  hipStream_t st = (hipStream_t)stream;
+  hipStream_t as = ctx ? ctx->aux : st;
+  disn_cam_param_layout_t L;
+  build_cam_layout(&L);
+  auto P = [&](int idx) { return params + L.offset[idx]; };
+  auto G = [&](int idx) { return grads + L.offset[idx]; };
+  BwdWs s = t.bw;
+  const int bf = compute_bf16 == 2 ? 3 : (compute_bf16 ? 1 : 0);
+  s.ns = bf;
+  float* gws = s.gemm_ws;
+  const size_t gwb = s.gemm_ws_bytes;
+
+  // ---------------- VGG forward, every activation kept (as disn_train_step) ----------------
+  const bool h2fwd = compute_bf16 != 0;
+  if (!h2fwd) {
+    PackJobs jobs{};
+    pack_job_add(jobs, P(0), t.conv_p[0], 0, 27, 64, 0);
+    for (int i = 1; i < 13; ++i) {
+      pack_job_add(jobs, P(2 * i), t.conv_p[i], 0, 9 * kConv[i].cin, kConv[i].cout, bf);
+      pack_job_add(jobs, P(2 * i), t.conv_bT[i], 2, kConv[i].cin, kConv[i].cout, bf);
+    }
+    DISN_TRY(pack_multi_launch(jobs, st));
+  }
+  DISN_TRY(hipMemsetAsync(s.zero, 0, 4096 * sizeof(float), st));
+  if (ctx) {
+    DISN_TRY(hipEventRecord(ctx->ev[0], st));
+    DISN_TRY(hipStreamWaitEvent(as, ctx->ev[0], 0));
+  }
+  {  // regularization: slim's l2_regularizer(wd) on the 16 VGG weights; the camera head has none
+    SumsqSegs segs{};
+    int n = 0;
+    for (int i = 0; i < 13; ++i) { segs.off[n] = L.offset[2 * i]; segs.cnt[n++] = L.count[2 * i]; }
+    for (int i = 0; i < 3; ++i) { segs.off[n] = L.offset[V_FC + 2 * i]; segs.cnt[n++] = L.count[V_FC + 2 * i]; }
+    segs.n = n;
+    DISN_TRY(sumsq_launch(params, segs, 0.5f * wd, losses + 5, t.sumsq_ws, as));
+  }
+  if (ctx) DISN_TRY(hipEventRecord(ctx->ev[1], as));
+  if (h2fwd) {
+    ConvH2PackJobs cj{};
+    cj.wmax = t.wmax;
+    for (int i = 1; i < 13; ++i) {
+      conv_h2_pack_job_add(cj, P(2 * i), kConv[i].cin, kConv[i].cout, t.conv_h2img[i], 0, i - 1);
+      conv_h2_pack_job_add(cj, P(2 * i), kConv[i].cin, kConv[i].cout, t.conv_h2bT[i], 1, i - 1);
+    }
+    DISN_TRY(conv_h2_pack_multi_launch(cj, st));
+  }
+  DISN_TRY(resize_bilinear_launch(img, B, DISN_IMG_H, DISN_IMG_W, 3, t.resized, DISN_VGG_SIZE, DISN_VGG_SIZE, 3, 0,
+                                  st, 0, h2fwd ? t.amax : nullptr, h2fwd ? 27 * B * 64 : 0));
+  const float* x = t.resized;
+  for (int i = 0; i < 13; ++i) {
+    const ConvL& c = kConv[i];
+    if (h2fwd && i == 0) {
+      DISN_TRY(conv1_1_direct_launch(x, B, c.hw, c.hw, P(0), P(1), 1, t.act[0], t.amax + (size_t)B * 64, st, 64));
+    } else if (h2fwd) {
+      DISN_TRY(conv_h2_launch(x, B, c.hw, c.hw, c.cin, t.conv_h2img[i], P(2 * i + 1), c.cout, 1,
+                              t.amax + (size_t)B * 64 * i, t.act[i], c.pool ? t.pooled[i] : nullptr,
+                              t.amax + (size_t)B * 64 * (i + 1), st, 18, 64));
+    } else {
+      DISN_RC(conv_fwd(x, B, c.hw, c.hw, c.cin, t.conv_p[i], P(2 * i + 1), c.cout, 1, t.act[i], gws, gwb, st, bf));
+    }
+    x = t.act[i];
+    if (c.pool) {
+      if (!h2fwd) DISN_TRY(maxpool2x2_launch(x, B, c.hw, c.hw, c.cout, t.pooled[i], st));
+      x = t.pooled[i];
+    }
+  }
+  const float* pool5 = x;
+  DISN_TRY(gemv_launch(pool5, B, 25088, P(V_FC), P(V_FC + 1), 4096, 1, t.h6, t.fc_ws, st));
+  DISN_TRY(gemv_launch(t.h6, B, 4096, P(V_FC + 2), P(V_FC + 3), 4096, 1, t.h7, t.fc_ws, st));
+  DISN_TRY(gemv_launch(t.h7, B, 4096, P(V_FC + 4), P(V_FC + 5), DISN_EMBED_DIM, 0, t.emb, t.fc_ws, st));
+
+  // ---------------- camera head, losses, head backward (cam_head.hip, cam_train.hip) ----------------
+  const disn_cam_weights_t cw = cam_weights_at(params, L);
+  const CamK K = cam_k(K_host);
+  DISN_TRY(cam_head_launch(cw, t.emb, K, B, t.rot, t.trans, t.pred_RT, pred_trans_mat, t.save, st));
+  if (ctx) DISN_TRY(hipStreamWaitEvent(st, ctx->ev[1], 0));  // losses[5]
+  DISN_TRY(cam_loss_launch(t.pred_RT, pred_trans_mat, pts, RT, trans_mat, K, B, N, loss_mode, losses + 5, losses,
+                           dists, t.dRT, t.loss_ws, st));
+  DISN_TRY(cam_head_bwd_launch(cw, t.save, t.dRT, B, t.dsave, t.demb, st));
+  {
+    CamGrads cg;
+    for (int j = 0; j < 18; ++j) cg.p[j] = G(V_G + j);
+    DISN_TRY(cam_head_wgrad_launch(t.emb, t.save, t.dsave, B, cg, st));
+  }
+
+  // ---------------- backward: fc8, fc7, fc6 ----------------
+  DISN_TRY(relu_bwd_colsum_launch(t.demb, nullptr, B, DISN_EMBED_DIM, 0, G(V_FC + 5), t.red_aux, st));
+  DISN_TRY(fc_bwd_launch(t.h7, t.demb, B, 4096, DISN_EMBED_DIM, P(V_FC + 4), wd, G(V_FC + 4), t.h7, t.dz7, st));
+  DISN_TRY(relu_bwd_colsum_launch(t.dz7, nullptr, B, 4096, 0, G(V_FC + 3), t.red_aux, st));
+  DISN_TRY(fc_bwd_launch(t.h6, t.dz7, B, 4096, 4096, P(V_FC + 2), wd, G(V_FC + 2), t.h6, t.dz6, st));
+  DISN_TRY(relu_bwd_colsum_launch(t.dz6, nullptr, B, 4096, 0, G(V_FC + 1), t.red_aux, st));
+  DISN_TRY(fc_bwd_launch(pool5, t.dz6, B, 25088, 4096, P(V_FC), wd, G(V_FC), nullptr, t.dpool5, st));
+
+  // ---------------- backward: conv stack (no feature-map tap gradient: the camera net samples no features) -------
+  const float* dcur = t.dpool5;
+  float* bufs[2] = {t.gA, t.gB};
+  int which = 0;
+  for (int i = 12; i >= 0; --i) {
+    const ConvL& c = kConv[i];
+    float* dy;
+    if (c.pool) {
+      dy = bufs[which];
+      which ^= 1;
+      DISN_TRY(maxpool_bwd_launch(t.act[i], dcur, B, c.hw, c.hw, c.cout, dy, st));
     } else {
       dy = const_cast<float*>(dcur);
     }

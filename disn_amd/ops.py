@@ -10,6 +10,7 @@ from __future__ import annotations
 import ctypes as C
 from typing import List, Optional, Sequence, Tuple
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -825,4 +826,79 @@ def conv3x3_bf16(x: torch.Tensor, w_hwio: torch.Tensor, bias: torch.Tensor, relu
     check("disn_conv3x3_bf16", lib().disn_conv3x3_bf16(
         x.data_ptr(), B, H, W, Cin, w_hwio.data_ptr(), _chk(bias, "bias").data_ptr(), Cout, int(relu),
         int(nsplit), out.data_ptr(), ws.data_ptr(), ws.numel(), _stream()))
+    return out
+
+
+# ---------------------------------------------------------------------------
+# camera network training (cam_est/model_cam.py, cam_est/train_sdf_cam.py)
+# ---------------------------------------------------------------------------
+CAM_LOSS_NAMES = ("rotpc_loss", "rot2d_loss", "rotmatrix_loss", "rot2d_dist", "rot3d_dist", "regularization",
+                  "overall_loss")
+CAM_LOSS_MODES = {"3D": 0, "2D": 1, "3DM": 2}   # anything else: rot2d + rotpc + rotmatrix (3)
+
+
+def cam_loss_mode(mode) -> int:
+    """the reference's --loss_mode string (or an int already) -> loss_mode of disn_cam_train_step"""
+    if isinstance(mode, int):
+        if not 0 <= mode <= 3:
+            raise ValueError("loss_mode must be in 0..3")
+        return mode
+    return CAM_LOSS_MODES.get(mode, 3)
+
+
+def _k9(K):
+    return None if K is None else (C.c_float * 9)(*[float(v) for v in np.asarray(K, np.float32).reshape(9)])
+
+
+def cam_param_layout() -> _lib.CamParamLayout:
+    """offsets / counts (in floats) of the 50 variables of the camera network's flat parameter buffer"""
+    L = _lib.CamParamLayout()
+    check("disn_cam_param_layout", lib().disn_cam_param_layout(C.byref(L)))
+    return L
+
+
+def cam_train_step(params: torch.Tensor, grads: torch.Tensor, img: torch.Tensor, pts: torch.Tensor,
+                   RT: torch.Tensor, trans_mat: torch.Tensor, wd: float = 2e-3, loss_mode="3D", K=None,
+                   compute_bf16: int = 2, ws: Optional[torch.Tensor] = None, ctx: Optional[int] = None):
+    """forward + get_loss + gradients of the camera network into `grads`:
+    -> (pred_trans_mat [B,4,3], losses [7] (CAM_LOSS_NAMES), dists [2,B]: rot2d_dist_all, rot3d_dist_all)"""
+    B, N = pts.shape[0], pts.shape[1]
+    dev = params.device
+    need = lib().disn_cam_train_workspace_bytes(B, N)
+    if need == 0:
+        raise ValueError("unsupported camera training shape B=%d N=%d (B <= 256)" % (B, N))
+    if ws is None or ws.numel() < need:
+        ws = _ws(need, dev)
+    tm = torch.empty((B, 4, 3), dtype=torch.float32, device=dev)
+    losses = torch.empty((7,), dtype=torch.float32, device=dev)
+    dists = torch.empty((2, B), dtype=torch.float32, device=dev)
+    check("disn_cam_train_step", lib().disn_cam_train_step(
+        ctx, _chk(params, "params").data_ptr(), _chk(grads, "grads").data_ptr(), _chk(img, "img").data_ptr(),
+        _chk(pts, "pts").data_ptr(), _chk(RT, "RT").data_ptr(), _chk(trans_mat, "trans_mat").data_ptr(), _k9(K),
+        B, N, float(wd), cam_loss_mode(loss_mode), int(compute_bf16), tm.data_ptr(), losses.data_ptr(),
+        dists.data_ptr(), ws.data_ptr(), ws.numel(), _stream()))
+    return tm, losses, dists
+
+
+def cam_loss_backward(w: "_lib.CamWeights", embedding: torch.Tensor, pts: torch.Tensor, RT: torch.Tensor,
+                      trans_mat: torch.Tensor, loss_mode="3D", K=None):
+    """the head part of the camera step alone: -> dict pred_trans_mat, losses [7] (regularization 0), dists [2,B],
+    dRT [B,4,3], demb [B,1024], head_grads (flat, disn_cam_param_layout offsets 32..49 minus offset[32])"""
+    e = _chk(embedding, "embedding")
+    B, N = pts.shape[0], pts.shape[1]
+    dev = e.device
+    L = cam_param_layout()
+    nh = int(L.total - L.offset[32])
+    out = {"pred_trans_mat": torch.empty((B, 4, 3), dtype=torch.float32, device=dev),
+           "losses": torch.empty((7,), dtype=torch.float32, device=dev),
+           "dists": torch.empty((2, B), dtype=torch.float32, device=dev),
+           "dRT": torch.empty((B, 4, 3), dtype=torch.float32, device=dev),
+           "demb": torch.empty((B, 1024), dtype=torch.float32, device=dev),
+           "head_grads": torch.zeros((nh,), dtype=torch.float32, device=dev)}
+    ws = _ws(lib().disn_cam_loss_backward_workspace_bytes(B, N), dev)
+    check("disn_cam_loss_backward", lib().disn_cam_loss_backward(
+        C.byref(w), e.data_ptr(), _k9(K), _chk(pts, "pts").data_ptr(), _chk(RT, "RT").data_ptr(),
+        _chk(trans_mat, "trans_mat").data_ptr(), B, N, cam_loss_mode(loss_mode), out["pred_trans_mat"].data_ptr(),
+        out["losses"].data_ptr(), out["dists"].data_ptr(), out["dRT"].data_ptr(), out["demb"].data_ptr(),
+        out["head_grads"].data_ptr(), ws.data_ptr(), ws.numel(), _stream()))
     return out

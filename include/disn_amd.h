@@ -719,6 +719,46 @@ int disn_cam_head(const disn_cam_weights_t* w, const float* embedding, const flo
                   float* rotation, float* translation, float* RT, float* trans_mat, void* stream);
 
 /* ---------------------------------------------------------------------- *
+ * Training of the camera network (cam_est/model_cam.py get_loss,           *
+ * cam_est/train_sdf_cam.py): its own VGG-16 (num_classes 1024) + the head. *
+ * Flat parameter buffer of DISN_CAM_NUM_VARS variables: 0..31 the VGG, at  *
+ * the offsets disn_param_layout gives them; 32..49                         *
+ * cameraprediction/<scale|ortho6d|translation>/fc{1,2,3}/{weights,biases}  *
+ * (disn_cam_weights_t order).  Offsets are multiples of 64 floats.         *
+ * ---------------------------------------------------------------------- */
+#define DISN_CAM_NUM_VARS 50
+typedef struct disn_cam_param_layout {
+  int64_t offset[DISN_CAM_NUM_VARS]; /* in floats */
+  int64_t count[DISN_CAM_NUM_VARS];
+  int64_t total; /* floats, multiple of 64 */
+} disn_cam_param_layout_t;
+int disn_cam_param_layout(disn_cam_param_layout_t* out);
+
+/* One forward + backward of the camera network, gradients of overall_loss w.r.t. all 50 variables into `grads`.
+ * img [B,137,137,3] (RGB / 255), pts [B,N,3] (sample_pc), RT [B,4,3] (the view's regress_mat), trans_mat [B,4,3]
+ * (the ground-truth camera), K_host: 9 floats in HOST memory or NULL (model_cam.py:28).
+ * loss_mode: 0 "3D" rotpc, 1 "2D" rot2d, 2 "3DM" rotpc + 0.3 rotmatrix, 3 rot2d + rotpc + rotmatrix; the
+ * regularization wd * sum over the 16 VGG weights of |w|^2 / 2 is always added (the head has no weight decay).
+ * Outputs: pred_trans_mat [B,4,3] (bit-identical to disn_cam_head on the same embedding); losses: 7 device floats
+ * {rotpc, rot2d, rotmatrix, rot2d_dist, rot3d_dist, regularization, overall}; dists [2][B] the per-image
+ * rot2d_dist_all, rot3d_dist_all.  compute_bf16 and ctx as in disn_train_step.  B <= 256.  Every reduction of the
+ * head and the losses runs in a fixed order (no float atomics): those values and the head gradients are bitwise
+ * repeatable. */
+size_t disn_cam_train_workspace_bytes(int B, int N);
+int disn_cam_train_step(disn_ctx_t* ctx, const float* params, float* grads, const float* img, const float* pts,
+                        const float* RT, const float* trans_mat, const float* K_host, int B, int N, float wd,
+                        int loss_mode, int compute_bf16, float* pred_trans_mat, float* losses, float* dists,
+                        void* ws, size_t ws_bytes, void* stream);
+/* The head part of the step alone (unit-test surface): head forward on `embedding` [B,1024], the losses (regularization
+ * 0), dRT [B,4,3] = d(overall)/d(pred_RT), demb [B,1024] = d(overall)/d(embedding), and the 18 head gradients into
+ * head_grads at disn_cam_param_layout offsets 32..49 minus offset[32]. */
+size_t disn_cam_loss_backward_workspace_bytes(int B, int N);
+int disn_cam_loss_backward(const disn_cam_weights_t* w, const float* embedding, const float* K_host, const float* pts,
+                           const float* RT, const float* trans_mat, int B, int N, int loss_mode, float* pred_trans_mat,
+                           float* losses, float* dists, float* dRT, float* demb, float* head_grads, void* ws,
+                           size_t ws_bytes, void* stream);
+
+/* ---------------------------------------------------------------------- *
  * Host utility (ABI 9): EQUALISED inference weights.  An exact power-of-two *
  * re-parametrisation of the hidden channels of the network                  *
  * (models/model_normalization.py:74-78,171-204; models/sdfnet.py:71-88,     *
