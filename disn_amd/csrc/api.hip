@@ -82,8 +82,6 @@ VggWs vgg_layout(void* ws, int B, int num_classes) {
   return w;
 }
 
-bool x3_enabled();
-
 int conv3x3_impl(const float* in, int B, int H, int W, int Cin, const float* w_packed,
                  const float* bias, int Cout, int relu, float* out, float* ws, size_t ws_bytes,
                  hipStream_t st, const void* x3 = nullptr, float* pool_out = nullptr,
@@ -100,7 +98,7 @@ int conv3x3_impl(const float* in, int B, int H, int W, int Cin, const float* w_p
   p.out = out; p.ldc = Cout; p.relu = relu;
   // measured at B = 1 and B = 8 (tools/bf16_time.py, prepacked): the three-term kernel wins on every
   // layer with Cin >= 64
-  if (x3 && Cin != 3 && x3_enabled()) {
+  if (x3 && Cin != 3) {
     DISN_TRY(gemm_bf16_launch(p, GEMM_CONV3, x3, ws, ws ? ws_bytes : 0, st, 3, pool_out, pooled));
     return 0;
   }
@@ -178,16 +176,11 @@ bool mlp_weights_ok(const disn_mlp_weights_t* w) {
   return true;
 }
 
-// fp32-accurate products on the bf16 MFMA pipes (three bf16 terms per operand, gemm_bf16_mfma.hip)
-// wherever the caller supplied the 3-plane weight image
-bool x3_enabled() { return tune::x3 != 0; }
-
 // The point-MLP layers of a SMALL point set (a few thousand rows: launch- and latency-bound in the GEMM kernels)
 // through dense_h2.hip when the weights carry its images: one short launch per layer, the two streams' same-shaped
 // layers paired in one launch, the per-image bias + ReLU of the split global fold2/conv1 applied by the consumer.
 bool mlp_h2(const disn_mlp_weights_t* w, long n) {
-  return x3_enabled() && n < 8192 && w->g_d2 && w->g_d3 && w->g_d4_point && w->g_d5 && w->l_d2 && w->l_d3 &&
-         w->l_d4 && w->l_d5;
+  return n < 8192 && w->g_d2 && w->g_d3 && w->g_d4_point && w->g_d5 && w->l_d2 && w->l_d3 && w->l_d4 && w->l_d5;
 }
 
 DenseH2Prob h2_prob(const float* a, int K, const void* img, const float* bias, int N, int relu, const float* in_amax,
@@ -278,7 +271,7 @@ int dense_layer(const float* a1, int lda1, int k1, const float* a2, int lda2, in
   // measured in the step (profiles/r01k_infer_step_trace.txt): at a 2048-point batch the 64..512-deep
   // layers are launch-latency bound and the f32-input kernel's stream-K plan is faster (14.6 vs 23 us);
   // the three-term kernel wins from ~8k rows on, and on the 1984-deep layer always (42 vs 54 us)
-  if (x3 && x3_enabled() && (n >= 8192 || K >= 1024)) {
+  if (x3 && (n >= 8192 || K >= 1024)) {
     DISN_TRY(gemm_bf16_launch(p, GEMM_DENSE, x3, ws, ws ? ws_bytes : 0, st, 3));
     return 0;
   }
@@ -408,7 +401,7 @@ const int kFeatPad = 1536;   // gathered feature rows zero-padded to a multiple 
 // them as 96 extra reduction blocks of fold2/conv1, mlp_fused_kernel<global> runs with the image's folded bias row and
 // adds the local sums: two launches per call behind the gather, every activation in registers.
 bool fused_small_ok(const disn_mlp_weights_t* w, int B, int N) {
-  return x3_enabled() && tune::fused_small != 0 && w->g_fused && w->l_feat && N % 128 == 0 && (long)B * N <= kChunk;
+  return w->g_fused && w->l_feat && N % 128 == 0 && (long)B * N <= kChunk;
 }
 // tap_slots[k]: image 0's 64 activation-maximum slots of tap k (image b's are slot_stride floats further each);
 // featmax: B floats of scratch; lsum: B * N floats of scratch
@@ -619,14 +612,6 @@ namespace {
 const int kTapHw[5] = {224, 112, 56, 28, 14}, kTapCh[5] = {64, 128, 256, 512, 512};
 const int kTapOff[5] = {0, 64, 192, 448, 960};
 
-// disn_encode_query runs on two streams (a tuning build can run the same launches on one).
-// Measured on MI355X (tools/overlap_sweep.py, cfg2 step of build r01c): single stream 0.886 ms, MLP
-// under the fc head 0.797 ms.  Two other overlaps were tried and removed: the 110 MB tap up-samples
-// on the auxiliary stream under the convolutions (0.86-0.98 ms at every throttle: their streamed
-// writes disturb the latency-sensitive convolution loads) and a trickle read of the fc6 weights
-// into the memory-side cache under conv4/conv5 (no gain up to 200 MB, slower beyond).
-bool two_streams() { return tune::overlap != 0; }
-
 bool vgg_weights_ok(const disn_vgg_weights_t* w) {
   if (!w) return false;
   for (int i = 0; i < 13; ++i)
@@ -643,7 +628,7 @@ int vgg_features(const disn_vgg_weights_t* w, const float* img, int B, float* re
                  hipStream_t st, int i0 = 0, int i1 = 13) {
   // the single-image kernels (conv_h2.hip) when every layer has its image: each layer's epilogue leaves the
   // maximum of its output in the slots the next layer scales its f16 split by (cleared by the resize launch)
-  bool h2 = x3_enabled();
+  bool h2 = true;
   for (int i = 0; i < 13; ++i) h2 = h2 && w->conv_w_h2[i] != nullptr;
   if (i0 == 0)
     DISN_TRY(resize_bilinear_launch(img, B, DISN_IMG_H, DISN_IMG_W, 3, resized, DISN_VGG_SIZE,
@@ -694,7 +679,7 @@ int fc_layer(const float* x, int B, int K, const float* w_kn, const float* wt_nk
   // the one-launch row form re-reads x (B x K floats) once per wave: right for one to three rows (launch-latency bound
   // layers), 4x the weight bytes in L2 traffic at eight -- a batched call takes the split-K stream kernel for every layer
   // single_form ("strict"): the forms of a call of one row for any B -- a row's sum is the same instruction sequence
-  if (wt_nk && (B < tune::conv_wide_min || single_form)) DISN_TRY(gemv_rows_launch(x, B, K, wt_nk, bias, N, relu, out, st));   // (one threshold for every form switch: ADVICE r3)
+  if (wt_nk && (B < kConvWideMinImages || single_form)) DISN_TRY(gemv_rows_launch(x, B, K, wt_nk, bias, N, relu, out, st));   // (one threshold for every form switch: ADVICE r3)
   else DISN_TRY(gemv_launch(x, B, K, w_kn, bias, N, relu, out, ws, st, single_form));
   return 0;
 }
@@ -896,8 +881,12 @@ int disn_encode_query(disn_ctx_t* ctx, const disn_vgg_weights_t* vw, const disn_
   // global fold2/conv1 (small GEMMs in the quantisation holes of the convolutions); behind conv5_3 the
   // gather and the local fold2 layers (MFMA bound), under the 495 MB fc weight stream (HBM bound).
   // Every event record / wait on `st` drains it (~6 us in the kernel trace): there are three.
-  const bool two = two_streams();
-  hipStream_t ms = two ? ctx->aux : st;
+  // Measured on MI355X (tools/overlap_sweep.py, cfg2 step of build r01c): single stream 0.886 ms, MLP
+  // under the fc head 0.797 ms.  Two other overlaps were tried and removed: the 110 MB tap up-samples
+  // on the auxiliary stream under the convolutions (0.86-0.98 ms at every throttle: their streamed
+  // writes disturb the latency-sensitive convolution loads) and a trickle read of the fc6 weights
+  // into the memory-side cache under conv4/conv5 (no gain up to 200 MB, slower beyond).
+  hipStream_t ms = ctx->aux;
   int rc;
   // Schedule (r02i / r02j traces).  The convolution kernels from conv2 on are ONE round of 112..224 workgroups that
   // each fill a CU: a point-MLP GEMM running beside them takes CUs away and doubles a layer (18 -> 34 us), so
@@ -906,12 +895,11 @@ int disn_encode_query(disn_ctx_t* ctx, const disn_vgg_weights_t* vw, const disn_
   // fold2/conv1 -- ~45 us of small launches beside resize / conv1_1 / conv1_2 (VALU work and a two-round kernel,
   // measured unaffected) -- then, behind conv5_3, the LOCAL stream's fold1, the gather and fold2 under the fc head.
   const float* pool5 = nullptr;
-  bool gather_on_st = false;
   if (ctx->pipe_wait) DISN_TRY(hipStreamWaitEvent(st, ctx->pipe_wait, 0));  // behind the previous step's convolutions
   // Round 4: a batched call (>= kConvWideMinImages images) with the fused small-set kernels -- nothing runs beside the
   // convolutions; behind conv5_3 the auxiliary stream gathers (split form) and runs the local stream's one launch
   // under the fc head; the global stream's one launch follows the folded bias and adds the local sums.
-  bool conv_h2_all = x3_enabled();
+  bool conv_h2_all = true;
   for (int i = 0; i < 13; ++i) conv_h2_all = conv_h2_all && vw->conv_w_h2[i] != nullptr;
   // (a call of one to three requests keeps the layer-by-layer dense_h2 form below 8192 points per request -- its bits
   // are a B = 1 call's; from 8192 points on it takes the fused kernels too: 2.13 -> 1.40 ms for one request of 65536 points
@@ -920,8 +908,8 @@ int disn_encode_query(disn_ctx_t* ctx, const disn_vgg_weights_t* vw, const disn_
   // "strict" (disn_vgg_weights_t.strict_forms = 1) in a call of >= 4 requests: the single-image forms of the convolutions
   // (vgg_features) AND of the point-MLP layers (dense_h2.hip's four-k-wave tiles, per-image scales) -- the request's taps
   // and, up to the fc head's form, its pred_sdf are those of the request alone
-  const bool strict = vw->strict_forms == 1 && B >= tune::conv_wide_min && mlp_h2(mw, N);
-  if (!strict && two && conv_h2_all && !featmap && (B >= tune::conv_wide_min || N >= 8192) && fused_small_ok(mw, B, Np)) {
+  const bool strict = vw->strict_forms == 1 && B >= kConvWideMinImages && mlp_h2(mw, N);
+  if (!strict && conv_h2_all && !featmap && (B >= kConvWideMinImages || N >= 8192) && fused_small_ok(mw, B, Np)) {
     float* sdf_out = sdf;
     if (Np != N) {   // pad the point sets (both streams run behind the fork / the convolutions anyway)
       DISN_TRY(restride_rows_launch(pts, B, N, e.pad_pts, Np, 3, st));
@@ -950,50 +938,43 @@ int disn_encode_query(disn_ctx_t* ctx, const disn_vgg_weights_t* vw, const disn_
     if (sdf != sdf_out) DISN_TRY(restride_rows_launch(sdf, B, N, sdf_out, N0, 1, st));
     return 0;
   }
-  const bool h2 = two && B <= kH2Imgs && mlp_h2(mw, N);   // small point sets: the dense_h2 layers, image by image
+  const bool h2 = B <= kH2Imgs && mlp_h2(mw, N);   // small point sets: the dense_h2 layers, image by image
   const int feat_ld = h2 && !featmap ? kFeatPad : DISN_FEAT_DIM;
   const int hb = h2 && N % 64 == 0 ? B : 1;   // images per h2 launch
-  if (two) {
-    DISN_TRY(hipEventRecord(ctx->ev[0], st));  // fork (orders aux behind the caller's inputs)
-    DISN_TRY(hipStreamWaitEvent(ctx->aux, ctx->ev[0], 0));
-    // host order: the caller's stream gets resize, conv1_1, conv1_2 first (it must never wait for the host), then
-    // the auxiliary stream its launches, then the rest of the stack
-    rc = vgg_features(vw, img, B, resized224 ? resized224 : e.vgg.resized, taps, featmap, e.vgg, &pool5, st, 0, 2);
-    if (rc) return rc;
-    if (h2) {  // fold1 of both streams (paired launches) and the point half of the global fold2/conv1: one launch
-               // per layer for the whole batch (hb = B images at once) or image by image (hb = 1)
-      for (int b = 0; b < B; b += hb) {
-        const size_t o = (size_t)b * N;
-        if ((rc = mlp_fold1_h2(mw, pts_rot + o * 3, N, e.q.mlp, b, o, hb, ctx->aux, strict))) return rc;
-        if ((rc = mlp_g4_pre_h2(mw, N, e.q.mlp, b, o, hb, e.q.mlp.g4pre + o * 512, ctx->aux, strict))) return rc;
-      }
-    } else {
-      DISN_TRY(pt_embed_launch(pts_rot, B * N, mw->g_w1, mw->g_b1, mw->l_w1, mw->l_b1, e.q.mlp.e1g, e.q.mlp.e1l, ctx->aux));
-      if ((rc = mlp_fold1_global(mw, B * N, e.q.mlp, e.q.mlp.gemm_ws2, ctx->aux))) return rc;
-      if ((rc = mlp_g4_pre(mw, B * N, e.q.mlp, e.q.mlp.gemm_ws2, ctx->aux))) return rc;
+  DISN_TRY(hipEventRecord(ctx->ev[0], st));  // fork (orders aux behind the caller's inputs)
+  DISN_TRY(hipStreamWaitEvent(ctx->aux, ctx->ev[0], 0));
+  // host order: the caller's stream gets resize, conv1_1, conv1_2 first (it must never wait for the host), then
+  // the auxiliary stream its launches, then the rest of the stack
+  rc = vgg_features(vw, img, B, resized224 ? resized224 : e.vgg.resized, taps, featmap, e.vgg, &pool5, st, 0, 2);
+  if (rc) return rc;
+  if (h2) {  // fold1 of both streams (paired launches) and the point half of the global fold2/conv1: one launch
+             // per layer for the whole batch (hb = B images at once) or image by image (hb = 1)
+    for (int b = 0; b < B; b += hb) {
+      const size_t o = (size_t)b * N;
+      if ((rc = mlp_fold1_h2(mw, pts_rot + o * 3, N, e.q.mlp, b, o, hb, ctx->aux, strict))) return rc;
+      if ((rc = mlp_g4_pre_h2(mw, N, e.q.mlp, b, o, hb, e.q.mlp.g4pre + o * 512, ctx->aux, strict))) return rc;
     }
-    DISN_TRY(hipEventRecord(ctx->ev[8], ctx->aux));
-    rc = vgg_features(vw, img, B, resized224 ? resized224 : e.vgg.resized, taps, featmap, e.vgg, &pool5, st, 2, 13);
-    if (rc) return rc;
-    // the gather from the taps on the caller's stream, BEFORE the fc head: alone it takes 14 us, under fc6's HBM
-    // stream 65-70 us (r02q trace) -- and the local fold2 layers behind it are the critical path of the tail
-    // The kernel also leaves max |feat| per image in the slots the local fold2/conv1 reads its scale from (cleared
-    // by pt_embed on the auxiliary stream, hence the ev[8] wait first -- recorded a whole convolution stack ago).
-    gather_on_st = h2 && !featmap;
-    DISN_TRY(hipStreamWaitEvent(st, ctx->ev[8], 0));   // (recorded behind g4_pre, a whole convolution stack ago)
-    if (gather_on_st)
-      DISN_TRY(project_gather_taps_launch(taps, trans_mat, pts, B, N, 0, 5, e.q.feat, st, feat_ld,
-                                          h2_slots(e.q.mlp, 0) + kFeatMaxSlot, 1024));
-    if (ctx->pipe_record) DISN_TRY(hipEventRecord(ctx->pipe_record, st));  // the next step's convolutions may start
-    DISN_TRY(hipEventRecord(ctx->ev[7], st));
-    DISN_TRY(hipStreamWaitEvent(ctx->aux, ctx->ev[7], 0));
-    if (!h2 && (rc = mlp_fold1_local(mw, B * N, e.q.mlp, e.q.mlp.gemm_ws, ctx->aux))) return rc;
   } else {
-    rc = vgg_features(vw, img, B, resized224 ? resized224 : e.vgg.resized, taps, featmap, e.vgg, &pool5, st);
-    if (rc) return rc;
-    if ((rc = mlp_phase0(mw, pts_rot, B * N, e.q.mlp, st))) return rc;
-    if ((rc = vgg_head(vw, pool5, B, embedding, e.vgg, st))) return rc;
+    DISN_TRY(pt_embed_launch(pts_rot, B * N, mw->g_w1, mw->g_b1, mw->l_w1, mw->l_b1, e.q.mlp.e1g, e.q.mlp.e1l, ctx->aux));
+    if ((rc = mlp_fold1_global(mw, B * N, e.q.mlp, e.q.mlp.gemm_ws2, ctx->aux))) return rc;
+    if ((rc = mlp_g4_pre(mw, B * N, e.q.mlp, e.q.mlp.gemm_ws2, ctx->aux))) return rc;
   }
+  DISN_TRY(hipEventRecord(ctx->ev[8], ctx->aux));
+  rc = vgg_features(vw, img, B, resized224 ? resized224 : e.vgg.resized, taps, featmap, e.vgg, &pool5, st, 2, 13);
+  if (rc) return rc;
+  // the gather from the taps on the caller's stream, BEFORE the fc head: alone it takes 14 us, under fc6's HBM
+  // stream 65-70 us (r02q trace) -- and the local fold2 layers behind it are the critical path of the tail
+  // The kernel also leaves max |feat| per image in the slots the local fold2/conv1 reads its scale from (cleared
+  // by pt_embed on the auxiliary stream, hence the ev[8] wait first -- recorded a whole convolution stack ago).
+  const bool gather_on_st = h2 && !featmap;
+  DISN_TRY(hipStreamWaitEvent(st, ctx->ev[8], 0));   // (recorded behind g4_pre, a whole convolution stack ago)
+  if (gather_on_st)
+    DISN_TRY(project_gather_taps_launch(taps, trans_mat, pts, B, N, 0, 5, e.q.feat, st, feat_ld,
+                                        h2_slots(e.q.mlp, 0) + kFeatMaxSlot, 1024));
+  if (ctx->pipe_record) DISN_TRY(hipEventRecord(ctx->pipe_record, st));  // the next step's convolutions may start
+  DISN_TRY(hipEventRecord(ctx->ev[7], st));
+  DISN_TRY(hipStreamWaitEvent(ctx->aux, ctx->ev[7], 0));
+  if (!h2 && (rc = mlp_fold1_local(mw, B * N, e.q.mlp, e.q.mlp.gemm_ws, ctx->aux))) return rc;
   if (gather_on_st) {
     // done above
   } else if (featmap) {
@@ -1011,10 +992,8 @@ int disn_encode_query(disn_ctx_t* ctx, const disn_vgg_weights_t* vw, const disn_
       if ((rc = mlp_phase1_h2(mw, N, e.q.feat + o * feat_ld, feat_ld, e.q.mlp, b, o, hb, ms, gather_on_st, strict))) return rc;
     }
   } else if ((rc = mlp_phase1(mw, B * N, e.q.feat, e.q.mlp, ms))) return rc;
-  if (two) {
-    DISN_TRY(hipEventRecord(ctx->ev[6], ctx->aux));
-    if ((rc = vgg_head(vw, pool5, B, embedding, e.vgg, st))) return rc;
-  }
+  DISN_TRY(hipEventRecord(ctx->ev[6], ctx->aux));
+  if ((rc = vgg_head(vw, pool5, B, embedding, e.vgg, st))) return rc;
   { const int grc = gbias_layer(mw, embedding, B, e.q.gbias, e.q.gemv_ws, st, vw->strict_forms == 1); if (grc) return grc; }
   if (h2) {  // global fold2/conv2 on relu(pre + bias) per image, then -- behind ev[6] -- both fold2/conv5 and the sum
     for (int b = 0; b < B; b += hb) {
@@ -1026,9 +1005,8 @@ int disn_encode_query(disn_ctx_t* ctx, const disn_vgg_weights_t* vw, const disn_
                               nullptr, 1.0f, st));
     return 0;
   }
-  if (two)  // bias + ReLU of the split layer, fold2/conv2, then -- behind ev[6] -- the final sum
-    return mlp_phase2_split(mw, B, N, e.q.gbias, sdf, e.q.mlp, st, ctx->ev[6]);
-  return mlp_phase2(mw, B, N, e.q.gbias, sdf, nullptr, nullptr, 1.0f, e.q.mlp, st);
+  // bias + ReLU of the split layer, fold2/conv2, then -- behind ev[6] -- the final sum
+  return mlp_phase2_split(mw, B, N, e.q.gbias, sdf, e.q.mlp, st, ctx->ev[6]);
 }
 
 int disn_build_featmap(const float* const taps[5], int B, float* featmap, void* stream) {
@@ -1589,23 +1567,8 @@ int disn_mesh_sign(const void* bvh, int64_t nf, const float* xs, const float* ys
 #ifdef DISN_TUNING
 namespace disn {
 namespace tune {
-int x3 = 1, overlap = 1, bf_splits = 0, skip_pack = 0, fused_safe = 0;
-int gemm_force[3] = {0, 0, 0};
-int gemv_wgs = 0;
-int dense_mb = 0, dense_nw = 0, dense_kpw = 0;
-int conv_occ = 0, conv_occ_mask = 7, conv_occ_min = 384;
+int fused_safe = 0;
 int aux_cu_mode = 0;
-int conv_img_major = -1;
-int conv_wide_min = 4;
-int l4_ranges = 2;
-int gather_l16 = 0;
-int densew_m64 = -1, densew_c128 = -1;
-int conv11_wgs = 0;
-int conv11_rt = 0;
-int tn_interleave = -1;
-int conv5_whole = 1;
-int fused_small = 1;
-int gemv_rows_cfg = 0;
 long long* ch2_stamps = nullptr;
 }
 }  // namespace disn
@@ -1614,17 +1577,10 @@ extern "C" int disn_tuning_set_ptr(int key, void* p) {
   disn::tune::ch2_stamps = static_cast<long long*>(p);
   return 0;
 }
-// tuning builds only (build.py --tuning -> libdisn_amd_tuning.so): 0 x3, 1 overlap, 2 bf_splits, 3 skip_pack,
-// 4 fused_safe, 5-7 gemm_force, 8 gemv_wgs, 9 dense_mb, 10 dense_nw, 11 dense_kpw, 12 conv_occ, 13 conv_occ_mask, 14 conv_occ_min, 15 aux_cu_mode, 16 conv_img_major, 17 conv_wide_min, 18 l4_ranges, 19 gather_l16, 20 densew_m64, 21 densew_c128, 22 conv11_wgs, 23 tn_interleave, 24 conv5_whole, 25 fused_small, 26 conv11_rt, 27 gemv_rows_cfg
+// tuning builds only (build.py --tuning -> libdisn_amd_tuning.so): 0 fused_safe, 1 aux_cu_mode
 extern "C" int disn_tuning_set(int key, int value) {
-  int* k[28] = {&disn::tune::x3, &disn::tune::overlap, &disn::tune::bf_splits, &disn::tune::skip_pack,
-                &disn::tune::fused_safe, &disn::tune::gemm_force[0], &disn::tune::gemm_force[1],
-                &disn::tune::gemm_force[2], &disn::tune::gemv_wgs, &disn::tune::dense_mb,
-                &disn::tune::dense_nw, &disn::tune::dense_kpw, &disn::tune::conv_occ, &disn::tune::conv_occ_mask,
-                &disn::tune::conv_occ_min, &disn::tune::aux_cu_mode,
-                &disn::tune::conv_img_major, &disn::tune::conv_wide_min, &disn::tune::l4_ranges, &disn::tune::gather_l16, &disn::tune::densew_m64, &disn::tune::densew_c128,
-                &disn::tune::conv11_wgs, &disn::tune::tn_interleave, &disn::tune::conv5_whole, &disn::tune::fused_small, &disn::tune::conv11_rt, &disn::tune::gemv_rows_cfg};
-  if (key < 0 || key > 27) return DISN_E_ARG;
+  int* k[2] = {&disn::tune::fused_safe, &disn::tune::aux_cu_mode};
+  if (key < 0 || key > 1) return DISN_E_ARG;
   *k[key] = value;
   return 0;
 }

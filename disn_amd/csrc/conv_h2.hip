@@ -286,7 +286,7 @@ hipError_t conv_h2_pack_launch(const float* w, int Cin, int Cout, void* image, f
 // cover.
 // ABL (tools/ubench/conv_h2_ablate.hip only; 0 in the library): 1 no weight loads in the loop, 2 no halo loads,
 // 4 no split + LDS store, 8 no A-fragment reads in the loop (wrong results: timing only)
-// OCC: workgroups per CU the register budget is cut for (2: the batched calls' multi-round grids, tuning builds)
+// OCC: workgroups per CU the register budget is cut for (2: the multi-round grids, see conv_h2_launch)
 // FL > 0 (the 14 x 14 layers of a batched call): a k-wave's accumulators restart every FL chunks (chains of 27 FL MFMAs)
 // and the finished segment is added to a second register set in fp32 VALU adds, as in conv_h2w.hip's SEG form
 template <int MB, int NW, int SEG, int TW, int D, int WK, int ABL = 0, int OCC = 1, int FL = 0>
@@ -818,12 +818,10 @@ __global__ __launch_bounds__(256) void conv1_1_direct_kernel(const float* __rest
 hipError_t conv1_1_direct_launch(const float* in, int B, int H, int W, const float* w_hwio, const float* bias, int relu,
                                  float* out, float* out_amax, hipStream_t st, int amax_stride) {
   // a step at a time: two-row tiles (784 per image fill the chip); a batched call: eight-row tiles
-  const int rt = B >= tune::conv_wide_min ? (tune::conv11_rt > 0 ? tune::conv11_rt : 4) : 1;
+  const int rt = B >= kConvWideMinImages ? 4 : 1;
   const long ntile = (long)B * ((H + 2 * rt - 1) / (2 * rt)) * ((W + 31) / 32);
-  const long cap = tune::conv11_wgs > 0 ? tune::conv11_wgs : 512;
-  const int grid = (int)(ntile < cap ? ntile : cap);  // two workgroups per CU
+  const int grid = (int)(ntile < 512 ? ntile : 512);  // two workgroups per CU
   if (rt == 4) hipLaunchKernelGGL(conv1_1_direct_kernel<4>, dim3(grid), dim3(256), 0, st, in, w_hwio, bias, B, H, W, relu, out, out_amax, amax_stride);
-  else if (rt == 2) hipLaunchKernelGGL(conv1_1_direct_kernel<2>, dim3(grid), dim3(256), 0, st, in, w_hwio, bias, B, H, W, relu, out, out_amax, amax_stride);
   else hipLaunchKernelGGL(conv1_1_direct_kernel<1>, dim3(grid), dim3(256), 0, st, in, w_hwio, bias, B, H, W, relu, out, out_amax, amax_stride);
   return hipGetLastError();
 }
@@ -858,11 +856,10 @@ hipError_t conv_h2_launch(const float* in, int B, int H, int W, int Cin, const v
 #endif
   // Which operand an XCD's L2 keeps: with the n-tile-major order every XCD streams the whole input of the launch
   // (8 x B H W Cin floats over the fabric) and reads its own eighth of the weights once; image-major it is the other
-  // way round.  Measured on the 13 layers of 2 / 4 / 8 images (tools/conv_stack_time.py, knob conv_img_major):
-  // image-major where B H W > 9 Cout 388 / 645-658 / 1059-1078 us against 385 / 627 / 1089 n-tile-major, everywhere
+  // way round.  Measured on the 13 layers of 2 / 4 / 8 images (tools/conv_stack_time.py, knob conv_img_major, since
+  // removed): image-major where B H W > 9 Cout 388 / 645-658 / 1059-1078 us against 385 / 627 / 1089 n-tile-major, everywhere
   // 399 / 665 / 1112 -- no gain: the launches are not bound by fabric traffic.  n-tile-major stays.
   d.img_major = 0;
-  if (tune::conv_img_major >= 0) d.img_major = tune::conv_img_major;
   // Calls of several images (the steps of a batched call): the batched form of conv_h2w.hip -- waves own n-blocks
   // and walk K sequentially, 12 .. 21 MFMAs per weight pair.  Its summation order differs from the k-wave tree
   // below (fp32 rounding; both inside the 1e-5 bar): an image's bits depend on WHICH FORM runs it (fewer than
@@ -882,7 +879,7 @@ hipError_t conv_h2_launch(const float* in, int B, int H, int W, int Cin, const v
   // cfg 18 (the training step): the batched forms of round 3 for every layer (conv_h2w_launch variant -1)
   const bool fast = cfg == 18;
   if (fast) cfg = 0;
-  if (!strict && cfg == 0 && tune::conv5_whole && W <= 14 && H <= 14 && B >= tune::conv_wide_min) {
+  if (!strict && cfg == 0 && W <= 14 && H <= 14 && B >= kConvWideMinImages) {
     if (fast || Cin % 128 != 0) {   // (the training step: round 3's chains of 216)
       if ((long)B * (Cout / 32) >= 200) return conv_h2_go<7, 1, 16, 14, 3, 4>(d, st);
       return conv_h2_go<1, 1, 16, 14, 3, 4, 2>(d, st);
@@ -892,7 +889,7 @@ hipError_t conv_h2_launch(const float* in, int B, int H, int W, int Cin, const v
     return conv_h2_go<1, 1, 16, 14, 3, 4, 2, 2>(d, st);
   }
   if (cfg >= 5) return conv_h2w_supported(H, W, Cin, Cout) ? conv_h2w_launch(d, st, cfg >= 12 ? cfg - 6 : cfg - 4) : hipErrorInvalidValue;
-  if (!strict && cfg == 0 && B >= tune::conv_wide_min && conv_h2w_supported(H, W, Cin, Cout)) return conv_h2w_launch(d, st, fast ? -1 : 0);
+  if (!strict && cfg == 0 && B >= kConvWideMinImages && conv_h2w_supported(H, W, Cin, Cout)) return conv_h2w_launch(d, st, fast ? -1 : 0);
   if (cfg == 0) {
     // patch shape by image width; n-blocks per workgroup so that one image still gives >= ~200 workgroups
     if (W <= 14) cfg = 1;
@@ -910,23 +907,17 @@ hipError_t conv_h2_launch(const float* in, int B, int H, int W, int Cin, const v
   // hide the L2 latency instead), <= 80 KB LDS (half-height patches at 16 x 16) -- so that one workgroup's prologue,
   // chunk barriers and epilogue run under the other's MFMAs.  Same k-waves, same summation order: same bits.
   // Measured (tools/conv_stack_time.py 4, r02v): the 13 layers of four images 697 -> 631 us.
-  if (tune::conv_occ != 1) {
-    const long per_img_tiles = cfg == 1 ? (long)((H + 1) / 2) * ((W + 13) / 14)
-                             : cfg == 3 ? (long)((H + 1) / 2) * ((W + 27) / 28)
-                             : cfg == 4 ? (long)((H + 3) / 4) * ((W + 15) / 16) : 0;
-    const long wgs = B * per_img_tiles * (Cout / (cfg == 1 ? 32 : 64));
-    const int m = tune::conv_occ_mask;   // bit per tiling (tuning builds)
-    // From 1.5 workgroups per CU on where the patch stays the same; where it is halved (more halo per output) from 6
-    // per CU on -- a single image's 224 / 112-pixel layers are slower with it (the 13 layers 276 -> 308 us), two
-    // images' the same, four images' faster.
-    if (cfg == 1 && wk8 && (m & 1) && wgs >= tune::conv_occ_min) return conv_h2_go<1, 1, 16, 14, 3, 8, 2>(d, st);
-    // 28-pixel layers with eight k-waves (conv4): their own tiling needs 131 KB of LDS; the 2 x 14 patch of conv5
-    // has the same halo overhead (2.3x against 2.1x) and fits twice
-    if (cfg == 2 && wk8 && (m & 8) && B * (long)((H + 1) / 2) * ((W + 13) / 14) * (Cout / 32) >= 4 * tune::conv_occ_min)
-      return conv_h2_go<1, 1, 16, 14, 3, 8, 2>(d, st);
-    if (cfg == 3 && (m & 2) && wgs >= tune::conv_occ_min) return conv_h2_go<2, 2, 32, 28, 1, 4, 2>(d, st);
-    if (cfg == 4 && (m & 4) && wgs >= 4 * tune::conv_occ_min) return conv_h2_go<2, 2, 16, 16, 1, 4, 2>(d, st);
-  }
+  const long per_img_tiles = cfg == 1 ? (long)((H + 1) / 2) * ((W + 13) / 14)
+                           : cfg == 3 ? (long)((H + 1) / 2) * ((W + 27) / 28)
+                           : cfg == 4 ? (long)((H + 3) / 4) * ((W + 15) / 16) : 0;
+  const long wgs = B * per_img_tiles * (Cout / (cfg == 1 ? 32 : 64));
+  // From 1.5 workgroups per CU on where the patch stays the same; where it is halved (more halo per output) from 6
+  // per CU on -- a single image's 224 / 112-pixel layers are slower with it (the 13 layers 276 -> 308 us), two
+  // images' the same, four images' faster.
+  constexpr long kOccMin = 384;
+  if (cfg == 1 && wk8 && wgs >= kOccMin) return conv_h2_go<1, 1, 16, 14, 3, 8, 2>(d, st);
+  if (cfg == 3 && wgs >= kOccMin) return conv_h2_go<2, 2, 32, 28, 1, 4, 2>(d, st);
+  if (cfg == 4 && wgs >= 4 * kOccMin) return conv_h2_go<2, 2, 16, 16, 1, 4, 2>(d, st);
   switch (cfg) {
     case 1: return wk8 ? conv_h2_go<1, 1, 16, 14, 9, 8>(d, st) : conv_h2_go<1, 1, 16, 14, 9, 4>(d, st);
     case 2: return wk8 ? conv_h2_go<2, 1, 32, 28, 9, 8>(d, st) : conv_h2_go<2, 1, 32, 28, 9, 4>(d, st);

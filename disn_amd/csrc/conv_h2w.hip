@@ -29,7 +29,6 @@
 // (fp32 rounding, both within the 1e-5 bar of the float64 oracle) from conv_h2.hip's four / eight-k-wave tree, which
 // serves calls of fewer than four images: see conv_h2_launch.
 #include "kernels.hpp"
-#include "tuning.hpp"
 #include "h2_common.hpp"
 
 #include <type_traits>

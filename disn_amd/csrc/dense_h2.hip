@@ -18,7 +18,6 @@
 // computed before its per-image bias existed (the split global fold2/conv1 of disn_encode_query).
 #include "kernels.hpp"
 #include "h2_common.hpp"
-#include "tuning.hpp"
 
 #include <type_traits>
 
@@ -253,7 +252,7 @@ hipError_t dense_h2_launch(const DenseH2Prob* probs, int nprob, hipStream_t st) 
   // Rows of >= kConvWideMinImages images (a batched call): the batched form of dense_h2w.hip (another K summation
   // order: fp32 rounding apart from the tiles below, not bit for bit; the rule looks at the call's image count and
   // the rows per image only, so an image's bits never depend on its companions)
-  if (!p.no_wide && p.amax_rows > 0 && p.amax_rows % 128 == 0 && p.M / p.amax_rows >= tune::conv_wide_min) {
+  if (!p.no_wide && p.amax_rows > 0 && p.amax_rows % 128 == 0 && p.M / p.amax_rows >= kConvWideMinImages) {
     bool ok = true;
     for (int i = 0; i < nprob; ++i) ok = ok && dense_h2w_supported(d.p[i]) && d.p[i].amax_rows == p.amax_rows;
     if (ok) return dense_h2w_go(d, st);
@@ -263,29 +262,23 @@ hipError_t dense_h2_launch(const DenseH2Prob* probs, int nprob, hipStream_t st) 
   // Tile rows BM = 32 MB.  Neither the tile shape nor the chunk width changes a result bit (a k-wave adds its k16
   // blocks in ascending order and the four partial tiles are summed in one fixed order whatever the tiling):
   //   64 rows when that gives ~200 workgroups, else 32 (a single image's 2048 rows: latency-bound); 128 rows
-  //   (instantiated, tuning builds) measured no faster than 64 at 8192 rows.
+  //   measured no faster than 64 at 8192 rows.
   const long t64 = (long)((p.M + 63) / 64) * (p.N / 64) * nprob;
-  int mb = t64 >= 192 ? 2 : 1;
-  if (tune::dense_mb > 0) mb = tune::dense_mb;
+  const int mb = t64 >= 192 ? 2 : 1;
   for (int i = 0; i < nprob; ++i)
     if (d.p[i].amax_rows > 0 && d.p[i].amax_rows % (32 * mb)) return hipErrorInvalidValue;  // a tile lies in one image
   d.mtiles = (p.M + 32 * mb - 1) / (32 * mb);
   // 128 columns (16 waves) when 64 x 128 tiles still give a full round: the batched calls' thousands of rows.  Every
   // workgroup splits its rows' operand chunk itself, so at 64 columns the split is done N / 64 times per element --
-  // measured at 8192 rows (tools/dense_h2_mb.py): 2048 -> 512: 123 -> 86 us, 512 -> 512: 50 -> 34 us.
+  // measured at 8192 rows (tools/dense_h2_mb.py, since removed): 2048 -> 512: 123 -> 86 us, 512 -> 512: 50 -> 34 us.
   const long t128 = (long)((p.M + 63) / 64) * (p.N / 128) * nprob;
-  int nw = mb == 2 && p.N % 128 == 0 && t128 >= 256 ? 4 : 2;
-  if (tune::dense_nw > 0) nw = tune::dense_nw == 4 && mb == 2 && p.N % 128 == 0 ? 4 : 2;
+  const int nw = mb == 2 && p.N % 128 == 0 && t128 >= 256 ? 4 : 2;
   const dim3 grid(d.mtiles * (p.N / (32 * nw)), nprob);
   const bool c256 = p.K % 256 == 0 && p.k1 % 256 == 0;  // 256-column chunks (four k16 blocks per wave and chunk)
   const bool c128 = p.K % 128 == 0 && p.k1 % 128 == 0;
   if (nw == 4) {
-    if (c256 && tune::dense_kpw == 4) hipLaunchKernelGGL((dense_h2_kernel<2, 4, 4>), grid, dim3(1024), 0, st, d);
-    else if (c128) hipLaunchKernelGGL((dense_h2_kernel<2, 4, 2>), grid, dim3(1024), 0, st, d);
+    if (c128) hipLaunchKernelGGL((dense_h2_kernel<2, 4, 2>), grid, dim3(1024), 0, st, d);
     else hipLaunchKernelGGL((dense_h2_kernel<2, 4, 1>), grid, dim3(1024), 0, st, d);
-  } else if (mb == 4) {
-    if (c128) hipLaunchKernelGGL((dense_h2_kernel<4, 2, 2>), grid, dim3(512), 0, st, d);
-    else hipLaunchKernelGGL((dense_h2_kernel<4, 2, 1>), grid, dim3(512), 0, st, d);
   } else if (c256) {
     if (mb == 2) hipLaunchKernelGGL((dense_h2_kernel<2, 2, 4>), grid, dim3(512), 0, st, d);
     else hipLaunchKernelGGL((dense_h2_kernel<1, 2, 4>), grid, dim3(512), 0, st, d);

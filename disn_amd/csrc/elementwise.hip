@@ -11,7 +11,6 @@
 //   maxpool2x2       -- slim.max_pool2d                  (models/CNN/vgg.py:188-196)
 //   grid_points      -- linspace/meshgrid grid           (test/create_sdf.py:246-256)
 #include "kernels.hpp"
-#include "tuning.hpp"
 
 namespace disn {
 
@@ -319,7 +318,6 @@ __device__ __forceinline__ float split_pow2_scale(float amax) {
   return __uint_as_float((unsigned)(127 + 14 - e) << 23);
 }
 
-template <bool L16>
 __global__ __launch_bounds__(1024) void project_gather_taps_kernel(TapSet t,
                                                                    const float* __restrict__ trans_mat,
                                                                    const float* __restrict__ pts, int B,
@@ -371,7 +369,6 @@ __global__ __launch_bounds__(1024) void project_gather_taps_kernel(TapSet t,
     const float* tap = t.p[k] + (size_t)b * t.stride[k];
     const float s = t.s[k];
     float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (!L16) {
     // the resampler of sample4, its four map reads replaced by tap_pixel
     const bool ok = x > -1.0f && y > -1.0f && x < (float)DISN_IMG && y < (float)DISN_IMG;
     if (ok) {
@@ -400,67 +397,6 @@ __global__ __launch_bounds__(1024) void project_gather_taps_kernel(TapSet t,
   }
       DISN_ACC(x) DISN_ACC(y) DISN_ACC(z) DISN_ACC(w)
 #undef DISN_ACC
-    }
-    } else {
-    // the resampler of sample4, its four map reads replaced by the up-sampled tap pixels (tap_pixel's expression).
-    // The four map pixels are {ify, icy} x {ifx, icx}, so their 16 tap pixels are a 4 x 4 grid {ylo, yhi of both map
-    // rows} x {xlo, xhi of both map columns}: all 16 loads are issued before any is used (one memory round trip per
-    // output instead of four; addresses of out-of-map pixels are clamped, their values replaced by the resampler's
-    // zeros afterwards -- no branch around a load).
-    const bool ok = x > -1.0f && y > -1.0f && x < (float)DISN_IMG && y < (float)DISN_IMG;
-    if (ok) {
-      const float fx = floorf(x), fy = floorf(y);
-      const float cx = fx + 1.0f, cy = fy + 1.0f;
-      const float dx = cx - x, dy = cy - y;
-      const int ifx = (int)fx, ify = (int)fy, icx = (int)cx, icy = (int)cy;
-      const float w_ff = dx * dy;
-      const float w_cc = (1.0f - dx) * (1.0f - dy);
-      const float w_fc = dx * (1.0f - dy);
-      const float w_cf = (1.0f - dx) * dy;
-      const bool xf = ifx >= 0 && ifx < DISN_IMG, xc = icx >= 0 && icx < DISN_IMG;
-      const bool yf = ify >= 0 && ify < DISN_IMG, yc = icy >= 0 && icy < DISN_IMG;
-      int roff[4], coff[4];
-      float yl[2], xl[2];
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        const int oy = min(max(h ? icy : ify, 0), DISN_IMG - 1), ox = min(max(h ? icx : ifx, 0), DISN_IMG - 1);
-        const float ty = (float)oy * s, tx = (float)ox * s;
-        const int ylo = (int)floorf(ty), xlo = (int)floorf(tx);
-        const int yhi = min(ylo + 1, hw - 1), xhi = min(xlo + 1, hw - 1);
-        yl[h] = ty - (float)ylo;
-        xl[h] = tx - (float)xlo;
-        roff[2 * h] = ylo * hw * ch;
-        roff[2 * h + 1] = yhi * hw * ch;
-        coff[2 * h] = xlo * ch;
-        coff[2 * h + 1] = xhi * ch;
-      }
-      const float* base = tap + cl;
-      float4 T[4][4];
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) T[r][q] = *reinterpret_cast<const float4*>(base + roff[r] + coff[q]);
-      // map pixel (row half hy, column half hx): tl, tr, bl, br = T[2 hy][2 hx], T[2 hy][2 hx + 1], T[2 hy + 1][..]
-#define DISN_LERP(hy, hx, f) \
-  ((T[2 * hy][2 * hx].f + (T[2 * hy][2 * hx + 1].f - T[2 * hy][2 * hx].f) * xl[hx]) + \
-   ((T[2 * hy + 1][2 * hx].f + (T[2 * hy + 1][2 * hx + 1].f - T[2 * hy + 1][2 * hx].f) * xl[hx]) - \
-    (T[2 * hy][2 * hx].f + (T[2 * hy][2 * hx + 1].f - T[2 * hy][2 * hx].f) * xl[hx])) * yl[hy])
-#define DISN_ACC(f)                                         \
-  {                                                         \
-    const float p_ff = (xf && yf) ? DISN_LERP(0, 0, f) : 0.f; \
-    const float p_cc = (xc && yc) ? DISN_LERP(1, 1, f) : 0.f; \
-    const float p_fc = (xf && yc) ? DISN_LERP(1, 0, f) : 0.f; \
-    const float p_cf = (xc && yf) ? DISN_LERP(0, 1, f) : 0.f; \
-    float v = w_ff * p_ff;                                  \
-    v = v + w_cc * p_cc;                                    \
-    v = v + w_fc * p_fc;                                    \
-    v = v + w_cf * p_cf;                                    \
-    o.f = v;                                                \
-  }
-      DISN_ACC(x) DISN_ACC(y) DISN_ACC(z) DISN_ACC(w)
-#undef DISN_ACC
-#undef DISN_LERP
-    }
     }
     if (split_amax) {
       const float sc = split_pow2_scale(feat_split_amax(split_amax[b]));
@@ -771,7 +707,7 @@ __global__ __launch_bounds__(256) void project_gather_taps_wave_kernel(TapSet t,
 
 bool project_gather_taps_takes_slots(int B, int n, int feat_ld) {
   if (feat_ld <= 0) feat_ld = DISN_FEAT;
-  return feat_ld >= DISN_FEAT && feat_ld <= DISN_FEAT + 64 && feat_ld % 4 == 0 && tune::gather_l16 == 0 && (size_t)B * n >= 10240;
+  return feat_ld >= DISN_FEAT && feat_ld <= DISN_FEAT + 64 && feat_ld % 4 == 0 && (size_t)B * n >= 10240;
 }
 
 // workgroups per image of the launch with maxima (1024 threads each) -- the count of entries the consumer reads.
@@ -806,7 +742,6 @@ hipError_t project_gather_taps_launch(const float* const taps[5], const float* t
   // the choice is free).  Its six passes per point are six dependent memory round trips: below ~5 x 2048 points, where
   // the chip is not filled with waves anyway, the thread-per-float4 kernel's 368 independent threads per point win
   // (profiles/r06j_gather_ab.txt: 1 x 2048 points 14 against 35 us, 4 x 2048 44 / 49, 8 x 2048 85 / 70, 16 x 2048 174 / 123).
-  // tune::gather_l16 != 0 (tuning builds) forces the thread-per-float4 kernel: 1 its all-loads-first schedule, 2 the default one
   if (tap_begin == 0 && tap_end == 5 && project_gather_taps_takes_slots(B, n, feat_ld)) {
     GatherSlots gs{};
     if (tap_slots && split_amax) {
@@ -833,15 +768,11 @@ hipError_t project_gather_taps_launch(const float* const taps[5], const float* t
   if (amax) {
     int G = project_gather_taps_amax_blocks(n, feat_ld, tap_begin, tap_end);
     if (amax_cap > 0 && G > amax_cap) G = amax_cap;   // entries the caller has room for
-    if (tune::gather_l16 == 1) hipLaunchKernelGGL(project_gather_taps_kernel<true>, dim3((unsigned)(B * G)), dim3(1024), 0, st, t, trans_mat, pts, B, n,
-                       c4_begin, c4_count, feat, feat_ld, amax, amax_stride, split_amax);
-    else hipLaunchKernelGGL(project_gather_taps_kernel<false>, dim3((unsigned)(B * G)), dim3(1024), 0, st, t, trans_mat, pts, B, n,
+    hipLaunchKernelGGL(project_gather_taps_kernel, dim3((unsigned)(B * G)), dim3(1024), 0, st, t, trans_mat, pts, B, n,
                        c4_begin, c4_count, feat, feat_ld, amax, amax_stride, split_amax);
     return hipGetLastError();
   }
-  if (tune::gather_l16 == 1) hipLaunchKernelGGL(project_gather_taps_kernel<true>, dim3(grid_for(total, 16384)), dim3(256), 0, st, t,
-                     trans_mat, pts, B, n, c4_begin, c4_count, feat, feat_ld, amax, amax_stride, split_amax);
-  else hipLaunchKernelGGL(project_gather_taps_kernel<false>, dim3(grid_for(total, 16384)), dim3(256), 0, st, t,
+  hipLaunchKernelGGL(project_gather_taps_kernel, dim3(grid_for(total, 16384)), dim3(256), 0, st, t,
                      trans_mat, pts, B, n, c4_begin, c4_count, feat, feat_ld, amax, amax_stride, split_amax);
   return hipGetLastError();
 }

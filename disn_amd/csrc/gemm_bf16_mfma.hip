@@ -20,7 +20,6 @@
 // batch every layer has >= 200 tiles and the kernel is L2-bandwidth bound, not MFMA bound:
 // 128x128x32 moves 32 KB per 256 MFMA cycles).
 #include "kernels.hpp"
-#include "tuning.hpp"
 
 namespace disn {
 
@@ -164,14 +163,6 @@ hipError_t pack_multi_launch(const PackJobs& jobs, hipStream_t st) {
   return hipGetLastError();
 }
 
-// Ablation mask of tools/ablate_x3.py (WRONG results, timing only; honoured by tuning builds alone):
-// 1: no residual chain in the A split, 2: B fragments loaded once, 4: A tile loaded once,
-// 8: one MFMA instead of six, 16: no LDS staging of A after the first tile
-#if !defined(DISN_TUNING) || !defined(DISN_ABL)
-#undef DISN_ABL
-#define DISN_ABL 0
-#endif
-
 // ---------------------------------------------------------------------------
 struct BfDev {
   GemmParams p;  // p.bp unused; p.K = padded reduction length (multiple of 32)
@@ -302,7 +293,7 @@ __global__ __launch_bounds__(256, (BM * BN >= 128 * 128) ? 2 : 3) void gemm_bf16
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           v[e] = (__bf16)x[e];
-          if (!(DISN_ABL & 1)) x[e] -= (float)v[e];  // exact: the residual of a nearest-even bf16 rounding fits in fp32
+          x[e] -= (float)v[e];  // exact: the residual of a nearest-even bf16 rounding fits in fp32
         }
         *reinterpret_cast<bf16x4*>(&la[pl * PLANE + (arow + 32 * i) * LDA + c4]) = v;
       }
@@ -352,12 +343,12 @@ __global__ __launch_bounds__(256, (BM * BN >= 128 * 128) ? 2 : 3) void gemm_bf16
   for (int s = s0; s < s1; ++s) {
     if constexpr (PF2) {
       const int sn = s + 2 < s1 ? s + 2 : s1 - 1;
-      if (!(DISN_ABL & 4)) load_a(sn, a2);
-      if (!(DISN_ABL & 2)) load_b(sn, b2);
+      load_a(sn, a2);
+      load_b(sn, b2);
     } else {
       const int sn = s + 1 < s1 ? s + 1 : s;
-      if (!(DISN_ABL & 4)) load_a(sn, a1);
-      if (!(DISN_ABL & 2)) load_b(sn, b1);
+      load_a(sn, a1);
+      load_b(sn, b1);
     }
     const __bf16* la = &lds[cur * NS * PLANE] + (wm * (BM / 2) + (lane & 31)) * LDA + 8 * (lane >> 5);
 #pragma unroll
@@ -372,7 +363,7 @@ __global__ __launch_bounds__(256, (BM * BN >= 128 * 128) ? 2 : 3) void gemm_bf16
       for (int i = 0; i < TM; ++i)
 #pragma unroll
         for (int j = 0; j < TN; ++j) {
-          if (NS == 3 && !(DISN_ABL & 8)) {  // small terms first
+          if (NS == 3) {  // small terms first
             acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[1][i], b0[1][kk][j], acc[i][j], 0, 0, 0);
             acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[0][i], b0[2][kk][j], acc[i][j], 0, 0, 0);
             acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[2][i], b0[0][kk][j], acc[i][j], 0, 0, 0);
@@ -382,13 +373,12 @@ __global__ __launch_bounds__(256, (BM * BN >= 128 * 128) ? 2 : 3) void gemm_bf16
           acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[0][i], b0[0][kk][j], acc[i][j], 0, 0, 0);
         }
     }
-    if (!(DISN_ABL & 16)) store_a(cur ^ 1, a1);
+    store_a(cur ^ 1, a1);
     __syncthreads();
     cur ^= 1;
     if constexpr (PF2) {
 #pragma unroll
-      for (int i = 0; i < APASS; ++i)
-        if (!(DISN_ABL & 4)) a1[i] = a2[i];
+      for (int i = 0; i < APASS; ++i) a1[i] = a2[i];
     }
 #pragma unroll
     for (int pl = 0; pl < NS; ++pl)
@@ -396,7 +386,6 @@ __global__ __launch_bounds__(256, (BM * BN >= 128 * 128) ? 2 : 3) void gemm_bf16
       for (int kk = 0; kk < 2; ++kk)
 #pragma unroll
         for (int j = 0; j < TN; ++j) {
-          if (DISN_ABL & 2) continue;
           b0[pl][kk][j] = b1[pl][kk][j];
           if constexpr (PF2) b1[pl][kk][j] = b2[pl][kk][j];
         }
@@ -497,15 +486,13 @@ static hipError_t bf_launch_mode(const BfDev& d, GemmMode mode, hipStream_t st) 
 // split-K factor for a layer with few 64x64 tiles (the 14x14 / 28x28 convolutions, small point
 // sets): enough workgroups for ~3 per CU, at least 4 k-steps each, partials within ws_bytes
 static int bf_splits(long tiles, int ksteps, int M, int N, size_t ws_bytes) {
-  const int forced = tune::bf_splits;  // 0 in the product build
-  if (tiles >= 512 && !forced) return 1;
-  // measured per layer at B = 1 (split-factor sweep of a tuning build): ~1200 workgroups in flight and at least
-  // 12 k-steps per workgroup (a shorter loop does not amortise its prologue and the reduce pass)
-  int s = forced ? forced : (int)((1176 + tiles / 2) / tiles);
+  if (tiles >= 512) return 1;
+  // measured per layer at B = 1 (split-factor sweep of a tuning build, knob since removed): ~1200 workgroups in flight
+  // and at least 12 k-steps per workgroup (a shorter loop does not amortise its prologue and the reduce pass)
+  int s = (int)((1176 + tiles / 2) / tiles);
   if (s < 1) s = 1;
   if (s > 16) s = 16;
-  const int min_steps = forced ? 1 : 12;
-  while (s > 1 && (ksteps / s < min_steps || (size_t)s * M * N * sizeof(float) > ws_bytes)) --s;
+  while (s > 1 && (ksteps / s < 12 || (size_t)s * M * N * sizeof(float) > ws_bytes)) --s;
   return s;
 }
 
@@ -617,7 +604,7 @@ int disn_conv3x3_bf16(const float* in, int B, int H, int W, int Cin, const float
   if (Cin <= 0 || Cin % 32 || Cout <= 0 || Cout % 64) return DISN_E_SHAPE;
   if (ws_bytes < disn_conv3x3_bf16_workspace_bytes(B, H, W, Cin, Cout)) return DISN_E_WS;
   hipStream_t st = (hipStream_t)stream;
-  hipError_t e = disn::tune::skip_pack ? hipSuccess : disn::pack_bf16_launch(w_hwio, 0, 9 * Cin, Cout, ws, st, nsplit);
+  hipError_t e = disn::pack_bf16_launch(w_hwio, 0, 9 * Cin, Cout, ws, st, nsplit);
   if (e != hipSuccess) return (int)e;
   disn::GemmParams p{};
   p.a1 = in; p.H = H; p.W = W; p.Cin = Cin;

@@ -20,7 +20,6 @@
 // k-permutation: MFMA k-index h of step t inside an 8-k block is k = 4h + t on
 // both operands, so one float4 per operand feeds four MFMAs.
 #include "kernels.hpp"
-#include "tuning.hpp"
 
 
 namespace disn {
@@ -588,7 +587,7 @@ GemmPlan gemm_plan(int M, int N, int K, size_t max_ws, const int* force) {
       const long resident = (W + 255) / 256 < occ ? (W + 255) / 256 : occ;   // per CU at a time
       // Co-resident workgroups share the CU's MFMA pipes, so the busiest CU needs
       // cu_wgs * per_wg * unit MFMA cycles however they are scheduled.  MFMA-busy fractions fitted
-      // to tools/sweep_gemm.py at B = 1 and B = 8: a wave alone on its SIMD loses ~14 % to the
+      // to tools/sweep_gemm.py (since removed) at B = 1 and B = 8: a wave alone on its SIMD loses ~14 % to the
       // per-step LDS/barrier bubble; bigger tiles re-use more of each staged operand, and the A
       // side (im2col gather) is the expensive one to widen.
       const double tile_eff = tq >= 4 ? 0.93 : (tq == 1 ? 0.84 : (bm == 128 ? 0.79 : 0.86));
@@ -609,7 +608,6 @@ GemmPlan gemm_plan(int M, int N, int K, size_t max_ws, const int* force) {
     }
   }
   // an explicit plan (disn_conv3x3_planned: the plan-invariance test surface): {BM, BN, workgroups}
-  if (!force && tune::gemm_force[0]) force = tune::gemm_force;  // tuning builds only
   int fbm = force ? force[0] : 0, fbn = force ? force[1] : 0, fw = force ? force[2] : 0;
   if (force && (fbm == 64 || fbm == 128) && (fbn == 64 || fbn == 128) && N % fbn == 0 &&
       (fw >= 1 || fw == -1)) {  // W = -1: one workgroup per tile

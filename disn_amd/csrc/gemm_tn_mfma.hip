@@ -17,7 +17,6 @@
 // whole tile is finished in place, any other goes to a slab and tn_fixup sums the slabs of a tile in
 // workgroup order (deterministic, no atomics).
 #include "kernels.hpp"
-#include "tuning.hpp"
 #include "h2_common.hpp"
 
 #include <type_traits>
@@ -545,11 +544,9 @@ static hipError_t tn_launch_tile(const TnParams& p, float* ws, hipStream_t st) {
   // measured at 8 samples (tools/conv_bwd_time.py, r03aa / r03ab) 56 x 56, 256 -> 256: 222 -> 194 us (bf16), 300 -> 275
   // (f16 split); 28 x 28, 256 -> 512: 132 -> 105, 177 -> 153; no gain with 9 tiles (112 x 112) and none for the
   // fp32-MFMA form (MFMA-bound), which keeps the contiguous stream-K ranges.
-  const int T0 = d.ptiles * d.qtiles;
-  const bool inter = tune::tn_interleave < 0 ? (p.bf16 != 0 && T0 >= 18) : tune::tn_interleave != 0;
-  if (inter) {
-    const int T = T0;
-    int kt = tune::tn_interleave > 1 ? tune::tn_interleave : kTnMaxW / T;
+  const int T = d.ptiles * d.qtiles;
+  if (p.bf16 != 0 && T >= 18) {
+    int kt = kTnMaxW / T;
     if (kt > d.msteps) kt = d.msteps;
     if (kt < 1) kt = 1;
     if ((long)T * kt <= 2 * kTnMaxW) {

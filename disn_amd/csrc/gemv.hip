@@ -9,7 +9,6 @@
 // interleaved rows, K is split across blockIdx.y; partials are combined by
 // splitk_reduce_kernel (deterministic, no atomics).  x[b][k] is wave-uniform -> scalar loads.
 #include "kernels.hpp"
-#include "tuning.hpp"
 
 namespace disn {
 
@@ -221,28 +220,12 @@ __global__ __launch_bounds__(256) void gemv_rows_kernel(const float* __restrict_
 // wt_nk: [N][K] (the TF [K][N] matrix transposed); K % 4 == 0
 hipError_t gemv_rows_launch(const float* x, int B, int K, const float* wt_nk, const float* bias, int N, int relu,
                             float* out, hipStream_t st) {
-#ifdef DISN_TUNING
-  if (tune::gemv_rows_cfg > 0 && B == 1) {   // (R, U) experiments on the one-row form: the bits do not depend on them
-    const int c = tune::gemv_rows_cfg;
-    const int R = c == 2 || c == 5 ? 2 : (c == 4 ? 4 : 1);
-    const dim3 g(((N + R - 1) / R + 3) / 4);
-    switch (c) {
-      case 1: hipLaunchKernelGGL((gemv_rows_kernel<1, 1, 8>), g, dim3(256), 0, st, x, K, wt_nk, N, bias, relu, out, 0); break;
-      case 2: hipLaunchKernelGGL((gemv_rows_kernel<1, 2, 8>), g, dim3(256), 0, st, x, K, wt_nk, N, bias, relu, out, 0); break;
-      case 3: hipLaunchKernelGGL((gemv_rows_kernel<1, 1, 16>), g, dim3(256), 0, st, x, K, wt_nk, N, bias, relu, out, 0); break;
-      case 4: hipLaunchKernelGGL((gemv_rows_kernel<1, 4, 4>), g, dim3(256), 0, st, x, K, wt_nk, N, bias, relu, out, 0); break;
-      case 5: hipLaunchKernelGGL((gemv_rows_kernel<1, 2, 4>), g, dim3(256), 0, st, x, K, wt_nk, N, bias, relu, out, 0); break;
-      default: hipLaunchKernelGGL((gemv_rows_kernel<1, 1, 4>), g, dim3(256), 0, st, x, K, wt_nk, N, bias, relu, out, 0); break;
-    }
-    return hipGetLastError();
-  }
-#endif
   // two rows per wave when there are enough outputs to fill the chip that way (halves the x re-reads)
   const bool two = N >= 4096;
   const int waves = two ? (N + 1) / 2 : N;
   const dim3 grid((waves + 3) / 4);
-  // Round 6 (tools/fc_rows_time.py, cold weights, one row): row pieces in flight per lane by K for the one-row-per-wave
-  // layers -- sixteen for the 4096-long rows of fc8 (16.8 -> 12.8 us), four for the 1000-long rows of the bias fold (18.3
+  // Round 6 (tools/fc_rows_time.py, since removed; cold weights, one row): row pieces in flight per lane by K for the
+  // one-row-per-wave layers -- sixteen for the 4096-long rows of fc8 (16.8 -> 12.8 us), four for the 1000-long rows of the bias fold (18.3
   // -> 11.9 us: the eight-deep form spent its time in masked tail pieces).  U does not change a lane's k order: the same
   // bits.  (fc7 with ONE row per wave is 6 us faster too, but the compiler contracts that body differently: other bits
   // for the single-image forms -- on the 48-set sweep their worst request moved from 8.8e-6 to 9.9e-6, r06t; not taken.)
@@ -276,12 +259,12 @@ hipError_t gemv_rows_launch(const float* x, int B, int K, const float* wt_nk, co
 // row never depends on the other rows' data.
 int gemv_splits(int K, int N, int B) {
   const int colblocks = N / 256;
-  const int wgs = tune::gemv_wgs > 0 ? tune::gemv_wgs : (B >= tune::conv_wide_min ? 1024 : 2048);
+  const int wgs = B >= kConvWideMinImages ? 1024 : 2048;
   int s = (wgs + colblocks - 1) / colblocks;
   // at least 32 k rows per split (a one-row call: 2048 workgroups want them short); a batched call: at least 128 -- its
   // small layers otherwise write more partial bytes than they read weights (round 5: fc8 128 splits, the bias fold 31:
   // 8 / 16 MB of slabs for 16 / 2 MB of weights, a 42 us reduce pass; round 6: 32 / 7)
-  const int per = B >= tune::conv_wide_min ? 128 : 32;
+  const int per = B >= kConvWideMinImages ? 128 : 32;
   const int smax = K / per > 0 ? K / per : 1;
   if (s > smax) s = smax;
   if (s < 1) s = 1;
@@ -299,7 +282,7 @@ hipError_t gemv_launch(const float* x, int B, int K, const float* w_kn, const fl
                        int relu, float* out, float* ws, hipStream_t st, bool single_form) {
   const int S = gemv_splits(K, N, single_form ? 1 : B);
   dim3 grid(N / 256, S);
-  if (!single_form && B >= tune::conv_wide_min && K % 4 == 0) {   // a batched call: sixteen rows per pass on the matrix pipe
+  if (!single_form && B >= kConvWideMinImages && K % 4 == 0) {   // a batched call: sixteen rows per pass on the matrix pipe
     for (int b0 = 0; b0 < B; b0 += 16) {
       hipLaunchKernelGGL(gemv_mfma_kernel, grid, dim3(256), 0, st, x, K, w_kn, N, ws, B, b0);
       const hipError_t e = hipGetLastError();

@@ -359,7 +359,7 @@ struct ConvH2Dev;
 bool conv_h2w_supported(int H, int W, int Cin, int Cout);
 int conv_h2w_kwaves(int H, int W, int Cin, int Cout);   // by layer shape only: fixes the summation order
 hipError_t conv_h2w_launch(ConvH2Dev d, hipStream_t st, int variant);  // variant 0: by shape and batch; 1..5 forced
-constexpr int kConvWideMinImages = 4;   // conv_h2_launch(tiling = 0) takes the batched form from this many images on
+constexpr int kConvWideMinImages = 4;   // images per call from which the launchers take their batched forms (one threshold)
 
 // conv1_1 (Cin = 3, Cout = 64) as a direct fp32 FMA convolution; w_hwio: the TF tensor [3][3][3][64] as is
 hipError_t conv1_1_direct_launch(const float* in, int B, int H, int W, const float* w_hwio, const float* bias, int relu,

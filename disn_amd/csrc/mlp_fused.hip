@@ -983,13 +983,15 @@ hipError_t mlp_fused_launch(bool local, const void* image, const float* w1, cons
   P.pmap = pmap; P.pmap_amax = pmap_amax; P.add_in = add_in; P.out = out; P.out_div = out_div;
   const long long tiles = (n + 127) / 128;
   const int grid_x = (int)(tiles < 256 ? tiles : 256);
-  if (local) {
-    if (tune::fused_safe) hipLaunchKernelGGL((mlp_fused_kernel<true, true>), dim3(grid_x), dim3(256), 0, st, P);
-    else hipLaunchKernelGGL((mlp_fused_kernel<true, false>), dim3(grid_x), dim3(256), 0, st, P);
-  } else {
-    if (tune::fused_safe) hipLaunchKernelGGL((mlp_fused_kernel<false, true>), dim3(grid_x), dim3(256), 0, st, P);
-    else hipLaunchKernelGGL((mlp_fused_kernel<false, false>), dim3(grid_x), dim3(256), 0, st, P);
+#ifdef DISN_TUNING
+  if (tune::fused_safe) {   // every LDS-DMA wait as vmcnt(0) (tools/fused_check.py)
+    if (local) hipLaunchKernelGGL((mlp_fused_kernel<true, true>), dim3(grid_x), dim3(256), 0, st, P);
+    else hipLaunchKernelGGL((mlp_fused_kernel<false, true>), dim3(grid_x), dim3(256), 0, st, P);
+    return hipGetLastError();
   }
+#endif
+  if (local) hipLaunchKernelGGL((mlp_fused_kernel<true, false>), dim3(grid_x), dim3(256), 0, st, P);
+  else hipLaunchKernelGGL((mlp_fused_kernel<false, false>), dim3(grid_x), dim3(256), 0, st, P);
   return hipGetLastError();
 }
 
@@ -1014,13 +1016,15 @@ hipError_t mlp_fused_small_launch(bool local, const void* image, const float* w1
   P.feat = static_cast<const unsigned char*>(feat_split); P.feat_amax = feat_amax; P.feat_ld = feat_ld;
   const long long tiles = P.n / 128;
   const int grid_x = (int)(tiles < 256 ? tiles : 256);
-  if (local) {
-    if (tune::fused_safe) hipLaunchKernelGGL((mlp_fused_kernel<true, true, true>), dim3(grid_x), dim3(256), 0, st, P);
-    else hipLaunchKernelGGL((mlp_fused_kernel<true, false, true>), dim3(grid_x), dim3(256), 0, st, P);
-  } else {
-    if (tune::fused_safe) hipLaunchKernelGGL((mlp_fused_kernel<false, true>), dim3(grid_x), dim3(256), 0, st, P);
-    else hipLaunchKernelGGL((mlp_fused_kernel<false, false>), dim3(grid_x), dim3(256), 0, st, P);
+#ifdef DISN_TUNING
+  if (tune::fused_safe) {
+    if (local) hipLaunchKernelGGL((mlp_fused_kernel<true, true, true>), dim3(grid_x), dim3(256), 0, st, P);
+    else hipLaunchKernelGGL((mlp_fused_kernel<false, true>), dim3(grid_x), dim3(256), 0, st, P);
+    return hipGetLastError();
   }
+#endif
+  if (local) hipLaunchKernelGGL((mlp_fused_kernel<true, false, true>), dim3(grid_x), dim3(256), 0, st, P);
+  else hipLaunchKernelGGL((mlp_fused_kernel<false, false>), dim3(grid_x), dim3(256), 0, st, P);
   return hipGetLastError();
 }
 

@@ -1,7 +1,7 @@
 """Phase timeline of the conv_h2 kernel from in-kernel clock stamps (tuning build only):
 python -m disn_amd.csrc.build --tuning; DISN_AMD_LIB=disn_amd/csrc/libdisn_amd_tuning.so python tools/conv_h2_stamps.py [B]
 B > 1: B copies of the image in one launch -- the multi-round launches of a batched call (two-workgroups-per-CU
-variants); KNOB=name=value[,name=value] sets tuning knobs first (e.g. conv_occ=1: the base tilings)."""
+variants)."""
 import ctypes as C, os, sys
 import numpy as np
 import torch
@@ -12,12 +12,6 @@ h = _lib.lib()
 h.disn_tuning_set_ptr.restype, h.disn_tuning_set_ptr.argtypes = C.c_int, [C.c_int, C.c_void_p]
 dev = torch.device("cuda:0")
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 1
-if os.environ.get("KNOB"):
-    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-    import _tuning
-    for kv in os.environ["KNOB"].split(","):
-        k, v = kv.split("=")
-        _tuning.set_knob(k, int(v))
 LAYERS = [(64, 64, 224), (128, 128, 112), (256, 256, 56), (512, 512, 28), (512, 512, 14)]
 if os.environ.get("LAYERS"):   # LAYERS=256x256x56,512x512x28 (cin x cout x hw)
     LAYERS = [tuple(int(v) for v in l.split("x")) for l in os.environ["LAYERS"].split(",")]

@@ -2,7 +2,7 @@
 
 Needs the tuning build:  python -m disn_amd.csrc.build --tuning
                          DISN_AMD_LIB=disn_amd/csrc/libdisn_amd_tuning.so python tools/fused_check.py
-Runs the same queries with tune::fused_safe = 0 (product behaviour) and 1 (s_waitcnt vmcnt(0) at every
+Runs the same queries with the knob fused_safe = 0 (product behaviour) and 1 (s_waitcnt vmcnt(0) at every
 sync) and demands bit-identical results, repeatedly and under a concurrent HBM stream (uneven load)."""
 import os
 import sys
@@ -12,17 +12,14 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 
 def main():
-    from disn_amd import _lib
     from disn_amd.engine import SdfEngine
     from disn_amd.weights import WeightStore
     from oracle import disn_oracle as O
-    import ctypes as C
-    h = _lib.lib()
-    setk = h.disn_tuning_set
-    setk.restype, setk.argtypes = C.c_int, [C.c_int, C.c_int]
+    from _tuning import set_knob
     eng = SdfEngine(WeightStore.random_init(2, mode="he"))
     rng = np.random.default_rng(0)
     enc = eng.encode(rng.random((1, 137, 137, 3), dtype=np.float32))
@@ -32,9 +29,9 @@ def main():
     bad = 0
     for n in (128, 5000, 65536, 400003):
         pts = torch.from_numpy(rng.uniform(-1, 1, (1, n, 3)).astype(np.float32)).cuda()
-        assert setk(4, 1) == 0
+        set_knob("fused_safe", 1)
         ref = eng.query(enc, pts, O.DEMO_TRANS_MAT, fold=True, fused=True).clone()
-        assert setk(4, 0) == 0
+        set_knob("fused_safe", 0)
         for rep in range(6):
             if rep >= 3:    # uneven load: an HBM stream on another HIP stream while the kernel runs
                 with torch.cuda.stream(side):
@@ -53,9 +50,9 @@ def main():
     from disn_amd import ops
     for n in (128, 2048, 8192):
         pts = torch.from_numpy(rng.uniform(-1, 1, (4, n, 3)).astype(np.float32)).cuda()
-        assert setk(4, 1) == 0
+        set_knob("fused_safe", 1)
         ref = ops.query_taps_fused(eng.weights.mlp, enc4.taps, enc4.embedding, tms, pts).clone()
-        assert setk(4, 0) == 0
+        set_knob("fused_safe", 0)
         for rep in range(6):
             if rep >= 3:
                 with torch.cuda.stream(side):
