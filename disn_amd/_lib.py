@@ -192,6 +192,14 @@ SIGNATURES = {
     "disn_mesh_udf_grid": (I, [P, L, P, P, P, I, I, I, I, P, P]),
     "disn_mesh_sign_workspace_bytes": (Z, [I, I, I]),
     "disn_mesh_sign": (I, [P, L, P, P, P, I, I, I, P, F, I, F, P, P, P, Z, P]),
+    "disn_mesh_components": (I, [P, L, L, I, P, C.POINTER(C.c_int64)]),
+    "disn_voxel_grid_words": (Z, [I]),
+    "disn_voxel_surface_workspace_bytes": (Z, [L]),
+    "disn_voxel_surface": (I, [P, L, P, L, I, I, I, P, P, P, Z, P]),
+    "disn_voxel_fill_workspace_bytes": (Z, [I]),
+    "disn_voxel_fill": (I, [P, I, P, P, Z, P]),
+    "disn_voxel_index_grid": (I, [P, I, P, I, P, P]),
+    "disn_voxel_iou": (I, [P, P, I, L, P, P, P]),
     "disn_metrics_workspace_bytes": (Z, [I, I, I]),
     "disn_nn_distance": (I, [P, P, I, I, I, P, P, P, P, P, Z, P]),
     "disn_approx_match": (I, [P, P, I, I, I, P, P, Z, P]),

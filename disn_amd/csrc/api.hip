@@ -1562,6 +1562,50 @@ int disn_mesh_sign(const void* bvh, int64_t nf, const float* xs, const float* ys
                           (hipStream_t)stream);
 }
 
+// ---- voxel IoU (voxel.hip) ----
+static int voxel_axis(int n) { return n < 1 ? DISN_E_ARG : (n > 1024 ? DISN_E_SHAPE : 0); }
+
+size_t disn_voxel_grid_words(int n) { return voxel_axis(n) ? 0 : voxel_grid_words(n); }
+
+size_t disn_voxel_surface_workspace_bytes(int64_t nf) { return nf < 0 ? 0 : voxel_surface_ws_bytes(nf); }
+
+int disn_voxel_surface(const float* verts, int64_t nv, const int32_t* faces, int64_t nf, int dim, int kmin, int nkeys,
+                       uint32_t* bits, int32_t* flags, void* ws, size_t ws_bytes, void* stream) {
+  if (!bits || !flags || !ws || nv < 0 || nf < 0 || dim < 1) return DISN_E_ARG;
+  if (nf > 0 && (!verts || !faces)) return DISN_E_ARG;
+  if (int rc = voxel_axis(nkeys)) return rc;
+  if (dim > 1024 || kmin < -4096 || kmin > 4096 || nf > INT32_MAX) return DISN_E_SHAPE;
+  if (ws_bytes < voxel_surface_ws_bytes(nf)) return DISN_E_WS;
+  DISN_TRY(voxel_surface_launch(verts, nv, faces, nf, dim, kmin, nkeys, bits, flags, ws, (hipStream_t)stream));
+  return 0;
+}
+
+size_t disn_voxel_fill_workspace_bytes(int n) { return voxel_axis(n) ? 0 : voxel_fill_ws_bytes(n); }
+
+int disn_voxel_fill(const uint32_t* surface, int n, uint32_t* solid, void* ws, size_t ws_bytes, void* stream) {
+  if (!surface || !solid || !ws) return DISN_E_ARG;
+  if (int rc = voxel_axis(n)) return rc;
+  if (ws_bytes < voxel_fill_ws_bytes(n)) return DISN_E_WS;
+  return voxel_fill_launch(surface, n, solid, ws, (hipStream_t)stream);
+}
+
+int disn_voxel_index_grid(const uint32_t* keys, int nkeys, const int32_t* lut, int dim, uint32_t* index_bits,
+                          void* stream) {
+  if (!keys || !lut || !index_bits) return DISN_E_ARG;
+  if (int rc = voxel_axis(nkeys)) return rc;
+  if (int rc = voxel_axis(dim)) return rc;
+  DISN_TRY(voxel_index_grid_launch(keys, nkeys, lut, dim, index_bits, (hipStream_t)stream));
+  return 0;
+}
+
+int disn_voxel_iou(const uint32_t* gt, const uint32_t* preds, int nviews, int64_t words, int64_t* inter,
+                   int64_t* uni, void* stream) {
+  if (!gt || !preds || !inter || !uni || nviews < 1 || words < 1) return DISN_E_ARG;
+  if (nviews > 65535 || words > ((int64_t)1 << 25)) return DISN_E_SHAPE;
+  DISN_TRY(voxel_iou_launch(gt, preds, nviews, words, inter, uni, (hipStream_t)stream));
+  return 0;
+}
+
 }  // extern "C"
 
 #ifdef DISN_TUNING

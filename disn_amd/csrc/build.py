@@ -41,6 +41,7 @@ SOURCES = {
     "marching_cubes.hip": ["-ffp-contract=off"],
     "metrics.hip": ["-ffp-contract=off"],       # nn_distance bit-identical to a float32 restatement
     "mesh_sdf.hip": ["-ffp-contract=off"],      # distances and crossings bit-identical to their restatements
+    "voxel.hip": ["-ffp-contract=off"],         # the overlap test bit-identical to its float32 restatement
     "api.hip": [],
     "host_util.cpp": ["-msse4.2"],
     "mesh_host.cpp": [],

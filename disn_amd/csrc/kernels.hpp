@@ -278,6 +278,19 @@ int mesh_sign_launch(const void* bvh, int64_t nf, const float* xs, const float* 
                      int nz, const float* u, float tau, int steps, float offset, float* sdf, unsigned char* outside,
                      void* ws, hipStream_t st);
 
+// ---- voxel.hip (compiled with -ffp-contract=off): voxel IoU; n^3 bit grids of n*n rows of ceil(n/32) words ----
+size_t voxel_grid_words(int n);
+size_t voxel_surface_ws_bytes(int64_t nf);
+size_t voxel_fill_ws_bytes(int n);
+hipError_t voxel_surface_launch(const float* verts, int64_t nv, const int* faces, int64_t nf, int dim, int kmin,
+                                int nkeys, unsigned* bits, int* flags, void* ws, hipStream_t st);
+// 0, a hipError_t, or DISN_E_CONVERGE; synchronises `st` once per batch of sweeps
+int voxel_fill_launch(const unsigned* surf, int n, unsigned* solid, void* ws, hipStream_t st);
+hipError_t voxel_index_grid_launch(const unsigned* keys, int nkeys, const int* lut, int dim, unsigned* out,
+                                   hipStream_t st);
+hipError_t voxel_iou_launch(const unsigned* gt, const unsigned* preds, int nviews, int64_t words, int64_t* inter,
+                            int64_t* uni, hipStream_t st);
+
 // ---- mlp_fused.hip: both point MLPs as one persistent kernel per stream, activations in registers ----
 size_t mlp_fused_image_bytes();
 size_t mlp_fused_feat_image_bytes();

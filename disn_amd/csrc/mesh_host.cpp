@@ -1,5 +1,6 @@
 // Host side of mesh-to-SDF preprocessing (no device code).
 //   disn_read_obj_mesh  -- Wavefront .obj vertices and faces (fan-triangulated polygons), count-then-fill
+//   disn_mesh_components -- connected components of the triangles (edge or vertex connectivity), union-find
 //   disn_mesh_bvh_build -- deterministic BVH over the triangle soup, laid out for the stackless walk of
 //                          mesh_sdf.hip (node format: mesh_bvh.hpp, private to the library)
 #include "../../include/disn_amd.h"
@@ -208,5 +209,75 @@ extern "C" int disn_mesh_bvh_build(const float* verts, int64_t nv, const int32_t
     for (int k = 0; k < 3; ++k) std::memcpy(tri + 9 * i + 3 * k, verts + 3 * (int64_t)faces[3 * (int64_t)t + k],
                                             3 * sizeof(float));
   }
+  return 0;
+}
+
+// ---- connected components of a triangle soup (postprocessing/clean_smallparts.py: pymesh.separate_mesh) ----
+namespace {
+
+struct DisjointSet {
+  std::vector<int32_t> parent;
+  explicit DisjointSet(int64_t n) : parent(n) {
+    for (int64_t i = 0; i < n; ++i) parent[i] = (int32_t)i;
+  }
+  int32_t find(int32_t x) {
+    while (parent[x] != x) {
+      parent[x] = parent[parent[x]];
+      x = parent[x];
+    }
+    return x;
+  }
+  void unite(int32_t a, int32_t b) {   // the smaller index becomes the root
+    a = find(a);
+    b = find(b);
+    if (a == b) return;
+    if (a < b) parent[b] = a;
+    else parent[a] = b;
+  }
+};
+
+}  // namespace
+
+extern "C" int disn_mesh_components(const int32_t* faces, int64_t nf, int64_t nv, int connectivity, int32_t* labels,
+                                    int64_t* ncomp) {
+  if (nf < 0 || nv < 0 || !ncomp || (nf > 0 && (!faces || !labels)) || (connectivity != 0 && connectivity != 1))
+    return DISN_E_ARG;
+  if (nf > INT32_MAX / 3 || nv > INT32_MAX) return DISN_E_SHAPE;
+  for (int64_t i = 0; i < 3 * nf; ++i)
+    if (faces[i] < 0 || faces[i] >= nv) return DISN_E_ARG;
+  DisjointSet ds(nf);
+  if (connectivity == 1) {
+    std::vector<int32_t> first(nv, -1);   // the first triangle seen at a vertex
+    for (int64_t t = 0; t < nf; ++t)
+      for (int k = 0; k < 3; ++k) {
+        int32_t& f = first[faces[3 * t + k]];
+        if (f < 0) f = (int32_t)t;
+        else ds.unite(f, (int32_t)t);
+      }
+  } else {
+    struct Edge {
+      uint64_t key;
+      int32_t tri;
+    };
+    std::vector<Edge> edges(3 * nf);
+    for (int64_t t = 0; t < nf; ++t)
+      for (int k = 0; k < 3; ++k) {
+        const uint64_t a = (uint64_t)faces[3 * t + k], b = (uint64_t)faces[3 * t + (k + 1) % 3];
+        edges[3 * t + k] = Edge{std::min(a, b) << 32 | std::max(a, b), (int32_t)t};
+      }
+    std::sort(edges.begin(), edges.end(),
+              [](const Edge& x, const Edge& y) { return x.key < y.key || (x.key == y.key && x.tri < y.tri); });
+    for (size_t i = 1; i < edges.size(); ++i)
+      if (edges[i].key == edges[i - 1].key) ds.unite(edges[i - 1].tri, edges[i].tri);
+  }
+  // a root is its component's smallest triangle, so roots appear in rank order
+  std::vector<int32_t> id(nf, -1);
+  int64_t n = 0;
+  for (int64_t t = 0; t < nf; ++t) {
+    const int32_t r = ds.find((int32_t)t);
+    if (id[r] < 0) id[r] = (int32_t)n++;
+    labels[t] = id[r];
+  }
+  *ncomp = n;
   return 0;
 }

@@ -1,9 +1,11 @@
 """Scoring of reconstructed meshes: the reference's ``test/test_cd_emd.py`` (Chamfer distance and approximate
 EMD, ``cd_emd_all`` / ``cd_emd_cat``) and ``test/test_f_score.py`` (``cal_f_score_all_cat`` / ``f_score_cat``),
-on ``disn_amd.metrics`` instead of the TF1 + CUDA custom ops.
+on ``disn_amd.metrics`` instead of the TF1 + CUDA custom ops, and ``test/test_iou.py`` (voxel IoU, ``iou_all`` /
+``iou_cat``) on ``disn_amd.voxel`` instead of PyMesh.
 
     python -m disn_amd.evaluate cd_emd  --cal_dir OBJS --gt_dir GT --test_lst_dir LSTS [--category all]
     python -m disn_amd.evaluate f_score --cal_dir OBJS --gt_dir GT --test_lst_dir LSTS [--truethreshold 2.5]
+    python -m disn_amd.evaluate iou     --cal_dir OBJS --gt_dir GT --test_lst_dir LSTS [--dim 110] [--mode reference]
 
 Layout, as the reference reads it:
   predictions  <cal_dir>/<cat_id>/<cat_id>_<obj_id>_<view>.obj    (what ``isosurface.create_obj`` writes)
@@ -14,6 +16,15 @@ Layout, as the reference reads it:
 Only the reference's ``batch_size == view_num`` path is mirrored: its other branch (test_cd_emd.py:259-280)
 stacks the ground truth with ``verts_batch[b]`` for b = 0, i.e. compares the ground truth with itself.
 Point sampling draws from ``numpy.random.Generator(seed)``, the view choice from ``random.Random(seed)``.
+
+IoU (``iou``), differences from test_iou.py: the views of an object are chosen with ``random.Random(seed)`` from
+its sorted file list (the reference samples the unsorted ``os.listdir`` order with the global generator); an object
+with fewer than ``view_num`` predictions is an error, not a resample with replacement; a listed object without
+predictions is an error, not a skipped line; a mesh that cannot be scored (it leaves the voxel key range, or the
+union is empty) raises, where the reference's bare ``try`` prints "error mesh" and then fails on the ``None``.
+Kept: the ``os.stat(...)[6] > 200`` size filter on prediction files, the float32 array of per-view values with its
+sum / mean / argmax, the category average over views, and the printed lines.  ``--mode solid`` (not in the
+reference, whose grids are surface shells) fills the voxel sets first.
 """
 from __future__ import annotations
 
@@ -45,13 +56,14 @@ def categories(category: str) -> Dict[str, str]:
     return {category: CATS_ALL[category]}
 
 
-def build_file_dict(dir: str) -> Dict[str, List[str]]:
+def build_file_dict(dir: str, min_size: Optional[int] = None) -> Dict[str, List[str]]:
     """object id -> prediction files of a category directory: field 1 of the file name split on '_'
-    (test_cd_emd.py:126-136); lists sorted, so that a seed picks the same views on any file system"""
+    (test_cd_emd.py:126-136); lists sorted, so that a seed picks the same views on any file system.
+    ``min_size``: only files of more than that many bytes (test_iou.py:124 keeps those above 200)"""
     d: Dict[str, List[str]] = {}
     for fn in sorted(os.listdir(dir)):
         full = os.path.join(dir, fn)
-        if os.path.isfile(full):
+        if os.path.isfile(full) and (min_size is None or os.stat(full).st_size > min_size):
             d.setdefault(fn.split("_")[1], []).append(full)
     return d
 
@@ -196,10 +208,59 @@ def cal_f_score_all_cat(cats: Dict[str, str], pred_dir: str, gt_dir: str, test_l
     return {"categories": per, "thresholds": thresholds, "precision": pre, "recall": rec, "f_score": f}
 
 
+def iou_cat(cat_id: str, cat_nm: str, pred_dir: str, gt_dir: str, test_lst_f: str, view_num: int = 24,
+            dim: int = 110, mode: str = "reference", pyrng: Optional[random.Random] = None, out=None) -> dict:
+    """voxel IoU of every listed object over ``view_num`` sampled views (test_iou.py:174-206)
+    -> {"objects": {obj_id: {...}}, "iou_avg", "count"}; iou_avg = sum of all view values / number of views"""
+    from . import mesh_sdf, voxel
+    pyrng = pyrng if pyrng is not None else random.Random(0)
+    out = out or sys.stdout
+    pred_dict = build_file_dict(pred_dir, min_size=200)
+    objs = read_list(test_lst_f)
+    for obj_id in objs:
+        _predictions(pred_dict, obj_id, cat_id, pred_dir)
+    res: Dict[str, dict] = {}
+    iou_sum, count = 0.0, 0.0
+    for obj_id in objs:
+        src_path = os.path.join(gt_dir, obj_id, "isosurf.obj")
+        preds = _predictions(pred_dict, obj_id, cat_id, pred_dir)
+        if len(preds) < view_num:
+            raise ValueError("object %s of category %s has %d predictions, --view_num is %d"
+                             % (obj_id, cat_id, len(preds), view_num))
+        views = pyrng.sample(preds, view_num)
+        meshes = [mesh_sdf.read_obj_mesh(p) for p in [src_path] + views]
+        iou, inter, union = voxel.iou_views(meshes[0], meshes[1:], dim=dim, mode=mode, names=[src_path] + views)
+        iou_vals = np.asarray(iou, dtype=np.float32)
+        iou_sum += float(np.sum(iou_vals))
+        count += len(iou_vals)
+        avg_iou = np.mean(iou_vals)
+        ind = int(np.argmax(iou_vals))
+        best = [float(iou[ind]), views[ind]]
+        res[obj_id] = {"avg_iou": float(avg_iou), "best": best, "views": views, "iou_views": iou,
+                       "inter": inter, "union": union}
+        print("obj_id iou avg: ", avg_iou, " best pred: ", best, file=out)
+    return {"cat_nm": cat_nm, "cat_id": cat_id, "objects": res, "iou_avg": float(iou_sum / count), "count": int(count)}
+
+
+def iou_all(cats: Dict[str, str], pred_dir: str, gt_dir: str, test_lst_dir: str, dim: int = 110,
+            mode: str = "reference", view_num: int = 24, seed: int = 0, out=None) -> Dict[str, dict]:
+    """test_iou.py:165-172"""
+    out = out or sys.stdout
+    pyrng = random.Random(seed)
+    res = {}
+    for cat_nm, cat_id in cats.items():
+        res[cat_id] = iou_cat(cat_id, cat_nm, os.path.join(pred_dir, cat_id), os.path.join(gt_dir, cat_id),
+                              os.path.join(test_lst_dir, cat_id + "_test.lst"), view_num=view_num, dim=dim, mode=mode,
+                              pyrng=pyrng, out=out)
+        print("cat_nm: {}, cat_id: {}, iou_avg: {}".format(cat_nm, cat_id, res[cat_id]["iou_avg"]), file=out)
+    print("done!", file=out)
+    return res
+
+
 def parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(prog="python -m disn_amd.evaluate",
-                                description="Chamfer / EMD / F-score of reconstructed meshes (test_cd_emd.py, "
-                                            "test_f_score.py)")
+                                description="Chamfer / EMD / F-score / voxel IoU of reconstructed meshes "
+                                            "(test_cd_emd.py, test_f_score.py, test_iou.py)")
     sub = p.add_subparsers(dest="command", required=True)
     for name, hlp in (("cd_emd", "Chamfer distance and approximate EMD per object and category"),
                       ("f_score", "precision, recall and F-score at six distance thresholds")):
@@ -212,12 +273,25 @@ def parser() -> argparse.ArgumentParser:
         s.add_argument("--num_sample_points", type=int, default=2048, help="points per mesh [default: 2048]")
         s.add_argument("--truethreshold", type=float, default=2.5, help="F-score side length [default: 2.5]")
         s.add_argument("--seed", type=int, default=0, help="seed of the point and view sampling [default: 0]")
+    s = sub.add_parser("iou", help="voxel IoU per object and category")
+    s.add_argument("--cal_dir", required=True, help="directory of the predicted meshes (<cat_id>/*.obj)")
+    s.add_argument("--gt_dir", required=True, help="ground-truth meshes (<cat_id>/<obj_id>/isosurf.obj)")
+    s.add_argument("--test_lst_dir", required=True, help="object lists (<cat_id>_test.lst)")
+    s.add_argument("--category", default="all", help="all, clean or one category name [default: all]")
+    s.add_argument("--view_num", type=int, default=24, help="views per object [default: 24]")
+    s.add_argument("--dim", type=int, default=110, help="voxels per axis of [-1, 1] [default: 110]")
+    s.add_argument("--mode", default="reference", choices=("reference", "solid"),
+                   help="reference: the shell IoU of test_iou.py; solid: filled voxels [default: reference]")
+    s.add_argument("--seed", type=int, default=0, help="seed of the view sampling [default: 0]")
     return p
 
 
 def main(argv=None) -> dict:
     a = parser().parse_args(argv)
     cats = categories(a.category)
+    if a.command == "iou":
+        return iou_all(cats, a.cal_dir, a.gt_dir, a.test_lst_dir, dim=a.dim, mode=a.mode, view_num=a.view_num,
+                       seed=a.seed)
     if a.command == "cd_emd":
         return cd_emd_all(cats, a.cal_dir, a.gt_dir, a.test_lst_dir, seed=a.seed, view_num=a.view_num,
                           num_sample_points=a.num_sample_points)

@@ -36,7 +36,7 @@ extern "C" {
 #define DISN_E_ARG (-1)   /* null pointer / non-positive size */
 #define DISN_E_SHAPE (-2) /* unsupported shape (channel multiple, image size ...) */
 #define DISN_E_WS (-3)    /* workspace too small */
-#define DISN_E_CONVERGE (-4) /* an iteration with a fixed cap did not converge (disn_mesh_sign) */
+#define DISN_E_CONVERGE (-4) /* an iteration with a fixed cap did not converge (disn_mesh_sign, disn_voxel_fill) */
 
 /* ABI version of this header; disn_abi_version() returns the library's. */
 #define DISN_ABI_VERSION 10
@@ -851,6 +851,56 @@ size_t disn_mesh_sign_workspace_bytes(int nx, int ny, int nz);
 int disn_mesh_sign(const void* bvh, int64_t nf, const float* xs, const float* ys, const float* zs, int nx, int ny,
                    int nz, const float* u, float tau, int steps, float offset, float* sdf, uint8_t* outside, void* ws,
                    size_t ws_bytes, void* stream);
+
+/* ---------------------------------------------------------------------- *
+ * Small-part cleanup (postprocessing/clean_smallparts.py of the reference; *
+ * pymesh.separate_mesh restated).  (host) labels_host[t] = the connected   *
+ * component of triangle t: connectivity 0 joins triangles that share an    *
+ * edge (an unordered vertex pair), 1 those that share a vertex.  A         *
+ * component's id is the rank of its smallest triangle index.  *ncomp = the *
+ * number of components.  DISN_E_ARG on an index outside [0, nv).           *
+ * ---------------------------------------------------------------------- */
+int disn_mesh_components(const int32_t* faces_host, int64_t nf, int64_t nv, int connectivity, int32_t* labels_host,
+                         int64_t* ncomp);
+
+/* ---------------------------------------------------------------------- *
+ * Voxel IoU (test/test_iou.py of the reference; pymesh.VoxelGrid restated, *
+ * parity with PyMesh itself unpinned).  Bit grids: an n^3 grid is n*n rows *
+ * of ceil(n/32) uint32 words, cell (x, y, z) = bit (x & 31) of word        *
+ * (z*n + y)*ceil(n/32) + (x >> 5), row padding bits 0;                     *
+ * disn_voxel_grid_words(n) words (0 unless 1 <= n <= 1024).                *
+ *   disn_voxel_surface  key-grid bits of the voxels a triangle soup        *
+ *       overlaps: h = 2.0f/dim, voxel k = the closed box of centre k*h and *
+ *       half side h/2, keys kmin .. kmin+nkeys-1 per axis, x = kx - kmin;  *
+ *       13-axis separating-axis test in fp32 (touching counts, degenerate  *
+ *       triangles are tested on the axes that remain).  `bits` is cleared  *
+ *       first.  flags[0] is OR-ed (never cleared) with 1 when a triangle   *
+ *       reaches outside the key range or is not finite and 2 when a face   *
+ *       index is outside [0, nv); such triangles set no bits.  nf = 0 is   *
+ *       an empty grid.  No host synchronisation.                           *
+ *   disn_voxel_fill  solid = surface + every cell the six faces of the     *
+ *       grid cannot reach through unoccupied cells by 6-connectivity.      *
+ *       Syncs the stream once per 8 sweeps; DISN_E_CONVERGE after 4096.    *
+ *   disn_voxel_index_grid  every occupied key sets, in a cleared dim^3     *
+ *       grid, the cells (lut[x + a], lut[y + b], lut[z + c]), a, b, c in   *
+ *       {0, 1}: lut [nkeys + 1] int32 (device) maps corner numbers to the  *
+ *       reference's indices; entries outside [0, dim) set nothing.         *
+ *   disn_voxel_iou  inter[v] = popcount(gt & preds[v]), uni[v] =           *
+ *       popcount(gt | preds[v]) for nviews grids of `words` words each,    *
+ *       one launch.                                                        *
+ * Every result is an integer or a bit set and does not depend on the order *
+ * of execution.                                                            *
+ * ---------------------------------------------------------------------- */
+size_t disn_voxel_grid_words(int n);
+size_t disn_voxel_surface_workspace_bytes(int64_t nf);
+int disn_voxel_surface(const float* verts, int64_t nv, const int32_t* faces, int64_t nf, int dim, int kmin, int nkeys,
+                       uint32_t* bits, int32_t* flags, void* ws, size_t ws_bytes, void* stream);
+size_t disn_voxel_fill_workspace_bytes(int n);
+int disn_voxel_fill(const uint32_t* surface, int n, uint32_t* solid, void* ws, size_t ws_bytes, void* stream);
+int disn_voxel_index_grid(const uint32_t* keys, int nkeys, const int32_t* lut, int dim, uint32_t* index_bits,
+                          void* stream);
+int disn_voxel_iou(const uint32_t* gt, const uint32_t* preds, int nviews, int64_t words, int64_t* inter,
+                   int64_t* uni, void* stream);
 
 /* Host utility (no device work): CRC-32C of a HOST buffer, continuing from `crc` (0 to start);
  * the checksum of TensorFlow's table blocks and tensor-bundle entries, used by the
