@@ -183,6 +183,9 @@ SIGNATURES = {
     "disn_mc_workspace_bytes": (Z, [I]),
     "disn_mc_count": (I, [P, I, F, P, P, Z, P]),
     "disn_mc_emit": (I, [P, C.POINTER(C.c_double * 6), I, F, P, P, P, Z, P]),
+    "disn_mc_batch_workspace_bytes": (Z, [I, I]),
+    "disn_mc_count_batch": (I, [P, I, I, F, P, P, Z, P]),
+    "disn_mc_emit_batch": (I, [P, P, I, I, F, P, P, P, Z, P]),
     "disn_write_obj": (I, [C.c_char_p, P, L, P, L]),
     "disn_read_obj_verts": (L, [C.c_char_p, P, L]),
     "disn_read_obj_mesh": (I, [C.c_char_p, P, L, P, L, P]),

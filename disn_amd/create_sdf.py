@@ -10,12 +10,37 @@ writer :292-303.  Differences by design (MI355X-first):
   * chunks stream through ``disn_query_grid`` in the flat (iz,iy,ix) order of the reference;
   * with ``torch.distributed`` initialised the flat index range is sharded contiguously
     across ranks and collected with one all_gather (RCCL over xGMI) -- see parallel.py.
+
+The test-set driver (``python -m disn_amd.create_sdf``, the reference's ``test/create_sdf.py --create_obj``):
+
+    python -m disn_amd.create_sdf --log_dir CKPT --test_lst_dir LSTS --sdf_dir SDF --rendered_dir VIEWS
+                                  [--category all] [--sdf_res 64] [--iso 0.0] [--view_num 24] [--cam_est]
+
+walks ``<test_lst_dir>/<cat_id>_test.lst``, encodes ``--batch_size`` views per call, fills their grids, meshes
+the whole group with one read-back (``isosurface.marching_cubes_batch``) and writes
+``<log_dir>/test_objs/[camest_]<res+1>_<iso>/<cat_id>/<cat_id>_<obj>_<view>.obj`` -- the directory
+``disn_amd.evaluate`` and ``disn_amd.postprocess`` read.  Differences from the reference, on purpose:
+  * groups are consecutive runs of ``--batch_size`` list entries and the LAST, shorter one is kept (the
+    reference runs ``len // batch_size`` batches and loses the tail);
+  * a missing or incomplete checkpoint is an error unless ``--random_init SEED`` is given (the reference
+    prints a line and goes on with the initialiser's weights);
+  * the views of an object are ``sorted(random.Random(seed).sample(range(24), view_num))``, drawn object by
+    object in list order from ONE generator (the reference draws from the unseeded global one, unsorted);
+  * categories come in the order of ``evaluate.CATS_ALL`` (``--category`` also takes several names separated
+    by commas); ``--num_shards`` / ``--shard_id`` split the OBJECTS
+    (never an object's views) after the views were drawn, so shards write what one run writes;
+  * an empty mesh is written (and logged), not skipped; a writer thread's exception fails the run;
+  * ``--skip_existing`` drops entries whose file exists with more than 200 bytes (the size filter of
+    ``evaluate.build_file_dict(min_size=200)``) before the groups are formed.
 """
 from __future__ import annotations
 
 import math
+import os
+import random
 import struct
-from typing import Optional, Sequence, Tuple
+import sys
+from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -97,3 +122,214 @@ def create_sdf(engine, imgs, trans_mats, sdf_params, sdf_res: int, sdf_weight: f
     for b in range(B):
         dense_grid_sdf(engine, enc, b, trans_mats, sp[b], sdf_res, sdf_weight, out=result[b])
     return result
+
+
+def reconstruct(engine, imgs, trans_mats, sdf_params, sdf_res: int, iso: float = 0.0):
+    """images -> meshes for one group of views: one ``engine.encode`` call, the per-image grids of
+    ``create_sdf`` in one [B,(res+1)^3] tensor, ONE batched meshing (one host sync for the group).
+    -> B x (verts [nv,3] float32, faces [nf,3] int32) device views; the bits are those of ``create_sdf``
+    followed by ``isosurface.marching_cubes`` image by image."""
+    from . import isosurface
+    grids = create_sdf(engine, imgs, trans_mats, sdf_params, sdf_res)
+    sp = np.asarray(sdf_params, dtype=np.float64).reshape(grids.shape[0], 6)
+    return isosurface.marching_cubes_batch(grids, sp, sdf_res, iso)
+
+
+# ---- the test-set driver ---------------------------------------------------------------------------
+MIN_OBJ_BYTES = 200          # evaluate.build_file_dict(min_size=200) / test_iou.py:124
+MAX_WRITERS = 16
+
+
+def sample_list(cats: Dict[str, str], test_lst_dir: str, view_num: int = 24, seed: int = 0,
+                num_shards: int = 1, shard_id: int = 0, all_views: int = 24) -> List[Tuple[str, str, int]]:
+    """(cat_id, obj, view) of the run: categories in the order of ``evaluate.CATS_ALL``, objects in list-file
+    order, ``sorted(sample(range(24), view_num))`` per object from one ``random.Random(seed)``; then the shard's
+    objects ``objects[shard_id::num_shards]`` with all their views"""
+    from .evaluate import CATS_ALL, read_list
+    if not 1 <= view_num <= all_views:
+        raise ValueError("--view_num must be in 1..%d, got %d" % (all_views, view_num))
+    if num_shards < 1 or not 0 <= shard_id < num_shards:
+        raise ValueError("--shard_id must be in 0..num_shards-1, got %d of %d" % (shard_id, num_shards))
+    rng = random.Random(seed)
+    objects = []
+    for cat_nm in CATS_ALL:
+        if cat_nm not in cats:
+            continue
+        cat_id = cats[cat_nm]
+        for obj in read_list(os.path.join(test_lst_dir, cat_id + "_test.lst")):
+            objects.append((cat_id, obj.strip(), sorted(rng.sample(range(all_views), view_num))))
+    return [(cat_id, obj, v) for cat_id, obj, views in objects[shard_id::num_shards] for v in views]
+
+
+def groups(entries: Sequence, batch_size: int) -> List[List]:
+    """consecutive runs of ``batch_size`` entries; the last one is shorter, nothing is dropped"""
+    if batch_size < 1:
+        raise ValueError("--batch_size must be positive")
+    return [list(entries[i:i + batch_size]) for i in range(0, len(entries), batch_size)]
+
+
+def result_obj_path(log_dir: str, sdf_res: int, iso: float, cam_est: bool = False) -> str:
+    """test/create_sdf.py:88-93: <log_dir>/test_objs/[camest_]<res+1>_<str(iso)>"""
+    return os.path.join(log_dir, "test_objs", ("camest_" if cam_est else "") + str(sdf_res + 1) + "_" + str(iso))
+
+
+def obj_path(out_dir: str, cat_id: str, obj: str, view: int) -> str:
+    return os.path.join(out_dir, cat_id, "%s_%s_%02d.obj" % (cat_id, obj, view))
+
+
+def pending(entries: Sequence, out_dir: str) -> List:
+    """--skip_existing: the entries whose file is missing or holds at most MIN_OBJ_BYTES bytes"""
+    def done(e):
+        p = obj_path(out_dir, *e)
+        return os.path.isfile(p) and os.stat(p).st_size > MIN_OBJ_BYTES
+    return [e for e in entries if not done(e)]
+
+
+def parser():
+    import argparse
+    p = argparse.ArgumentParser(prog="python -m disn_amd.create_sdf",
+                                description="meshes of the test set (test/create_sdf.py --create_obj)")
+    p.add_argument("--log_dir", default="checkpoint/exp_200", help="checkpoint directory; results go below it")
+    p.add_argument("--test_lst_dir", required=True, help="object lists (<cat_id>_test.lst)")
+    p.add_argument("--category", default="all", help="all, or category names separated by commas [default: all]")
+    p.add_argument("--sdf_res", type=int, default=64, help="cells per axis of the grid [default: 64]")
+    p.add_argument("--iso", type=float, default=0.0, help="iso value [default: 0.0]")
+    p.add_argument("--view_num", type=int, default=24, help="views per object [default: 24]")
+    p.add_argument("--batch_size", type=int, default=None, help="images per encode call [default: view_num]")
+    p.add_argument("--cam_est", action="store_true", help="--rendered_dir holds the estimated cameras "
+                                                          "(what train_cam --create wrote)")
+    p.add_argument("--backcolorwhite", action="store_true")
+    for flag in ("binary", "threedcnn", "img_feat_onestream", "multi_view", "alpha"):
+        p.add_argument("--" + flag, action="store_true", help="not supported")
+    p.add_argument("--img_feat_twostream", action="store_true", help="the one supported mode (implied)")
+    # storage of this implementation (the reference takes them from its info.json)
+    p.add_argument("--sdf_dir", default="")
+    p.add_argument("--rendered_dir", default="")
+    p.add_argument("--seed", type=int, default=0, help="seed of the view choice [default: 0]")
+    p.add_argument("--random_init", type=int, default=None, metavar="SEED",
+                   help="run on freshly initialised weights when log_dir holds no complete checkpoint")
+    p.add_argument("--strict", action="store_true", help="single-image kernel forms for every call size: a view's "
+                                                         "mesh does not depend on the group it was encoded in")
+    p.add_argument("--skip_existing", action="store_true", help="leave out views whose .obj exists (> 200 bytes)")
+    p.add_argument("--writers", type=int, default=4, help="writer threads, at most %d [default: 4]" % MAX_WRITERS)
+    p.add_argument("--num_shards", type=int, default=1)
+    p.add_argument("--shard_id", type=int, default=0)
+    return p
+
+
+def check_flags(a) -> None:
+    from . import model_normalization as model
+    F = model._flags(a)
+    F.img_feat_twostream = True
+    model._check_supported(F)
+    if not 1 <= a.writers <= MAX_WRITERS:
+        raise ValueError("--writers must be in 1..%d, got %d" % (MAX_WRITERS, a.writers))
+    if a.sdf_res < 1:
+        raise ValueError("--sdf_res must be positive")
+
+
+def restore_weights(log_dir: str, random_init: Optional[int]):
+    """``WeightStore.restore_latest``; absent or incomplete -> error, or ``--random_init SEED``'s weights"""
+    from .weights import WeightStore
+    store = WeightStore.restore_latest(log_dir) if os.path.isdir(log_dir) else None
+    if store is not None and store.complete():
+        return store, "restored from %s" % log_dir
+    what = "no checkpoint" if store is None else "an incomplete checkpoint (%d of %d variables)" % (
+        len(store.arrays), len(store.shapes))
+    if random_init is None:
+        raise FileNotFoundError("%s holds %s; give --random_init SEED to run on initialised weights" % (log_dir, what))
+    return WeightStore.random_init(random_init), "%s holds %s: random init, seed %d" % (log_dir, what, random_init)
+
+
+def load_group(group: Sequence, sdf_dir: str, rendered_dir: str, backcolorwhite: bool = False,
+               num_sample_points: int = 1, rot: bool = False, seed: Optional[int] = None) -> dict:
+    """the loader's batch dictionary (data_sdf.Pt_sdf_img, shuffle=False) for one group of list entries"""
+    from types import SimpleNamespace
+
+    from .data_sdf import Pt_sdf_img
+    F = SimpleNamespace(num_points=1, num_sample_points=num_sample_points, batch_size=len(group), img_h=137,
+                        img_w=137, backcolorwhite=backcolorwhite, rot=rot, max_epoch=1)
+    data = Pt_sdf_img(F, listinfo=list(group), info={"sdf_dir": sdf_dir, "rendered_dir": rendered_dir},
+                      shuffle=False, seed=seed)
+    return data.get_batch(0)
+
+
+def main(argv=None, reconstruct_fn: Optional[Callable] = None) -> dict:
+    """-> {"written", "skipped", "empty", "out_dir"}.  ``reconstruct_fn(imgs, trans_mats, sdf_params)`` replaces
+    the device work (engine + ``reconstruct``) -- for host-side tests of the driver."""
+    from concurrent.futures import ThreadPoolExecutor
+    from datetime import datetime
+
+    from . import isosurface
+    from .evaluate import categories
+    a = parser().parse_args(argv)
+    check_flags(a)
+    batch_size = a.view_num if a.batch_size is None else a.batch_size
+    out_dir = result_obj_path(a.log_dir, a.sdf_res, a.iso, a.cam_est)
+    entries = sample_list(categories(a.category), a.test_lst_dir, a.view_num, a.seed, a.num_shards, a.shard_id)
+    todo = pending(entries, out_dir) if a.skip_existing else entries
+    work = groups(todo, batch_size)
+    note = "device work replaced by the caller"
+    if reconstruct_fn is None and work:
+        store, note = restore_weights(a.log_dir, a.random_init)       # before any device work
+        import torch
+
+        from .engine import SdfEngine
+        engine = SdfEngine(store, torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available()
+                           else None, strict=a.strict)
+
+        def reconstruct_fn(imgs, trans_mats, sdf_params):
+            return reconstruct(engine, imgs, trans_mats, sdf_params, a.sdf_res, a.iso)
+
+    os.makedirs(out_dir, exist_ok=True)
+    logf = open(os.path.join(a.log_dir, "log_test.txt"), "a")
+
+    def log_string(s):
+        logf.write(s + "\n")
+        logf.flush()
+        print(s)
+
+    def write(path, verts, faces):
+        isosurface.write_obj(path, verts, faces)           # device-to-host copy + file, on a writer thread
+        return path
+
+    written = empty = 0
+    try:
+        log_string(str(a))
+        log_string("%s; %d views listed, %d to do in %d groups -> %s  (%s)"
+                   % (note, len(entries), len(todo), len(work), out_dir, datetime.now()))
+        with ThreadPoolExecutor(max_workers=a.writers) as writers, ThreadPoolExecutor(max_workers=1) as loader:
+            def fetch(g):
+                return loader.submit(load_group, g, a.sdf_dir, a.rendered_dir, a.backcolorwhite)
+
+            nxt = fetch(work[0]) if work else None
+            in_flight: List = []
+            for gi, group in enumerate(work):
+                batch = nxt.result()
+                nxt = fetch(work[gi + 1]) if gi + 1 < len(work) else None
+                meshes = reconstruct_fn(batch["img"], batch["trans_mat"], batch["sdf_params"])
+                if len(meshes) != len(group):
+                    raise RuntimeError("group %d: %d meshes for %d views" % (gi, len(meshes), len(group)))
+                for f in in_flight:                         # the group before this one: a writer's exception surfaces
+                    f.result()
+                in_flight = []
+                for (cat_id, obj, view), (verts, faces) in zip(group, meshes):
+                    path = obj_path(out_dir, cat_id, obj, view)
+                    if len(verts) == 0 or len(faces) == 0:
+                        empty += 1
+                        log_string("%d/%d, EMPTY mesh (no surface at iso %s): %s" % (gi, len(work), a.iso, path))
+                    else:
+                        log_string("%d/%d, submit create_obj %s, %s, %s" % (gi, len(work), cat_id, obj, view))
+                    in_flight.append(writers.submit(write, path, verts, faces))
+                    written += 1
+            for f in in_flight:
+                f.result()
+        log_string("done: %d written (%d empty), %d skipped  (%s)"
+                   % (written, empty, len(entries) - len(todo), datetime.now()))
+    finally:
+        logf.close()
+    return {"written": written, "skipped": len(entries) - len(todo), "empty": empty, "out_dir": out_dir}
+
+
+if __name__ == "__main__":
+    main()

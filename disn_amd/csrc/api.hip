@@ -1475,6 +1475,40 @@ int disn_mc_emit(const float* sdf, const double* sdf_params_host, int R, float i
   return 0;
 }
 
+// a batch is supported when its 3*B*(R+1)^3 edge slots fit the 32-bit scan
+static bool mc_batch_ok(int B, int R) {
+  if (B < 1 || R < 1 || R > 1290) return false;
+  const unsigned long long n = (unsigned long long)R + 1;
+  return 3ull * (unsigned long long)B * n * n * n < (1ull << 32);
+}
+
+size_t disn_mc_batch_workspace_bytes(int B, int R) { return mc_batch_ok(B, R) ? mc_batch_ws_bytes(B, R) : 0; }
+
+int disn_mc_count_batch(const float* sdf, int B, int R, float iso, uint64_t* counts, void* ws, size_t ws_bytes,
+                        void* stream) {
+  if (!sdf || !counts || !ws || B < 1 || R < 1) return DISN_E_ARG;
+  if (!mc_batch_ok(B, R)) return DISN_E_SHAPE;
+  if (ws_bytes < mc_batch_ws_bytes(B, R)) return DISN_E_WS;
+  DISN_TRY(mc_count_batch_launch(sdf, B, R, iso, reinterpret_cast<unsigned long long*>(counts), ws,
+                                 (hipStream_t)stream));
+  return 0;
+}
+
+int disn_mc_emit_batch(const float* sdf, const double* sdf_params_host, int B, int R, float iso, float* verts,
+                       int32_t* faces, void* ws, size_t ws_bytes, void* stream) {
+  if (!sdf || !verts || !faces || !ws || !sdf_params_host || B < 1 || R < 1) return DISN_E_ARG;
+  if (!mc_batch_ok(B, R)) return DISN_E_SHAPE;
+  if (ws_bytes < mc_batch_ws_bytes(B, R)) return DISN_E_WS;
+  GridSpec g[kMcBatchBoxes];  // the boxes travel as kernel arguments, kMcBatchBoxes grids per vertex launch
+  for (int b0 = 0; b0 < B; b0 += kMcBatchBoxes) {
+    const int nb = B - b0 < kMcBatchBoxes ? B - b0 : kMcBatchBoxes;
+    for (int i = 0; i < nb; ++i) grid_spec(sdf_params_host + 6 * (size_t)(b0 + i), R, &g[i]);
+    DISN_TRY(mc_verts_batch_launch(sdf, g, b0, nb, B, R, iso, verts, ws, (hipStream_t)stream));
+  }
+  DISN_TRY(mc_faces_batch_launch(sdf, B, R, iso, faces, ws, (hipStream_t)stream));
+  return 0;
+}
+
 // ---- evaluation metrics (metrics.hip) ----
 size_t disn_metrics_workspace_bytes(int b, int n, int m) {
   return (b < 1 || n < 1 || m < 1) ? 0 : metrics_ws_bytes(b, n, m);

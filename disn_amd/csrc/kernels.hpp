@@ -255,6 +255,16 @@ hipError_t mc_count_launch(const float* vol, int R, float iso, unsigned long lon
                            hipStream_t st);
 hipError_t mc_emit_launch(const float* vol, const GridSpec& g, float iso, float* verts, int* faces,
                           void* ws, hipStream_t st);
+// B grids [B,(R+1)^3] in one set of passes (B*3*(R+1)^3 < 2^32): counts [B,2] per grid; verts / faces of all grids
+// back to back in grid order, face indices local to their grid
+size_t mc_batch_ws_bytes(int B, int R);
+hipError_t mc_count_batch_launch(const float* vol, int B, int R, float iso, unsigned long long* counts, void* ws,
+                                 hipStream_t st);
+constexpr int kMcBatchBoxes = 32;  // grids per vertex launch (their boxes are kernel arguments)
+// vertices of grids b0 .. b0+nb-1 (g[0..nb), nb <= kMcBatchBoxes) / triangles of all B grids
+hipError_t mc_verts_batch_launch(const float* vol, const GridSpec* g, int b0, int nb, int B, int R, float iso,
+                                 float* verts, void* ws, hipStream_t st);
+hipError_t mc_faces_batch_launch(const float* vol, int B, int R, float iso, int* faces, void* ws, hipStream_t st);
 
 // ---- metrics.hip (compiled with -ffp-contract=off): evaluation metrics, one workspace for every entry ----
 size_t metrics_ws_bytes(int b, int n, int m);

@@ -10,7 +10,8 @@
 //   position   = c0 + t*(c1 - c0) on the cut axis, t = (iso - v0)/(v1 - v0), float32
 //   faces      = cells in flat order (iz,iy,ix) over R^3, triangles in table order
 // All kernels are HBM-bound streaming passes over the (R+1)^3 grid; the scans are three-pass
-// (block scan, scan of block sums, add).
+// (block scan, scan of block sums, add).  The per-element bodies are shared by the single-grid kernels and
+// the batched ones (B grids, one scan, one read-back of the sizes: a group of views of the test set).
 #include "kernels.hpp"
 
 #define DISN_MC_QUAL __constant__ const
@@ -108,35 +109,41 @@ static hipError_t exclusive_scan(const unsigned* in, unsigned* out, size_t n, un
 // ---------------------------------------------------------------------------
 // pass 1: cut-edge flags (3 per grid point) and triangle counts (1 per cell)
 // ---------------------------------------------------------------------------
+// one grid point p of an n^3 grid: its three edge flags and (where it is the low corner of a cell) the cell's count;
+// vol, eflag and ccount are the grid's OWN blocks, so no neighbour (+1, +n, +n^2) leaves the grid
+__device__ __forceinline__ void mc_flags_point(const float* __restrict__ vol, int n, float iso, size_t p,
+                                               unsigned* __restrict__ eflag, unsigned* __restrict__ ccount) {
+  const int R = n - 1;
+  const int ix = (int)(p % n), iy = (int)((p / n) % n), iz = (int)(p / ((size_t)n * n));
+  const bool in0 = vol[p] < iso;
+  const bool hx = ix < R, hy = iy < R, hz = iz < R;
+  const bool inx = hx ? vol[p + 1] < iso : in0;
+  const bool iny = hy ? vol[p + n] < iso : in0;
+  const bool inz = hz ? vol[p + (size_t)n * n] < iso : in0;
+  eflag[3 * p + 0] = (hx && inx != in0) ? 1u : 0u;
+  eflag[3 * p + 1] = (hy && iny != in0) ? 1u : 0u;
+  eflag[3 * p + 2] = (hz && inz != in0) ? 1u : 0u;
+  if (hx && hy && hz) {
+    const size_t nn = (size_t)n * n;
+    unsigned mask = in0 ? 1u : 0u;
+    mask |= inx ? 2u : 0u;
+    mask |= (vol[p + 1 + n] < iso) ? 4u : 0u;
+    mask |= iny ? 8u : 0u;
+    mask |= inz ? 16u : 0u;
+    mask |= (vol[p + nn + 1] < iso) ? 32u : 0u;
+    mask |= (vol[p + nn + 1 + n] < iso) ? 64u : 0u;
+    mask |= (vol[p + nn + n] < iso) ? 128u : 0u;
+    ccount[((size_t)iz * R + iy) * R + ix] = kMcNtri[mask];
+  }
+}
+
 __global__ __launch_bounds__(256) void mc_flags_kernel(const float* __restrict__ vol, int n,
                                                        float iso, unsigned* __restrict__ eflag,
                                                        unsigned* __restrict__ ccount) {
   const size_t total = (size_t)n * n * n;
-  const int R = n - 1;
   for (size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x; p < total;
-       p += (size_t)gridDim.x * blockDim.x) {
-    const int ix = (int)(p % n), iy = (int)((p / n) % n), iz = (int)(p / ((size_t)n * n));
-    const bool in0 = vol[p] < iso;
-    const bool hx = ix < R, hy = iy < R, hz = iz < R;
-    const bool inx = hx ? vol[p + 1] < iso : in0;
-    const bool iny = hy ? vol[p + n] < iso : in0;
-    const bool inz = hz ? vol[p + (size_t)n * n] < iso : in0;
-    eflag[3 * p + 0] = (hx && inx != in0) ? 1u : 0u;
-    eflag[3 * p + 1] = (hy && iny != in0) ? 1u : 0u;
-    eflag[3 * p + 2] = (hz && inz != in0) ? 1u : 0u;
-    if (hx && hy && hz) {
-      const size_t nn = (size_t)n * n;
-      unsigned mask = in0 ? 1u : 0u;
-      mask |= inx ? 2u : 0u;
-      mask |= (vol[p + 1 + n] < iso) ? 4u : 0u;
-      mask |= iny ? 8u : 0u;
-      mask |= inz ? 16u : 0u;
-      mask |= (vol[p + nn + 1] < iso) ? 32u : 0u;
-      mask |= (vol[p + nn + 1 + n] < iso) ? 64u : 0u;
-      mask |= (vol[p + nn + n] < iso) ? 128u : 0u;
-      ccount[((size_t)iz * R + iy) * R + ix] = kMcNtri[mask];
-    }
-  }
+       p += (size_t)gridDim.x * blockDim.x)
+    mc_flags_point(vol, n, iso, p, eflag, ccount);
 }
 
 __device__ __forceinline__ float grid_coord(const GridSpec& g, int a, int i) {
@@ -146,7 +153,25 @@ __device__ __forceinline__ float grid_coord(const GridSpec& g, int a, int i) {
   return (float)v;
 }
 
-// pass 2: one vertex per cut edge
+// pass 2: one vertex per cut edge.  e: edge slot of this grid (3*p + axis), o: where its vertex goes
+__device__ __forceinline__ void mc_edge_vertex(const float* __restrict__ vol, const GridSpec& g, float iso,
+                                               size_t e, float* __restrict__ o) {
+  const int n = g.res;
+  const size_t p = e / 3;
+  const int a = (int)(e - 3 * p);
+  const int idx[3] = {(int)(p % n), (int)((p / n) % n), (int)(p / ((size_t)n * n))};
+  const size_t step = a == 0 ? 1 : (a == 1 ? (size_t)n : (size_t)n * n);
+  const float v0 = vol[p], v1 = vol[p + step];
+  const float t = (iso - v0) / (v1 - v0);
+  float pos[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) pos[k] = grid_coord(g, k, idx[k]);
+  const float c0 = pos[a], c1 = grid_coord(g, a, idx[a] + 1);
+  const float d = t * (c1 - c0);
+  pos[a] = c0 + d;
+  o[0] = pos[0]; o[1] = pos[1]; o[2] = pos[2];
+}
+
 __global__ __launch_bounds__(256) void mc_verts_kernel(const float* __restrict__ vol, GridSpec g,
                                                        float iso, const unsigned* __restrict__ eflag,
                                                        const unsigned* __restrict__ eidx,
@@ -156,50 +181,119 @@ __global__ __launch_bounds__(256) void mc_verts_kernel(const float* __restrict__
   for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total;
        e += (size_t)gridDim.x * blockDim.x) {
     if (!eflag[e]) continue;
-    const size_t p = e / 3;
-    const int a = (int)(e - 3 * p);
-    const int idx[3] = {(int)(p % n), (int)((p / n) % n), (int)(p / ((size_t)n * n))};
-    const size_t step = a == 0 ? 1 : (a == 1 ? (size_t)n : (size_t)n * n);
-    const float v0 = vol[p], v1 = vol[p + step];
-    const float t = (iso - v0) / (v1 - v0);
-    float pos[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) pos[k] = grid_coord(g, k, idx[k]);
-    const float c0 = pos[a], c1 = grid_coord(g, a, idx[a] + 1);
-    const float d = t * (c1 - c0);
-    pos[a] = c0 + d;
-    float* o = verts + (size_t)eidx[e] * 3;
-    o[0] = pos[0]; o[1] = pos[1]; o[2] = pos[2];
+    mc_edge_vertex(vol, g, iso, e, verts + (size_t)eidx[e] * 3);
   }
 }
 
-// pass 3: index triples
+// pass 3: index triples.  c: cell of this grid, coff/eidx: the grid's own blocks of the two scans; vbase is taken off
+// every vertex id (0 for a grid scanned alone, the grid's first vertex rank in a batch scan)
+__device__ __forceinline__ void mc_cell_faces(const float* __restrict__ vol, int n, float iso, size_t c,
+                                              const unsigned* __restrict__ coff,
+                                              const unsigned* __restrict__ eidx, unsigned vbase,
+                                              int* __restrict__ faces) {
+  const int R = n - 1;
+  const size_t nn = (size_t)n * n;
+  const int ix = (int)(c % R), iy = (int)((c / R) % R), iz = (int)(c / ((size_t)R * R));
+  const size_t p = ((size_t)iz * n + iy) * n + ix;
+  unsigned mask = (vol[p] < iso) ? 1u : 0u;
+  mask |= (vol[p + 1] < iso) ? 2u : 0u;
+  mask |= (vol[p + 1 + n] < iso) ? 4u : 0u;
+  mask |= (vol[p + n] < iso) ? 8u : 0u;
+  mask |= (vol[p + nn] < iso) ? 16u : 0u;
+  mask |= (vol[p + nn + 1] < iso) ? 32u : 0u;
+  mask |= (vol[p + nn + 1 + n] < iso) ? 64u : 0u;
+  mask |= (vol[p + nn + n] < iso) ? 128u : 0u;
+  const int nt = kMcNtri[mask];
+  if (!nt) return;
+  int* o = faces + (size_t)coff[c] * 3;
+  for (int k = 0; k < 3 * nt; ++k) {
+    const int e = kMcTri[mask][k];
+    const size_t gp = ((size_t)(iz + kMcEdge[e][2]) * n + (iy + kMcEdge[e][1])) * n + (ix + kMcEdge[e][0]);
+    o[k] = (int)(eidx[3 * gp + kMcEdge[e][3]] - vbase);
+  }
+}
+
 __global__ __launch_bounds__(256) void mc_faces_kernel(const float* __restrict__ vol, int n,
                                                        float iso, const unsigned* __restrict__ coff,
                                                        const unsigned* __restrict__ eidx,
                                                        int* __restrict__ faces) {
   const int R = n - 1;
-  const size_t cells = (size_t)R * R * R, nn = (size_t)n * n;
+  const size_t cells = (size_t)R * R * R;
   for (size_t c = (size_t)blockIdx.x * blockDim.x + threadIdx.x; c < cells;
-       c += (size_t)gridDim.x * blockDim.x) {
-    const int ix = (int)(c % R), iy = (int)((c / R) % R), iz = (int)(c / ((size_t)R * R));
-    const size_t p = ((size_t)iz * n + iy) * n + ix;
-    unsigned mask = (vol[p] < iso) ? 1u : 0u;
-    mask |= (vol[p + 1] < iso) ? 2u : 0u;
-    mask |= (vol[p + 1 + n] < iso) ? 4u : 0u;
-    mask |= (vol[p + n] < iso) ? 8u : 0u;
-    mask |= (vol[p + nn] < iso) ? 16u : 0u;
-    mask |= (vol[p + nn + 1] < iso) ? 32u : 0u;
-    mask |= (vol[p + nn + 1 + n] < iso) ? 64u : 0u;
-    mask |= (vol[p + nn + n] < iso) ? 128u : 0u;
-    const int nt = kMcNtri[mask];
-    if (!nt) continue;
-    int* o = faces + (size_t)coff[c] * 3;
-    for (int k = 0; k < 3 * nt; ++k) {
-      const int e = kMcTri[mask][k];
-      const size_t gp = ((size_t)(iz + kMcEdge[e][2]) * n + (iy + kMcEdge[e][1])) * n + (ix + kMcEdge[e][0]);
-      o[k] = (int)eidx[3 * gp + kMcEdge[e][3]];
+       c += (size_t)gridDim.x * blockDim.x)
+    mc_cell_faces(vol, n, iso, c, coff, eidx, 0u, faces);
+}
+
+// ---------------------------------------------------------------------------
+// B grids of one resolution in one set of passes: the flags and counts of grid b lie at b*3*n^3 and b*R^3 of the
+// concatenated arrays, ONE scan runs over each, and a grid's first scan value is its vertex / triangle base.  Every
+// grid is addressed through its own block of vol (the element bodies above see one grid and nothing else), so the
+// order and the arithmetic per grid are those of the single-grid kernels.  All flat counts are below 2^32 (the API
+// refuses larger batches), so the split of a flat index into (grid, element) is 32-bit.
+// ---------------------------------------------------------------------------
+struct McBox { double start[3], step[3], stop[3]; };
+struct McBoxes { McBox b[kMcBatchBoxes]; };   // 32 * 72 B of kernel arguments
+
+__global__ __launch_bounds__(256) void mc_flags_batch_kernel(const float* __restrict__ vol, int n, unsigned np,
+                                                             unsigned total, float iso,
+                                                             unsigned* __restrict__ eflag,
+                                                             unsigned* __restrict__ ccount) {
+  const unsigned R = (unsigned)n - 1, nc = R * R * R;
+  for (size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x; q < total; q += (size_t)gridDim.x * blockDim.x) {
+    const unsigned b = (unsigned)q / np, p = (unsigned)q - b * np;
+    mc_flags_point(vol + (size_t)b * np, n, iso, p, eflag + (size_t)3 * b * np, ccount + (size_t)b * nc);
+  }
+}
+
+// counts[b] = {vertices, triangles} of grid b: the difference of consecutive bases, the grand totals closing the last
+__global__ void mc_batch_counts_kernel(const unsigned* __restrict__ eidx, const unsigned* __restrict__ coff,
+                                       size_t ne, size_t nc, int B,
+                                       const unsigned long long* __restrict__ totals,
+                                       unsigned long long* __restrict__ counts) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  const unsigned long long v0 = eidx[(size_t)b * ne], f0 = coff[(size_t)b * nc];
+  const unsigned long long v1 = b + 1 < B ? eidx[(size_t)(b + 1) * ne] : totals[0];
+  const unsigned long long f1 = b + 1 < B ? coff[(size_t)(b + 1) * nc] : totals[1];
+  counts[2 * b + 0] = v1 - v0;
+  counts[2 * b + 1] = f1 - f0;
+}
+
+// grids b0 .. b0+nb-1 (boxes.b[0..nb)); the vertex goes to its GLOBAL rank
+__global__ __launch_bounds__(256) void mc_verts_batch_kernel(const float* __restrict__ vol, McBoxes boxes, int n,
+                                                             unsigned ne, unsigned b0, unsigned nb, float iso,
+                                                             const unsigned* __restrict__ eflag,
+                                                             const unsigned* __restrict__ eidx,
+                                                             float* __restrict__ verts) {
+  const size_t first = (size_t)b0 * ne, total = (size_t)nb * ne;
+  const unsigned np = ne / 3;
+  for (size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x; q < total; q += (size_t)gridDim.x * blockDim.x) {
+    if (!eflag[first + q]) continue;
+    const unsigned lb = (unsigned)q / ne, e = (unsigned)q - lb * ne;
+    GridSpec g;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      g.start[a] = boxes.b[lb].start[a];
+      g.step[a] = boxes.b[lb].step[a];
+      g.stop[a] = boxes.b[lb].stop[a];
     }
+    g.res = n;
+    mc_edge_vertex(vol + (size_t)(b0 + lb) * np, g, iso, e, verts + (size_t)eidx[first + q] * 3);
+  }
+}
+
+// the triangle goes to its GLOBAL rank; its vertex ids are LOCAL to the grid (the grid's vertex base taken off)
+__global__ __launch_bounds__(256) void mc_faces_batch_kernel(const float* __restrict__ vol, int n, unsigned np,
+                                                             unsigned total, float iso,
+                                                             const unsigned* __restrict__ coff,
+                                                             const unsigned* __restrict__ eidx,
+                                                             int* __restrict__ faces) {
+  const unsigned R = (unsigned)n - 1, nc = R * R * R;
+  for (size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x; q < total; q += (size_t)gridDim.x * blockDim.x) {
+    const unsigned b = (unsigned)q / nc, c = (unsigned)q - b * nc;
+    const unsigned* ei = eidx + (size_t)3 * b * np;
+    // (coff is indexed at the flat cell, so its values are global ranks; faces is the whole batch's array)
+    mc_cell_faces(vol + (size_t)b * np, n, iso, c, coff + (size_t)b * nc, ei, ei[0], faces);
   }
 }
 
@@ -233,6 +327,35 @@ static McWs mc_layout(void* ws, int R) {
 
 size_t mc_ws_bytes(int R) { return mc_layout(nullptr, R).total; }
 
+struct McBatchWs {
+  unsigned *eflag, *eidx, *ccount, *coff, *bsum;
+  unsigned long long* totals;  // {vertices, triangles} of the whole batch
+  size_t total;
+};
+
+static McBatchWs mc_batch_layout(void* ws, int B, int R) {
+  const size_t n = (size_t)R + 1, ne = (size_t)B * 3 * n * n * n, nc = (size_t)B * R * R * R;
+  char* base = static_cast<char*>(ws);
+  size_t off = 0;
+  auto take = [&](size_t bytes) {
+    off = (off + 255) & ~size_t(255);
+    unsigned* p = base ? reinterpret_cast<unsigned*>(base + off) : nullptr;
+    off += bytes;
+    return p;
+  };
+  McBatchWs w;
+  w.eflag = take(ne * 4);
+  w.eidx = take(ne * 4);
+  w.ccount = take(nc * 4);
+  w.coff = take(nc * 4);
+  w.bsum = take(((ne + kScanBlock - 1) / kScanBlock + 1) * 4);
+  w.totals = reinterpret_cast<unsigned long long*>(take(2 * sizeof(unsigned long long)));
+  w.total = (off + 255) & ~size_t(255);
+  return w;
+}
+
+size_t mc_batch_ws_bytes(int B, int R) { return mc_batch_layout(nullptr, B, R).total; }
+
 static inline int blocks_for(size_t total) {
   size_t b = (total + 255) / 256;
   if (b > 16384) b = 16384;
@@ -261,6 +384,49 @@ hipError_t mc_emit_launch(const float* vol, const GridSpec& g, float iso, float*
                      w.eflag, w.eidx, verts);
   hipLaunchKernelGGL(mc_faces_kernel, dim3(blocks_for(nc)), dim3(256), 0, st, vol, g.res, iso, w.coff,
                      w.eidx, faces);
+  return hipGetLastError();
+}
+
+// B*3*(R+1)^3 < 2^32 is the caller's to check (api.hip)
+hipError_t mc_count_batch_launch(const float* vol, int B, int R, float iso, unsigned long long* counts, void* ws,
+                                 hipStream_t st) {
+  const McBatchWs w = mc_batch_layout(ws, B, R);
+  const int n = R + 1;
+  const size_t np = (size_t)n * n * n, nc = (size_t)R * R * R;
+  hipLaunchKernelGGL(mc_flags_batch_kernel, dim3(blocks_for(B * np)), dim3(256), 0, st, vol, n, (unsigned)np,
+                     (unsigned)(B * np), iso, w.eflag, w.ccount);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  if ((e = exclusive_scan(w.eflag, w.eidx, B * 3 * np, w.bsum, w.totals, st)) != hipSuccess) return e;
+  if ((e = exclusive_scan(w.ccount, w.coff, B * nc, w.bsum, w.totals + 1, st)) != hipSuccess) return e;
+  hipLaunchKernelGGL(mc_batch_counts_kernel, dim3((B + 255) / 256), dim3(256), 0, st, w.eidx, w.coff, 3 * np, nc, B,
+                     w.totals, counts);
+  return hipGetLastError();
+}
+
+hipError_t mc_verts_batch_launch(const float* vol, const GridSpec* g, int b0, int nb, int B, int R, float iso,
+                                 float* verts, void* ws, hipStream_t st) {
+  const McBatchWs w = mc_batch_layout(ws, B, R);
+  const int n = R + 1;
+  const size_t np = (size_t)n * n * n;
+  McBoxes boxes = {};
+  for (int i = 0; i < nb; ++i)
+    for (int a = 0; a < 3; ++a) {
+      boxes.b[i].start[a] = g[i].start[a];
+      boxes.b[i].step[a] = g[i].step[a];
+      boxes.b[i].stop[a] = g[i].stop[a];
+    }
+  hipLaunchKernelGGL(mc_verts_batch_kernel, dim3(blocks_for(3 * np * nb)), dim3(256), 0, st, vol, boxes, n,
+                     (unsigned)(3 * np), (unsigned)b0, (unsigned)nb, iso, w.eflag, w.eidx, verts);
+  return hipGetLastError();
+}
+
+hipError_t mc_faces_batch_launch(const float* vol, int B, int R, float iso, int* faces, void* ws, hipStream_t st) {
+  const McBatchWs w = mc_batch_layout(ws, B, R);
+  const int n = R + 1;
+  const size_t np = (size_t)n * n * n, nc = (size_t)R * R * R;
+  hipLaunchKernelGGL(mc_faces_batch_kernel, dim3(blocks_for(B * nc)), dim3(256), 0, st, vol, n, (unsigned)np,
+                     (unsigned)(B * nc), iso, w.coff, w.eidx, faces);
   return hipGetLastError();
 }
 

@@ -1,0 +1,111 @@
+"""One image to one mesh: the reference's ``demo/demo.py [--cam_est]`` on the HIP engine.
+
+    python -m disn_amd.demo --img VIEW.png --log_dir CKPT [--cam_est --cam_log_dir CAM_CKPT]
+                            [--sdf_res 64] [--iso 0.0] [--out demo/result.obj]
+
+The image is read as demo/demo.py:261-279 reads it (``cv2.imread(IMREAD_UNCHANGED)[:, :, :3] / 255``: the
+channels in B, G, R order, alpha dropped) -- through PIL, which is what this project has.  Without ``--cam_est``
+the camera is the ground-truth matrix the reference hard-codes for its demo image (:272-276); with it the
+matrix is ``pred_trans_mat`` of ``posenet.CameraEstimator``, restored from ``--cam_log_dir``.  The box is
+[-1,-1,-1,1,1,1] (:278), and the mesh comes from ONE ``create_sdf.reconstruct`` call.  As everywhere in this
+project a missing checkpoint is an error unless ``--random_init SEED`` asks for initialised weights (the
+reference goes on silently).
+"""
+from __future__ import annotations
+
+import argparse
+import os
+from typing import Optional
+
+import numpy as np
+
+DEMO_TRANS_MAT = np.asarray(           # demo/demo.py:272-276
+    [[[-68.453156, 5.5086656, -0.37556022],
+      [-17.138561, -84.685486, -0.250198],
+      [-47.284092, -3.6569588, 0.2493176],
+      [101.133705, 101.34268, 1.4305686]]], dtype=np.float32)
+DEMO_SDF_PARAMS = np.array([[-1, -1, -1, 1, 1, 1]], np.float64)     # demo/demo.py:278
+
+
+def read_image(path: str) -> np.ndarray:
+    """-> [1,H,W,3] float32 in [0,1], channels B,G,R (what cv2 gives the reference), alpha dropped"""
+    from PIL import Image
+    rgba = np.asarray(Image.open(path).convert("RGBA"), dtype=np.uint8)
+    return (rgba[:, :, [2, 1, 0]].astype(np.float32) / np.float32(255.0))[None]
+
+
+def restore_camera(cam_log_dir: str, random_init: Optional[int]):
+    """(encoder store, head arrays) of the camera network from the latest checkpoint of ``cam_log_dir`` (what
+    ``train_cam`` saves: 32 vgg_16/* and 18 cameraprediction/* variables).  The engine uploads a whole SDF-network
+    store; the point-MLP variables, which the camera network does not have and its encoder call never reads, are
+    ``WeightStore.random_init(0)``'s."""
+    from . import posenet, tf_checkpoint as tfc, train_cam
+    from .weights import WeightStore
+    prefix = tfc.get_checkpoint_state(cam_log_dir) if cam_log_dir and os.path.isdir(cam_log_dir) else None
+    arrays = None
+    if prefix is not None:
+        shapes = train_cam.variable_shapes()
+        have = tfc.list_variables(prefix)
+        if all(n in have for n in shapes):
+            arrays = tfc.load_checkpoint(prefix, list(shapes))
+            if any(tuple(arrays[n].shape) != tuple(shp) for n, shp in shapes.items()):
+                arrays = None
+    if arrays is None:
+        if random_init is None:
+            raise FileNotFoundError("%r holds no complete camera checkpoint; give --random_init SEED to run on "
+                                    "initialised weights" % cam_log_dir)
+        arrays = train_cam.random_init(random_init)
+    store = WeightStore.random_init(0)
+    store.assign({k: v for k, v in arrays.items() if k.startswith("vgg_16/")}, strict=True)
+    return store, {k: np.asarray(arrays[k], np.float32) for k in posenet.variable_shapes()}
+
+
+def estimate_camera(img: np.ndarray, cam_log_dir: str, random_init: Optional[int] = None):
+    """pred_trans_mat [1,4,3] (device tensor) of the camera network for the image"""
+    from .posenet import CameraEstimator
+    store, head = restore_camera(cam_log_dir, random_init)
+    return CameraEstimator(store, head).get_model(img)["pred_trans_mat"]
+
+
+def parser() -> argparse.ArgumentParser:
+    p = argparse.ArgumentParser(prog="python -m disn_amd.demo", description="one image -> one mesh (demo/demo.py)")
+    p.add_argument("--img", required=True, help="137x137 RGBA rendering (.png)")
+    p.add_argument("--log_dir", default="checkpoint/SDF_DISN", help="checkpoint directory of the SDF network")
+    p.add_argument("--cam_est", action="store_true", help="estimate the camera instead of the demo image's own")
+    p.add_argument("--cam_log_dir", default="cam_est/checkpoint/cam_DISN", help="checkpoint of the camera network")
+    p.add_argument("--sdf_res", type=int, default=64, help="cells per axis of the grid [default: 64]")
+    p.add_argument("--iso", type=float, default=0.0, help="iso value [default: 0.0]")
+    p.add_argument("--out", default=os.path.join("demo", "result.obj"), help="the mesh to write")
+    p.add_argument("--random_init", type=int, default=None, metavar="SEED",
+                   help="run on freshly initialised weights where a checkpoint is missing")
+    return p
+
+
+def main(argv=None) -> dict:
+    """-> {"out", "verts", "faces", "trans_mat"}"""
+    a = parser().parse_args(argv)
+    from . import isosurface
+    from .create_sdf import reconstruct, restore_weights
+    img = read_image(a.img)
+    if img.shape[1:3] != (137, 137):
+        raise ValueError("%s is %dx%d; the network reads 137x137 renderings" % (a.img, img.shape[2], img.shape[1]))
+    store, note = restore_weights(a.log_dir, a.random_init)            # before any device work
+    print(note)
+    from .engine import SdfEngine
+    if a.cam_est:
+        print("here we use our cam est network to estimate cam parameters:")
+        trans_mat = estimate_camera(img, a.cam_log_dir, a.random_init)
+        print("pred_trans_mat_val", trans_mat.cpu().numpy())
+    else:
+        print("here we use gt cam parameters")
+        trans_mat = DEMO_TRANS_MAT
+    engine = SdfEngine(store)
+    verts, faces = reconstruct(engine, img, trans_mat, DEMO_SDF_PARAMS, a.sdf_res, a.iso)[0]
+    isosurface.write_obj(a.out, verts, faces)
+    print("wrote %s: %d vertices, %d triangles" % (a.out, len(verts), len(faces)))
+    tm = trans_mat.cpu().numpy() if hasattr(trans_mat, "cpu") else trans_mat
+    return {"out": a.out, "verts": len(verts), "faces": len(faces), "trans_mat": tm}
+
+
+if __name__ == "__main__":
+    main()

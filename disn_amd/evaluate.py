@@ -6,6 +6,7 @@ on ``disn_amd.metrics`` instead of the TF1 + CUDA custom ops, and ``test/test_io
     python -m disn_amd.evaluate cd_emd  --cal_dir OBJS --gt_dir GT --test_lst_dir LSTS [--category all]
     python -m disn_amd.evaluate f_score --cal_dir OBJS --gt_dir GT --test_lst_dir LSTS [--truethreshold 2.5]
     python -m disn_amd.evaluate iou     --cal_dir OBJS --gt_dir GT --test_lst_dir LSTS [--dim 110] [--mode reference]
+    python -m disn_amd.evaluate sdf_acc --log_dir CKPT --test_lst_dir LSTS --sdf_dir SDF --rendered_dir VIEWS
 
 Layout, as the reference reads it:
   predictions  <cal_dir>/<cat_id>/<cat_id>_<obj_id>_<view>.obj    (what ``isosurface.create_obj`` writes)
@@ -25,6 +26,15 @@ union is empty) raises, where the reference's bare ``try`` prints "error mesh" a
 Kept: the ``os.stat(...)[6] > 200`` size filter on prediction files, the float32 array of per-view values with its
 sum / mean / argmax, the category average over views, and the printed lines.  ``--mode solid`` (not in the
 reference, whose grids are surface shells) fills the voxel sets first.
+
+SDF accuracy (``sdf_acc``, the reference's ``test/test_sdf_acc.py``): the five scalars of ``get_loss`` on sampled
+query points of the test views -- all 24 views of every listed object, ``sdf = sdf_val - 0.003``, one
+``engine.encode_query`` + ``ops.get_loss`` per batch, the reference's per-batch lines and its ``Summary:`` (the mean
+of the per-batch values).  Differences: batches are consecutive runs of ``--batch_size`` list entries in list
+order, the last, shorter one included (the reference shuffles and drops the tail); the points of a batch are
+drawn from ``numpy.random.default_rng(seed + batch index)``; a missing checkpoint is an error unless
+``--random_init SEED`` is given; ``--view_num`` below 24 scores a seeded choice of views (the sample list of
+``disn_amd.create_sdf``).
 """
 from __future__ import annotations
 
@@ -46,7 +56,13 @@ CATS_CLEAN = {"cabinet": "02933112", "display": "03211117", "speaker": "03691459
 
 
 def categories(category: str) -> Dict[str, str]:
-    """--category: "all", "clean" or one category name (test_cd_emd.py / test_f_score.py __main__)"""
+    """--category: "all", "clean", one category name (test_cd_emd.py / test_f_score.py __main__), or several
+    names separated by commas"""
+    if "," in category:
+        out: Dict[str, str] = {}
+        for name in category.split(","):
+            out.update(categories(name.strip()))
+        return out
     if category == "all":
         return dict(CATS_ALL)
     if category == "clean":
@@ -257,6 +273,53 @@ def iou_all(cats: Dict[str, str], pred_dir: str, gt_dir: str, test_lst_dir: str,
     return res
 
 
+SDF_ACC_NAMES = ("accuracy", "sdf_loss_realvalue", "sdf_loss", "regularization", "overall_loss")
+SDF_WEIGHT = 10.0            # test/test_sdf_acc.py:61
+
+
+def regularization_of(store, wd: float = 1e-5) -> float:
+    """wd * sum(w^2) / 2 over every '/weights' variable: the scalar the trainer adds to its loss, a function of the
+    weights alone (float64 on the host, once per weight set)"""
+    return float(sum(wd * 0.5 * float(np.sum(np.asarray(store[k], np.float64) ** 2))
+                     for k in store.keys() if k.endswith("/weights")))
+
+
+def sdf_acc(cats: Dict[str, str], log_dir: str, test_lst_dir: str, sdf_dir: str, rendered_dir: str,
+            batch_size: int = 1, num_sample_points: int = 2048, mask_weight: float = 4.0, view_num: int = 24,
+            seed: int = 0, random_init: Optional[int] = None, rot: bool = False, backcolorwhite: bool = False,
+            wd: float = 1e-5, out=None) -> dict:
+    """test/test_sdf_acc.py test_one_epoch -> {"accuracy", "sdf_loss_realvalue", "sdf_loss", "regularization",
+    "overall_loss"} (means of the per-batch values) and "batches" (the per-batch values, [n,5])"""
+    import torch
+
+    from . import create_sdf as cs, ops
+    from .engine import SdfEngine
+    out = out or sys.stdout
+    if batch_size < 1 or batch_size * num_sample_points > 65536:
+        raise ValueError("--batch_size x --num_sample_points must be in 1..65536 (one encode_query call), got %d x %d"
+                         % (batch_size, num_sample_points))
+    work = cs.groups(cs.sample_list(cats, test_lst_dir, view_num, seed), batch_size)
+    store, note = cs.restore_weights(log_dir, random_init)            # before any device work
+    print(note, file=out)
+    engine = SdfEngine(store)
+    reg = regularization_of(store, wd)
+    rows = []
+    for gi, group in enumerate(work):
+        batch = cs.load_group(group, sdf_dir, rendered_dir, backcolorwhite, num_sample_points, rot, seed + gi)
+        gt = torch.from_numpy(np.ascontiguousarray(batch["sdf_val"] - 0.003, np.float32)).to(engine.device)
+        pred = engine.encode_query(batch["img"], batch["sdf_pt"], batch["trans_mat"], batch["sdf_pt_rot"])[1]
+        with torch.cuda.device(engine.device):
+            vals = ops.get_loss(pred, gt, SDF_WEIGHT, mask_weight, reg).cpu().numpy().astype(np.float64)
+        rows.append(vals)
+        print(" -- %03d / %03d -- " % (gi + 1, len(work)) + "".join("%s: %f, " % (n, v)
+                                                                    for n, v in zip(SDF_ACC_NAMES, vals)), file=out)
+    mean = np.mean(np.asarray(rows), axis=0)
+    print("Summary: " + "".join("%s: %f, " % (n, v) for n, v in zip(SDF_ACC_NAMES, mean)), file=out)
+    res = {n: float(v) for n, v in zip(SDF_ACC_NAMES, mean)}
+    res["batches"] = np.asarray(rows)
+    return res
+
+
 def parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(prog="python -m disn_amd.evaluate",
                                 description="Chamfer / EMD / F-score / voxel IoU of reconstructed meshes "
@@ -283,12 +346,31 @@ def parser() -> argparse.ArgumentParser:
     s.add_argument("--mode", default="reference", choices=("reference", "solid"),
                    help="reference: the shell IoU of test_iou.py; solid: filled voxels [default: reference]")
     s.add_argument("--seed", type=int, default=0, help="seed of the view sampling [default: 0]")
+    s = sub.add_parser("sdf_acc", help="accuracy and losses of the predicted SDF on sampled points of the test views")
+    s.add_argument("--log_dir", required=True, help="checkpoint directory of the SDF network")
+    s.add_argument("--test_lst_dir", required=True, help="object lists (<cat_id>_test.lst)")
+    s.add_argument("--sdf_dir", required=True, help="sampled SDF values (<cat_id>/<obj_id>/ori_sample.h5)")
+    s.add_argument("--rendered_dir", required=True, help="rendered views (<cat_id>/<obj_id>/%%02d.h5)")
+    s.add_argument("--category", default="all", help="all, clean or one category name [default: all]")
+    s.add_argument("--batch_size", type=int, default=1, help="views per encode_query call [default: 1]")
+    s.add_argument("--num_sample_points", type=int, default=2048, help="points per view [default: 2048]")
+    s.add_argument("--mask_weight", type=float, default=4.0)
+    s.add_argument("--view_num", type=int, default=24, help="views per object [default: 24, all]")
+    s.add_argument("--rot", action="store_true")
+    s.add_argument("--backcolorwhite", action="store_true")
+    s.add_argument("--seed", type=int, default=0, help="seed of the view and point sampling [default: 0]")
+    s.add_argument("--random_init", type=int, default=None, metavar="SEED",
+                   help="run on freshly initialised weights when log_dir holds no complete checkpoint")
     return p
 
 
 def main(argv=None) -> dict:
     a = parser().parse_args(argv)
     cats = categories(a.category)
+    if a.command == "sdf_acc":
+        return sdf_acc(cats, a.log_dir, a.test_lst_dir, a.sdf_dir, a.rendered_dir, batch_size=a.batch_size,
+                       num_sample_points=a.num_sample_points, mask_weight=a.mask_weight, view_num=a.view_num,
+                       seed=a.seed, random_init=a.random_init, rot=a.rot, backcolorwhite=a.backcolorwhite)
     if a.command == "iou":
         return iou_all(cats, a.cal_dir, a.gt_dir, a.test_lst_dir, dim=a.dim, mode=a.mode, view_num=a.view_num,
                        seed=a.seed)

@@ -13,7 +13,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-from typing import Optional, Tuple
+from typing import List, Optional, Tuple
 
 import numpy as np
 import torch
@@ -50,6 +50,56 @@ def marching_cubes(sdf: torch.Tensor, sdf_params, res: int, iso: float = 0.0,
                                                      verts.data_ptr(), faces.data_ptr(), ws.data_ptr(),
                                                      ws.numel(), st))
     return verts, faces
+
+
+MC_EDGE_SLOTS = 1 << 32      # a batch's 3*B*(res+1)^3 edge slots must stay below this (the 32-bit scan)
+
+
+def marching_cubes_batch(sdf: torch.Tensor, sdf_params, res: int, iso: float = 0.0,
+                         ws: Optional[torch.Tensor] = None, max_edge_slots: int = MC_EDGE_SLOTS
+                         ) -> List[Tuple[torch.Tensor, torch.Tensor]]:
+    """sdf: float32 device tensor [B,(res+1)^3], sdf_params [B,6] -> B x (verts [nv,3], faces [nf,3]), views of
+    two device tensors; every pair is bit for bit what ``marching_cubes`` gives for that grid alone.  One count
+    call, ONE device-to-host copy of the [B,2] sizes and one emit call for the whole batch; a batch whose
+    3*B*(res+1)^3 edge slots reach ``max_edge_slots`` is meshed in several such rounds."""
+    n = res + 1
+    if sdf.dim() != 2 or sdf.shape[1] != n * n * n:
+        raise ValueError("sdf must be [B, (res+1)^3 = %d], got %s" % (n * n * n, tuple(sdf.shape)))
+    sdf = ops._chk(sdf, "sdf")
+    B = sdf.shape[0]
+    sp = np.ascontiguousarray(np.asarray(sdf_params, np.float64).reshape(-1, 6))
+    if sp.shape[0] != B:
+        raise ValueError("sdf_params must be [B,6] with B = %d, got %s" % (B, sp.shape))
+    per = (min(int(max_edge_slots), MC_EDGE_SLOTS) - 1) // (3 * n * n * n)      # grids per round
+    if B and (per < 1 or lib().disn_mc_batch_workspace_bytes(1, res) == 0):
+        raise ValueError("unsupported resolution %d" % res)
+    dev = sdf.device
+    out: List[Tuple[torch.Tensor, torch.Tensor]] = []
+    with torch.cuda.device(dev):
+        st = ops._stream()
+        for b0 in range(0, B, max(per, 1)):
+            nb = min(per, B - b0)
+            need = lib().disn_mc_batch_workspace_bytes(nb, res)
+            if ws is None or ws.numel() < need:
+                ws = torch.empty(need, dtype=torch.uint8, device=dev)
+            part = sdf[b0:b0 + nb]
+            counts = torch.zeros((nb, 2), dtype=torch.int64, device=dev)
+            check("disn_mc_count_batch", lib().disn_mc_count_batch(part.data_ptr(), nb, res, float(iso),
+                                                                   counts.data_ptr(), ws.data_ptr(), ws.numel(), st))
+            sizes = counts.cpu().numpy()                   # the one host sync of the round: sizes are data dependent
+            nv, nf = int(sizes[:, 0].sum()), int(sizes[:, 1].sum())
+            verts = torch.empty((nv, 3), dtype=torch.float32, device=dev)
+            faces = torch.empty((nf, 3), dtype=torch.int32, device=dev)
+            if nv and nf:
+                check("disn_mc_emit_batch", lib().disn_mc_emit_batch(part.data_ptr(), sp[b0:b0 + nb].ctypes.data, nb,
+                                                                     res, float(iso), verts.data_ptr(),
+                                                                     faces.data_ptr(), ws.data_ptr(), ws.numel(), st))
+            v0 = f0 = 0
+            for k in range(nb):
+                out.append((verts[v0:v0 + int(sizes[k, 0])], faces[f0:f0 + int(sizes[k, 1])]))
+                v0 += int(sizes[k, 0])
+                f0 += int(sizes[k, 1])
+    return out
 
 
 def write_obj(path: str, verts, faces) -> None:

@@ -559,6 +559,21 @@ int disn_mc_count(const float* sdf, int R, float iso, uint64_t* counts, void* ws
 int disn_mc_emit(const float* sdf, const double* sdf_params_host, int R, float iso, float* verts,
                  int32_t* faces, void* ws, size_t ws_bytes, void* stream);
 
+/* B grids of one resolution, sdf [B,(R+1)^3], in one set of passes and with ONE
+ * read-back: what a group of views of the test set needs.
+ *   disn_mc_count_batch -> counts [B,2] (uint64, DEVICE): #vertices, #triangles of each grid
+ *   disn_mc_emit_batch  -> verts [sum nv,3] and faces [sum nf,3] of all grids back to back in
+ *                          grid order; face indices are LOCAL to their grid (0-based);
+ *                          sdf_params_host [B,6]: one box per grid
+ * Every grid's vertices and faces are bit for bit those of disn_mc_count / disn_mc_emit on that
+ * grid alone.  disn_mc_batch_workspace_bytes is 0 for an unsupported batch: B < 1, R out of
+ * range, or B*3*(R+1)^3 >= 2^32 (split such a batch). */
+size_t disn_mc_batch_workspace_bytes(int B, int R);
+int disn_mc_count_batch(const float* sdf, int B, int R, float iso, uint64_t* counts, void* ws,
+                        size_t ws_bytes, void* stream);
+int disn_mc_emit_batch(const float* sdf, const double* sdf_params_host, int B, int R, float iso,
+                       float* verts, int32_t* faces, void* ws, size_t ws_bytes, void* stream);
+
 /* ---------------------------------------------------------------------- *
  * Evaluation metrics: the two custom ops behind the paper's CD / EMD /     *
  * F-score tables (models/tf_ops/nn_distance, models/tf_ops/approxmatch;    *
