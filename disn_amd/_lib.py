@@ -203,6 +203,7 @@ SIGNATURES = {
     "disn_voxel_fill": (I, [P, I, P, P, Z, P]),
     "disn_voxel_index_grid": (I, [P, I, P, I, P, P]),
     "disn_voxel_iou": (I, [P, P, I, L, P, P, P]),
+    "disn_assemble_batch": (I, [P, P, L, P, P, P, L, P, P, P, I, I, I, I, P, P, P, P, P, P, P]),
     "disn_metrics_workspace_bytes": (Z, [I, I, I]),
     "disn_nn_distance": (I, [P, P, I, I, I, P, P, P, P, P, Z, P]),
     "disn_approx_match": (I, [P, P, I, I, I, P, P, Z, P]),

@@ -42,6 +42,7 @@ SOURCES = {
     "metrics.hip": ["-ffp-contract=off"],       # nn_distance bit-identical to a float32 restatement
     "mesh_sdf.hip": ["-ffp-contract=off"],      # distances and crossings bit-identical to their restatements
     "voxel.hip": ["-ffp-contract=off"],         # the overlap test bit-identical to its float32 restatement
+    "batch_assemble.hip": ["-ffp-contract=off"],   # sample_pc_rot in the order its bound is derived for
     "api.hip": [],
     "host_util.cpp": ["-msse4.2"],
     "mesh_host.cpp": [],

@@ -301,6 +301,13 @@ hipError_t voxel_index_grid_launch(const unsigned* keys, int nkeys, const int* l
 hipError_t voxel_iou_launch(const unsigned* gt, const unsigned* preds, int nviews, int64_t words, int64_t* inter,
                             int64_t* uni, hipStream_t st);
 
+// ---- batch_assemble.hip (compiled with -ffp-contract=off): a training batch out of the device-resident set ----
+hipError_t assemble_batch_launch(const float* samples, const int64_t* sample_off, int64_t n_obj,
+                                 const unsigned char* img, const float* trans_mat_all, const float* rot_all,
+                                 int64_t n_view, const int* obj_idx, const int* view_idx, const int* choice, int B,
+                                 int S, int rot, int white, float* imgs, float* sample_pc, float* sample_pc_rot,
+                                 float* sdf, float* trans_mat, int* flags, hipStream_t st);
+
 // ---- mlp_fused.hip: both point MLPs as one persistent kernel per stream, activations in registers ----
 size_t mlp_fused_image_bytes();
 size_t mlp_fused_feat_image_bytes();

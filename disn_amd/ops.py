@@ -902,3 +902,41 @@ def cam_loss_backward(w: "_lib.CamWeights", embedding: torch.Tensor, pts: torch.
         out["losses"].data_ptr(), out["dists"].data_ptr(), out["dRT"].data_ptr(), out["demb"].data_ptr(),
         out["head_grads"].data_ptr(), ws.data_ptr(), ws.numel(), _stream()))
     return out
+
+
+def _chk_as(t: torch.Tensor, name: str, dtype: torch.dtype) -> torch.Tensor:
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dtype and t.is_contiguous()):
+        raise TypeError("%s must be a contiguous %s CUDA tensor" % (name, str(dtype).replace("torch.", "")))
+    return t
+
+
+def assemble_batch(samples: torch.Tensor, sample_off: torch.Tensor, img: torch.Tensor, trans_mat_all: torch.Tensor,
+                   rot_all: torch.Tensor, obj_idx: torch.Tensor, view_idx: torch.Tensor, choice: torch.Tensor,
+                   flags: torch.Tensor, rot: bool = False, backcolorwhite: bool = False):
+    """one training batch out of the device-resident set (disn_assemble_batch): samples [total,4] f32, sample_off
+    [n_obj+1] i64, img [n_view,137,137,4] u8, trans_mat_all [n_view,4,3], rot_all [n_view,3,3]; obj_idx / view_idx [B]
+    and choice [B,S] i32; flags [1] i32 (set to 1 by an index outside its range, never cleared).
+    -> the feed of train_step: imgs, sample_pc, sample_pc_rot, sdf [B,S,1], trans_mat"""
+    samples = _chk_as(samples, "samples", torch.float32)
+    B, S = choice.shape
+    n_obj, n_view = sample_off.numel() - 1, img.shape[0]
+    if samples.dim() != 2 or samples.shape[1] != 4 or tuple(img.shape[1:]) != (IMG, IMG, 4):
+        raise ValueError("samples must be [total,4] and img [n_view,%d,%d,4]" % (IMG, IMG))
+    if trans_mat_all.shape != (n_view, 4, 3) or rot_all.shape != (n_view, 3, 3) or obj_idx.shape != (B,) \
+            or view_idx.shape != (B,) or flags.numel() < 1:
+        raise ValueError("assemble_batch: inconsistent shapes")
+    dev = samples.device
+    feed = {"imgs": torch.empty((B, IMG, IMG, 3), dtype=torch.float32, device=dev),
+            "sample_pc": torch.empty((B, S, 3), dtype=torch.float32, device=dev),
+            "sample_pc_rot": torch.empty((B, S, 3), dtype=torch.float32, device=dev),
+            "trans_mat": torch.empty((B, 4, 3), dtype=torch.float32, device=dev),
+            "sdf": torch.empty((B, S, 1), dtype=torch.float32, device=dev)}
+    check("disn_assemble_batch", lib().disn_assemble_batch(
+        samples.data_ptr(), _chk_as(sample_off, "sample_off", torch.int64).data_ptr(), n_obj,
+        _chk_as(img, "img", torch.uint8).data_ptr(), _chk(trans_mat_all, "trans_mat_all").data_ptr(),
+        _chk(rot_all, "rot_all").data_ptr(), n_view, _chk_as(obj_idx, "obj_idx", torch.int32).data_ptr(),
+        _chk_as(view_idx, "view_idx", torch.int32).data_ptr(), _chk_as(choice, "choice", torch.int32).data_ptr(),
+        B, S, int(bool(rot)), int(bool(backcolorwhite)), feed["imgs"].data_ptr(), feed["sample_pc"].data_ptr(),
+        feed["sample_pc_rot"].data_ptr(), feed["sdf"].data_ptr(), feed["trans_mat"].data_ptr(),
+        _chk_as(flags, "flags", torch.int32).data_ptr(), _stream()))
+    return feed

@@ -917,6 +917,35 @@ int disn_voxel_index_grid(const uint32_t* keys, int nkeys, const int32_t* lut, i
 int disn_voxel_iou(const uint32_t* gt, const uint32_t* preds, int nviews, int64_t words, int64_t* inter,
                    int64_t* uni, void* stream);
 
+/* ---------------------------------------------------------------------- *
+ * Training batches out of a device-resident training set                   *
+ * (data/data_sdf_h5_queue.py get_batch + the feed of train/train_sdf.py    *
+ * :371-378, without a file read or a host copy of the data per batch).     *
+ * The set, uploaded once:                                                  *
+ *   samples [total][4] float32 (16-byte aligned): the pc_sdf_sample rows   *
+ *       (x, y, z, sdf) of all objects, object o at rows sample_off[o] ..   *
+ *       sample_off[o+1]-1; sample_off [n_obj+1] int64                      *
+ *   img [n_view][137][137][4] uint8 RGBA, trans_mat_all [n_view][4][3],    *
+ *   rot_all [n_view][3][3] (obj_rot_mat; may be NULL when rot = 0)         *
+ * Per batch, B samples x S points: obj_idx [B], view_idx [B], choice       *
+ * [B][S] int32 (row of the object's range).  Outputs, the arguments of     *
+ * disn_train_step:                                                         *
+ *   imgs [B][137][137][3] = rgb / 255 (IEEE division); backcolorwhite:     *
+ *       pixels of alpha 0 are 1.0                                          *
+ *   sample_pc [B][S][3], sdf [B][S] = row.w - 0.003f                       *
+ *   sample_pc_rot [B][S][3] = sample_pc, or with rot column j =            *
+ *       (p0*R[0][j] + p1*R[1][j]) + p2*R[2][j], not contracted             *
+ *   trans_mat [B][4][3] = trans_mat_all[view]                              *
+ * One launch on `stream`, no host synchronisation.  An index outside its   *
+ * range reads nothing: its outputs are 0 (sdf included) and flags[0] (int32, *
+ * device, never cleared here) becomes 1.  B <= 65535.                      *
+ * ---------------------------------------------------------------------- */
+int disn_assemble_batch(const float* samples, const int64_t* sample_off, int64_t n_obj, const uint8_t* img,
+                        const float* trans_mat_all, const float* rot_all, int64_t n_view, const int32_t* obj_idx,
+                        const int32_t* view_idx, const int32_t* choice, int B, int S, int rot, int backcolorwhite,
+                        float* imgs, float* sample_pc, float* sample_pc_rot, float* sdf, float* trans_mat,
+                        int32_t* flags, void* stream);
+
 /* Host utility (no device work): CRC-32C of a HOST buffer, continuing from `crc` (0 to start);
  * the checksum of TensorFlow's table blocks and tensor-bundle entries, used by the
  * TensorFlow-free checkpoint reader/writer (train/train_sdf.py:285-299, test/create_sdf.py:180-192). */
