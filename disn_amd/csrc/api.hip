@@ -15,6 +15,12 @@ using namespace disn;
     hipError_t _e = (expr);               \
     if (_e != hipSuccess) return (int)_e; \
   } while (0)
+// the same for a call that returns the library's own int status (0 ok, DISN_E_*, or a hipError_t)
+#define DISN_RC(expr)        \
+  do {                       \
+    const int _rc = (expr);  \
+    if (_rc) return _rc;     \
+  } while (0)
 
 namespace {
 
@@ -43,6 +49,25 @@ const bool kPoolAfter[13] = {false, true, false, true, false, false, true,
                              false, false, true, false, false, true};
 
 inline int conv_k(int cin) { return cin == 3 ? 32 : 9 * cin; }
+
+// the five taps (conv1_2, conv2_2, conv3_3, conv4_3, conv5_3): side, channels, channel offset in a 1472-wide feature row
+struct TapGeom {
+  int hw, ch, off;
+};
+const TapGeom kTap[5] = {{224, 64, 0}, {112, 128, 64}, {56, 256, 192}, {28, 512, 448}, {14, 512, 960}};
+
+int tap_layer(int k) {  // index of the convolution layer that writes tap k
+  int i = 0;
+  while (kVgg[i].tap != k) ++i;
+  return i;
+}
+
+bool taps_ok(const float* const* taps) {
+  if (!taps) return false;
+  for (int i = 0; i < 5; ++i)
+    if (!taps[i]) return false;
+  return true;
+}
 
 struct VggWs {
   float *resized, *bufA, *bufB, *bufP, *gemm_ws, *fc_ws, *fc6, *fc7;
@@ -179,8 +204,9 @@ bool mlp_weights_ok(const disn_mlp_weights_t* w) {
 // The point-MLP layers of a SMALL point set (a few thousand rows: launch- and latency-bound in the GEMM kernels)
 // through dense_h2.hip when the weights carry its images: one short launch per layer, the two streams' same-shaped
 // layers paired in one launch, the per-image bias + ReLU of the split global fold2/conv1 applied by the consumer.
+const int kH2MaxPoints = 8192;  // points per image from which the GEMM chain / the fused kernels take over
 bool mlp_h2(const disn_mlp_weights_t* w, long n) {
-  return n < 8192 && w->g_d2 && w->g_d3 && w->g_d4_point && w->g_d5 && w->l_d2 && w->l_d3 && w->l_d4 && w->l_d5;
+  return n < kH2MaxPoints && w->g_d2 && w->g_d3 && w->g_d4_point && w->g_d5 && w->l_d2 && w->l_d3 && w->l_d4 && w->l_d5;
 }
 
 DenseH2Prob h2_prob(const float* a, int K, const void* img, const float* bias, int N, int relu, const float* in_amax,
@@ -287,44 +313,32 @@ int dense_layer(const float* a1, int lda1, int k1, const float* a2, int lda2, in
 //              both fold2/conv5 and the sum  (:78-88, :186; models/model_normalization.py:204)
 // fold1/conv2, conv3 of one stream (after pt_embed); `gws`: the GEMM scratch this stream may use
 int mlp_fold1_local(const disn_mlp_weights_t* w, int n, const MlpWs& s, float* gws, hipStream_t st) {
-  int rc;
-  if ((rc = dense_layer(s.e1l, 64, 64, nullptr, 0, 64, n, w->l_w2, w->l_b2, 256, s.h256, gws, s.gemm_ws_bytes, st, w->l_x2))) return rc;
+  DISN_RC(dense_layer(s.e1l, 64, 64, nullptr, 0, 64, n, w->l_w2, w->l_b2, 256, s.h256, gws, s.gemm_ws_bytes, st, w->l_x2));
   return dense_layer(s.h256, 256, 256, nullptr, 0, 256, n, w->l_w3, w->l_b3, 512, s.h512a, gws, s.gemm_ws_bytes, st, w->l_x3);
 }
 int mlp_fold1_global(const disn_mlp_weights_t* w, int n, const MlpWs& s, float* gws, hipStream_t st) {
-  int rc;
-  if ((rc = dense_layer(s.e1g, 64, 64, nullptr, 0, 64, n, w->g_w2, w->g_b2, 256, s.g256, gws, s.gemm_ws_bytes, st, w->g_x2))) return rc;
+  DISN_RC(dense_layer(s.e1g, 64, 64, nullptr, 0, 64, n, w->g_w2, w->g_b2, 256, s.g256, gws, s.gemm_ws_bytes, st, w->g_x2));
   return dense_layer(s.g256, 256, 256, nullptr, 0, 256, n, w->g_w3, w->g_b3, 512, s.g512, gws, s.gemm_ws_bytes, st, w->g_x3);
 }
 int mlp_phase0(const disn_mlp_weights_t* w, const float* pts_rot, int n, const MlpWs& s,
                hipStream_t st) {
-  int rc;
   DISN_TRY(pt_embed_launch(pts_rot, n, w->g_w1, w->g_b1, w->l_w1, w->l_b1, s.e1g, s.e1l, st));
-  if ((rc = mlp_fold1_local(w, n, s, s.gemm_ws, st))) return rc;
+  DISN_RC(mlp_fold1_local(w, n, s, s.gemm_ws, st));
   return mlp_fold1_global(w, n, s, s.gemm_ws, st);
 }
 
 int mlp_phase1(const disn_mlp_weights_t* w, int n, const float* feat, const MlpWs& s,
                hipStream_t st) {
-  int rc;
-  if ((rc = dense_layer(s.h512a, 512, 512, feat, DISN_FEAT_DIM, 512 + DISN_FEAT_DIM, n, w->l_w4, w->l_b4, 512, s.h512b, s.gemm_ws, s.gemm_ws_bytes, st, w->l_x4))) return rc;
-  if ((rc = dense_layer(s.h512b, 512, 512, nullptr, 0, 512, n, w->l_w5, w->l_b5, 256, s.l5, s.gemm_ws, s.gemm_ws_bytes, st, w->l_x5))) return rc;
-  return 0;
+  DISN_RC(dense_layer(s.h512a, 512, 512, feat, DISN_FEAT_DIM, 512 + DISN_FEAT_DIM, n, w->l_w4, w->l_b4, 512, s.h512b, s.gemm_ws, s.gemm_ws_bytes, st, w->l_x4));
+  return dense_layer(s.h512b, 512, 512, nullptr, 0, 512, n, w->l_w5, w->l_b5, 256, s.l5, s.gemm_ws, s.gemm_ws_bytes, st, w->l_x5);
 }
 
-// B images x N points (rows image-major); gbias [B][512]
-int mlp_phase2(const disn_mlp_weights_t* w, int B, int N, const float* gbias, float* sdf,
+// the global fold2 layers of n points of ONE image (gbias = that image's folded bias row), both conv5 and the sum
+int mlp_phase2(const disn_mlp_weights_t* w, int n, const float* gbias, float* sdf,
                float* sdf_g, float* sdf_l, float out_div, const MlpWs& s, hipStream_t st) {
-  int rc;
-  for (int b = 0; b < B; ++b) {
-    const size_t o = (size_t)b * N;
-    if ((rc = dense_layer(s.g512 + o * 512, 512, 512, nullptr, 0, 512, N, w->g_w4_point,
-                          gbias + (size_t)b * 512, 512, s.h512b + o * 512, s.gemm_ws,
-                          s.gemm_ws_bytes, st, w->g_x4_point)))
-      return rc;
-  }
-  const int n = B * N;
-  if ((rc = dense_layer(s.h512b, 512, 512, nullptr, 0, 512, n, w->g_w5, w->g_b5, 256, s.g5, s.gemm_ws, s.gemm_ws_bytes, st, w->g_x5))) return rc;
+  DISN_RC(dense_layer(s.g512, 512, 512, nullptr, 0, 512, n, w->g_w4_point, gbias, 512, s.h512b, s.gemm_ws,
+                      s.gemm_ws_bytes, st, w->g_x4_point));
+  DISN_RC(dense_layer(s.h512b, 512, 512, nullptr, 0, 512, n, w->g_w5, w->g_b5, 256, s.g5, s.gemm_ws, s.gemm_ws_bytes, st, w->g_x5));
   DISN_TRY(final_dot_launch(s.g5, s.l5, n, w->g_w6, w->g_b6, w->l_w6, w->l_b6, sdf, sdf_g, sdf_l,
                             out_div, st));
   return 0;
@@ -341,10 +355,9 @@ int mlp_g4_pre(const disn_mlp_weights_t* w, int n, const MlpWs& s, float* gws, h
 
 int mlp_phase2_split(const disn_mlp_weights_t* w, int B, int N, const float* gbias, float* sdf,
                      const MlpWs& s, hipStream_t st, hipEvent_t joined) {
-  int rc;
   const int n = B * N;
   DISN_TRY(splitk_reduce_launch(s.g4pre, 1, n, 512, gbias, N, 1, s.g512, 512, st));
-  if ((rc = dense_layer(s.g512, 512, 512, nullptr, 0, 512, n, w->g_w5, w->g_b5, 256, s.g5, s.gemm_ws2, s.gemm_ws_bytes, st, w->g_x5))) return rc;
+  DISN_RC(dense_layer(s.g512, 512, 512, nullptr, 0, 512, n, w->g_w5, w->g_b5, 256, s.g5, s.gemm_ws2, s.gemm_ws_bytes, st, w->g_x5));
   DISN_TRY(hipStreamWaitEvent(st, joined, 0));
   DISN_TRY(final_dot_launch(s.g5, s.l5, n, w->g_w6, w->g_b6, w->l_w6, w->l_b6, sdf, nullptr, nullptr,
                             1.0f, st));
@@ -355,10 +368,8 @@ int mlp_phase2_split(const disn_mlp_weights_t* w, int B, int N, const float* gbi
 // features, then + resampled pmap rows + bias, ReLU in one gather pass; no [n,1472] feature rows
 int mlp_phase1_folded(const disn_mlp_weights_t* w, int n, const float* pmap_b, const float* trans_mat_b,
                       const float* pts, const MlpWs& s, hipStream_t st) {
-  int rc;
-  if ((rc = dense_layer(s.h512a, 512, 512, nullptr, 0, 512, n, w->l_w4_point, s.zero512, 512, s.h512b,
-                        s.gemm_ws, s.gemm_ws_bytes, st, w->l_x4_point, 0)))
-    return rc;
+  DISN_RC(dense_layer(s.h512a, 512, 512, nullptr, 0, 512, n, w->l_w4_point, s.zero512, 512, s.h512b,
+                      s.gemm_ws, s.gemm_ws_bytes, st, w->l_x4_point, 0));
   DISN_TRY(gather_fold_launch(pmap_b, trans_mat_b, pts, n, s.h512b, w->l_b4, s.h512b, st));
   return dense_layer(s.h512b, 512, 512, nullptr, 0, 512, n, w->l_w5, w->l_b5, 256, s.l5, s.gemm_ws,
                      s.gemm_ws_bytes, st, w->l_x5);
@@ -367,62 +378,31 @@ int mlp_phase1_folded(const disn_mlp_weights_t* w, int n, const float* pmap_b, c
 int mlp_chunk_folded(const disn_mlp_weights_t* w, const float* pts, const float* pts_rot, int n,
                      const float* gbias, const float* pmap_b, const float* trans_mat_b, float* sdf,
                      float out_div, const MlpWs& s, hipStream_t st) {
-  int rc;
-  if ((rc = mlp_phase0(w, pts_rot, n, s, st))) return rc;
-  if ((rc = mlp_phase1_folded(w, n, pmap_b, trans_mat_b, pts, s, st))) return rc;
-  return mlp_phase2(w, 1, n, gbias, sdf, nullptr, nullptr, out_div, s, st);
+  DISN_RC(mlp_phase0(w, pts_rot, n, s, st));
+  DISN_RC(mlp_phase1_folded(w, n, pmap_b, trans_mat_b, pts, s, st));
+  return mlp_phase2(w, n, gbias, sdf, nullptr, nullptr, out_div, s, st);
 }
 
 // both MLP streams for n points of ONE image on one stream (gbias = that image's folded bias row)
 int mlp_chunk(const disn_mlp_weights_t* w, const float* pts_rot, int n, const float* gbias,
               const float* feat, float* sdf, float* sdf_g, float* sdf_l, float out_div,
               const MlpWs& s, hipStream_t st) {
-  int rc;
   if (mlp_h2(w, n)) {  // the same launches as disn_encode_query, on one stream (bit-identical results)
-    if ((rc = mlp_fold1_h2(w, pts_rot, n, s, 0, 0, 1, st))) return rc;
-    if ((rc = mlp_phase1_h2(w, n, feat, DISN_FEAT_DIM, s, 0, 0, 1, st))) return rc;
-    if ((rc = mlp_g4_pre_h2(w, n, s, 0, 0, 1, s.h512a, st))) return rc;   // h512a is free once the local fold2/conv1 ran
-    if ((rc = mlp_g5_h2(w, n, s.h512a, gbias, s, 0, 0, 1, st))) return rc;
+    DISN_RC(mlp_fold1_h2(w, pts_rot, n, s, 0, 0, 1, st));
+    DISN_RC(mlp_phase1_h2(w, n, feat, DISN_FEAT_DIM, s, 0, 0, 1, st));
+    DISN_RC(mlp_g4_pre_h2(w, n, s, 0, 0, 1, s.h512a, st));   // h512a is free once the local fold2/conv1 ran
+    DISN_RC(mlp_g5_h2(w, n, s.h512a, gbias, s, 0, 0, 1, st));
     DISN_TRY(final_dot_launch(s.g5, s.l5, n, w->g_w6, w->g_b6, w->l_w6, w->l_b6, sdf, sdf_g, sdf_l, out_div, st));
     return 0;
   }
-  if ((rc = mlp_phase0(w, pts_rot, n, s, st))) return rc;
-  if ((rc = mlp_phase1(w, n, feat, s, st))) return rc;
-  return mlp_phase2(w, 1, n, gbias, sdf, sdf_g, sdf_l, out_div, s, st);
+  DISN_RC(mlp_phase0(w, pts_rot, n, s, st));
+  DISN_RC(mlp_phase1(w, n, feat, s, st));
+  return mlp_phase2(w, n, gbias, sdf, sdf_g, sdf_l, out_div, s, st);
 }
 
 const int kMapPixels = DISN_IMG_H * DISN_IMG_W;
 
 const int kFeatPad = 1536;   // gathered feature rows zero-padded to a multiple of 256 columns (dense_h2 chunks)
-
-// ---- the fused point MLP of a SMALL point set (round 4; models/sdfnet.py:71-90,173-186 + model_normalization.py:171-204)
-// B images x N points (N % 128 == 0), no feature map and no folded map: the gather from the taps writes the 1472
-// features in split form (one power-of-two scale per image from the taps' maxima), mlp_fused_kernel<local, FEAT> takes
-// them as 96 extra reduction blocks of fold2/conv1, mlp_fused_kernel<global> runs with the image's folded bias row and
-// adds the local sums: two launches per call behind the gather, every activation in registers.
-bool fused_small_ok(const disn_mlp_weights_t* w, int B, int N) {
-  return w->g_fused && w->l_feat && N % 128 == 0 && (long)B * N <= kChunk;
-}
-// tap_slots[k]: image 0's 64 activation-maximum slots of tap k (image b's are slot_stride floats further each);
-// featmax: B floats of scratch; lsum: B * N floats of scratch
-int fused_small_local(const disn_mlp_weights_t* w, float* const taps[5], const float* const tap_slots[5],
-                      size_t slot_stride, const float* trans_mat, const float* pts, const float* pts_rot, int B, int N,
-                      float* feat_split, float* featmax, float* lsum, hipStream_t st) {
-  // (the one-wave-per-point gather takes the images' tap maxima from the slots itself and leaves them in featmax)
-  const bool slots_in_gather = project_gather_taps_takes_slots(B, N, kFeatPad);
-  if (!slots_in_gather) DISN_TRY(tap_amax_launch(tap_slots, slot_stride, B, featmax, st));
-  DISN_TRY(project_gather_taps_launch(taps, trans_mat, pts, B, N, 0, 5, feat_split, st, kFeatPad, nullptr, 0, 0, featmax,
-                                      slots_in_gather ? tap_slots : nullptr, slot_stride));
-  DISN_TRY(mlp_fused_small_launch(true, w->l_feat, w->l_w1, w->l_b1, w->l_b2, w->l_b3, w->l_b4, w->l_b5, w->l_w6, w->l_b6,
-                                  pts_rot, N, B, feat_split, kFeatPad, featmax, nullptr, lsum, 1.0f, st));
-  return 0;
-}
-int fused_small_global(const disn_mlp_weights_t* w, const float* gbias, const float* pts_rot, int B, int N,
-                       const float* lsum, float* sdf, float out_div, hipStream_t st) {
-  DISN_TRY(mlp_fused_small_launch(false, w->g_fused, w->g_w1, w->g_b1, w->g_b2, w->g_b3, gbias, w->g_b5, w->g_w6, w->g_b6,
-                                  pts_rot, N, B, nullptr, 0, nullptr, lsum, sdf, out_div, st));
-  return 0;
-}
 
 
 struct QueryWs {
@@ -454,6 +434,13 @@ bool grid_spec(const double* p, int R, GridSpec* g) {
     g->step[a] = (p[a + 3] - p[a]) / (double)R;  // numpy.linspace: delta / div
   }
   return true;
+}
+
+// ... and the range k0..k1-1 of its (R+1)^3 points: false for a bad box or an empty / out-of-grid range
+bool grid_range(const double* p, int R, int64_t k0, int64_t k1, GridSpec* g) {
+  if (!grid_spec(p, R, g)) return false;
+  const int64_t total = (int64_t)g->res * g->res * g->res;
+  return k0 >= 0 && k1 <= total && k0 < k1;
 }
 
 }  // namespace
@@ -604,13 +591,10 @@ size_t disn_vgg16_workspace_bytes(int B) {
 
 }  // extern "C"
 
-// struct disn_ctx (kernels.hpp) as used here -- ev 0: fork, 1..4: grid pipeline buffers, 6: aux done,
-// 7: features done, 8: g4_pre done
-
 namespace {
 
-const int kTapHw[5] = {224, 112, 56, 28, 14}, kTapCh[5] = {64, 128, 256, 512, 512};
-const int kTapOff[5] = {0, 64, 192, 448, 960};
+// struct disn_ctx (kernels.hpp) as used here; events 1..4: the grid pipeline's buffers (disn_query_grid_ctx)
+enum { kEvFork = 0, kEvAuxDone = 6, kEvFeatures = 7, kEvG4Pre = 8 };
 
 bool vgg_weights_ok(const disn_vgg_weights_t* w) {
   if (!w) return false;
@@ -621,6 +605,12 @@ bool vgg_weights_ok(const disn_vgg_weights_t* w) {
   return true;
 }
 
+bool vgg_all_h2(const disn_vgg_weights_t* w) {  // every layer has its conv_h2 image
+  for (int i = 0; i < 13; ++i)
+    if (!w->conv_w_h2[i]) return false;
+  return true;
+}
+
 // rows A, B (+E when featmap != nullptr): resize, conv stack, pools, all on `st`.  Returns pool5.
 // layers [i0, i1) of the stack; i0 == 0 starts with the resize; *xio carries the current activation between calls
 int vgg_features(const disn_vgg_weights_t* w, const float* img, int B, float* resized,
@@ -628,8 +618,7 @@ int vgg_features(const disn_vgg_weights_t* w, const float* img, int B, float* re
                  hipStream_t st, int i0 = 0, int i1 = 13) {
   // the single-image kernels (conv_h2.hip) when every layer has its image: each layer's epilogue leaves the
   // maximum of its output in the slots the next layer scales its f16 split by (cleared by the resize launch)
-  bool h2 = true;
-  for (int i = 0; i < 13; ++i) h2 = h2 && w->conv_w_h2[i] != nullptr;
+  const bool h2 = vgg_all_h2(w);
   if (i0 == 0)
     DISN_TRY(resize_bilinear_launch(img, B, DISN_IMG_H, DISN_IMG_W, 3, resized, DISN_VGG_SIZE,
                                     DISN_VGG_SIZE, 3, 0, st, 0, h2 ? s.amax : nullptr, h2 ? 14 * B * 64 : 0));
@@ -644,7 +633,6 @@ int vgg_features(const disn_vgg_weights_t* w, const float* img, int B, float* re
     if (i < i0) continue;  // replay of the buffer choice only
     // a layer the pool follows: when its split-K reduce runs anyway, that pass also emits the pool
     bool pooled = false;
-    int rc = 0;
     if (h2 && i == 0) {
       DISN_TRY(conv1_1_direct_launch(x, B, L.hw, L.hw, static_cast<const float*>(w->conv_w_h2[0]), w->conv_b[0], 1, out,
                                      s.amax + (size_t)B * 64, st, 64));
@@ -654,15 +642,14 @@ int vgg_features(const disn_vgg_weights_t* w, const float* img, int B, float* re
                               s.amax + (size_t)B * 64 * (i + 1), st, w->strict_forms == 1 ? 11 : 0, 64));
       pooled = kPoolAfter[i];
     } else {
-      rc = conv3x3_impl(x, B, L.hw, L.hw, L.cin, w->conv_w[i], w->conv_b[i], L.cout, 1, out, s.gemm_ws, gws_cap, st,
-                        w->conv_w_x3[i], kPoolAfter[i] ? s.bufP : nullptr, &pooled);
+      DISN_RC(conv3x3_impl(x, B, L.hw, L.hw, L.cin, w->conv_w[i], w->conv_b[i], L.cout, 1, out, s.gemm_ws, gws_cap, st,
+                           w->conv_w_x3[i], kPoolAfter[i] ? s.bufP : nullptr, &pooled));
     }
-    if (rc) return rc;
     x = out;
     if (L.tap >= 0 && featmap)
-      DISN_TRY(resize_bilinear_launch(taps[L.tap], B, kTapHw[L.tap], kTapHw[L.tap], kTapCh[L.tap],
+      DISN_TRY(resize_bilinear_launch(taps[L.tap], B, kTap[L.tap].hw, kTap[L.tap].hw, kTap[L.tap].ch,
                                       featmap, DISN_IMG_H, DISN_IMG_W, DISN_FEAT_DIM,
-                                      kTapOff[L.tap], st, 0));
+                                      kTap[L.tap].off, st, 0));
     if (kPoolAfter[i]) {
       if (!pooled) DISN_TRY(maxpool2x2_launch(x, B, L.hw, L.hw, L.cout, s.bufP, st));
       x = s.bufP;
@@ -686,12 +673,11 @@ int fc_layer(const float* x, int B, int K, const float* w_kn, const float* wt_nk
 
 int vgg_head(const disn_vgg_weights_t* w, const float* pool5, int B, float* embedding,
              const VggWs& s, hipStream_t st) {
-  int rc;
   const bool sf = w->strict_forms == 1;   // "strict": every row as in a call of one image
   // fc6 (411 MB) stays on the split-K stream kernel: 6.2 TB/s there against 2.8 for the row form (r02i); the
   // 67 / 17 / 2 MB layers are launch-latency bound and take the one-launch row form
-  if ((rc = fc_layer(pool5, B, 25088, w->fc_w[0], nullptr, w->fc_b[0], 4096, 1, s.fc6, s.fc_ws, st, sf))) return rc;
-  if ((rc = fc_layer(s.fc6, B, 4096, w->fc_w[1], w->fc_w_t[1], w->fc_b[1], 4096, 1, s.fc7, s.fc_ws, st, sf))) return rc;
+  DISN_RC(fc_layer(pool5, B, 25088, w->fc_w[0], nullptr, w->fc_b[0], 4096, 1, s.fc6, s.fc_ws, st, sf));
+  DISN_RC(fc_layer(s.fc6, B, 4096, w->fc_w[1], w->fc_w_t[1], w->fc_b[1], 4096, 1, s.fc7, s.fc_ws, st, sf));
   return fc_layer(s.fc7, B, 4096, w->fc_w[2], w->fc_w_t[2], w->fc_b[2], w->num_classes, 0, embedding, s.fc_ws, st, sf);
 }
 
@@ -726,6 +712,297 @@ EncQueryWs encq_layout(void* ws, int B, int N, int num_classes) {
   e.pad_sdf = b.take((size_t)B * Np * sizeof(float));
   e.total = e.vgg.total + e.q.total + ((b.off + 255) & ~size_t(255));
   return e;
+}
+
+// the point sets a fused-small call runs on: the caller's own, or their copies padded to pad128(N) points per image
+struct PaddedSets {
+  const float *pts, *pts_rot;
+  float* sdf;
+  int N;
+};
+// pad points (0, 0, 0) in (see pad128) ...
+int pad_sets(const float* pts, const float* pts_rot, float* sdf, int B, int N, float* pad_pts, float* pad_rot,
+             float* pad_sdf, hipStream_t st, PaddedSets* p) {
+  *p = PaddedSets{pts, pts_rot, sdf, N};
+  const int Np = pad128(N);
+  if (Np == N) return 0;
+  DISN_TRY(restride_rows_launch(pts, B, N, pad_pts, Np, 3, st));
+  if (pts_rot != pts) DISN_TRY(restride_rows_launch(pts_rot, B, N, pad_rot, Np, 3, st));
+  *p = PaddedSets{pad_pts, pts_rot != pts ? pad_rot : pad_pts, pad_sdf, Np};
+  return 0;
+}
+// ... and the first N results of every image out
+int unpad_sdf(const PaddedSets& p, int B, int N, float* sdf, hipStream_t st) {
+  if (p.sdf != sdf) DISN_TRY(restride_rows_launch(p.sdf, B, p.N, sdf, N, 1, st));
+  return 0;
+}
+
+// ---- the fused point MLP of a SMALL point set (round 4; models/sdfnet.py:71-90,173-186 + model_normalization.py:171-204)
+// B images x N points (N % 128 == 0), no feature map and no folded map: the gather from the taps writes the 1472
+// features in split form (one power-of-two scale per image from the taps' maxima), mlp_fused_kernel<local, FEAT> takes
+// them as 96 extra reduction blocks of fold2/conv1, mlp_fused_kernel<global> runs with the image's folded bias row and
+// adds the local sums: two launches per call behind the gather, every activation in registers.
+// tap_slots[k]: image 0's 64 activation-maximum slots of tap k (image b's are slot_stride floats further each);
+// featmax: B floats of scratch; lsum: B * N floats of scratch
+int fused_small_local(const disn_mlp_weights_t* w, float* const taps[5], const float* const tap_slots[5],
+                      size_t slot_stride, const float* trans_mat, const float* pts, const float* pts_rot, int B, int N,
+                      float* feat_split, float* featmax, float* lsum, hipStream_t st) {
+  // (the one-wave-per-point gather takes the images' tap maxima from the slots itself and leaves them in featmax)
+  const bool slots_in_gather = project_gather_taps_takes_slots(B, N, kFeatPad);
+  if (!slots_in_gather) DISN_TRY(tap_amax_launch(tap_slots, slot_stride, B, featmax, st));
+  DISN_TRY(project_gather_taps_launch(taps, trans_mat, pts, B, N, 0, 5, feat_split, st, kFeatPad, nullptr, 0, 0, featmax,
+                                      slots_in_gather ? tap_slots : nullptr, slot_stride));
+  DISN_TRY(mlp_fused_small_launch(true, w->l_feat, w->l_w1, w->l_b1, w->l_b2, w->l_b3, w->l_b4, w->l_b5, w->l_w6, w->l_b6,
+                                  pts_rot, N, B, feat_split, kFeatPad, featmax, nullptr, lsum, 1.0f, st));
+  return 0;
+}
+// the folded global bias, then -- behind `local_done` when the local stream ran on another HIP stream -- the global
+// stream's one launch, which adds the local sums
+int fused_small_global(const disn_mlp_weights_t* w, const float* embedding, bool single_form, float* gbias,
+                       float* gemv_ws, const float* pts_rot, int B, int N, const float* lsum, float* sdf,
+                       hipEvent_t local_done, hipStream_t st) {
+  DISN_RC(gbias_layer(w, embedding, B, gbias, gemv_ws, st, single_form));
+  if (local_done) DISN_TRY(hipStreamWaitEvent(st, local_done, 0));
+  DISN_TRY(mlp_fused_small_launch(false, w->g_fused, w->g_w1, w->g_b1, w->g_b2, w->g_b3, gbias, w->g_b5, w->g_w6, w->g_b6,
+                                  pts_rot, N, B, nullptr, 0, nullptr, lsum, sdf, 1.0f, st));
+  return 0;
+}
+
+// ---- disn_encode_query: which form runs, and one function per form ---------------------------------------------------
+enum EncForm { ENC_FUSED_SMALL, ENC_DENSE_H2, ENC_GEMM_CHAIN };
+struct EncPlan {
+  EncForm form;
+  bool strict;  // ENC_DENSE_H2 only: never the batched form of dense_h2w.hip
+  int hb;       // ENC_DENSE_H2 only: images per launch
+};
+// THE selection rules of the point MLPs inside disn_encode_query (include/disn_amd.h, "WHICH KERNELS RUN").
+EncPlan encq_plan(const disn_vgg_weights_t* vw, const disn_mlp_weights_t* mw, int B, int N, bool want_featmap) {
+  EncPlan p;
+  // "strict" (disn_vgg_weights_t.strict_forms = 1) in a call of >= 4 requests: the single-image forms of the convolutions
+  // (vgg_features) AND of the point-MLP layers (dense_h2.hip's four-k-wave tiles, per-image scales) -- the request's taps
+  // and, up to the fc head's form, its pred_sdf are those of the request alone
+  p.strict = vw->strict_forms == 1 && B >= kConvWideMinImages && mlp_h2(mw, N);
+  // Round 4: a batched call (>= kConvWideMinImages images) takes the fused small-set kernels, any N (padded to
+  // pad128(N) points per image: only when the padded B * N exceeds kChunk does it fall through).
+  // (a call of one to three requests keeps the layer-by-layer dense_h2 form below 8192 points per request -- its bits
+  // are a B = 1 call's; from 8192 points on it takes the fused kernels too: 2.13 -> 1.40 ms for one request of 65536 points
+  // against the three-term GEMM chain this shape ran until round 4, tools/encode_query_forms_time.py)
+  const bool fused = !p.strict && vgg_all_h2(vw) && !want_featmap && (B >= kConvWideMinImages || N >= kH2MaxPoints) &&
+                     mw->g_fused && mw->l_feat && (long)B * pad128(N) <= kChunk;
+  const bool h2 = B <= kH2Imgs && mlp_h2(mw, N);   // small point sets: the dense_h2 layers
+  p.form = fused ? ENC_FUSED_SMALL : h2 ? ENC_DENSE_H2 : ENC_GEMM_CHAIN;
+  // one launch per layer for the whole batch when a 64-row tile lies in one image, else image by image
+  p.hb = N % 64 == 0 ? B : 1;
+  return p;
+}
+
+// gather from the feature map, image by image
+int gather_from_map(const float* featmap, const float* trans_mat, const float* pts, int B, int N, float* feat,
+                    hipStream_t st) {
+  const size_t map_stride = (size_t)DISN_IMG_H * DISN_IMG_W * DISN_FEAT_DIM;
+  for (int b = 0; b < B; ++b)
+    DISN_TRY(project_gather_launch(featmap + b * map_stride, trans_mat + (size_t)b * 12, pts + (size_t)b * N * 3, N,
+                                   feat + (size_t)b * N * DISN_FEAT_DIM, st));
+  return 0;
+}
+
+// ENC_FUSED_SMALL -- nothing runs beside the convolutions; behind conv5_3 the auxiliary stream gathers (split form)
+// and runs the local stream's one launch under the fc head; the global stream's one launch follows the folded bias
+// and adds the local sums.
+int encq_fused_small(disn_ctx_t* ctx, const disn_vgg_weights_t* vw, const disn_mlp_weights_t* mw, const float* img,
+                     const float* trans_mat, const float* pts, const float* pts_rot, int B, int N, float* resized,
+                     float* const taps[5], float* embedding, float* sdf, const EncQueryWs& e, hipStream_t st) {
+  PaddedSets p;   // (both streams run behind the fork / the convolutions anyway)
+  DISN_RC(pad_sets(pts, pts_rot, sdf, B, N, e.pad_pts, e.pad_rot, e.pad_sdf, st, &p));
+  const float* pool5 = nullptr;
+  DISN_RC(vgg_features(vw, img, B, resized, taps, nullptr, e.vgg, &pool5, st));
+  DISN_TRY(hipEventRecord(ctx->ev[kEvFeatures], st));
+  DISN_TRY(hipStreamWaitEvent(ctx->aux, ctx->ev[kEvFeatures], 0));
+  const float* slots[5];   // the taps' maxima, left by the convolutions' epilogues
+  for (int k = 0; k < 5; ++k) slots[k] = e.vgg.amax + (size_t)B * 64 * (tap_layer(k) + 1);
+  DISN_RC(fused_small_local(mw, taps, slots, 64, trans_mat, p.pts, p.pts_rot, B, p.N, e.q.feat, e.q.mlp.amax, e.q.mlp.l5,
+                            ctx->aux));
+  DISN_TRY(hipEventRecord(ctx->ev[kEvAuxDone], ctx->aux));
+  if (ctx->pipe_record) DISN_TRY(hipEventRecord(ctx->pipe_record, st));
+  DISN_RC(vgg_head(vw, pool5, B, embedding, e.vgg, st));
+  DISN_RC(fused_small_global(mw, embedding, vw->strict_forms == 1, e.q.gbias, e.q.gemv_ws, p.pts_rot, B, p.N,
+                             e.q.mlp.l5, p.sdf, ctx->ev[kEvAuxDone], st));
+  return unpad_sdf(p, B, N, sdf, st);
+}
+
+// The two layer-by-layer forms run on two streams.  `st` (the caller's): resize, conv stack, fc6..fc8, the folded
+// global bias, then the short tail of the global MLP stream.  ctx->aux: everything of the MLPs that does not need the
+// embedding -- from the fork on the point-only layers of both streams and the point half of the
+// global fold2/conv1 (small GEMMs in the quantisation holes of the convolutions); behind conv5_3 the
+// gather and the local fold2 layers (MFMA bound), under the 495 MB fc weight stream (HBM bound).
+// Every event record / wait on `st` drains it (~6 us in the kernel trace): there are three.
+// Measured on MI355X (tools/overlap_sweep.py, cfg2 step of build r01c): single stream 0.886 ms, MLP
+// under the fc head 0.797 ms.  Two other overlaps were tried and removed: the 110 MB tap up-samples
+// on the auxiliary stream under the convolutions (0.86-0.98 ms at every throttle: their streamed
+// writes disturb the latency-sensitive convolution loads) and a trickle read of the fc6 weights
+// into the memory-side cache under conv4/conv5 (no gain up to 200 MB, slower beyond).
+// Schedule (r02i / r02j traces).  The convolution kernels from conv2 on are ONE round of 112..224 workgroups that
+// each fill a CU: a point-MLP GEMM running beside them takes CUs away and doubles a layer (18 -> 34 us), so
+// nothing runs beside conv2_1 .. conv5_3.  `st`: resize, the convolutions, the HBM-bound fc head, the short
+// global tail.  ctx->aux: from the fork, the point embedding, the GLOBAL stream's fold1 and the point half of its
+// fold2/conv1 -- ~45 us of small launches beside resize / conv1_1 / conv1_2 (VALU work and a two-round kernel,
+// measured unaffected) -- then, behind conv5_3, the LOCAL stream's fold1, the gather and fold2 under the fc head.
+// Host order: the caller's stream gets resize, conv1_1, conv1_2 first (it must never wait for the host), then
+// the auxiliary stream its launches, then the rest of the stack.
+
+// ENC_DENSE_H2 -- the dense_h2 layers: one launch per layer for the whole batch (hb = B images at once) or image by
+// image (hb = 1)
+int encq_dense_h2(disn_ctx_t* ctx, const disn_vgg_weights_t* vw, const disn_mlp_weights_t* mw, const float* img,
+                  const float* trans_mat, const float* pts, const float* pts_rot, int B, int N, float* resized,
+                  float* const taps[5], float* embedding, float* featmap, float* sdf, int hb, bool strict,
+                  const EncQueryWs& e, hipStream_t st) {
+  const MlpWs& m = e.q.mlp;
+  hipStream_t ms = ctx->aux;
+  const float* pool5 = nullptr;
+  DISN_TRY(hipEventRecord(ctx->ev[kEvFork], st));  // fork (orders aux behind the caller's inputs)
+  DISN_TRY(hipStreamWaitEvent(ms, ctx->ev[kEvFork], 0));
+  DISN_RC(vgg_features(vw, img, B, resized, taps, featmap, e.vgg, &pool5, st, 0, 2));
+  // fold1 of both streams (paired launches) and the point half of the global fold2/conv1
+  for (int b = 0; b < B; b += hb) {
+    const size_t o = (size_t)b * N;
+    DISN_RC(mlp_fold1_h2(mw, pts_rot + o * 3, N, m, b, o, hb, ms, strict));
+    DISN_RC(mlp_g4_pre_h2(mw, N, m, b, o, hb, m.g4pre + o * 512, ms, strict));
+  }
+  DISN_TRY(hipEventRecord(ctx->ev[kEvG4Pre], ms));
+  DISN_RC(vgg_features(vw, img, B, resized, taps, featmap, e.vgg, &pool5, st, 2, 13));
+  // the gather from the taps on the caller's stream, BEFORE the fc head: alone it takes 14 us, under fc6's HBM
+  // stream 65-70 us (r02q trace) -- and the local fold2 layers behind it are the critical path of the tail
+  // The kernel also leaves max |feat| per image in the slots the local fold2/conv1 reads its scale from (cleared
+  // by pt_embed on the auxiliary stream, hence the kEvG4Pre wait first -- recorded a whole convolution stack ago).
+  const int feat_ld = featmap ? DISN_FEAT_DIM : kFeatPad;
+  DISN_TRY(hipStreamWaitEvent(st, ctx->ev[kEvG4Pre], 0));
+  if (!featmap)
+    DISN_TRY(project_gather_taps_launch(taps, trans_mat, pts, B, N, 0, 5, e.q.feat, st, feat_ld,
+                                        h2_slots(m, 0) + kFeatMaxSlot, 1024));
+  if (ctx->pipe_record) DISN_TRY(hipEventRecord(ctx->pipe_record, st));  // the next step's convolutions may start
+  DISN_TRY(hipEventRecord(ctx->ev[kEvFeatures], st));
+  DISN_TRY(hipStreamWaitEvent(ms, ctx->ev[kEvFeatures], 0));
+  if (featmap) DISN_RC(gather_from_map(featmap, trans_mat, pts, B, N, e.q.feat, ms));
+  for (int b = 0; b < B; b += hb) {
+    const size_t o = (size_t)b * N;
+    DISN_RC(mlp_phase1_h2(mw, N, e.q.feat + o * feat_ld, feat_ld, m, b, o, hb, ms, !featmap, strict));
+  }
+  DISN_TRY(hipEventRecord(ctx->ev[kEvAuxDone], ms));
+  DISN_RC(vgg_head(vw, pool5, B, embedding, e.vgg, st));
+  DISN_RC(gbias_layer(mw, embedding, B, e.q.gbias, e.q.gemv_ws, st, vw->strict_forms == 1));
+  // global fold2/conv2 on relu(pre + bias) per image, then -- behind kEvAuxDone -- both fold2/conv5 and the sum
+  for (int b = 0; b < B; b += hb) {
+    const size_t o = (size_t)b * N;
+    DISN_RC(mlp_g5_h2(mw, N, m.g4pre + o * 512, e.q.gbias + (size_t)b * 512, m, b, o, hb, st, strict));
+  }
+  DISN_TRY(hipStreamWaitEvent(st, ctx->ev[kEvAuxDone], 0));
+  DISN_TRY(final_dot_launch(m.g5, m.l5, (int64_t)B * N, mw->g_w6, mw->g_b6, mw->l_w6, mw->l_b6, sdf, nullptr, nullptr,
+                            1.0f, st));
+  return 0;
+}
+
+// ENC_GEMM_CHAIN -- the three-term bf16 / f32-input GEMM layers over all B * N rows
+int encq_gemm_chain(disn_ctx_t* ctx, const disn_vgg_weights_t* vw, const disn_mlp_weights_t* mw, const float* img,
+                    const float* trans_mat, const float* pts, const float* pts_rot, int B, int N, float* resized,
+                    float* const taps[5], float* embedding, float* featmap, float* sdf, const EncQueryWs& e,
+                    hipStream_t st) {
+  const MlpWs& m = e.q.mlp;
+  hipStream_t ms = ctx->aux;
+  const float* pool5 = nullptr;
+  DISN_TRY(hipEventRecord(ctx->ev[kEvFork], st));  // fork (orders aux behind the caller's inputs)
+  DISN_TRY(hipStreamWaitEvent(ms, ctx->ev[kEvFork], 0));
+  DISN_RC(vgg_features(vw, img, B, resized, taps, featmap, e.vgg, &pool5, st, 0, 2));
+  DISN_TRY(pt_embed_launch(pts_rot, B * N, mw->g_w1, mw->g_b1, mw->l_w1, mw->l_b1, m.e1g, m.e1l, ms));
+  DISN_RC(mlp_fold1_global(mw, B * N, m, m.gemm_ws2, ms));
+  DISN_RC(mlp_g4_pre(mw, B * N, m, m.gemm_ws2, ms));
+  DISN_TRY(hipEventRecord(ctx->ev[kEvG4Pre], ms));
+  DISN_RC(vgg_features(vw, img, B, resized, taps, featmap, e.vgg, &pool5, st, 2, 13));
+  DISN_TRY(hipStreamWaitEvent(st, ctx->ev[kEvG4Pre], 0));   // (recorded behind g4_pre, a whole convolution stack ago)
+  if (ctx->pipe_record) DISN_TRY(hipEventRecord(ctx->pipe_record, st));  // the next step's convolutions may start
+  DISN_TRY(hipEventRecord(ctx->ev[kEvFeatures], st));
+  DISN_TRY(hipStreamWaitEvent(ms, ctx->ev[kEvFeatures], 0));
+  DISN_RC(mlp_fold1_local(mw, B * N, m, m.gemm_ws, ms));
+  if (featmap) DISN_RC(gather_from_map(featmap, trans_mat, pts, B, N, e.q.feat, ms));
+  else  // no map: up-sample the taps at the touched pixels (bit-identical), all images in one launch
+    DISN_TRY(project_gather_taps_launch(taps, trans_mat, pts, B, N, 0, 5, e.q.feat, ms, DISN_FEAT_DIM));
+  DISN_RC(mlp_phase1(mw, B * N, e.q.feat, m, ms));
+  DISN_TRY(hipEventRecord(ctx->ev[kEvAuxDone], ms));
+  DISN_RC(vgg_head(vw, pool5, B, embedding, e.vgg, st));
+  DISN_RC(gbias_layer(mw, embedding, B, e.q.gbias, e.q.gemv_ws, st, vw->strict_forms == 1));
+  // bias + ReLU of the split layer, fold2/conv2, then -- behind kEvAuxDone -- the final sum
+  return mlp_phase2_split(mw, B, N, e.q.gbias, sdf, m, st, ctx->ev[kEvAuxDone]);
+}
+
+// ---- the chunked queries ---------------------------------------------------------------------------------------------
+// what the local stream of a chunk reads: feature rows gathered by the caller (disn_sdf_mlp), the feature map
+// (disn_query*), or the folded map (disn_query*_folded, disn_fold_local)
+enum LocalSrc { SRC_FEAT_ROWS, SRC_FEATMAP, SRC_PMAP };
+
+// B images x N points in chunks of at most `chunk` points of one image; q.gbias holds the images' folded bias rows
+int mlp_images(const disn_mlp_weights_t* w, LocalSrc src, const float* local, const float* trans_mat, const float* pts,
+               const float* pts_rot, int B, int N, float* sdf, float* sdf_g, float* sdf_l, const QueryWs& q, int chunk,
+               hipStream_t st) {
+  const size_t map_stride = (size_t)DISN_IMG_H * DISN_IMG_W * DISN_FEAT_DIM;
+  for (int b = 0; b < B; ++b)
+    for (int n0 = 0; n0 < N; n0 += chunk) {
+      const int n = (N - n0) < chunk ? (N - n0) : chunk;
+      const size_t o = (size_t)b * N + n0;
+      const float* gbias_b = q.gbias + (size_t)b * 512;
+      if (src == SRC_PMAP) {
+        DISN_RC(mlp_chunk_folded(w, pts + o * 3, pts_rot + o * 3, n, gbias_b, local + (size_t)b * kMapPixels * 512,
+                                 trans_mat + (size_t)b * 12, sdf + o, 1.0f, q.mlp, st));
+        continue;
+      }
+      if (src == SRC_FEATMAP)
+        DISN_TRY(project_gather_launch(local + b * map_stride, trans_mat + (size_t)b * 12, pts + o * 3, n, q.feat, st));
+      const float* feat = src == SRC_FEATMAP ? q.feat : local + o * DISN_FEAT_DIM;
+      DISN_RC(mlp_chunk(w, pts_rot + o * 3, n, gbias_b, feat, sdf + o, sdf_g ? sdf_g + o : nullptr,
+                        sdf_l ? sdf_l + o : nullptr, 1.0f, q.mlp, st));
+    }
+  return 0;
+}
+
+// disn_query (map = featmap) and disn_query_folded (map = pmap)
+int query_impl(const disn_mlp_weights_t* w, bool folded, const float* map, const float* embedding,
+               const float* trans_mat, const float* pts, const float* pts_rot, int B, int N, float* sdf, void* ws,
+               size_t ws_bytes, hipStream_t st) {
+  if (!mlp_weights_ok(w) || (folded && !w->l_w4_point) || !map || !embedding || !trans_mat || !pts || !pts_rot ||
+      !sdf || !ws || B <= 0 || N <= 0)
+    return DISN_E_ARG;
+  const int chunk = chunk_for(N);
+  const QueryWs q = query_layout(ws, B, chunk, true, false);
+  if (q.total > ws_bytes) return DISN_E_WS;
+  if (folded) DISN_TRY(hipMemsetAsync(q.mlp.zero512, 0, 512 * sizeof(float), st));
+  DISN_RC(gbias_layer(w, embedding, B, q.gbias, q.gemv_ws, st));
+  return mlp_images(w, folded ? SRC_PMAP : SRC_FEATMAP, map, trans_mat, pts, pts_rot, B, N, sdf, nullptr, nullptr, q,
+                    chunk, st);
+}
+
+// disn_query_grid (map = featmap of the image) and disn_query_grid_folded (map = its pmap)
+int query_grid_impl(const disn_mlp_weights_t* w, bool folded, const float* map, const float* embedding,
+                    const float* trans_mat, const double* sdf_params_host, int R, int64_t k0, int64_t k1,
+                    float sdf_weight, float* out, void* ws, size_t ws_bytes, hipStream_t st) {
+  GridSpec g;
+  if (!mlp_weights_ok(w) || (folded && !w->l_w4_point) || !map || !embedding || !trans_mat || !out || !ws ||
+      !grid_range(sdf_params_host, R, k0, k1, &g) || sdf_weight == 0.0f)
+    return DISN_E_ARG;
+  const int chunk = chunk_for(k1 - k0);
+  const QueryWs q = query_layout(ws, 1, chunk, true, true);
+  if (q.total > ws_bytes) return DISN_E_WS;
+  if (folded) DISN_TRY(hipMemsetAsync(q.mlp.zero512, 0, 512 * sizeof(float), st));
+  DISN_RC(gbias_layer(w, embedding, 1, q.gbias, q.gemv_ws, st));
+  for (int64_t k = k0; k < k1; k += chunk) {
+    const int n = (int)((k1 - k) < chunk ? (k1 - k) : chunk);
+    DISN_TRY(grid_points_launch(g, k, k + n, q.pts, st));
+    // sample_pc == sample_pc_rot on this caller (test/create_sdf.py:268-269)
+    if (folded) {
+      DISN_RC(mlp_chunk_folded(w, q.pts, q.pts, n, q.gbias, map, trans_mat, out + (k - k0), sdf_weight, q.mlp, st));
+    } else {
+      DISN_TRY(project_gather_launch(map, trans_mat, q.pts, n, q.feat, st));
+      DISN_RC(mlp_chunk(w, q.pts, n, q.gbias, q.feat, out + (k - k0), nullptr, nullptr, sdf_weight, q.mlp, st));
+    }
+  }
+  return 0;
 }
 
 }  // namespace
@@ -806,31 +1083,24 @@ int disn_ctx_destroy(disn_ctx_t* c) {
 int disn_vgg16_forward(const disn_vgg_weights_t* w, const float* img, int B, float* resized224,
                        float* const taps[5], float* embedding, void* ws, size_t ws_bytes,
                        void* stream) {
-  if (!vgg_weights_ok(w) || !img || !taps || !embedding || !ws || B <= 0) return DISN_E_ARG;
-  for (int i = 0; i < 5; ++i)
-    if (!taps[i]) return DISN_E_ARG;
+  if (!vgg_weights_ok(w) || !img || !taps_ok(taps) || !embedding || !ws || B <= 0) return DISN_E_ARG;
   if (w->num_classes <= 0 || w->num_classes % 256) return DISN_E_SHAPE;
   hipStream_t st = (hipStream_t)stream;
   const VggWs s = vgg_layout(ws, B, w->num_classes);
   if (s.total > ws_bytes) return DISN_E_WS;
   const float* pool5 = nullptr;
-  int rc = vgg_features(w, img, B, resized224 ? resized224 : s.resized, taps, nullptr, s,
-                        &pool5, st);
-  if (rc) return rc;
+  DISN_RC(vgg_features(w, img, B, resized224 ? resized224 : s.resized, taps, nullptr, s, &pool5, st));
   return vgg_head(w, pool5, B, embedding, s, st);
 }
 
 int disn_vgg16_conv_stack(const disn_vgg_weights_t* w, const float* img, int B, float* resized224,
                           float* const taps[5], float* pool5, void* ws, size_t ws_bytes, void* stream) {
-  if (!vgg_weights_ok(w) || !img || !taps || !ws || B <= 0) return DISN_E_ARG;
-  for (int i = 0; i < 5; ++i)
-    if (!taps[i]) return DISN_E_ARG;
+  if (!vgg_weights_ok(w) || !img || !taps_ok(taps) || !ws || B <= 0) return DISN_E_ARG;
   hipStream_t st = (hipStream_t)stream;
   const VggWs s = vgg_layout(ws, B, w->num_classes > 0 ? w->num_classes : DISN_EMBED_DIM);
   if (s.total > ws_bytes) return DISN_E_WS;
   const float* p5 = nullptr;
-  const int rc = vgg_features(w, img, B, resized224 ? resized224 : s.resized, taps, nullptr, s, &p5, st);
-  if (rc) return rc;
+  DISN_RC(vgg_features(w, img, B, resized224 ? resized224 : s.resized, taps, nullptr, s, &p5, st));
   if (pool5) DISN_TRY(hipMemcpyAsync(pool5, p5, (size_t)B * 7 * 7 * 512 * sizeof(float), hipMemcpyDeviceToDevice, st));
   return 0;
 }
@@ -840,18 +1110,15 @@ size_t disn_encode_workspace_bytes(int B) { return disn_vgg16_workspace_bytes(B)
 int disn_encode(disn_ctx_t* ctx, const disn_vgg_weights_t* w, const float* img, int B,
                 float* resized224, float* const taps[5], float* embedding, float* featmap, void* ws,
                 size_t ws_bytes, void* stream) {
-  if (!vgg_weights_ok(w) || !img || !taps || !embedding || !featmap || !ws || B <= 0)
+  if (!vgg_weights_ok(w) || !img || !taps_ok(taps) || !embedding || !featmap || !ws || B <= 0)
     return DISN_E_ARG;
-  for (int i = 0; i < 5; ++i)
-    if (!taps[i]) return DISN_E_ARG;
   if (w->num_classes <= 0 || w->num_classes % 256) return DISN_E_SHAPE;
   hipStream_t st = (hipStream_t)stream;
   const VggWs s = vgg_layout(ws, B, w->num_classes);
   if (s.total > ws_bytes) return DISN_E_WS;
   (void)ctx;  // everything runs on `st`: nothing in the encoder alone is worth a second stream
   const float* pool5 = nullptr;
-  int rc = vgg_features(w, img, B, resized224 ? resized224 : s.resized, taps, featmap, s, &pool5, st);
-  if (rc) return rc;
+  DISN_RC(vgg_features(w, img, B, resized224 ? resized224 : s.resized, taps, featmap, s, &pool5, st));
   return vgg_head(w, pool5, B, embedding, s, st);
 }
 
@@ -866,159 +1133,32 @@ int disn_encode_query(disn_ctx_t* ctx, const disn_vgg_weights_t* vw, const disn_
                       float* embedding, float* featmap, float* sdf, void* ws, size_t ws_bytes,
                       void* stream) {
   if (!ctx || !vgg_weights_ok(vw) || !mlp_weights_ok(mw) || !img || !trans_mat || !pts || !pts_rot ||
-      !taps || !embedding || !sdf || !ws || B <= 0 || N <= 0)
+      !taps_ok(taps) || !embedding || !sdf || !ws || B <= 0 || N <= 0)
     return DISN_E_ARG;
-  for (int i = 0; i < 5; ++i)
-    if (!taps[i]) return DISN_E_ARG;
   if ((long)B * N > kChunk || vw->num_classes != DISN_EMBED_DIM) return DISN_E_SHAPE;
   hipStream_t st = (hipStream_t)stream;
-  const int N0 = N;
   const EncQueryWs e = encq_layout(ws, B, N, vw->num_classes);
   if (e.total > ws_bytes) return DISN_E_WS;
-  // Two streams.  `st` (the caller's): resize, conv stack, fc6..fc8, the folded global bias, then the
-  // short tail of the global MLP stream.  ctx->aux: everything of the MLPs that does not need the
-  // embedding -- from the fork on the point-only layers of both streams and the point half of the
-  // global fold2/conv1 (small GEMMs in the quantisation holes of the convolutions); behind conv5_3 the
-  // gather and the local fold2 layers (MFMA bound), under the 495 MB fc weight stream (HBM bound).
-  // Every event record / wait on `st` drains it (~6 us in the kernel trace): there are three.
-  // Measured on MI355X (tools/overlap_sweep.py, cfg2 step of build r01c): single stream 0.886 ms, MLP
-  // under the fc head 0.797 ms.  Two other overlaps were tried and removed: the 110 MB tap up-samples
-  // on the auxiliary stream under the convolutions (0.86-0.98 ms at every throttle: their streamed
-  // writes disturb the latency-sensitive convolution loads) and a trickle read of the fc6 weights
-  // into the memory-side cache under conv4/conv5 (no gain up to 200 MB, slower beyond).
-  hipStream_t ms = ctx->aux;
-  int rc;
-  // Schedule (r02i / r02j traces).  The convolution kernels from conv2 on are ONE round of 112..224 workgroups that
-  // each fill a CU: a point-MLP GEMM running beside them takes CUs away and doubles a layer (18 -> 34 us), so
-  // nothing runs beside conv2_1 .. conv5_3.  `st`: resize, the convolutions, the HBM-bound fc head, the short
-  // global tail.  ctx->aux: from the fork, the point embedding, the GLOBAL stream's fold1 and the point half of its
-  // fold2/conv1 -- ~45 us of small launches beside resize / conv1_1 / conv1_2 (VALU work and a two-round kernel,
-  // measured unaffected) -- then, behind conv5_3, the LOCAL stream's fold1, the gather and fold2 under the fc head.
-  const float* pool5 = nullptr;
+  float* resized = resized224 ? resized224 : e.vgg.resized;
   if (ctx->pipe_wait) DISN_TRY(hipStreamWaitEvent(st, ctx->pipe_wait, 0));  // behind the previous step's convolutions
-  // Round 4: a batched call (>= kConvWideMinImages images) with the fused small-set kernels -- nothing runs beside the
-  // convolutions; behind conv5_3 the auxiliary stream gathers (split form) and runs the local stream's one launch
-  // under the fc head; the global stream's one launch follows the folded bias and adds the local sums.
-  bool conv_h2_all = true;
-  for (int i = 0; i < 13; ++i) conv_h2_all = conv_h2_all && vw->conv_w_h2[i] != nullptr;
-  // (a call of one to three requests keeps the layer-by-layer dense_h2 form below 8192 points per request -- its bits
-  // are a B = 1 call's; from 8192 points on it takes the fused kernels too: 2.13 -> 1.40 ms for one request of 65536 points
-  // against the three-term GEMM chain this shape ran until round 4, tools/encode_query_forms_time.py)
-  const int Np = pad128(N);
-  // "strict" (disn_vgg_weights_t.strict_forms = 1) in a call of >= 4 requests: the single-image forms of the convolutions
-  // (vgg_features) AND of the point-MLP layers (dense_h2.hip's four-k-wave tiles, per-image scales) -- the request's taps
-  // and, up to the fc head's form, its pred_sdf are those of the request alone
-  const bool strict = vw->strict_forms == 1 && B >= kConvWideMinImages && mlp_h2(mw, N);
-  if (!strict && conv_h2_all && !featmap && (B >= kConvWideMinImages || N >= 8192) && fused_small_ok(mw, B, Np)) {
-    float* sdf_out = sdf;
-    if (Np != N) {   // pad the point sets (both streams run behind the fork / the convolutions anyway)
-      DISN_TRY(restride_rows_launch(pts, B, N, e.pad_pts, Np, 3, st));
-      if (pts_rot != pts) DISN_TRY(restride_rows_launch(pts_rot, B, N, e.pad_rot, Np, 3, st));
-      pts_rot = pts_rot != pts ? e.pad_rot : e.pad_pts;
-      pts = e.pad_pts;
-      sdf = e.pad_sdf;
-      N = Np;
-    }
-    rc = vgg_features(vw, img, B, resized224 ? resized224 : e.vgg.resized, taps, nullptr, e.vgg, &pool5, st);
-    if (rc) return rc;
-    DISN_TRY(hipEventRecord(ctx->ev[7], st));
-    DISN_TRY(hipStreamWaitEvent(ctx->aux, ctx->ev[7], 0));
-    static const int tap_layer[5] = {1, 3, 6, 9, 12};
-    const float* slots[5];
-    for (int k = 0; k < 5; ++k) slots[k] = e.vgg.amax + (size_t)B * 64 * (tap_layer[k] + 1);
-    if ((rc = fused_small_local(mw, taps, slots, 64, trans_mat, pts, pts_rot, B, N, e.q.feat, e.q.mlp.amax, e.q.mlp.l5,
-                                ctx->aux)))
-      return rc;
-    DISN_TRY(hipEventRecord(ctx->ev[6], ctx->aux));
-    if (ctx->pipe_record) DISN_TRY(hipEventRecord(ctx->pipe_record, st));
-    if ((rc = vgg_head(vw, pool5, B, embedding, e.vgg, st))) return rc;
-    { const int grc = gbias_layer(mw, embedding, B, e.q.gbias, e.q.gemv_ws, st, vw->strict_forms == 1); if (grc) return grc; }
-    DISN_TRY(hipStreamWaitEvent(st, ctx->ev[6], 0));
-    if ((rc = fused_small_global(mw, e.q.gbias, pts_rot, B, N, e.q.mlp.l5, sdf, 1.0f, st))) return rc;
-    if (sdf != sdf_out) DISN_TRY(restride_rows_launch(sdf, B, N, sdf_out, N0, 1, st));
-    return 0;
+  const EncPlan p = encq_plan(vw, mw, B, N, featmap != nullptr);
+  switch (p.form) {
+    case ENC_FUSED_SMALL:
+      return encq_fused_small(ctx, vw, mw, img, trans_mat, pts, pts_rot, B, N, resized, taps, embedding, sdf, e, st);
+    case ENC_DENSE_H2:
+      return encq_dense_h2(ctx, vw, mw, img, trans_mat, pts, pts_rot, B, N, resized, taps, embedding, featmap, sdf,
+                           p.hb, p.strict, e, st);
+    default:
+      return encq_gemm_chain(ctx, vw, mw, img, trans_mat, pts, pts_rot, B, N, resized, taps, embedding, featmap, sdf,
+                             e, st);
   }
-  const bool h2 = B <= kH2Imgs && mlp_h2(mw, N);   // small point sets: the dense_h2 layers, image by image
-  const int feat_ld = h2 && !featmap ? kFeatPad : DISN_FEAT_DIM;
-  const int hb = h2 && N % 64 == 0 ? B : 1;   // images per h2 launch
-  DISN_TRY(hipEventRecord(ctx->ev[0], st));  // fork (orders aux behind the caller's inputs)
-  DISN_TRY(hipStreamWaitEvent(ctx->aux, ctx->ev[0], 0));
-  // host order: the caller's stream gets resize, conv1_1, conv1_2 first (it must never wait for the host), then
-  // the auxiliary stream its launches, then the rest of the stack
-  rc = vgg_features(vw, img, B, resized224 ? resized224 : e.vgg.resized, taps, featmap, e.vgg, &pool5, st, 0, 2);
-  if (rc) return rc;
-  if (h2) {  // fold1 of both streams (paired launches) and the point half of the global fold2/conv1: one launch
-             // per layer for the whole batch (hb = B images at once) or image by image (hb = 1)
-    for (int b = 0; b < B; b += hb) {
-      const size_t o = (size_t)b * N;
-      if ((rc = mlp_fold1_h2(mw, pts_rot + o * 3, N, e.q.mlp, b, o, hb, ctx->aux, strict))) return rc;
-      if ((rc = mlp_g4_pre_h2(mw, N, e.q.mlp, b, o, hb, e.q.mlp.g4pre + o * 512, ctx->aux, strict))) return rc;
-    }
-  } else {
-    DISN_TRY(pt_embed_launch(pts_rot, B * N, mw->g_w1, mw->g_b1, mw->l_w1, mw->l_b1, e.q.mlp.e1g, e.q.mlp.e1l, ctx->aux));
-    if ((rc = mlp_fold1_global(mw, B * N, e.q.mlp, e.q.mlp.gemm_ws2, ctx->aux))) return rc;
-    if ((rc = mlp_g4_pre(mw, B * N, e.q.mlp, e.q.mlp.gemm_ws2, ctx->aux))) return rc;
-  }
-  DISN_TRY(hipEventRecord(ctx->ev[8], ctx->aux));
-  rc = vgg_features(vw, img, B, resized224 ? resized224 : e.vgg.resized, taps, featmap, e.vgg, &pool5, st, 2, 13);
-  if (rc) return rc;
-  // the gather from the taps on the caller's stream, BEFORE the fc head: alone it takes 14 us, under fc6's HBM
-  // stream 65-70 us (r02q trace) -- and the local fold2 layers behind it are the critical path of the tail
-  // The kernel also leaves max |feat| per image in the slots the local fold2/conv1 reads its scale from (cleared
-  // by pt_embed on the auxiliary stream, hence the ev[8] wait first -- recorded a whole convolution stack ago).
-  const bool gather_on_st = h2 && !featmap;
-  DISN_TRY(hipStreamWaitEvent(st, ctx->ev[8], 0));   // (recorded behind g4_pre, a whole convolution stack ago)
-  if (gather_on_st)
-    DISN_TRY(project_gather_taps_launch(taps, trans_mat, pts, B, N, 0, 5, e.q.feat, st, feat_ld,
-                                        h2_slots(e.q.mlp, 0) + kFeatMaxSlot, 1024));
-  if (ctx->pipe_record) DISN_TRY(hipEventRecord(ctx->pipe_record, st));  // the next step's convolutions may start
-  DISN_TRY(hipEventRecord(ctx->ev[7], st));
-  DISN_TRY(hipStreamWaitEvent(ctx->aux, ctx->ev[7], 0));
-  if (!h2 && (rc = mlp_fold1_local(mw, B * N, e.q.mlp, e.q.mlp.gemm_ws, ctx->aux))) return rc;
-  if (gather_on_st) {
-    // done above
-  } else if (featmap) {
-    const size_t map_stride = (size_t)DISN_IMG_H * DISN_IMG_W * DISN_FEAT_DIM;
-    for (int b = 0; b < B; ++b)
-      DISN_TRY(project_gather_launch(featmap + b * map_stride, trans_mat + (size_t)b * 12,
-                                     pts + (size_t)b * N * 3, N,
-                                     e.q.feat + (size_t)b * N * DISN_FEAT_DIM, ms));
-  } else {  // no map: up-sample the taps at the touched pixels (bit-identical), all images in one launch
-    DISN_TRY(project_gather_taps_launch(taps, trans_mat, pts, B, N, 0, 5, e.q.feat, ms, feat_ld));
-  }
-  if (h2) {
-    for (int b = 0; b < B; b += hb) {
-      const size_t o = (size_t)b * N;
-      if ((rc = mlp_phase1_h2(mw, N, e.q.feat + o * feat_ld, feat_ld, e.q.mlp, b, o, hb, ms, gather_on_st, strict))) return rc;
-    }
-  } else if ((rc = mlp_phase1(mw, B * N, e.q.feat, e.q.mlp, ms))) return rc;
-  DISN_TRY(hipEventRecord(ctx->ev[6], ctx->aux));
-  if ((rc = vgg_head(vw, pool5, B, embedding, e.vgg, st))) return rc;
-  { const int grc = gbias_layer(mw, embedding, B, e.q.gbias, e.q.gemv_ws, st, vw->strict_forms == 1); if (grc) return grc; }
-  if (h2) {  // global fold2/conv2 on relu(pre + bias) per image, then -- behind ev[6] -- both fold2/conv5 and the sum
-    for (int b = 0; b < B; b += hb) {
-      const size_t o = (size_t)b * N;
-      if ((rc = mlp_g5_h2(mw, N, e.q.mlp.g4pre + o * 512, e.q.gbias + (size_t)b * 512, e.q.mlp, b, o, hb, st, strict))) return rc;
-    }
-    DISN_TRY(hipStreamWaitEvent(st, ctx->ev[6], 0));
-    DISN_TRY(final_dot_launch(e.q.mlp.g5, e.q.mlp.l5, (int64_t)B * N, mw->g_w6, mw->g_b6, mw->l_w6, mw->l_b6, sdf, nullptr,
-                              nullptr, 1.0f, st));
-    return 0;
-  }
-  // bias + ReLU of the split layer, fold2/conv2, then -- behind ev[6] -- the final sum
-  return mlp_phase2_split(mw, B, N, e.q.gbias, sdf, e.q.mlp, st, ctx->ev[6]);
 }
 
 int disn_build_featmap(const float* const taps[5], int B, float* featmap, void* stream) {
-  if (!taps || !featmap || B <= 0) return DISN_E_ARG;
-  const int hw[5] = {224, 112, 56, 28, 14}, ch[5] = {64, 128, 256, 512, 512};
-  int coff = 0;
-  for (int i = 0; i < 5; ++i) {
-    if (!taps[i]) return DISN_E_ARG;
-    DISN_TRY(resize_bilinear_launch(taps[i], B, hw[i], hw[i], ch[i], featmap, DISN_IMG_H,
-                                    DISN_IMG_W, DISN_FEAT_DIM, coff, (hipStream_t)stream));
-    coff += ch[i];
-  }
+  if (!taps_ok(taps) || !featmap || B <= 0) return DISN_E_ARG;
+  for (int i = 0; i < 5; ++i)
+    DISN_TRY(resize_bilinear_launch(taps[i], B, kTap[i].hw, kTap[i].hw, kTap[i].ch, featmap, DISN_IMG_H,
+                                    DISN_IMG_W, DISN_FEAT_DIM, kTap[i].off, (hipStream_t)stream));
   return 0;
 }
 
@@ -1036,18 +1176,14 @@ int disn_gather(const float* featmap, const float* xy, int B, int N, float* feat
 
 int disn_gather_taps(const float* const taps[5], const float* trans_mat, const float* pts, int B, int N,
                      float* feat, void* stream) {
-  if (!taps || !trans_mat || !pts || !feat || B <= 0 || N <= 0) return DISN_E_ARG;
-  for (int i = 0; i < 5; ++i)
-    if (!taps[i]) return DISN_E_ARG;
+  if (!taps_ok(taps) || !trans_mat || !pts || !feat || B <= 0 || N <= 0) return DISN_E_ARG;
   DISN_TRY(project_gather_taps_launch(taps, trans_mat, pts, B, N, 0, 5, feat, (hipStream_t)stream));
   return 0;
 }
 
 int disn_gather_taps_split(const float* const taps[5], const float* trans_mat, const float* pts, int B, int N,
                            const float* feat_amax, void* feat_split, void* stream) {
-  if (!taps || !trans_mat || !pts || !feat_amax || !feat_split || B <= 0 || N <= 0) return DISN_E_ARG;
-  for (int i = 0; i < 5; ++i)
-    if (!taps[i]) return DISN_E_ARG;
+  if (!taps_ok(taps) || !trans_mat || !pts || !feat_amax || !feat_split || B <= 0 || N <= 0) return DISN_E_ARG;
   DISN_TRY(project_gather_taps_launch(taps, trans_mat, pts, B, N, 0, 5, static_cast<float*>(feat_split),
                                       (hipStream_t)stream, kFeatPad, nullptr, 0, 0, feat_amax));
   return 0;
@@ -1074,17 +1210,8 @@ int disn_sdf_mlp(const disn_mlp_weights_t* w, const float* pts_rot, const float*
   const int chunk = chunk_for(N);
   const QueryWs q = query_layout(ws, B, chunk, false, false);
   if (q.total > ws_bytes) return DISN_E_WS;
-  { const int grc = gbias_layer(w, embedding, B, q.gbias, q.gemv_ws, st); if (grc) return grc; }
-  for (int b = 0; b < B; ++b)
-    for (int n0 = 0; n0 < N; n0 += chunk) {
-      const int n = (N - n0) < chunk ? (N - n0) : chunk;
-      const size_t o = (size_t)b * N + n0;
-      const int rc = mlp_chunk(w, pts_rot + o * 3, n, q.gbias + (size_t)b * 512,
-                               feat + o * DISN_FEAT_DIM, sdf + o, sdf_global ? sdf_global + o : nullptr,
-                               sdf_local ? sdf_local + o : nullptr, 1.0f, q.mlp, st);
-      if (rc) return rc;
-    }
-  return 0;
+  DISN_RC(gbias_layer(w, embedding, B, q.gbias, q.gemv_ws, st));
+  return mlp_images(w, SRC_FEAT_ROWS, feat, nullptr, nullptr, pts_rot, B, N, sdf, sdf_global, sdf_local, q, chunk, st);
 }
 
 size_t disn_query_workspace_bytes(int B, int N) {
@@ -1095,26 +1222,8 @@ size_t disn_query_workspace_bytes(int B, int N) {
 int disn_query(const disn_mlp_weights_t* w, const float* featmap, const float* embedding,
                const float* trans_mat, const float* pts, const float* pts_rot, int B, int N,
                float* sdf, void* ws, size_t ws_bytes, void* stream) {
-  if (!mlp_weights_ok(w) || !featmap || !embedding || !trans_mat || !pts || !pts_rot || !sdf ||
-      !ws || B <= 0 || N <= 0)
-    return DISN_E_ARG;
-  hipStream_t st = (hipStream_t)stream;
-  const int chunk = chunk_for(N);
-  const QueryWs q = query_layout(ws, B, chunk, true, false);
-  if (q.total > ws_bytes) return DISN_E_WS;
-  { const int grc = gbias_layer(w, embedding, B, q.gbias, q.gemv_ws, st); if (grc) return grc; }
-  const size_t map_stride = (size_t)DISN_IMG_H * DISN_IMG_W * DISN_FEAT_DIM;
-  for (int b = 0; b < B; ++b)
-    for (int n0 = 0; n0 < N; n0 += chunk) {
-      const int n = (N - n0) < chunk ? (N - n0) : chunk;
-      const size_t o = (size_t)b * N + n0;
-      DISN_TRY(project_gather_launch(featmap + b * map_stride, trans_mat + (size_t)b * 12,
-                                     pts + o * 3, n, q.feat, st));
-      const int rc = mlp_chunk(w, pts_rot + o * 3, n, q.gbias + (size_t)b * 512, q.feat, sdf + o,
-                               nullptr, nullptr, 1.0f, q.mlp, st);
-      if (rc) return rc;
-    }
-  return 0;
+  return query_impl(w, false, featmap, embedding, trans_mat, pts, pts_rot, B, N, sdf, ws, ws_bytes,
+                    (hipStream_t)stream);
 }
 
 // ---- folded local stream (include/disn_amd.h) -------------------------------------------------
@@ -1143,51 +1252,15 @@ int disn_fold_local(const disn_mlp_weights_t* w, const float* featmap_b, float* 
 int disn_query_folded(const disn_mlp_weights_t* w, const float* pmap, const float* embedding,
                       const float* trans_mat, const float* pts, const float* pts_rot, int B, int N,
                       float* sdf, void* ws, size_t ws_bytes, void* stream) {
-  if (!mlp_weights_ok(w) || !w->l_w4_point || !pmap || !embedding || !trans_mat || !pts || !pts_rot ||
-      !sdf || !ws || B <= 0 || N <= 0)
-    return DISN_E_ARG;
-  hipStream_t st = (hipStream_t)stream;
-  const int chunk = chunk_for(N);
-  const QueryWs q = query_layout(ws, B, chunk, true, false);
-  if (q.total > ws_bytes) return DISN_E_WS;
-  DISN_TRY(hipMemsetAsync(q.mlp.zero512, 0, 512 * sizeof(float), st));
-  { const int grc = gbias_layer(w, embedding, B, q.gbias, q.gemv_ws, st); if (grc) return grc; }
-  for (int b = 0; b < B; ++b)
-    for (int n0 = 0; n0 < N; n0 += chunk) {
-      const int n = (N - n0) < chunk ? (N - n0) : chunk;
-      const size_t o = (size_t)b * N + n0;
-      const int rc = mlp_chunk_folded(w, pts + o * 3, pts_rot + o * 3, n, q.gbias + (size_t)b * 512,
-                                      pmap + (size_t)b * kMapPixels * 512, trans_mat + (size_t)b * 12,
-                                      sdf + o, 1.0f, q.mlp, st);
-      if (rc) return rc;
-    }
-  return 0;
+  return query_impl(w, true, pmap, embedding, trans_mat, pts, pts_rot, B, N, sdf, ws, ws_bytes, (hipStream_t)stream);
 }
 
 int disn_query_grid_folded(const disn_mlp_weights_t* w, const float* pmap, const float* embedding,
                            const float* trans_mat, const double* sdf_params_host, int R,
                            int64_t k0, int64_t k1, float sdf_weight, float* out, void* ws,
                            size_t ws_bytes, void* stream) {
-  GridSpec g;
-  if (!mlp_weights_ok(w) || !w->l_w4_point || !pmap || !embedding || !trans_mat || !out || !ws ||
-      !grid_spec(sdf_params_host, R, &g))
-    return DISN_E_ARG;
-  const int64_t total = (int64_t)g.res * g.res * g.res;
-  if (k0 < 0 || k1 > total || k0 >= k1 || sdf_weight == 0.0f) return DISN_E_ARG;
-  hipStream_t st = (hipStream_t)stream;
-  const int chunk = chunk_for(k1 - k0);
-  const QueryWs q = query_layout(ws, 1, chunk, true, true);
-  if (q.total > ws_bytes) return DISN_E_WS;
-  DISN_TRY(hipMemsetAsync(q.mlp.zero512, 0, 512 * sizeof(float), st));
-  { const int grc = gbias_layer(w, embedding, 1, q.gbias, q.gemv_ws, st); if (grc) return grc; }
-  for (int64_t k = k0; k < k1; k += chunk) {
-    const int n = (int)((k1 - k) < chunk ? (k1 - k) : chunk);
-    DISN_TRY(grid_points_launch(g, k, k + n, q.pts, st));
-    const int rc = mlp_chunk_folded(w, q.pts, q.pts, n, q.gbias, pmap, trans_mat, out + (k - k0),
-                                    sdf_weight, q.mlp, st);
-    if (rc) return rc;
-  }
-  return 0;
+  return query_grid_impl(w, true, pmap, embedding, trans_mat, sdf_params_host, R, k0, k1, sdf_weight, out, ws,
+                         ws_bytes, (hipStream_t)stream);
 }
 
 // ---- fused point MLP (mlp_fused.hip) -----------------------------------------------------------------
@@ -1239,42 +1312,29 @@ size_t disn_query_taps_fused_workspace_bytes(int B, int N) {
 int disn_query_taps_fused(const disn_mlp_weights_t* w, const float* const taps[5], const float* embedding,
                           const float* trans_mat, const float* pts, const float* pts_rot, int B, int N, float* sdf,
                           void* ws, size_t ws_bytes, void* stream) {
-  if (!mlp_weights_ok(w) || !w->g_fused || !w->l_feat || !taps || !embedding || !trans_mat || !pts || !pts_rot || !sdf ||
-      !ws || B <= 0 || N <= 0)
+  if (!mlp_weights_ok(w) || !w->g_fused || !w->l_feat || !taps_ok(taps) || !embedding || !trans_mat || !pts ||
+      !pts_rot || !sdf || !ws || B <= 0 || N <= 0)
     return DISN_E_ARG;
-  for (int i = 0; i < 5; ++i)
-    if (!taps[i]) return DISN_E_ARG;
-  const int N0 = N, Np = pad128(N);
-  if ((long)B * Np > kChunk) return DISN_E_SHAPE;
+  if ((long)B * pad128(N) > kChunk) return DISN_E_SHAPE;
   hipStream_t st = (hipStream_t)stream;
-  const TapsFusedWs f = taps_fused_layout(ws, B, Np);
+  const TapsFusedWs f = taps_fused_layout(ws, B, pad128(N));
   if (f.total > ws_bytes) return DISN_E_WS;
-  float* sdf_out = sdf;
-  if (Np != N) {   // pad points (0, 0, 0) in, the first N results out (see pad128)
-    DISN_TRY(restride_rows_launch(pts, B, N, f.pad_pts, Np, 3, st));
-    if (pts_rot != pts) DISN_TRY(restride_rows_launch(pts_rot, B, N, f.pad_rot, Np, 3, st));
-    pts_rot = pts_rot != pts ? f.pad_rot : f.pad_pts;
-    pts = f.pad_pts;
-    sdf = f.pad_sdf;
-    N = Np;
-  }
+  PaddedSets p;
+  DISN_RC(pad_sets(pts, pts_rot, sdf, B, N, f.pad_pts, f.pad_rot, f.pad_sdf, st, &p));
   // the taps' exact maxima, per image (inside disn_encode_query they come out of the convolutions' epilogues: the
   // same numbers, hence the same split scale and the same bits)
-  static const int hw[5] = {224, 112, 56, 28, 14}, ch[5] = {64, 128, 256, 512, 512};
   DISN_TRY(hipMemsetAsync(f.slots, 0, (size_t)5 * B * 64 * sizeof(float), st));
   const float* slots[5];
+  float* tp[5];
   for (int k = 0; k < 5; ++k) {
     slots[k] = f.slots + (size_t)k * B * 64;
-    DISN_TRY(amax64_accumulate_launch(taps[k], (size_t)hw[k] * hw[k] * ch[k], f.slots + (size_t)k * B * 64, st, B, 64));
+    tp[k] = const_cast<float*>(taps[k]);
+    DISN_TRY(amax64_accumulate_launch(taps[k], (size_t)kTap[k].hw * kTap[k].hw * kTap[k].ch,
+                                      f.slots + (size_t)k * B * 64, st, B, 64));
   }
-  float* tp[5];
-  for (int k = 0; k < 5; ++k) tp[k] = const_cast<float*>(taps[k]);
-  int rc = fused_small_local(w, tp, slots, 64, trans_mat, pts, pts_rot, B, N, f.feat, f.featmax, f.lsum, st);
-  if (rc) return rc;
-  { const int grc = gbias_layer(w, embedding, B, f.gbias, f.gemv_ws, st); if (grc) return grc; }
-  if ((rc = fused_small_global(w, f.gbias, pts_rot, B, N, f.lsum, sdf, 1.0f, st))) return rc;
-  if (sdf != sdf_out) DISN_TRY(restride_rows_launch(sdf, B, N, sdf_out, N0, 1, st));
-  return 0;
+  DISN_RC(fused_small_local(w, tp, slots, 64, trans_mat, p.pts, p.pts_rot, B, p.N, f.feat, f.featmax, f.lsum, st));
+  DISN_RC(fused_small_global(w, embedding, false, f.gbias, f.gemv_ws, p.pts_rot, B, p.N, f.lsum, p.sdf, nullptr, st));
+  return unpad_sdf(p, B, N, sdf, st);
 }
 
 int disn_amax(const float* x, int64_t n, float* out, void* stream) {
@@ -1329,13 +1389,12 @@ int disn_query_fused(const disn_mlp_weights_t* w, const float* pmap, const float
   hipStream_t st = (hipStream_t)stream;
   const FusedWs f = fused_layout(ws, B, N);
   if (f.total > ws_bytes) return DISN_E_WS;
-  { const int grc = gbias_layer(w, embedding, B, f.gbias, f.gemv_ws, st); if (grc) return grc; }
+  DISN_RC(gbias_layer(w, embedding, B, f.gbias, f.gemv_ws, st));
   for (int b = 0; b < B; ++b) {
     const size_t o = (size_t)b * N;
-    const int rc = fused_streams(w, f.gbias + (size_t)b * 512, pmap + (size_t)b * kMapPixels * 512, pmap_amax + b,
-                                 trans_mat + (size_t)b * 12, pts + o * 3, pts_rot + o * 3, nullptr, 0, N, f.gsum,
-                                 sdf + o, 1.0f, st);
-    if (rc) return rc;
+    DISN_RC(fused_streams(w, f.gbias + (size_t)b * 512, pmap + (size_t)b * kMapPixels * 512, pmap_amax + b,
+                          trans_mat + (size_t)b * 12, pts + o * 3, pts_rot + o * 3, nullptr, 0, N, f.gsum,
+                          sdf + o, 1.0f, st));
   }
   return 0;
 }
@@ -1351,14 +1410,12 @@ int disn_query_grid_fused(const disn_mlp_weights_t* w, const float* pmap, const 
                           void* stream) {
   GridSpec g;
   if (!fused_ok(w) || !pmap || !pmap_amax || !embedding || !trans_mat || !out || !ws ||
-      !grid_spec(sdf_params_host, R, &g))
+      !grid_range(sdf_params_host, R, k0, k1, &g) || sdf_weight == 0.0f)
     return DISN_E_ARG;
-  const int64_t total = (int64_t)g.res * g.res * g.res;
-  if (k0 < 0 || k1 > total || k0 >= k1 || sdf_weight == 0.0f) return DISN_E_ARG;
   hipStream_t st = (hipStream_t)stream;
   const FusedWs f = fused_layout(ws, 1, k1 - k0);
   if (f.total > ws_bytes) return DISN_E_WS;
-  { const int grc = gbias_layer(w, embedding, 1, f.gbias, f.gemv_ws, st); if (grc) return grc; }
+  DISN_RC(gbias_layer(w, embedding, 1, f.gbias, f.gemv_ws, st));
   // one launch per stream over the whole range: no chunking, no per-point workspace but the global sums
   return fused_streams(w, f.gbias, pmap, pmap_amax, trans_mat, nullptr, nullptr, &g, k0, k1 - k0, f.gsum, out,
                        sdf_weight, st);
@@ -1367,9 +1424,7 @@ int disn_query_grid_fused(const disn_mlp_weights_t* w, const float* pmap, const 
 int disn_grid_points(const double* sdf_params_host, int R, int64_t k0, int64_t k1, float* pts,
                      void* stream) {
   GridSpec g;
-  if (!pts || !grid_spec(sdf_params_host, R, &g)) return DISN_E_ARG;
-  const int64_t total = (int64_t)g.res * g.res * g.res;
-  if (k0 < 0 || k1 > total || k0 >= k1) return DISN_E_ARG;
+  if (!pts || !grid_range(sdf_params_host, R, k0, k1, &g)) return DISN_E_ARG;
   DISN_TRY(grid_points_launch(g, k0, k1, pts, (hipStream_t)stream));
   return 0;
 }
@@ -1383,27 +1438,8 @@ int disn_query_grid(const disn_mlp_weights_t* w, const float* featmap, const flo
                     const float* trans_mat, const double* sdf_params_host, int R, int64_t k0,
                     int64_t k1, float sdf_weight, float* out, void* ws, size_t ws_bytes,
                     void* stream) {
-  GridSpec g;
-  if (!mlp_weights_ok(w) || !featmap || !embedding || !trans_mat || !out || !ws ||
-      !grid_spec(sdf_params_host, R, &g))
-    return DISN_E_ARG;
-  const int64_t total = (int64_t)g.res * g.res * g.res;
-  if (k0 < 0 || k1 > total || k0 >= k1 || sdf_weight == 0.0f) return DISN_E_ARG;
-  hipStream_t st = (hipStream_t)stream;
-  const int chunk = chunk_for(k1 - k0);
-  const QueryWs q = query_layout(ws, 1, chunk, true, true);
-  if (q.total > ws_bytes) return DISN_E_WS;
-  { const int grc = gbias_layer(w, embedding, 1, q.gbias, q.gemv_ws, st); if (grc) return grc; }
-  for (int64_t k = k0; k < k1; k += chunk) {
-    const int n = (int)((k1 - k) < chunk ? (k1 - k) : chunk);
-    DISN_TRY(grid_points_launch(g, k, k + n, q.pts, st));
-    DISN_TRY(project_gather_launch(featmap, trans_mat, q.pts, n, q.feat, st));
-    // sample_pc == sample_pc_rot on this caller (test/create_sdf.py:268-269)
-    const int rc = mlp_chunk(w, q.pts, n, q.gbias, q.feat, out + (k - k0), nullptr, nullptr,
-                             sdf_weight, q.mlp, st);
-    if (rc) return rc;
-  }
-  return 0;
+  return query_grid_impl(w, false, featmap, embedding, trans_mat, sdf_params_host, R, k0, k1, sdf_weight, out, ws,
+                         ws_bytes, (hipStream_t)stream);
 }
 
 // Same result as disn_query_grid, chunk-pipelined over two streams: the HBM-bound front of chunk
@@ -1422,10 +1458,8 @@ int disn_query_grid_ctx(disn_ctx_t* ctx, const disn_mlp_weights_t* w, const floa
                         float sdf_weight, float* out, void* ws, size_t ws_bytes, void* stream) {
   GridSpec g;
   if (!ctx || !mlp_weights_ok(w) || !featmap || !embedding || !trans_mat || !out || !ws ||
-      !grid_spec(sdf_params_host, R, &g))
+      !grid_range(sdf_params_host, R, k0, k1, &g) || sdf_weight == 0.0f)
     return DISN_E_ARG;
-  const int64_t total = (int64_t)g.res * g.res * g.res;
-  if (k0 < 0 || k1 > total || k0 >= k1 || sdf_weight == 0.0f) return DISN_E_ARG;
   hipStream_t st = (hipStream_t)stream;
   const int chunk = chunk_for(k1 - k0);
   const QueryWs q = query_layout(ws, 1, chunk, true, true);
@@ -1433,9 +1467,9 @@ int disn_query_grid_ctx(disn_ctx_t* ctx, const disn_mlp_weights_t* w, const floa
   float* feat[2] = {q.feat, reinterpret_cast<float*>(static_cast<char*>(ws) + q.total)};
   float* pts[2] = {q.pts, feat[1] + (size_t)chunk * DISN_FEAT_DIM};
   // events: 0 fork, 1/2 buffer ready (aux -> main), 3/4 buffer free (main -> aux)
-  DISN_TRY(hipEventRecord(ctx->ev[0], st));
-  DISN_TRY(hipStreamWaitEvent(ctx->aux, ctx->ev[0], 0));
-  { const int grc = gbias_layer(w, embedding, 1, q.gbias, q.gemv_ws, st); if (grc) return grc; }
+  DISN_TRY(hipEventRecord(ctx->ev[kEvFork], st));
+  DISN_TRY(hipStreamWaitEvent(ctx->aux, ctx->ev[kEvFork], 0));
+  DISN_RC(gbias_layer(w, embedding, 1, q.gbias, q.gemv_ws, st));
   int i = 0;
   for (int64_t k = k0; k < k1; k += chunk, ++i) {
     const int n = (int)((k1 - k) < chunk ? (k1 - k) : chunk);
@@ -1445,9 +1479,7 @@ int disn_query_grid_ctx(disn_ctx_t* ctx, const disn_mlp_weights_t* w, const floa
     DISN_TRY(project_gather_launch(featmap, trans_mat, pts[b], n, feat[b], ctx->aux));
     DISN_TRY(hipEventRecord(ctx->ev[1 + b], ctx->aux));
     DISN_TRY(hipStreamWaitEvent(st, ctx->ev[1 + b], 0));
-    const int rc = mlp_chunk(w, pts[b], n, q.gbias, feat[b], out + (k - k0), nullptr, nullptr,
-                             sdf_weight, q.mlp, st);
-    if (rc) return rc;
+    DISN_RC(mlp_chunk(w, pts[b], n, q.gbias, feat[b], out + (k - k0), nullptr, nullptr, sdf_weight, q.mlp, st));
     DISN_TRY(hipEventRecord(ctx->ev[3 + b], st));
   }
   return 0;

@@ -17,7 +17,7 @@ import numpy as np
 import torch
 
 from . import ops
-from ._lib import MLP_FIELDS, MlpWeights, VggWeights
+from ._lib import MLP_FIELDS, MlpWeights, VggWeights, lib
 from .weights import MLP_SCOPES, VGG_CONV_NAMES, WeightStore
 
 
@@ -253,7 +253,6 @@ class SdfEngine:
     def encode(self, imgs) -> Encoded:
         imgs = self._dev(imgs)
         with torch.cuda.device(self.device):
-            from ._lib import lib
             ws = self._workspace("vgg", lib().disn_encode_workspace_bytes(imgs.shape[0]))
             resized, taps, emb, featmap = ops.encode(self._ctx, self._vgg, imgs, ws)
         return Encoded(resized, taps, emb, featmap, units=self._units())
@@ -296,7 +295,6 @@ class SdfEngine:
         imgs, pts, trans_mat = self._dev(imgs), self._dev(pts), self._dev(trans_mat)
         pts_rot = pts if pts_rot is None else self._dev(pts_rot)
         with torch.cuda.device(self.device):
-            from ._lib import lib
             ws = self._workspace("encq", lib().disn_encode_query_workspace_bytes(pts.shape[0], pts.shape[1]))
             resized, taps, emb, featmap, sdf = ops.encode_query(self._ctx, self._vgg, self.weights.mlp,
                                                                 imgs, trans_mat, pts, pts_rot, ws, keep_featmap)
@@ -313,7 +311,6 @@ class SdfEngine:
         pts_rot = pts if pts_rot is None else self._dev(pts_rot)
         trans_mat = self._dev(trans_mat)
         with torch.cuda.device(self.device):
-            from ._lib import lib
             ws = self._workspace("query", lib().disn_query_workspace_bytes(pts.shape[0], pts.shape[1]))
             if fold is None:
                 fold = pts.shape[1] >= FOLD_MIN_POINTS
@@ -342,7 +339,6 @@ class SdfEngine:
         tm = self._dev(trans_mat).reshape(-1, 4, 3)
         tm = tm[image_index if tm.shape[0] > 1 else 0]
         with torch.cuda.device(self.device):
-            from ._lib import lib
             ctx = self._ctx if pipelined else None
             if fold is None:
                 fold = not pipelined

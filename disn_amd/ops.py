@@ -35,6 +35,33 @@ def _ws(nbytes: int, device) -> torch.Tensor:
     return torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=device)
 
 
+def _fit_ws(ws: Optional[torch.Tensor], need: int, device) -> torch.Tensor:
+    """``ws`` when it holds ``need`` bytes, else a fresh workspace"""
+    return ws if ws is not None and ws.numel() >= need else _ws(need, device)
+
+
+def _tap_ptrs(taps: Sequence[torch.Tensor], chk: bool = True) -> C.Array:
+    """the float*[5] argument of the entry points that read or write the five taps"""
+    return (C.c_void_p * 5)(*[(_chk(t, "tap") if chk else t).data_ptr() for t in taps])
+
+
+def _chk_img(img: torch.Tensor) -> torch.Tensor:
+    img = _chk(img, "img")
+    if tuple(img.shape[1:]) != (IMG, IMG, 3):
+        raise ValueError("img must be [B,137,137,3] (models/model_normalization.py:249-250 hard-codes 137)")
+    return img
+
+
+def _query_args(pts: torch.Tensor, pts_rot: Optional[torch.Tensor], out: Optional[torch.Tensor]):
+    """shared prologue of the query_* wrappers -> (pts, pts_rot (default: pts), B, N, out [B,N])"""
+    pts = _chk(pts, "pts")
+    pts_rot = pts if pts_rot is None else _chk(pts_rot, "pts_rot")
+    B, N, _ = pts.shape
+    if out is None:
+        out = torch.empty((B, N), dtype=torch.float32, device=pts.device)
+    return pts, pts_rot, B, N, out
+
+
 def pack_kn(w_kn: torch.Tensor, kpad: Optional[int] = None) -> torch.Tensor:
     """[K,N] -> MFMA B-fragment order (disn_pack_kn)."""
     w_kn = _chk(w_kn, "w_kn")
@@ -259,18 +286,11 @@ def dense(a1: torch.Tensor, w_packed: torch.Tensor, bias: torch.Tensor, n_out: i
 def vgg16_forward(w: VggWeights, img: torch.Tensor, ws: Optional[torch.Tensor] = None
                   ) -> Tuple[torch.Tensor, List[torch.Tensor], torch.Tensor]:
     """-> (resized224 [B,224,224,3], taps[5], embedding [B,num_classes])."""
-    img = _chk(img, "img")
+    img = _chk_img(img)
     B = img.shape[0]
-    if tuple(img.shape[1:]) != (IMG, IMG, 3):
-        raise ValueError("img must be [B,137,137,3] (models/model_normalization.py:249-250 hard-codes 137)")
-    dev = img.device
-    resized = torch.empty((B, 224, 224, 3), dtype=torch.float32, device=dev)
-    taps = [torch.empty((B, hw, hw, ch), dtype=torch.float32, device=dev) for hw, ch in TAP_SHAPES]
-    emb = torch.empty((B, w.num_classes), dtype=torch.float32, device=dev)
-    need = lib().disn_vgg16_workspace_bytes(B)
-    if ws is None or ws.numel() < need:
-        ws = _ws(need, dev)
-    tp = (C.c_void_p * 5)(*[t.data_ptr() for t in taps])
+    resized, taps, emb, _ = _alloc_encoder_outputs(B, w.num_classes, img.device, featmap=False)
+    ws = _fit_ws(ws, lib().disn_vgg16_workspace_bytes(B), img.device)
+    tp = _tap_ptrs(taps, chk=False)
     check("disn_vgg16_forward", lib().disn_vgg16_forward(
         C.byref(w), img.data_ptr(), B, resized.data_ptr(), C.byref(tp), emb.data_ptr(), ws.data_ptr(),
         ws.numel(), _stream()))
@@ -284,11 +304,10 @@ class ConvStackRun:
         self.w, self.img = w, _chk(img, "img")
         B, dev = img.shape[0], img.device
         self.B = B
-        self.resized = torch.empty((B, 224, 224, 3), dtype=torch.float32, device=dev)
-        self.taps = [torch.empty((B, hw, hw, ch), dtype=torch.float32, device=dev) for hw, ch in TAP_SHAPES]
+        self.resized, self.taps, _, _ = _alloc_encoder_outputs(B, 0, dev, featmap=False)
         self.pool5 = torch.empty((B, 7, 7, 512), dtype=torch.float32, device=dev) if want_pool5 else None
         self.ws = _ws(lib().disn_vgg16_workspace_bytes(B), dev)
-        self.tp = (C.c_void_p * 5)(*[t.data_ptr() for t in self.taps])
+        self.tp = _tap_ptrs(self.taps, chk=False)
 
     def run(self) -> None:
         check("disn_vgg16_conv_stack", lib().disn_vgg16_conv_stack(
@@ -337,15 +356,11 @@ def _alloc_encoder_outputs(B: int, num_classes: int, dev, featmap: bool = True):
 def encode(ctx: Optional[int], w: VggWeights, img: torch.Tensor, ws: Optional[torch.Tensor] = None):
     """rows A, B, C, E -> (resized224, taps[5], embedding, featmap); the tap up-samples overlap the
     convolutions on the context's auxiliary stream."""
-    img = _chk(img, "img")
+    img = _chk_img(img)
     B = img.shape[0]
-    if tuple(img.shape[1:]) != (IMG, IMG, 3):
-        raise ValueError("img must be [B,137,137,3] (models/model_normalization.py:249-250 hard-codes 137)")
     resized, taps, emb, featmap = _alloc_encoder_outputs(B, w.num_classes, img.device)
-    need = lib().disn_encode_workspace_bytes(B)
-    if ws is None or ws.numel() < need:
-        ws = _ws(need, img.device)
-    tp = (C.c_void_p * 5)(*[t.data_ptr() for t in taps])
+    ws = _fit_ws(ws, lib().disn_encode_workspace_bytes(B), img.device)
+    tp = _tap_ptrs(taps, chk=False)
     check("disn_encode", lib().disn_encode(ctx, C.byref(w), img.data_ptr(), B, resized.data_ptr(), C.byref(tp),
                                            emb.data_ptr(), featmap.data_ptr(), ws.data_ptr(), ws.numel(), _stream()))
     return resized, taps, emb, featmap
@@ -366,9 +381,8 @@ def encode_query(ctx: int, vw: VggWeights, mw: MlpWeights, img: torch.Tensor, tr
     need = lib().disn_encode_query_workspace_bytes(B, N)
     if need == 0:
         raise ValueError("encode_query needs B*N <= 65536")
-    if ws is None or ws.numel() < need:
-        ws = _ws(need, img.device)
-    tp = (C.c_void_p * 5)(*[t.data_ptr() for t in taps])
+    ws = _fit_ws(ws, need, img.device)
+    tp = _tap_ptrs(taps, chk=False)
     check("disn_encode_query", lib().disn_encode_query(
         ctx, C.byref(vw), C.byref(mw), img.data_ptr(), trans_mat.data_ptr(), pts.data_ptr(), pts_rot.data_ptr(),
         B, N, resized.data_ptr(), C.byref(tp), emb.data_ptr(), featmap.data_ptr() if keep_featmap else None,
@@ -380,7 +394,7 @@ def build_featmap(taps: Sequence[torch.Tensor], out: Optional[torch.Tensor] = No
     B = taps[0].shape[0]
     if out is None:
         out = torch.empty((B, IMG, IMG, FEAT_DIM), dtype=torch.float32, device=taps[0].device)
-    tp = (C.c_void_p * 5)(*[_chk(t, "tap").data_ptr() for t in taps])
+    tp = _tap_ptrs(taps)
     check("disn_build_featmap", lib().disn_build_featmap(C.byref(tp), B, out.data_ptr(), _stream()))
     return out
 
@@ -426,7 +440,7 @@ def gather_taps(taps: Sequence[torch.Tensor], trans_mat: torch.Tensor, pts: torc
     B, N, _ = pts.shape
     if out is None:
         out = torch.empty((B, N, FEAT_DIM), dtype=torch.float32, device=pts.device)
-    arr = (C.c_void_p * 5)(*[_chk(t, "tap").data_ptr() for t in taps])
+    arr = _tap_ptrs(taps)
     check("disn_gather_taps", lib().disn_gather_taps(C.byref(arr), _chk(trans_mat, "trans_mat").data_ptr(),
                                                      pts.data_ptr(), B, N, out.data_ptr(), _stream()))
     return out
@@ -439,7 +453,7 @@ def gather_taps_split(taps: Sequence[torch.Tensor], trans_mat: torch.Tensor, pts
     pts = _chk(pts, "pts")
     B, N, _ = pts.shape
     out = torch.empty((B, N, 1536 * 4), dtype=torch.uint8, device=pts.device)
-    arr = (C.c_void_p * 5)(*[_chk(t, "tap").data_ptr() for t in taps])
+    arr = _tap_ptrs(taps)
     check("disn_gather_taps_split", lib().disn_gather_taps_split(
         C.byref(arr), _chk(trans_mat, "trans_mat").data_ptr(), pts.data_ptr(), B, N, _chk(feat_amax, "feat_amax").data_ptr(),
         out.data_ptr(), _stream()))
@@ -492,17 +506,12 @@ def query_taps_fused(w: MlpWeights, taps: Sequence[torch.Tensor], embedding: tor
     """disn_query_taps_fused: rows D..H of B images x N points (any N: padded to a multiple of 128 inside the library;
     B * padded N <= 65536) from the five taps through the fused small-set kernels (split-form gather + one launch per
     MLP stream)"""
-    pts = _chk(pts, "pts")
-    pts_rot = pts if pts_rot is None else _chk(pts_rot, "pts_rot")
-    B, N, _ = pts.shape
-    if out is None:
-        out = torch.empty((B, N), dtype=torch.float32, device=pts.device)
+    pts, pts_rot, B, N, out = _query_args(pts, pts_rot, out)
     need = lib().disn_query_taps_fused_workspace_bytes(B, N)
     if need == 0:
         raise ValueError("query_taps_fused: B * N (N rounded up to a multiple of 128) must be <= 65536, got B %d N %d" % (B, N))
-    if ws is None or ws.numel() < need:
-        ws = _ws(need, pts.device)
-    tp = (C.c_void_p * 5)(*[_chk(t, "tap").data_ptr() for t in taps])
+    ws = _fit_ws(ws, need, pts.device)
+    tp = _tap_ptrs(taps)
     check("disn_query_taps_fused", lib().disn_query_taps_fused(
         C.byref(w), C.byref(tp), _chk(embedding, "embedding").data_ptr(), _chk(trans_mat, "trans_mat").data_ptr(),
         pts.data_ptr(), pts_rot.data_ptr(), B, N, out.data_ptr(), ws.data_ptr(), ws.numel(), _stream()))
@@ -522,14 +531,8 @@ def query_fused(w: MlpWeights, pmap: torch.Tensor, pmap_amax: torch.Tensor, embe
                 trans_mat: torch.Tensor, pts: torch.Tensor, pts_rot: Optional[torch.Tensor] = None,
                 ws: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """query_folded() through the fused point-MLP kernels; pmap [B,137*137,512], pmap_amax [B]"""
-    pts = _chk(pts, "pts")
-    pts_rot = pts if pts_rot is None else _chk(pts_rot, "pts_rot")
-    B, N, _ = pts.shape
-    if out is None:
-        out = torch.empty((B, N), dtype=torch.float32, device=pts.device)
-    need = lib().disn_query_fused_workspace_bytes(B, N)
-    if ws is None or ws.numel() < need:
-        ws = _ws(need, pts.device)
+    pts, pts_rot, B, N, out = _query_args(pts, pts_rot, out)
+    ws = _fit_ws(ws, lib().disn_query_fused_workspace_bytes(B, N), pts.device)
     check("disn_query_fused", lib().disn_query_fused(
         C.byref(w), _chk(pmap, "pmap").data_ptr(), _chk(pmap_amax, "pmap_amax").data_ptr(),
         _chk(embedding, "embedding").data_ptr(), _chk(trans_mat, "trans_mat").data_ptr(), pts.data_ptr(),
@@ -545,9 +548,7 @@ def query_grid_fused(w: MlpWeights, pmap: torch.Tensor, pmap_amax: torch.Tensor,
     n = k1 - k0
     if out is None:
         out = torch.empty(n, dtype=torch.float32, device=dev)
-    need = lib().disn_query_grid_fused_workspace_bytes(n)
-    if ws is None or ws.numel() < need:
-        ws = _ws(need, dev)
+    ws = _fit_ws(ws, lib().disn_query_grid_fused_workspace_bytes(n), dev)
     p6 = _params6(sdf_params)
     check("disn_query_grid_fused", lib().disn_query_grid_fused(
         C.byref(w), _chk(pmap, "pmap").data_ptr(), _chk(pmap_amax, "pmap_amax").data_ptr(),
@@ -575,14 +576,8 @@ def sdf_mlp(w: MlpWeights, pts_rot: torch.Tensor, embedding: torch.Tensor, feat:
 def query(w: MlpWeights, featmap: torch.Tensor, embedding: torch.Tensor, trans_mat: torch.Tensor,
           pts: torch.Tensor, pts_rot: Optional[torch.Tensor] = None, ws: Optional[torch.Tensor] = None,
           out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    pts = _chk(pts, "pts")
-    pts_rot = pts if pts_rot is None else _chk(pts_rot, "pts_rot")
-    B, N, _ = pts.shape
-    if out is None:
-        out = torch.empty((B, N), dtype=torch.float32, device=pts.device)
-    need = lib().disn_query_workspace_bytes(B, N)
-    if ws is None or ws.numel() < need:
-        ws = _ws(need, pts.device)
+    pts, pts_rot, B, N, out = _query_args(pts, pts_rot, out)
+    ws = _fit_ws(ws, lib().disn_query_workspace_bytes(B, N), pts.device)
     check("disn_query", lib().disn_query(
         C.byref(w), _chk(featmap, "featmap").data_ptr(), _chk(embedding, "embedding").data_ptr(),
         _chk(trans_mat, "trans_mat").data_ptr(), pts.data_ptr(), pts_rot.data_ptr(), B, N,
@@ -611,16 +606,10 @@ def query_folded(w: MlpWeights, pmap: torch.Tensor, embedding: torch.Tensor, tra
                  pts: torch.Tensor, pts_rot: Optional[torch.Tensor] = None, ws: Optional[torch.Tensor] = None,
                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """query() with pmap [B,137*137,512] (fold_local per image) in place of the feature map"""
-    pts = _chk(pts, "pts")
-    pts_rot = pts if pts_rot is None else _chk(pts_rot, "pts_rot")
-    B, N, _ = pts.shape
+    pts, pts_rot, B, N, out = _query_args(pts, pts_rot, out)
     if pmap.numel() != B * MAP_PIXELS * 512:
         raise ValueError("pmap must be [B,137*137,512]")
-    if out is None:
-        out = torch.empty((B, N), dtype=torch.float32, device=pts.device)
-    need = lib().disn_query_workspace_bytes(B, N)
-    if ws is None or ws.numel() < need:
-        ws = _ws(need, pts.device)
+    ws = _fit_ws(ws, lib().disn_query_workspace_bytes(B, N), pts.device)
     check("disn_query_folded", lib().disn_query_folded(
         C.byref(w), _chk(pmap, "pmap").data_ptr(), _chk(embedding, "embedding").data_ptr(),
         _chk(trans_mat, "trans_mat").data_ptr(), pts.data_ptr(), pts_rot.data_ptr(), B, N,
@@ -650,35 +639,21 @@ def query_grid(w: MlpWeights, featmap: torch.Tensor, embedding: torch.Tensor, tr
     """SDF of grid points k0..k1-1 of ONE image (featmap [137,137,1472] or [1,...]).  With a
     context the chunks are pipelined over two streams (gather of chunk i+1 under the MLP of chunk i).
     With ``pmap`` (fold_local of that image) the folded local stream runs and featmap is not read."""
-    dev = pmap.device if pmap is not None else featmap.device
+    folded = pmap is not None
+    src = _chk(pmap, "pmap") if folded else _chk(featmap, "featmap")
+    dev = src.device
     if out is None:
         out = torch.empty((k1 - k0,), dtype=torch.float32, device=dev)
     p6 = _params6(sdf_params)
-    if pmap is not None:
-        need = lib().disn_query_grid_workspace_bytes(k1 - k0)
-        if ws is None or ws.numel() < need:
-            ws = _ws(need, dev)
-        check("disn_query_grid_folded", lib().disn_query_grid_folded(
-            C.byref(w), _chk(pmap, "pmap").data_ptr(), _chk(embedding, "embedding").data_ptr(),
-            _chk(trans_mat, "trans_mat").data_ptr(), C.byref(p6), res, k0, k1, float(sdf_weight),
-            out.data_ptr(), ws.data_ptr(), ws.numel(), _stream()))
+    args = (C.byref(w), src.data_ptr(), _chk(embedding, "embedding").data_ptr(), _chk(trans_mat, "trans_mat").data_ptr(),
+            C.byref(p6), res, k0, k1, float(sdf_weight), out.data_ptr())
+    if ctx and not folded:
+        ws = _fit_ws(ws, lib().disn_query_grid_ctx_workspace_bytes(k1 - k0), dev)
+        check("disn_query_grid_ctx", lib().disn_query_grid_ctx(ctx, *args, ws.data_ptr(), ws.numel(), _stream()))
         return out
-    if ctx:
-        need = lib().disn_query_grid_ctx_workspace_bytes(k1 - k0)
-        if ws is None or ws.numel() < need:
-            ws = _ws(need, dev)
-        check("disn_query_grid_ctx", lib().disn_query_grid_ctx(
-            ctx, C.byref(w), _chk(featmap, "featmap").data_ptr(), _chk(embedding, "embedding").data_ptr(),
-            _chk(trans_mat, "trans_mat").data_ptr(), C.byref(p6), res, k0, k1, float(sdf_weight),
-            out.data_ptr(), ws.data_ptr(), ws.numel(), _stream()))
-        return out
-    need = lib().disn_query_grid_workspace_bytes(k1 - k0)
-    if ws is None or ws.numel() < need:
-        ws = _ws(need, dev)
-    check("disn_query_grid", lib().disn_query_grid(
-        C.byref(w), _chk(featmap, "featmap").data_ptr(), _chk(embedding, "embedding").data_ptr(),
-        _chk(trans_mat, "trans_mat").data_ptr(), C.byref(p6), res, k0, k1, float(sdf_weight),
-        out.data_ptr(), ws.data_ptr(), ws.numel(), _stream()))
+    name = "disn_query_grid_folded" if folded else "disn_query_grid"
+    ws = _fit_ws(ws, lib().disn_query_grid_workspace_bytes(k1 - k0), dev)
+    check(name, getattr(lib(), name)(*args, ws.data_ptr(), ws.numel(), _stream()))
     return out
 
 
@@ -779,8 +754,7 @@ def train_step(params: torch.Tensor, grads: torch.Tensor, img: torch.Tensor, tra
     need = lib().disn_train_workspace_bytes(B, N)
     if need == 0:
         raise ValueError("unsupported training shape B=%d N=%d (B*N <= 65536)" % (B, N))
-    if ws is None or ws.numel() < need:
-        ws = _ws(need, dev)
+    ws = _fit_ws(ws, need, dev)
     pred = torch.empty((B, N), dtype=torch.float32, device=dev)
     losses = torch.empty((5,), dtype=torch.float32, device=dev)
     check("disn_train_step", lib().disn_train_step(
@@ -867,8 +841,7 @@ def cam_train_step(params: torch.Tensor, grads: torch.Tensor, img: torch.Tensor,
     need = lib().disn_cam_train_workspace_bytes(B, N)
     if need == 0:
         raise ValueError("unsupported camera training shape B=%d N=%d (B <= 256)" % (B, N))
-    if ws is None or ws.numel() < need:
-        ws = _ws(need, dev)
+    ws = _fit_ws(ws, need, dev)
     tm = torch.empty((B, 4, 3), dtype=torch.float32, device=dev)
     losses = torch.empty((7,), dtype=torch.float32, device=dev)
     dists = torch.empty((2, B), dtype=torch.float32, device=dev)

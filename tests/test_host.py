@@ -79,6 +79,54 @@ def test_argument_validation_without_gpu():
                                     None) == -1                                     # k1 > 5^3
     # disn_encode_query takes featmap = NULL (map not materialised) but still validates the rest
     assert h.disn_encode_query(None, None, None, 1, 1, 1, 1, 1, 8, None, None, 1, None, 1, 1, 0, None) == -1
+    # a NULL tap among the five is an argument error in every entry point that takes them
+    wr = ctypes.byref(w)
+    for f in _lib.MLP_FUSED_FIELDS + _lib.MLP_FEAT_FIELDS:
+        setattr(w, f, 1)
+    v = _lib.VggWeights()
+    for i in range(13):
+        v.conv_w[i] = v.conv_b[i] = 1
+    for i in range(3):
+        v.fc_w[i] = v.fc_b[i] = 1
+    v.num_classes = 1024
+    vr = ctypes.byref(v)
+    taps = ctypes.byref((ctypes.c_void_p * 5)(1, 1, 1, 1, 1))
+    bad = ctypes.byref((ctypes.c_void_p * 5)(1, 1, 1, 1, None))
+    big = 1 << 40
+
+    def encq(B, N, tp=taps, nbytes=big):
+        return h.disn_encode_query(1, vr, wr, 1, 1, 1, 1, B, N, None, tp, 1, None, 1, 1, nbytes, None)
+
+    assert h.disn_build_featmap(bad, 1, 1, None) == -1
+    assert h.disn_gather_taps(bad, 1, 1, 1, 8, 1, None) == -1
+    assert h.disn_query_taps_fused(wr, bad, 1, 1, 1, 1, 1, 8, 1, 1, big, None) == -1
+    assert encq(1, 8, bad) == -1
+    assert h.disn_vgg16_forward(vr, 1, 1, None, bad, 1, 1, big, None) == -1
+    # grid ranges at R = 4 (125 points): bad range or sdf_weight == 0 -> -1, then the workspace check -> -3
+    pr = ctypes.byref(p6)
+    grids = (lambda *a: h.disn_query_grid(wr, 1, 1, 1, *a, None),
+             lambda *a: h.disn_query_grid_folded(wr, 1, 1, 1, *a, None),
+             lambda *a: h.disn_query_grid_fused(wr, 1, 1, 1, 1, *a, None))
+    for grid in grids:
+        assert grid(pr, 4, -1, 125, 10.0, 1, 1, big) == -1
+        assert grid(pr, 4, 0, 126, 10.0, 1, 1, big) == -1
+        assert grid(pr, 4, 10, 10, 10.0, 1, 1, big) == -1
+        assert grid(pr, 4, 0, 125, 0.0, 1, 1, big) == -1
+        assert grid(pr, 4, 0, 125, 10.0, 1, 1, 16) == -3
+    assert h.disn_query(wr, 1, 1, 1, 1, 1, 2, 700, 1, 1, 16, None) == -3
+    assert h.disn_query_folded(wr, 1, 1, 1, 1, 1, 2, 700, 1, 1, 16, None) == -3
+    assert h.disn_query_fused(wr, 1, 1, 1, 1, 1, 1, 2, 700, 1, 1, 16, None) == -3
+    assert h.disn_sdf_mlp(wr, 1, 1, 1, 2, 700, 1, None, None, 1, 16, None) == -3
+    # the fused small-set entry: 512 x pad128(129) points exceed one chunk
+    assert h.disn_query_taps_fused(wr, taps, 1, 1, 1, 1, 512, 129, 1, 1, big, None) == -2
+    assert h.disn_query_taps_fused_workspace_bytes(512, 129) == 0
+    assert h.disn_query_taps_fused_workspace_bytes(512, 128) > 0
+    assert h.disn_query_taps_fused(wr, taps, 1, 1, 1, 1, 4, 100, 1, 1, 16, None) == -3
+    assert encq(64, 2048) == -2 and h.disn_encode_query_workspace_bytes(64, 2048) == 0
+    v.num_classes = 1000
+    assert encq(4, 2048) == -2
+    v.num_classes = 1024
+    assert encq(4, 2048, nbytes=16) == -3
     with pytest.raises(_lib.DisnError):
         _lib.check("x", -3)
 
