@@ -100,6 +100,7 @@ SIGNATURES = {
     "disn_conv1_1": (I, [P, I, I, I, P, P, I, P, P, P, Z, P]),
     "disn_conv3x3_h2_workspace_bytes": (Z, [I]),
     "disn_conv3x3_h2": (I, [P, I, I, I, I, P, P, I, I, P, P, P, I, P, Z, P]),
+    "disn_conv3x3_h2_plan": (I, [I, I, I, I, I, I, P, P]),
     "disn_resize_bilinear": (I, [P, I, I, I, I, P, I, I, I, I, P]),
     "disn_vgg16_workspace_bytes": (Z, [I]),
     "disn_vgg16_forward": (I, [C.POINTER(VggWeights), P, I, P, C.POINTER(C.c_void_p * 5), P, P, Z, P]),

@@ -639,7 +639,7 @@ int vgg_features(const disn_vgg_weights_t* w, const float* img, int B, float* re
     } else if (h2) {
       DISN_TRY(conv_h2_launch(x, B, L.hw, L.hw, L.cin, w->conv_w_h2[i], w->conv_b[i], L.cout, 1,
                               s.amax + (size_t)B * 64 * i, out, kPoolAfter[i] ? s.bufP : nullptr,
-                              s.amax + (size_t)B * 64 * (i + 1), st, w->strict_forms == 1 ? 11 : 0, 64));
+                              s.amax + (size_t)B * 64 * (i + 1), st, w->strict_forms == 1 ? kConvTilingStrict : kConvTilingAuto, 64));
       pooled = kPoolAfter[i];
     } else {
       DISN_RC(conv3x3_impl(x, B, L.hw, L.hw, L.cin, w->conv_w[i], w->conv_b[i], L.cout, 1, out, s.gemm_ws, gws_cap, st,

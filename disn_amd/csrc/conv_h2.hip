@@ -44,7 +44,6 @@
 
 namespace disn {
 
-
 // ---------------------------------------------------------------------------------------------------
 // weight image: for n-block nb (32 output channels), k16 block kb (input channels 16 kb .. 16 kb + 15), tap t:
 //   two 1-KiB planes (h, l), lane (j, g) holds W[t][16 kb + 8 g + e][32 nb + j] * s_w[32 nb + j], e = 0..7
@@ -109,41 +108,45 @@ __device__ __forceinline__ float* h2_tail(unsigned char* image, int Cin, int Cou
   return reinterpret_cast<float*>(image + (size_t)Cin * taps * Cout * 4);  // inv_sw[Cout], then cmax[Cout]
 }
 
-__global__ __launch_bounds__(256) void conv_h2_pack_kernel(const float* __restrict__ w, int Cin, int Cout, int taps,
-                                                           unsigned char* __restrict__ image, int flip_t) {
+// fragment f (n-block, k16 block, tap) of an image, this lane's eight channels: scale, split, the two 16-byte stores
+__device__ __forceinline__ void h2_pack_fragment(const float* __restrict__ w, int Cin, int Cout, int taps, int flip_t,
+                                                 unsigned char* __restrict__ image, size_t f, int lane) {
   const int KB = Cin >> 4;
-  const size_t frags = (size_t)(Cout >> 5) * KB * taps;
   float* tail = h2_tail(image, Cin, Cout, taps);
   const float* cmax = tail + Cout;
-  for (size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x; idx < frags * 64; idx += (size_t)gridDim.x * 256) {
-    const int lane = (int)(idx & 63);
-    size_t f = idx >> 6;
-    int t = (int)(f % taps);
-    int kb = (int)((f / taps) % KB);
-    const int nb = (int)(f / ((size_t)taps * KB));
-    if (flip_t) {  // walk the k16 blocks fastest: a lane's reads of consecutive fragments are consecutive 32-byte pieces of
-                   // one row of the forward tensor (whole cache lines per workgroup pass instead of a quarter of each)
-      kb = (int)(f % KB);
-      t = (int)((f / KB) % taps);
-      f = ((size_t)nb * KB + kb) * taps + t;
-    }
-    const int j = lane & 31, g = lane >> 5;
-    const float s = ch2::pow2_scale(cmax[32 * nb + j], 13);
-    if (kb == 0 && t == 0 && g == 0) tail[32 * nb + j] = 1.0f / s;
-    ch_h8 hi, lo;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const int ci = 16 * kb + 8 * g + e;
-      const float v = (flip_t ? w[((size_t)(taps - 1 - t) * Cout + 32 * nb + j) * Cin + ci]
-                              : w[((size_t)t * Cin + ci) * Cout + 32 * nb + j]) * s;
-      const _Float16 h = (_Float16)v;
-      hi[e] = h;
-      lo[e] = (_Float16)(v - (float)h);
-    }
-    ch_h8* out = reinterpret_cast<ch_h8*>(image);
-    out[(f * 2) * 64 + lane] = hi;
-    out[(f * 2 + 1) * 64 + lane] = lo;
+  int t = (int)(f % taps);
+  int kb = (int)((f / taps) % KB);
+  const int nb = (int)(f / ((size_t)taps * KB));
+  if (flip_t) {  // walk the k16 blocks fastest: a lane's reads of consecutive fragments are consecutive 32-byte pieces of
+                 // one row of the forward tensor (whole cache lines per workgroup pass instead of a quarter of each)
+    kb = (int)(f % KB);
+    t = (int)((f / KB) % taps);
+    f = ((size_t)nb * KB + kb) * taps + t;
   }
+  const int j = lane & 31, g = lane >> 5;
+  const float s = ch2::pow2_scale(cmax[32 * nb + j], 13);
+  if (kb == 0 && t == 0 && g == 0) tail[32 * nb + j] = 1.0f / s;
+  ch_h8 hi, lo;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    const int ci = 16 * kb + 8 * g + e;
+    const float v = (flip_t ? w[((size_t)(taps - 1 - t) * Cout + 32 * nb + j) * Cin + ci]
+                            : w[((size_t)t * Cin + ci) * Cout + 32 * nb + j]) * s;
+    _Float16 h, l;
+    ch2::split(v, h, l);
+    hi[e] = h;
+    lo[e] = l;
+  }
+  ch_h8* out = reinterpret_cast<ch_h8*>(image);
+  out[(f * 2) * 64 + lane] = hi;
+  out[(f * 2 + 1) * 64 + lane] = lo;
+}
+
+__global__ __launch_bounds__(256) void conv_h2_pack_kernel(const float* __restrict__ w, int Cin, int Cout, int taps,
+                                                           unsigned char* __restrict__ image, int flip_t) {
+  const size_t frags = (size_t)(Cout >> 5) * (Cin >> 4) * taps;
+  for (size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x; idx < frags * 64; idx += (size_t)gridDim.x * 256)
+    h2_pack_fragment(w, Cin, Cout, taps, flip_t, image, idx >> 6, (int)(idx & 63));
 }
 
 size_t h2_image_bytes(int K, int N, int taps) { return (size_t)K * taps * N * 4 + (size_t)N * 8 + 256; }
@@ -180,35 +183,7 @@ __global__ __launch_bounds__(256) void conv_h2_pack_multi_kernel(const ConvH2Pac
     ji = lo;
   }
   const ConvH2PackJob& J = jobs.j[ji];
-  const int Cin = J.Cin, Cout = J.Cout, KB = Cin >> 4, taps = 9;
-  float* tail = h2_tail(J.image, Cin, Cout, taps);
-  const float* cmax = tail + Cout;
-  size_t f = (size_t)(f0 - J.frag_begin) + (threadIdx.x >> 6);
-  const int lane = threadIdx.x & 63;
-  int t = (int)(f % taps);
-  int kb = (int)((f / taps) % KB);
-  const int nb = (int)(f / ((size_t)taps * KB));
-  if (J.flip_t) {  // as conv_h2_pack_kernel: k16 blocks fastest
-    kb = (int)(f % KB);
-    t = (int)((f / KB) % taps);
-    f = ((size_t)nb * KB + kb) * taps + t;
-  }
-  const int j = lane & 31, g = lane >> 5;
-  const float s = ch2::pow2_scale(cmax[32 * nb + j], 13);
-  if (kb == 0 && t == 0 && g == 0) tail[32 * nb + j] = 1.0f / s;
-  ch_h8 hi, lo;
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    const int ci = 16 * kb + 8 * g + e;
-    const float v = (J.flip_t ? J.w[((size_t)(taps - 1 - t) * Cout + 32 * nb + j) * Cin + ci]
-                              : J.w[((size_t)t * Cin + ci) * Cout + 32 * nb + j]) * s;
-    const _Float16 h = (_Float16)v;
-    hi[e] = h;
-    lo[e] = (_Float16)(v - (float)h);
-  }
-  ch_h8* out = reinterpret_cast<ch_h8*>(J.image);
-  out[(f * 2) * 64 + lane] = hi;
-  out[(f * 2 + 1) * 64 + lane] = lo;
+  h2_pack_fragment(J.w, J.Cin, J.Cout, 9, J.flip_t, J.image, (size_t)(f0 - J.frag_begin) + (threadIdx.x >> 6), threadIdx.x & 63);
 }
 
 void conv_h2_pack_job_add(ConvH2PackJobs& jobs, const float* w_fwd, int Cin_fwd, int Cout_fwd, void* image, int flip_t,
@@ -241,14 +216,10 @@ hipError_t conv_h2_pack_multi_launch(const ConvH2PackJobs& jobs, hipStream_t st)
   hipLaunchKernelGGL(conv_h2_pack_multi_kernel, dim3((unsigned)(jobs.total_frags / 4)), dim3(256), 0, st, jobs);
   return hipGetLastError();
 }
-#endif
 
-#ifndef CH2_UBENCH
 // w: TF HWIO [taps][Cin][Cout] (flip_t: the forward tensor [taps][Cout][Cin] of the image's layer); the column maxima
-// are collected in the image's own tail (`scratch` is no longer used)
-hipError_t conv_h2_pack_launch(const float* w, int Cin, int Cout, void* image, float* scratch, hipStream_t st,
-                               int taps, int flip_t) {
-  (void)scratch;
+// are collected in the image's own tail
+hipError_t conv_h2_pack_launch(const float* w, int Cin, int Cout, void* image, hipStream_t st, int taps, int flip_t) {
   if (((size_t)taps * Cin * Cout) % 4096) return hipErrorInvalidValue;   // (Cin, Cout multiples of 64: always true)
   unsigned char* img = static_cast<unsigned char*>(image);
   float* cmax = reinterpret_cast<float*>(img + (size_t)Cin * taps * Cout * 4) + Cout;
@@ -271,14 +242,7 @@ hipError_t conv_h2_pack_launch(const float* w, int Cin, int Cout, void* image, f
 #endif  // CH2_UBENCH
 
 // ---------------------------------------------------------------------------------------------------
-// struct ConvH2Dev: h2_common.hpp (shared with conv_h2w.hip)
-
-#ifdef DISN_TUNING
-#define CH2_STAMP(i) \
-  if (P.stamps && threadIdx.x == 0) P.stamps[(size_t)blockIdx.x * 16 + (i)] = (i) == 0 ? (long long)wall_clock64() : (long long)clock64()
-#else
-#define CH2_STAMP(i)
-#endif
+// struct ConvH2Dev, CH2_STAMP: h2_common.hpp (shared with conv_h2w.hip)
 
 // WK k-waves per n-block (4 or 8): a chunk is CK = 16 WK input channels.  Eight k-waves put two waves on every
 // SIMD of the CU: a global_load_dwordx4 blocks its wave's in-order issue for ~50 cycles (measured: a chunk with
@@ -286,7 +250,7 @@ hipError_t conv_h2_pack_launch(const float* w, int Cin, int Cout, void* image, f
 // cover.
 // ABL (tools/ubench/conv_h2_ablate.hip only; 0 in the library): 1 no weight loads in the loop, 2 no halo loads,
 // 4 no split + LDS store, 8 no A-fragment reads in the loop (wrong results: timing only)
-// OCC: workgroups per CU the register budget is cut for (2: the multi-round grids, see conv_h2_launch)
+// OCC: workgroups per CU the register budget is cut for (2: the multi-round grids, see conv_h2_plan)
 // FL > 0 (the 14 x 14 layers of a batched call): a k-wave's accumulators restart every FL chunks (chains of 27 FL MFMAs)
 // and the finished segment is added to a second register set in fp32 VALU adds, as in conv_h2w.hip's SEG form
 template <int MB, int NW, int SEG, int TW, int D, int WK, int ABL = 0, int OCC = 1, int FL = 0>
@@ -316,26 +280,13 @@ __global__ __launch_bounds__(64 * WK * NW, OCC == 1 ? 1 : OCC * WK * NW / 4) voi
   CH2_STAMP(1);
 
   // ---- tile: n-tile major, every XCD (hardware workgroup L runs on XCD L % 8) a contiguous eighth --------
-  int l;
-  {
-    const int T = gridDim.x, L = blockIdx.x, q = T >> 3, r = T & 7, xcd = L & 7, idx = L >> 3;
-    l = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
+  const int l = xcd_tile(gridDim.x, blockIdx.x);
   const int per_img = P.tiles_y * P.tiles_x;
-  int nt, b, mt;
-  if (P.img_major) {   // an XCD's eighth = whole images (or a share of one): its L2 keeps the image's input
-    const int per_b = (P.Cout / (32 * NW)) * per_img;
-    b = l / per_b;
-    mt = l - b * per_b;
-    nt = mt / per_img;
-    mt -= nt * per_img;
-  } else {             // an XCD's eighth = whole n-tiles: its L2 keeps their weights
-    const int mtiles = P.B * per_img;
-    nt = l / mtiles;
-    mt = l - nt * mtiles;
-    b = mt / per_img;
-    mt -= b * per_img;
-  }
+  const int mtiles = P.B * per_img;   // an XCD's eighth = whole n-tiles: its L2 keeps their weights
+  const int nt = l / mtiles;
+  int mt = l - nt * mtiles;
+  const int b = mt / per_img;
+  mt -= b * per_img;
   const int tyi = mt / P.tiles_x, txi = mt - tyi * P.tiles_x;
   const int y0 = tyi * TH, x0 = txi * TW;
   const int n0 = (nt * NW + wn) * 32;
@@ -390,13 +341,7 @@ __global__ __launch_bounds__(64 * WK * NW, OCC == 1 ? 1 : OCC * WK * NW / 4) voi
     }
     const float x[4] = {ra[k].x, ra[k].y, ra[k].z, ra[k].w};
     ch_h4 hh, ll;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const float v = __uint_as_float(__float_as_uint(x[e]) & gm) * sa;
-      const _Float16 h = (_Float16)v;
-      hh[e] = h;
-      ll[e] = (_Float16)(v - (float)h);
-    }
+    ch2::split4(x, sa, hh, ll, gm);
     *reinterpret_cast<ch_h4*>(&lds[buf * BUF + wo]) = hh;
     *reinterpret_cast<ch_h4*>(&lds[buf * BUF + wo + CK * 2]) = ll;
   };
@@ -440,8 +385,7 @@ __global__ __launch_bounds__(64 * WK * NW, OCC == 1 ? 1 : OCC * WK * NW / 4) voi
   for (int mb = 0; mb < MB; ++mb)
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[mb][r] = 0.f;
-  typedef float f2v __attribute__((ext_vector_type(2)));
-  f2v tot[FL > 0 ? MB : 1][8];
+  ch_f2v tot[FL > 0 ? MB : 1][8];
   ch_f16v zero16;
 #pragma unroll
   for (int r = 0; r < 16; ++r) zero16[r] = 0.f;
@@ -449,12 +393,10 @@ __global__ __launch_bounds__(64 * WK * NW, OCC == 1 ? 1 : OCC * WK * NW / 4) voi
 #pragma unroll
     for (int mb = 0; mb < MB; ++mb)
 #pragma unroll
-      for (int r = 0; r < 8; ++r) tot[mb][r] = f2v{0.f, 0.f};
+      for (int r = 0; r < 8; ++r) tot[mb][r] = ch_f2v{0.f, 0.f};
   }
 
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) amax_lane = fmaxf(amax_lane, __shfl_xor(amax_lane, off));
-  sa = ch2::pow2_scale(amax_lane, 14);
+  sa = ch2::pow2_scale(ch2::wave_max(amax_lane), 14);
   const float descale = (1.0f / sa) * inv_sw;
 
   CH2_STAMP(2);
@@ -513,15 +455,7 @@ __global__ __launch_bounds__(64 * WK * NW, OCC == 1 ? 1 : OCC * WK * NW / 4) voi
           const int sidx = t * MB + mb;
           if (sidx + AH < S) rd(sidx + AH);
           const bool f = FIRST && t == 0;
-          if (f) {   // (accumulation registers -> arch VGPR pair -> v_pk_add_f32, as conv_h2w.hip's flush)
-#pragma unroll
-            for (int r = 0; r < 8; ++r) {
-              f2v tt;
-              asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(tt[0]) : "a"(acc[mb][2 * r]));
-              asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(tt[1]) : "a"(acc[mb][2 * r + 1]));
-              asm volatile("v_pk_add_f32 %0, %0, %1" : "+v"(tot[mb][r]) : "v"(tt));
-            }
-          }
+          if (f) ch2::flush_segment(acc[mb], tot[mb]);
           acc[mb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(rl[sidx % NBR], bh, f ? zero16 : acc[mb], 0, 0, 0);
           acc[mb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(rh[sidx % NBR], bl, acc[mb], 0, 0, 0);
           acc[mb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(rh[sidx % NBR], bh, acc[mb], 0, 0, 0);
@@ -555,7 +489,7 @@ __global__ __launch_bounds__(64 * WK * NW, OCC == 1 ? 1 : OCC * WK * NW / 4) voi
         const bool f = FIRST && t == 0;   // the block's finished segment -> tot, the new one starts from C = 0
         if (f) {
 #pragma unroll
-          for (int r = 0; r < 8; ++r) tot[mb][r] += f2v{acc[mb][2 * r], acc[mb][2 * r + 1]};
+          for (int r = 0; r < 8; ++r) tot[mb][r] += ch_f2v{acc[mb][2 * r], acc[mb][2 * r + 1]};
         }
         acc[mb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[t & 1][mb], bh, f ? zero16 : acc[mb], 0, 0, 0);
         acc[mb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[t & 1][mb], bl, acc[mb], 0, 0, 0);
@@ -599,7 +533,7 @@ __global__ __launch_bounds__(64 * WK * NW, OCC == 1 ? 1 : OCC * WK * NW / 4) voi
     for (int mb = 0; mb < MB; ++mb)
 #pragma unroll
       for (int r = 0; r < 8; ++r) {
-        const f2v t = tot[mb][r] + f2v{acc[mb][2 * r], acc[mb][2 * r + 1]};
+        const ch_f2v t = tot[mb][r] + ch_f2v{acc[mb][2 * r], acc[mb][2 * r + 1]};
         acc[mb][2 * r] = t[0];
         acc[mb][2 * r + 1] = t[1];
       }
@@ -648,13 +582,7 @@ __global__ __launch_bounds__(64 * WK * NW, OCC == 1 ? 1 : OCC * WK * NW / 4) voi
       }
     }
   }
-  if (P.out_amax) {  // 64 slots: same-address atomics serialise in L2 (~10 ns each)
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) vmax = fmaxf(vmax, __shfl_xor(vmax, off));
-    if (lane == 0)
-      atomicMax(reinterpret_cast<unsigned*>(P.out_amax) + (size_t)b * P.amax_stride + ((blockIdx.x * WK * NW + wave) & 63),
-                __float_as_uint(vmax));
-  }
+  if (P.out_amax) ch2::publish_wave_max(vmax, P.out_amax + (size_t)b * P.amax_stride + ((blockIdx.x * WK * NW + wave) & 63));
   if (P.pool_out) {  // H, W even; y0, x0 even: a 2x2 window never leaves the tile, nor this wave's quad
     const int Hp = H >> 1, Wp = W >> 1;
     float* pb = P.pool_out + (size_t)b * Hp * Wp * Cout + n0 + j;
@@ -826,79 +754,41 @@ hipError_t conv1_1_direct_launch(const float* in, int B, int H, int W, const flo
   return hipGetLastError();
 }
 
-template <int MB, int NW, int SEG, int TW, int D, int WK, int OCC = 1, int FL = 0>
-static hipError_t conv_h2_go(ConvH2Dev d, hipStream_t st) {
-  if (FL > 0 && (d.Cin / (16 * WK)) % FL != 0) return hipErrorInvalidValue;
-  constexpr int TH = MB * (32 / SEG);
-  d.tiles_x = (d.W + TW - 1) / TW;
-  d.tiles_y = (d.H + TH - 1) / TH;
-  const int grid = d.B * d.tiles_x * d.tiles_y * (d.Cout / (32 * NW));
-  hipLaunchKernelGGL((conv_h2_kernel<MB, NW, SEG, TW, D, WK, 0, OCC, FL>), dim3(grid), dim3(64 * WK * NW), 0, st, d);
-  return hipGetLastError();
-}
-
 bool conv_h2_supported(int H, int W, int Cin, int Cout) {
   return Cin > 0 && Cin % 64 == 0 && Cout > 0 && Cout % 64 == 0 && H > 0 && W > 0 && H < 32768 && W < 32768 &&
          (size_t)H * W * (Cin > Cout ? Cin : Cout) < (size_t)1 << 31;
 }
 
-// cfg: 0 = by shape and batch; 1..4 force <1,1,16,14>, <2,1,32,28>, <2,2,32,28>, <4,2,16,16> (tests: every shape through
-// every tiling); 5..9 force variants 1..5 of the batched form (conv_h2w.hip)
-hipError_t conv_h2_launch(const float* in, int B, int H, int W, int Cin, const void* wimg, const float* bias,
-                          int Cout, int relu, const float* in_amax, float* out, float* pool_out, float* out_amax,
-                          hipStream_t st, int cfg, int amax_stride) {
-  ConvH2Dev d{};
-  d.in = in; d.wimg = static_cast<const unsigned char*>(wimg); d.bias = bias; d.in_amax = in_amax;
-  d.out = out; d.pool_out = pool_out; d.out_amax = out_amax;
-  d.B = B; d.H = H; d.W = W; d.Cin = Cin; d.Cout = Cout; d.relu = relu; d.amax_stride = amax_stride;
-#ifdef DISN_TUNING
-  d.stamps = tune::ch2_stamps;
-#endif
-  // Which operand an XCD's L2 keeps: with the n-tile-major order every XCD streams the whole input of the launch
-  // (8 x B H W Cin floats over the fabric) and reads its own eighth of the weights once; image-major it is the other
-  // way round.  Measured on the 13 layers of 2 / 4 / 8 images (tools/conv_stack_time.py, knob conv_img_major, since
-  // removed): image-major where B H W > 9 Cout 388 / 645-658 / 1059-1078 us against 385 / 627 / 1089 n-tile-major, everywhere
-  // 399 / 665 / 1112 -- no gain: the launches are not bound by fabric traffic.  n-tile-major stays.
-  d.img_major = 0;
-  // Calls of several images (the steps of a batched call): the batched form of conv_h2w.hip -- waves own n-blocks
-  // and walk K sequentially, 12 .. 21 MFMAs per weight pair.  Its summation order differs from the k-wave tree
-  // below (fp32 rounding; both inside the 1e-5 bar): an image's bits depend on WHICH FORM runs it (fewer than
-  // kConvWideMinImages images per call or not), never on the other images of its call.  tiling 5..9: forced variants.
-  // 14 x 14 layers (conv5_x) of a batched call (B >= 4, as for the batched form below): FOUR k-waves, whatever B -- so
-  // their bits, like the other layers', depend on "four images or more per call" only.  Where that fills the chip
-  // (B Cout / 32 >= 200 workgroups: from 13 images on at 512 channels) ONE workgroup per image and n-block takes the
-  // whole image as one patch of seven 32-pixel blocks: the two-row patches give a weight pair three MFMAs (1.03 GB of
-  // fragment reads for conv5_x of 16 images: L2-bound, 32 % MFMA busy, 65 us), the whole image 21 (52 us).  Smaller
-  // calls keep the two-row patches (measured equal to the eight-k-wave tiling at 4 / 8 / 12 images: r03ad).
-  if (cfg == 10) return conv_h2_go<7, 1, 16, 14, 3, 4>(d, st);
-  if (cfg == 19) return conv_h2_go<7, 1, 16, 14, 3, 4, 1, 2>(d, st);   // the whole-image tiling in segments of two chunks
-  // cfg 11 ("strict", disn_vgg_weights_t.strict_forms = 1): the single-image tilings below by shape, whatever B -- the same
-  // k-waves and summation tree as a call of one image: the same bits
-  const bool strict = cfg == 11;
-  if (strict) cfg = 0;
-  // cfg 18 (the training step): the batched forms of round 3 for every layer (conv_h2w_launch variant -1)
-  const bool fast = cfg == 18;
-  if (fast) cfg = 0;
-  if (!strict && cfg == 0 && W <= 14 && H <= 14 && B >= kConvWideMinImages) {
-    if (fast || Cin % 128 != 0) {   // (the training step: round 3's chains of 216)
-      if ((long)B * (Cout / 32) >= 200) return conv_h2_go<7, 1, 16, 14, 3, 4>(d, st);
-      return conv_h2_go<1, 1, 16, 14, 3, 4, 2>(d, st);
-    }
-    // inference: the four k-waves in segments of two chunks (chains of 54), whatever the patch
-    if ((long)B * (Cout / 32) >= 200) return conv_h2_go<7, 1, 16, 14, 3, 4, 1, 2>(d, st);
-    return conv_h2_go<1, 1, 16, 14, 3, 4, 2, 2>(d, st);
-  }
-  if (cfg >= 5) return conv_h2w_supported(H, W, Cin, Cout) ? conv_h2w_launch(d, st, cfg >= 12 ? cfg - 6 : cfg - 4) : hipErrorInvalidValue;
-  if (!strict && cfg == 0 && B >= kConvWideMinImages && conv_h2w_supported(H, W, Cin, Cout)) return conv_h2w_launch(d, st, fast ? -1 : 0);
-  if (cfg == 0) {
+#ifndef CH2_UBENCH   // (the ablation tool launches conv_h2_kernel itself; conv_h2w.hip is not part of it)
+// ---------------------------------------------------------------------------------------------------
+// conv_h2_plan(): which form runs (geometry of the forms: kConvForms, h2_common.hpp)
+// ---------------------------------------------------------------------------------------------------
+namespace {
+long form_grid(int form, int B, int H, int W, int Cout) {
+  const ConvFormGeom& g = kConvForms[form];
+  return (long)B * ((H + g.th - 1) / g.th) * ((W + g.tw - 1) / g.tw) * (Cout / g.nch);
+}
+
+// "This many workgroups fill the chip": one round of the 256 CUs less the tail a launch can do without.
+constexpr long kChipFillWgs = 200;
+// The batched forms take 128-channel workgroups (four n-waves per halo: half the loader work per MFMA of the 64-channel
+// ones) from about kChipFillWgs of them on; below, 64-channel workgroups are what fills the chip.
+bool wg128_fill_chip(int B, int H, int W, int Cout) {
+  return Cout % 128 == 0 && form_grid(CONVW_N4, B, H, W, Cout) >= kChipFillWgs;
+}
+
+// A call of one image, or of a few (and every call under kConvTilingStrict): the k-wave forms of conv_h2.hip.
+// patch 1..4: 2 x 14, 2 x 28 one n-block, 2 x 28 two n-blocks, 8 x 16; 0: by shape.  The patch fixes the number of
+// k-waves, i.e. the summation order; B only chooses between siblings with the same bits.
+int single_form(int B, int H, int W, int Cin, int Cout, int patch) {
+  if (patch == 0) {
     // patch shape by image width; n-blocks per workgroup so that one image still gives >= ~200 workgroups
-    if (W <= 14) cfg = 1;
+    if (W <= 14) patch = 1;
     else if (W <= 28 || (W % 28 == 0 && W % 16 != 0)) {
       // by the workgroups ONE image gives, whatever the batch: the tiling fixes the number of k-waves, i.e. the
       // summation order -- an image's bits must not depend on the batch it travels in
-      const long wgs1 = (long)((H + 1) / 2) * ((W + 27) / 28) * (Cout / 32);
-      cfg = wgs1 <= 320 ? 2 : 3;
-    } else cfg = 4;
+      patch = form_grid(CONV_P28_N1_K4, 1, H, W, Cout) <= 320 ? 2 : 3;
+    } else patch = 4;
   }
   // one n-block per workgroup: eight k-waves (two waves per SIMD) when the channel count allows 128-channel chunks
   const bool wk8 = Cin % 128 == 0;
@@ -907,24 +797,141 @@ hipError_t conv_h2_launch(const float* in, int B, int H, int W, int Cin, const v
   // hide the L2 latency instead), <= 80 KB LDS (half-height patches at 16 x 16) -- so that one workgroup's prologue,
   // chunk barriers and epilogue run under the other's MFMAs.  Same k-waves, same summation order: same bits.
   // Measured (tools/conv_stack_time.py 4, r02v): the 13 layers of four images 697 -> 631 us.
-  const long per_img_tiles = cfg == 1 ? (long)((H + 1) / 2) * ((W + 13) / 14)
-                           : cfg == 3 ? (long)((H + 1) / 2) * ((W + 27) / 28)
-                           : cfg == 4 ? (long)((H + 3) / 4) * ((W + 15) / 16) : 0;
-  const long wgs = B * per_img_tiles * (Cout / (cfg == 1 ? 32 : 64));
   // From 1.5 workgroups per CU on where the patch stays the same; where it is halved (more halo per output) from 6
   // per CU on -- a single image's 224 / 112-pixel layers are slower with it (the 13 layers 276 -> 308 us), two
   // images' the same, four images' faster.
   constexpr long kOccMin = 384;
-  if (cfg == 1 && wk8 && wgs >= kOccMin) return conv_h2_go<1, 1, 16, 14, 3, 8, 2>(d, st);
-  if (cfg == 3 && wgs >= kOccMin) return conv_h2_go<2, 2, 32, 28, 1, 4, 2>(d, st);
-  if (cfg == 4 && wgs >= 4 * kOccMin) return conv_h2_go<2, 2, 16, 16, 1, 4, 2>(d, st);
-  switch (cfg) {
-    case 1: return wk8 ? conv_h2_go<1, 1, 16, 14, 9, 8>(d, st) : conv_h2_go<1, 1, 16, 14, 9, 4>(d, st);
-    case 2: return wk8 ? conv_h2_go<2, 1, 32, 28, 9, 8>(d, st) : conv_h2_go<2, 1, 32, 28, 9, 4>(d, st);
-    case 3: return conv_h2_go<2, 2, 32, 28, 9, 4>(d, st);
-    default: return conv_h2_go<4, 2, 16, 16, 3, 4>(d, st);
+  switch (patch) {
+    case 1:
+      if (wk8 && form_grid(CONV_P14_K8_OCC2, B, H, W, Cout) >= kOccMin) return CONV_P14_K8_OCC2;
+      return wk8 ? CONV_P14_K8 : CONV_P14_K4;
+    case 2: return wk8 ? CONV_P28_N1_K8 : CONV_P28_N1_K4;
+    case 3: return form_grid(CONV_P28_N2_OCC2, B, H, W, Cout) >= kOccMin ? CONV_P28_N2_OCC2 : CONV_P28_N2;
+    default: return form_grid(CONV_P16H_N2_OCC2, B, H, W, Cout) >= 4 * kOccMin ? CONV_P16H_N2_OCC2 : CONV_P16_N2;
   }
 }
+
+// A call of kConvWideMinImages images or more: by LAYER SHAPE only which summation order, by B only between forms with
+// the same bits -- an image's bits depend on "four images or more per call", never on the other images of its call.
+// The orders differ from single_form's k-wave trees (fp32 rounding; all inside the 1e-5 bar).  -1: the layer has no
+// batched form.  train (kConvTilingTrain): round 3's selection for every layer -- unsegmented chains of up to 432 MFMAs
+// per accumulator: faster at 4 .. 11 images per call, 1.7 x the error.
+int batched_form(int B, int H, int W, int Cin, int Cout, bool train) {
+  if (H <= 14 && W <= 14) {
+    // the 14 x 14 layers (conv5_x): FOUR k-waves, whatever B.  Where that fills the chip (from 13 images on at 512
+    // channels) ONE workgroup per image and n-block takes the whole image as one patch of seven 32-pixel blocks: the
+    // two-row patches give a weight pair three MFMAs (1.03 GB of fragment reads for conv5_x of 16 images: L2-bound,
+    // 32 % MFMA busy, 65 us), the whole image 21 (52 us).  Smaller calls keep the two-row patches (measured equal to
+    // the eight-k-wave tiling at 4 / 8 / 12 images: r03ad).
+    const bool whole = form_grid(CONV_IMG14_K4, B, H, W, Cout) >= kChipFillWgs;
+    // inference: in segments of two chunks (chains of 54), whatever the patch; the training step (and Cin = 64, one
+    // chunk per k-wave pair of segments): round 3's chains of 216
+    if (train || Cin % 128 != 0) return whole ? CONV_IMG14_K4 : CONV_P14_K4_OCC2;
+    return whole ? CONV_IMG14_K4_SEG : CONV_P14_K4_OCC2_SEG;
+  }
+  if (!conv_h2w_supported(H, W, Cin, Cout)) return -1;
+  // Inference: layers whose one-k-wave chain would exceed 108 MFMAs per accumulator (Cin >= 128) take the SEGMENTED
+  // form -- two K halves (lower / upper k16 blocks), each in segments of two chunks (chains of 54), p0 + p1 -- whatever
+  // the batch: as two k-waves over 64-channel workgroups while that is what fills the chip, as ONE k-wave that parks
+  // p0 in LDS from then on -- the same bits.  conv1_2 / conv2_1 (Cin = 64: chains of 108 as they are): round 3's forms.
+  const bool fill128 = wg128_fill_chip(B, H, W, Cout);
+  if (!train && Cin >= 128 && Cout % 128 == 0) return fill128 ? CONVW_N4_PARK : CONVW_N2_K2_SEG;
+  // Round 3's forms.  k-waves by LAYER SHAPE only (the summation order must not depend on the batch): one where M x N
+  // of a few images already fills the chip's 1024 SIMDs with 7-block waves (conv1_2, conv2_x, conv3_x), two from the
+  // 28-pixel layers on (conv4_x).  (Until r04j the 56-pixel layers had two as well: at 12 and 16 images per call the
+  // one-k-wave form with two workgroups per CU is 6-8 % faster there -- 158 against 168 us for conv3_2 at 16 images,
+  // tools/conv_h2w_variants_time.py -- and equal at 4 and 8 with the 64-channel patch variant below.)
+  if ((long)H * W * Cout >= (long)56 * 56 * 256) {
+    if (fill128) return CONVW_N4;   // two workgroups per CU
+    return W % 32 == 0 || Cout % 128 == 0 ? CONVW_P32_N2 : CONVW_N2;   // the 64-channel 8 x 32 patches, else 8 x 28
+  }
+  return fill128 ? CONVW_N4_K2 : CONVW_N2_K2;   // eight waves (two per SIMD) / four
+}
+
+// disn_conv3x3_h2's public `tiling` numbers
+enum TilingKind { TILING_INVALID, TILING_AUTO, TILING_STRICT, TILING_TRAIN, TILING_PATCH, TILING_FORM };
+constexpr struct { TilingKind kind; int arg; } kTilings[20] = {
+    {TILING_AUTO, 0},                                                                               // 0 kConvTilingAuto
+    {TILING_PATCH, 1},          {TILING_PATCH, 2},         {TILING_PATCH, 3},     {TILING_PATCH, 4},   // 1..4
+    {TILING_FORM, CONVW_P32_N2}, {TILING_FORM, CONVW_N4},  {TILING_FORM, CONVW_N2},                     // 5..7
+    {TILING_FORM, CONVW_N4_K2}, {TILING_FORM, CONVW_N2_K2},                                          // 8, 9
+    {TILING_FORM, CONV_IMG14_K4},                                                                    // 10
+    {TILING_STRICT, 0},                                                                              // 11 kConvTilingStrict
+    {TILING_FORM, CONVW_N4_PARK}, {TILING_FORM, CONVW_N2_K2_SEG},                                    // 12, 13
+    {TILING_INVALID, 0},        {TILING_INVALID, 0},       {TILING_INVALID, 0},   {TILING_INVALID, 0},  // 14..17
+    {TILING_TRAIN, 0},                                                                               // 18 kConvTilingTrain
+    {TILING_FORM, CONV_IMG14_K4_SEG},                                                                // 19
+};
+}  // namespace
+
+ConvPlan conv_h2_plan(int B, int H, int W, int Cin, int Cout, int tiling) {
+  const ConvPlan invalid{-1, 0, 0, 0, 0};
+  if (B <= 0 || tiling < 0 || tiling >= 20 || !conv_h2_supported(H, W, Cin, Cout)) return invalid;
+  int form = -1;
+  switch (kTilings[tiling].kind) {
+    case TILING_INVALID: return invalid;
+    case TILING_AUTO:
+    case TILING_TRAIN:
+      if (B >= kConvWideMinImages) form = batched_form(B, H, W, Cin, Cout, kTilings[tiling].kind == TILING_TRAIN);
+      if (form < 0) form = single_form(B, H, W, Cin, Cout, 0);
+      break;
+    case TILING_STRICT: form = single_form(B, H, W, Cin, Cout, 0); break;
+    case TILING_PATCH: form = single_form(B, H, W, Cin, Cout, kTilings[tiling].arg); break;
+    case TILING_FORM: form = kTilings[tiling].arg; break;
+  }
+  const ConvFormGeom& g = kConvForms[form];
+  if (Cout % g.nch || Cin % g.cin_mult || Cin < g.cin_min) return invalid;
+  if (form >= CONVW_FIRST && !conv_h2w_supported(H, W, Cin, Cout)) return invalid;
+  if ((form == CONV_IMG14_K4 || form == CONV_IMG14_K4_SEG) && (H > g.th || W > g.tw)) return invalid;  // one patch per image
+  ConvPlan p;
+  p.form = form;
+  p.tiles_x = (W + g.tw - 1) / g.tw;
+  p.tiles_y = (H + g.th - 1) / g.th;
+  p.grid = (int)form_grid(form, B, H, W, Cout);
+  p.block = g.block;
+  return p;
+}
+
+template <ConvForm F, int MB, int NW, int SEG, int TW, int D, int WK, int OCC = 1, int FL = 0>
+static hipError_t conv_h2_go(const ConvH2Dev& d, const ConvPlan& p, hipStream_t st) {
+  constexpr ConvFormGeom g = kConvForms[F];
+  static_assert(g.th == MB * (32 / SEG) && g.tw == TW && g.nch == 32 * NW && g.block == 64 * WK * NW &&
+                    g.cin_mult == 16 * WK * (FL > 0 ? FL : 1), "kConvForms");
+  hipLaunchKernelGGL((conv_h2_kernel<MB, NW, SEG, TW, D, WK, 0, OCC, FL>), dim3(p.grid), dim3(p.block), 0, st, d);
+  return hipGetLastError();
+}
+
+hipError_t conv_h2_launch(const float* in, int B, int H, int W, int Cin, const void* wimg, const float* bias,
+                          int Cout, int relu, const float* in_amax, float* out, float* pool_out, float* out_amax,
+                          hipStream_t st, int tiling, int amax_stride) {
+  const ConvPlan p = conv_h2_plan(B, H, W, Cin, Cout, tiling);
+  if (p.form < 0) return hipErrorInvalidValue;
+  ConvH2Dev d{};
+  d.in = in; d.wimg = static_cast<const unsigned char*>(wimg); d.bias = bias; d.in_amax = in_amax;
+  d.out = out; d.pool_out = pool_out; d.out_amax = out_amax;
+  d.B = B; d.H = H; d.W = W; d.Cin = Cin; d.Cout = Cout; d.relu = relu; d.amax_stride = amax_stride;
+  d.tiles_x = p.tiles_x; d.tiles_y = p.tiles_y;
+#ifdef DISN_TUNING
+  d.stamps = tune::ch2_stamps;
+#endif
+  switch (p.form) {
+    case CONV_P14_K4: return conv_h2_go<CONV_P14_K4, 1, 1, 16, 14, 9, 4>(d, p, st);
+    case CONV_P14_K8: return conv_h2_go<CONV_P14_K8, 1, 1, 16, 14, 9, 8>(d, p, st);
+    case CONV_P14_K8_OCC2: return conv_h2_go<CONV_P14_K8_OCC2, 1, 1, 16, 14, 3, 8, 2>(d, p, st);
+    case CONV_P14_K4_OCC2: return conv_h2_go<CONV_P14_K4_OCC2, 1, 1, 16, 14, 3, 4, 2>(d, p, st);
+    case CONV_P14_K4_OCC2_SEG: return conv_h2_go<CONV_P14_K4_OCC2_SEG, 1, 1, 16, 14, 3, 4, 2, 2>(d, p, st);
+    case CONV_IMG14_K4: return conv_h2_go<CONV_IMG14_K4, 7, 1, 16, 14, 3, 4>(d, p, st);
+    case CONV_IMG14_K4_SEG: return conv_h2_go<CONV_IMG14_K4_SEG, 7, 1, 16, 14, 3, 4, 1, 2>(d, p, st);
+    case CONV_P28_N1_K4: return conv_h2_go<CONV_P28_N1_K4, 2, 1, 32, 28, 9, 4>(d, p, st);
+    case CONV_P28_N1_K8: return conv_h2_go<CONV_P28_N1_K8, 2, 1, 32, 28, 9, 8>(d, p, st);
+    case CONV_P28_N2: return conv_h2_go<CONV_P28_N2, 2, 2, 32, 28, 9, 4>(d, p, st);
+    case CONV_P28_N2_OCC2: return conv_h2_go<CONV_P28_N2_OCC2, 2, 2, 32, 28, 1, 4, 2>(d, p, st);
+    case CONV_P16_N2: return conv_h2_go<CONV_P16_N2, 4, 2, 16, 16, 3, 4>(d, p, st);
+    case CONV_P16H_N2_OCC2: return conv_h2_go<CONV_P16H_N2_OCC2, 2, 2, 16, 16, 1, 4, 2>(d, p, st);
+    default: return conv_h2w_launch(d, p, st);
+  }
+}
+#endif  // CH2_UBENCH
 
 }  // namespace disn
 
@@ -942,7 +949,7 @@ size_t disn_pack_conv_h2_bytes(int Cin, int Cout) {
 int disn_pack_conv_h2(const float* w_hwio, int Cin, int Cout, void* image, void* stream) {
   if (!w_hwio || !image || Cin <= 0 || Cout <= 0) return DISN_E_ARG;
   if (Cin % 64 || Cout % 64) return DISN_E_SHAPE;
-  const hipError_t e = disn::conv_h2_pack_launch(w_hwio, Cin, Cout, image, nullptr, (hipStream_t)stream);
+  const hipError_t e = disn::conv_h2_pack_launch(w_hwio, Cin, Cout, image, (hipStream_t)stream);
   return e == hipSuccess ? 0 : (int)e;
 }
 
@@ -968,17 +975,19 @@ int disn_conv_h2_gain_span(const void* image, int Cin, int Cout, float* span_log
 
 size_t disn_conv3x3_h2_workspace_bytes(int B) { return B > 0 ? (size_t)B * 512 : 0; }
 
+int disn_conv3x3_h2_plan(int B, int H, int W, int Cin, int Cout, int tiling, int* grid, int* block) {
+  const disn::ConvPlan p = disn::conv_h2_plan(B, H, W, Cin, Cout, tiling);
+  if (p.form < 0) return DISN_E_SHAPE;
+  if (grid) *grid = p.grid;
+  if (block) *block = p.block;
+  return p.form;
+}
+
 int disn_conv3x3_h2(const float* in, int B, int H, int W, int Cin, const void* image, const float* bias, int Cout,
                     int relu, float* out, float* pool_out, float* out_amax, int tiling, void* ws, size_t ws_bytes,
                     void* stream) {
   if (!in || !image || !bias || !out || !ws || B <= 0 || H <= 0 || W <= 0) return DISN_E_ARG;
-  if (!disn::conv_h2_supported(H, W, Cin, Cout) || tiling < 0 || tiling > 19 || (tiling >= 14 && tiling <= 17) || (pool_out && ((H | W) & 1)))
-    return DISN_E_SHAPE;
-  if (((tiling >= 5 && tiling <= 9) || tiling == 12 || tiling == 13) && !disn::conv_h2w_supported(H, W, Cin, Cout)) return DISN_E_SHAPE;
-  if ((tiling == 6 || tiling == 8 || tiling == 12) && Cout % 128) return DISN_E_SHAPE;   // four n-waves = 128 channels per workgroup
-  if ((tiling == 12 || tiling == 13) && (Cin % 64 || Cin < 128)) return DISN_E_SHAPE;       // two K halves of whole segments
-  if (tiling == 19 && (H > 14 || W > 14 || Cin % 128)) return DISN_E_SHAPE;
-  if (tiling == 10 && (H > 14 || W > 14)) return DISN_E_SHAPE;
+  if (disn::conv_h2_plan(B, H, W, Cin, Cout, tiling).form < 0 || (pool_out && ((H | W) & 1))) return DISN_E_SHAPE;
   if (ws_bytes < (size_t)B * 512) return DISN_E_WS;
   hipStream_t st = (hipStream_t)stream;
   // every image its own 64 slots in / 64 slots out, as inside disn_encode*: an image's scale, hence its bits, do

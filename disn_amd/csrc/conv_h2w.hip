@@ -27,7 +27,7 @@
 // block, then (two k-waves) p0 + p1.  It depends on WK only -- fixed per LAYER by the launcher -- never on the patch,
 // the number of n-waves or the batch: an image's bits do not depend on the images it travels with.  They DO differ
 // (fp32 rounding, both within the 1e-5 bar of the float64 oracle) from conv_h2.hip's four / eight-k-wave tree, which
-// serves calls of fewer than four images: see conv_h2_launch.
+// serves calls of fewer than four images: see conv_h2_plan (conv_h2.hip).
 #include "kernels.hpp"
 #include "h2_common.hpp"
 
@@ -42,18 +42,11 @@ constexpr int w_row_bytes(int raw) {  // smallest size >= raw that is 128 (mod 2
 }
 }  // namespace
 
-#ifdef DISN_TUNING
-#define CH2W_STAMP(i) \
-  if (P.stamps && threadIdx.x == 0) P.stamps[(size_t)blockIdx.x * 16 + (i)] = (i) == 0 ? (long long)wall_clock64() : (long long)clock64()
-#else
-#define CH2W_STAMP(i)
-#endif
-
 // MB row blocks per wave, MWV m-waves x NWV n-waves x WK k-waves per workgroup, patch TH x TW (= 32 MB MWV pixels),
 // OCC workgroups per CU the register budget is cut for
 // PARK (WK == 1, SEG == 2): the TWO-K-HALVES order of the two-k-wave segmented variant in ONE k-wave -- the lower half of the
 // k16 blocks first (p0: what k-wave 0 of <.., WK = 2, .., SEG = 2> sums), that total parked in LDS, then the upper half (p1), p0 + p1:
-// bit for bit the two-k-wave variant's result with four n-waves per halo instead of two (large calls), see conv_h2w_launch
+// bit for bit the two-k-wave variant's result with four n-waves per halo instead of two (large calls), see conv_h2_plan
 template <int MB, int MWV, int NWV, int WK, int TH, int TW, int OCC, int SEG = 0, bool PARK = false>
 __global__ __launch_bounds__(64 * MWV * NWV * WK, (OCC * MWV * NWV * WK + 3) / 4) void conv_h2w_kernel(const ConvH2Dev P) {
   constexpr int NWAVES = MWV * NWV * WK, NT = 64 * NWAVES;
@@ -80,15 +73,11 @@ __global__ __launch_bounds__(64 * MWV * NWV * WK, (OCC * MWV * NWV * WK + 3) / 4
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wk = wave % WK, wn = (wave / WK) % NWV, wm = wave / (WK * NWV);
   const int j = lane & 31, g = lane >> 5;
-  CH2W_STAMP(0);
-  CH2W_STAMP(1);
+  CH2_STAMP(0);
+  CH2_STAMP(1);
 
   // ---- tile: n-tile major, every XCD (hardware workgroup L runs on XCD L % 8) a contiguous eighth --------------
-  int l;
-  {
-    const int T = gridDim.x, L = blockIdx.x, q = T >> 3, r = T & 7, xcd = L & 7, idx = L >> 3;
-    l = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
+  const int l = xcd_tile(gridDim.x, blockIdx.x);
   const int per_img = P.tiles_y * P.tiles_x;
   const int mtiles = P.B * per_img;
   const int nt = l / mtiles;
@@ -136,12 +125,14 @@ __global__ __launch_bounds__(64 * MWV * NWV * WK, (OCC * MWV * NWV * WK + 3) / 4
     const unsigned msk = 0u - ((vbits >> k) & 1u);
     const float x[4] = {ra[k].x, ra[k].y, ra[k].z, ra[k].w};
     ch_h4 hh, ll;
+    // (the scalar form in a loop of its own: through ch2::split4 this kernel's register allocation comes out different --
+    // two of its forms then spill)
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      const float v = __uint_as_float(__float_as_uint(x[e]) & msk) * sa;
-      const _Float16 h = (_Float16)v;
+      _Float16 h, l;
+      ch2::split(__uint_as_float(__float_as_uint(x[e]) & msk) * sa, h, l);
       hh[e] = h;
-      ll[e] = (_Float16)(v - (float)h);
+      ll[e] = l;
     }
     *reinterpret_cast<ch_h4*>(&lds[buf * BUF + woff[k]]) = hh;
     *reinterpret_cast<ch_h4*>(&lds[buf * BUF + woff[k] + CK * 2]) = ll;
@@ -187,8 +178,7 @@ __global__ __launch_bounds__(64 * MWV * NWV * WK, (OCC * MWV * NWV * WK + 3) / 4
   // SEG > 0: the accumulators restart every SEG chunks (chains of 27 SEG MFMAs) and the finished segment is added to
   // a second register set: out = ((s0 + s1) + s2) + ... in fp32 VALU adds
   // (tot as register PAIRS, never an MFMA operand: no 16-register tuples to keep aligned; one v_pk_add_f32 per pair)
-  typedef float f2v __attribute__((ext_vector_type(2)));
-  f2v tot[SEG > 0 ? MB : 1][8];
+  ch_f2v tot[SEG > 0 ? MB : 1][8];
   ch_f16v zero16;
 #pragma unroll
   for (int r = 0; r < 16; ++r) zero16[r] = 0.f;
@@ -196,40 +186,31 @@ __global__ __launch_bounds__(64 * MWV * NWV * WK, (OCC * MWV * NWV * WK + 3) / 4
 #pragma unroll
     for (int mb = 0; mb < MB; ++mb)
 #pragma unroll
-      for (int r = 0; r < 8; ++r) tot[mb][r] = f2v{0.f, 0.f};
+      for (int r = 0; r < 8; ++r) tot[mb][r] = ch_f2v{0.f, 0.f};
   }
-  // (the finished segment sits in accumulation registers -- the 256 arch VGPRs are taken by tot, the A ring and the loader --
-  // and VALU cannot read those: two v_accvgpr_read + one v_pk_add_f32 per register pair, written out so that the compiler
-  // keeps tot in arch VGPRs instead of shuttling it through the accumulation file around every add)
+  // (the finished segment sits in accumulation registers -- the 256 arch VGPRs are taken by tot, the A ring and the loader:
+  // ch2::flush_segment)
   bool park_now = false;   // PARK: wave-uniform, true in the first chunk of the second K half
   auto park_at = [&](int mb, int r) __attribute__((always_inline)) { return 2 * BUF + (((wave * MB + mb) * 8 + r) * 64 + lane) * 8; };
   auto flush = [&](int mb) __attribute__((always_inline)) {
-#pragma unroll
-    for (int r = 0; r < 8; ++r) {
-      f2v t;
-      asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(t[0]) : "a"(acc[mb][2 * r]));
-      asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(t[1]) : "a"(acc[mb][2 * r + 1]));
-      asm volatile("v_pk_add_f32 %0, %0, %1" : "+v"(tot[mb][r]) : "v"(t));
-    }
+    ch2::flush_segment(acc[mb], tot[mb]);
     if (PARK && park_now) {   // p0 = the first half's total: parked, the second half starts from zero
 #pragma unroll
       for (int r = 0; r < 8; ++r) {
-        *reinterpret_cast<f2v*>(&lds[park_at(mb, r)]) = tot[mb][r];
-        tot[mb][r] = f2v{0.f, 0.f};
+        *reinterpret_cast<ch_f2v*>(&lds[park_at(mb, r)]) = tot[mb][r];
+        tot[mb][r] = ch_f2v{0.f, 0.f};
       }
     }
   };
 
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) amax_lane = fmaxf(amax_lane, __shfl_xor(amax_lane, off));
-  sa = ch2::pow2_scale(amax_lane, 14);
+  sa = ch2::pow2_scale(ch2::wave_max(amax_lane), 14);
   const float descale = (1.0f / sa) * inv_sw;
 
-  CH2W_STAMP(2);
+  CH2_STAMP(2);
 #pragma unroll
   for (int k = 0; k < LP; ++k) store_unit(0, ra0, k);
   __syncthreads();
-  CH2W_STAMP(3);
+  CH2_STAMP(3);
 
   // ---- one chunk: 9 taps x MB blocks = 9 MB sub-steps (tap t = s / MB, block s % MB) of three MFMAs from LDS buffer
   // c & 1, issued as PAIRS of sub-steps: l0 l1 | h0 h1 | h0 h1 -- consecutive MFMAs never wait for each other's
@@ -321,7 +302,7 @@ __global__ __launch_bounds__(64 * MWV * NWV * WK, (OCC * MWV * NWV * WK + 3) / 4
 #pragma unroll 1
     for (int c = 0; c + 1 < NC; ++c) {
       chunk(c, std::true_type{}, std::false_type{});
-      if (c < 8) { CH2W_STAMP(4 + c); }
+      if (c < 8) { CH2_STAMP(4 + c); }
     }
     chunk(NC - 1, std::false_type{}, std::false_type{});
   } else {
@@ -336,7 +317,7 @@ __global__ __launch_bounds__(64 * MWV * NWV * WK, (OCC * MWV * NWV * WK + 3) / 4
       chunk(c, T, T);
       if constexpr (SEG >= 2) chunk(c + 1, T, F);
       if constexpr (SEG >= 4) { chunk(c + 2, T, F); chunk(c + 3, T, F); }
-      if (c / SEG < 8) { CH2W_STAMP(4 + c / SEG); }
+      if (c / SEG < 8) { CH2_STAMP(4 + c / SEG); }
     }
     if constexpr (SEG == 1) chunk(NC - 1, F, T);
     if (PARK) park_now = false;   // (NC >= 8: the second half starts inside the loop above)
@@ -346,13 +327,13 @@ __global__ __launch_bounds__(64 * MWV * NWV * WK, (OCC * MWV * NWV * WK + 3) / 4
     for (int mb = 0; mb < MB; ++mb)
 #pragma unroll
       for (int r = 0; r < 8; ++r) {
-        f2v t = tot[mb][r] + f2v{acc[mb][2 * r], acc[mb][2 * r + 1]};
-        if (PARK) t = *reinterpret_cast<const f2v*>(&lds[park_at(mb, r)]) + t;   // p0 + p1
+        ch_f2v t = tot[mb][r] + ch_f2v{acc[mb][2 * r], acc[mb][2 * r + 1]};
+        if (PARK) t = *reinterpret_cast<const ch_f2v*>(&lds[park_at(mb, r)]) + t;   // p0 + p1
         acc[mb][2 * r] = t[0];
         acc[mb][2 * r + 1] = t[1];
       }
   }
-  CH2W_STAMP(12);
+  CH2_STAMP(12);
 
   // ---- two k-waves: p0 + p1 through LDS.  k-wave 0 finishes blocks 0 .. MBH - 1, k-wave 1 the others: each hands
   // over the blocks it does not finish ----------------------------------------------------------------------------
@@ -383,7 +364,7 @@ __global__ __launch_bounds__(64 * MWV * NWV * WK, (OCC * MWV * NWV * WK + 3) / 4
       }
     }
   }
-  CH2W_STAMP(13);
+  CH2_STAMP(13);
 
   // ---- epilogue: bias, ReLU, fp32 NHWC store, 2x2 max pool of the lane's window, maximum of |out| for the next
   // layer's scale.  Round 4: the C layout hands lane (j, g) ONE channel of 16 pixels -- sixteen 4-byte stores per block,
@@ -444,78 +425,34 @@ __global__ __launch_bounds__(64 * MWV * NWV * WK, (OCC * MWV * NWV * WK + 3) / 4
       if (pb && y + 1 < H && x + 1 < W) *reinterpret_cast<float4*>(pb + (wy * Wp + wx) * Cout + c4) = m4;
     }
   }
-  if (P.out_amax) {  // 64 slots: same-address atomics serialise in L2 (~10 ns each)
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) vmax = fmaxf(vmax, __shfl_xor(vmax, off));
-    if (lane == 0)
-      atomicMax(reinterpret_cast<unsigned*>(P.out_amax) + (size_t)b * P.amax_stride + ((blockIdx.x * NWAVES + wave) & 63),
-                __float_as_uint(vmax));
-  }
-  CH2W_STAMP(14);
-}
-
-template <int MB, int MWV, int NWV, int WK, int TH, int TW, int OCC, int SEG = 0, bool PARK = false>
-static hipError_t conv_h2w_go(ConvH2Dev d, hipStream_t st) {
-  if (SEG > 0 && (d.Cin / (16 * WK)) % SEG != 0) return hipErrorInvalidValue;   // whole segments only
-  if (PARK && (d.Cin % 64 != 0 || d.Cin < 128)) return hipErrorInvalidValue;    // two halves of whole segments, the second one starting inside the loop
-  d.tiles_x = (d.W + TW - 1) / TW;
-  d.tiles_y = (d.H + TH - 1) / TH;
-  const int grid = d.B * d.tiles_x * d.tiles_y * (d.Cout / (32 * NWV));
-  hipLaunchKernelGGL((conv_h2w_kernel<MB, MWV, NWV, WK, TH, TW, OCC, SEG, PARK>), dim3(grid), dim3(64 * MWV * NWV * WK), 0, st, d);
-  return hipGetLastError();
-}
-
-// k-waves of the batched form, by LAYER SHAPE only (the summation order must not depend on the batch): one where
-// M x N of a few images already fills the chip's 1024 SIMDs with 7-block waves, two from the 28-pixel layers on.
-// (Until r04j the 56-pixel layers had two as well: at 12 and 16 images per call the one-k-wave form with two workgroups
-// per CU is 6-8 % faster there -- 158 against 168 us for conv3_2 at 16 images, tools/conv_h2w_variants_time.py -- and
-// equal at 4 and 8 with the 64-channel patch variant below.)
-int conv_h2w_kwaves(int H, int W, int Cin, int Cout) {
-  (void)Cin;
-  return (long)H * W * Cout >= (long)56 * 56 * 256 ? 1 : 2;  // conv1_2, conv2_x, conv3_x: 1; conv4_x: 2
+  if (P.out_amax) ch2::publish_wave_max(vmax, P.out_amax + (size_t)b * P.amax_stride + ((blockIdx.x * NWAVES + wave) & 63));
+  CH2_STAMP(14);
 }
 
 bool conv_h2w_supported(int H, int W, int Cin, int Cout) {
   return conv_h2_supported(H, W, Cin, Cout) && Cin % 32 == 0 && (long)H * W >= 28 * 28;
 }
 
-// variant: 0 = by shape (the inference path), -1 = round 3's selection by shape and batch (the training step); 1..5 force
-// <4,2,2,1,8,32>, <7,1,4,1,8,28>, <7,1,2,1,8,28>, <7,1,4,2,8,28>, <7,1,2,2,8,28>, 6 the segmented <7,1,4,1,8,28,1,SEG=2>
-// (tests: every shape through every variant; 1..3 have one k-wave, 4..5 two -- variants with the same number of
-// k-waves give the same bits; 6 has its own: one k-wave in segments of two chunks)
-hipError_t conv_h2w_launch(ConvH2Dev d, hipStream_t st, int variant) {
-  // variant 0 (the inference path): layers whose one-k-wave chain would exceed 108 MFMAs per accumulator (Cin >= 128)
-  // take the SEGMENTED form -- chains of 54, the segments summed in fp32 -- whatever the batch; conv1_2 / conv2_1
-  // (Cin = 64: chains of 108 as they are) the round-3 variants below.  variant -1 (the training step): round 3's
-  // selection for every layer (chains of up to 432: faster at 4 .. 11 images per call, 1.7 x the error)
-  if (variant == 0 && d.Cin >= 128 && d.Cout % 128 == 0) {
-    // two K halves (lower / upper k16 blocks), each in segments of two chunks, p0 + p1: as two k-waves over 64-channel
-    // workgroups (variant 7) while that is what fills the chip, as ONE k-wave that parks p0 in LDS (variant 6: four n-waves
-    // per halo, half the loader work per MFMA) from ~200 128-channel workgroups on -- the same bits
-    const long wg128 = (long)d.B * ((d.H + 7) / 8) * ((d.W + 27) / 28) * (d.Cout / 128);
-    variant = wg128 >= 200 ? 6 : 7;
-  }
-  if (variant == 0 || variant == -1) {
-    const int wk = conv_h2w_kwaves(d.H, d.W, d.Cin, d.Cout);
-    if (wk == 1) {
-      // 128-channel workgroups (two per CU) while they give >= ~200 workgroups, else the 64-channel 8 x 32 patches
-      const long wg128 = (long)d.B * ((d.H + 7) / 8) * ((d.W + 27) / 28) * (d.Cout / 128);
-      if (d.Cout % 128 == 0 && wg128 >= 200) variant = 2;
-      else variant = d.W % 32 == 0 || d.Cout % 128 == 0 ? 1 : 3;
-    } else {
-      // 128-channel workgroups of eight waves (two per SIMD) while they still give >= ~200 workgroups, else 64-channel ones
-      const long wg128 = (long)d.B * ((d.H + 7) / 8) * ((d.W + 27) / 28) * (d.Cout / 128);
-      variant = d.Cout % 128 == 0 && wg128 >= 200 ? 4 : 5;
-    }
-  }
-  switch (variant) {
-    case 1: return conv_h2w_go<4, 2, 2, 1, 8, 32, 2>(d, st);
-    case 2: return conv_h2w_go<7, 1, 4, 1, 8, 28, 2>(d, st);
-    case 3: return conv_h2w_go<7, 1, 2, 1, 8, 28, 2>(d, st);
-    case 4: return conv_h2w_go<7, 1, 4, 2, 8, 28, 1>(d, st);
-    case 5: return conv_h2w_go<7, 1, 2, 2, 8, 28, 1>(d, st);
-    case 6: return conv_h2w_go<7, 1, 4, 1, 8, 28, 1, 2, true>(d, st);
-    case 7: return conv_h2w_go<7, 1, 2, 2, 8, 28, 1, 2>(d, st);
+template <ConvForm F, int MB, int MWV, int NWV, int WK, int TH, int TW, int OCC, int SEG = 0, bool PARK = false>
+static hipError_t conv_h2w_go(const ConvH2Dev& d, const ConvPlan& p, hipStream_t st) {
+  constexpr ConvFormGeom g = kConvForms[F];
+  // whole segments; PARK: two K halves of whole segments, the second one starting inside the chunk loop
+  static_assert(g.th == TH && g.tw == TW && g.nch == 32 * NWV && g.block == 64 * MWV * NWV * WK &&
+                    g.cin_mult == (PARK ? 64 : 16 * WK * (SEG > 0 ? SEG : 1)) && (!PARK || g.cin_min == 128), "kConvForms");
+  hipLaunchKernelGGL((conv_h2w_kernel<MB, MWV, NWV, WK, TH, TW, OCC, SEG, PARK>), dim3(p.grid), dim3(p.block), 0, st, d);
+  return hipGetLastError();
+}
+
+// forms with the same number of k-waves and the same segments give the same bits (tests: every shape through every form)
+hipError_t conv_h2w_launch(const ConvH2Dev& d, const ConvPlan& p, hipStream_t st) {
+  switch (p.form) {
+    case CONVW_P32_N2: return conv_h2w_go<CONVW_P32_N2, 4, 2, 2, 1, 8, 32, 2>(d, p, st);
+    case CONVW_N4: return conv_h2w_go<CONVW_N4, 7, 1, 4, 1, 8, 28, 2>(d, p, st);
+    case CONVW_N2: return conv_h2w_go<CONVW_N2, 7, 1, 2, 1, 8, 28, 2>(d, p, st);
+    case CONVW_N4_K2: return conv_h2w_go<CONVW_N4_K2, 7, 1, 4, 2, 8, 28, 1>(d, p, st);
+    case CONVW_N2_K2: return conv_h2w_go<CONVW_N2_K2, 7, 1, 2, 2, 8, 28, 1>(d, p, st);
+    case CONVW_N4_PARK: return conv_h2w_go<CONVW_N4_PARK, 7, 1, 4, 1, 8, 28, 1, 2, true>(d, p, st);
+    case CONVW_N2_K2_SEG: return conv_h2w_go<CONVW_N2_K2_SEG, 7, 1, 2, 2, 8, 28, 1, 2>(d, p, st);
     default: return hipErrorInvalidValue;
   }
 }

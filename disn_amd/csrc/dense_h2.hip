@@ -46,11 +46,7 @@ __global__ __launch_bounds__(256 * NW, 1) void dense_h2_kernel(const DenseH2Dev 
   const int j = lane & 31, g = lane >> 5;
 
   // n-tile major, every XCD a contiguous eighth of the tiles (as conv_h2_kernel)
-  int l;
-  {
-    const int T = gridDim.x, L = blockIdx.x, q = T >> 3, r = T & 7, xcd = L & 7, idx = L >> 3;
-    l = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
+  const int l = xcd_tile(gridDim.x, blockIdx.x);
   const int nt = l / D.mtiles, mt = l - nt * D.mtiles;
   const int m0 = mt * BM;
   const int n0 = (nt * NW + wn) * 32;
@@ -88,15 +84,8 @@ __global__ __launch_bounds__(256 * NW, 1) void dense_h2_kernel(const DenseH2Dev 
       x[0] = fmaxf(x[0] + bb.x, 0.f); x[1] = fmaxf(x[1] + bb.y, 0.f);
       x[2] = fmaxf(x[2] + bb.z, 0.f); x[3] = fmaxf(x[3] + bb.w, 0.f);
     }
-    const float s = sa * gscale[k];
     ch_h4 hh, ll;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const float v = x[e] * s;
-      const _Float16 h = (_Float16)v;
-      hh[e] = h;
-      ll[e] = (_Float16)(v - (float)h);
-    }
+    ch2::split4(x, sa * gscale[k], hh, ll);
     *reinterpret_cast<ch_h4*>(&lds[buf * BUF + woff[k]]) = hh;
     *reinterpret_cast<ch_h4*>(&lds[buf * BUF + woff[k] + CK * 2]) = ll;
   };
@@ -108,20 +97,8 @@ __global__ __launch_bounds__(256 * NW, 1) void dense_h2_kernel(const DenseH2Dev 
   const int Kimg = P.Kimg > 0 ? P.Kimg : K;
   const float* meta = reinterpret_cast<const float*>(P.wimg + (size_t)Kimg * N * 4);
   const size_t aoff = P.amax_rows > 0 ? (size_t)(m0 / P.amax_rows) * P.amax_stride : 0;  // this tile's image
-  float amax_lane = P.in_amax[aoff + lane];
-  if (P.in_amax2) {
-    const int n2 = P.in_amax2_n > 0 ? P.in_amax2_n : 64;
-    for (int i = lane; i < n2; i += 64) amax_lane = fmaxf(amax_lane, P.in_amax2[aoff + i]);
-  }
-  float bmax_lane = 0.f;
-  if (P.in_bias) {
-    // the bound max|a| + max|in_bias|: over this tile's image when the maxima are per image (tiles do not straddle
-    // images then: the scale must not depend on the batch), else over every bias row of the call
-    const float* ib = P.in_bias;
-    int nb = P.in_bias_rows > 0 ? ((M + P.in_bias_rows - 1) / P.in_bias_rows) * K : K;
-    if (P.amax_rows > 0 && P.in_bias_rows > 0) { ib += (size_t)(m0 / P.in_bias_rows) * K; nb = K; }
-    for (int i = lane; i < nb; i += 64) bmax_lane = fmaxf(bmax_lane, fabsf(ib[i]));
-  }
+  float amax_lane, bmax_lane;
+  ch2::dense_operand_maxima(P, m0, aoff, lane, 64, amax_lane, bmax_lane);   // (dense_h2_launch rejects in_amax_n)
   const float inv_sw = meta[n0 + (lane & 31)];  // per output channel (column): the pack scales every column to [2^13, 2^14)
 
   int arow[MB];
@@ -146,12 +123,7 @@ __global__ __launch_bounds__(256 * NW, 1) void dense_h2_kernel(const DenseH2Dev 
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[mb][r] = 0.f;
 
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) {
-    amax_lane = fmaxf(amax_lane, __shfl_xor(amax_lane, off));
-    bmax_lane = fmaxf(bmax_lane, __shfl_xor(bmax_lane, off));
-  }
-  sa = ch2::pow2_scale(amax_lane + bmax_lane, 14);   // |relu(a + b)| <= max|a| + max|b|
+  sa = ch2::pow2_scale(ch2::wave_max(amax_lane) + ch2::wave_max(bmax_lane), 14);   // ch2::dense_operand_maxima
   const float descale = (1.0f / sa) * inv_sw;
 
 #pragma unroll
@@ -222,12 +194,7 @@ __global__ __launch_bounds__(256 * NW, 1) void dense_h2_kernel(const DenseH2Dev 
         vmax = fmaxf(vmax, fabsf(v));
       }
     }
-  if (P.out_amax) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) vmax = fmaxf(vmax, __shfl_xor(vmax, off));
-    if (lane == 0)
-      atomicMax(reinterpret_cast<unsigned*>(P.out_amax) + aoff + ((blockIdx.x * WK * NW + wave) & 63), __float_as_uint(vmax));
-  }
+  if (P.out_amax) ch2::publish_wave_max(vmax, P.out_amax + aoff + ((blockIdx.x * WK * NW + wave) & 63));
 }
 
 bool dense_h2_supported(int M, int K, int N, int k1) {
@@ -304,7 +271,7 @@ size_t disn_pack_dense_h2_bytes(int K, int N) {
 int disn_pack_dense_h2(const float* w_kn, int K, int N, void* image, void* stream) {
   if (!w_kn || !image || K <= 0 || N <= 0) return DISN_E_ARG;
   if (K % 64 || N % 64) return DISN_E_SHAPE;
-  const hipError_t e = disn::conv_h2_pack_launch(w_kn, K, N, image, nullptr, (hipStream_t)stream, 1);
+  const hipError_t e = disn::conv_h2_pack_launch(w_kn, K, N, image, (hipStream_t)stream, 1);
   return e == hipSuccess ? 0 : (int)e;
 }
 

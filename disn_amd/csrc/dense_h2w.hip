@@ -45,11 +45,7 @@ __global__ __launch_bounds__(64 * NWV, NWV / 4) void dense_h2w_kernel(const Dens
   const int j = lane & 31, g = lane >> 5;
 
   // n-tile major, every XCD a contiguous eighth of the tiles (as conv_h2w_kernel)
-  int l;
-  {
-    const int T = gridDim.x, L = blockIdx.x, q = T >> 3, r = T & 7, xcd = L & 7, idx = L >> 3;
-    l = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
+  const int l = xcd_tile(gridDim.x, blockIdx.x);
   const int nt = l / D.mtiles, mt = l - nt * D.mtiles;
   const int m0 = mt * BM;
   const int n0 = (nt * NWV + wn) * 32;
@@ -87,15 +83,8 @@ __global__ __launch_bounds__(64 * NWV, NWV / 4) void dense_h2w_kernel(const Dens
       x[0] = fmaxf(x[0] + bb.x, 0.f); x[1] = fmaxf(x[1] + bb.y, 0.f);
       x[2] = fmaxf(x[2] + bb.z, 0.f); x[3] = fmaxf(x[3] + bb.w, 0.f);
     }
-    const float s = sa * gscale[k];
     ch_h4 hh, ll;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const float v = x[e] * s;
-      const _Float16 h = (_Float16)v;
-      hh[e] = h;
-      ll[e] = (_Float16)(v - (float)h);
-    }
+    ch2::split4(x, sa * gscale[k], hh, ll);
     const int wo = buf * BUF + woff0 + k * (NT / UPP) * KPIX;
     *reinterpret_cast<ch_h4*>(&lds[wo]) = hh;
     *reinterpret_cast<ch_h4*>(&lds[wo + CK * 2]) = ll;
@@ -108,22 +97,8 @@ __global__ __launch_bounds__(64 * NWV, NWV / 4) void dense_h2w_kernel(const Dens
   const int Kimg = P.Kimg > 0 ? P.Kimg : K;
   const float* meta = reinterpret_cast<const float*>(P.wimg + (size_t)Kimg * N * 4);
   const size_t aoff = P.amax_rows > 0 ? (size_t)(m0 / P.amax_rows) * P.amax_stride : 0;  // this tile's image
-  float amax_lane = 0.f;
-  {
-    const int n1 = P.in_amax_n > 0 ? P.in_amax_n : 64;
-    for (int i = lane; i < n1; i += 64) amax_lane = fmaxf(amax_lane, P.in_amax[aoff + i]);
-  }
-  if (P.in_amax2) {
-    const int n2 = P.in_amax2_n > 0 ? P.in_amax2_n : 64;
-    for (int i = lane; i < n2; i += 64) amax_lane = fmaxf(amax_lane, P.in_amax2[aoff + i]);
-  }
-  float bmax_lane = 0.f;
-  if (P.in_bias) {  // the bound max|a| + max|in_bias| over this tile's image (dense_h2_kernel's rule)
-    const float* ib = P.in_bias;
-    int nb = P.in_bias_rows > 0 ? ((M + P.in_bias_rows - 1) / P.in_bias_rows) * K : K;
-    if (P.amax_rows > 0 && P.in_bias_rows > 0) { ib += (size_t)(m0 / P.in_bias_rows) * K; nb = K; }
-    for (int i = lane; i < nb; i += 64) bmax_lane = fmaxf(bmax_lane, fabsf(ib[i]));
-  }
+  float amax_lane, bmax_lane;
+  ch2::dense_operand_maxima(P, m0, aoff, lane, P.in_amax_n > 0 ? P.in_amax_n : 64, amax_lane, bmax_lane);
   const float inv_sw = meta[n0 + (lane & 31)];  // per output channel (column): the pack scales every column to [2^13, 2^14)
 
   int arow[MB];
@@ -151,12 +126,7 @@ __global__ __launch_bounds__(64 * NWV, NWV / 4) void dense_h2w_kernel(const Dens
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[mb][r] = 0.f;
 
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) {
-    amax_lane = fmaxf(amax_lane, __shfl_xor(amax_lane, off));
-    bmax_lane = fmaxf(bmax_lane, __shfl_xor(bmax_lane, off));
-  }
-  sa = ch2::pow2_scale(amax_lane + bmax_lane, 14);   // |relu(a + b)| <= max|a| + max|b|
+  sa = ch2::pow2_scale(ch2::wave_max(amax_lane) + ch2::wave_max(bmax_lane), 14);   // ch2::dense_operand_maxima
   const float descale = (1.0f / sa) * inv_sw;
 
 #pragma unroll
@@ -249,12 +219,7 @@ __global__ __launch_bounds__(64 * NWV, NWV / 4) void dense_h2w_kernel(const Dens
         }
       }
     }
-  if (P.out_amax) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) vmax = fmaxf(vmax, __shfl_xor(vmax, off));
-    if (lane == 0)
-      atomicMax(reinterpret_cast<unsigned*>(P.out_amax) + aoff + ((blockIdx.x * NWV + wn) & 63), __float_as_uint(vmax));
-  }
+  if (P.out_amax) ch2::publish_wave_max(vmax, P.out_amax + aoff + ((blockIdx.x * NWV + wn) & 63));
 }
 
 bool dense_h2w_supported(const DenseH2Prob& p) {

@@ -11,6 +11,7 @@
 //   maxpool2x2       -- slim.max_pool2d                  (models/CNN/vgg.py:188-196)
 //   grid_points      -- linspace/meshgrid grid           (test/create_sdf.py:246-256)
 #include "kernels.hpp"
+#include "h2_common.hpp"
 
 namespace disn {
 
@@ -310,14 +311,6 @@ __device__ __forceinline__ float4 tap_pixel(const float* __restrict__ tap, int h
   return o;
 }
 
-// power of two s with amax * s in [2^14, 2^15) (amax > 0 after feat_split_amax's floor); as pow2_scale_for of
-// mlp_fused.hip: the two sides of the split form must pick the same scale
-__device__ __forceinline__ float split_pow2_scale(float amax) {
-  const int e = (int)((__float_as_uint(amax) >> 23) & 0xffu) - 127;
-  if (!(amax > 0.f) || e > 100 || e < -100) return 1.0f;
-  return __uint_as_float((unsigned)(127 + 14 - e) << 23);
-}
-
 __global__ __launch_bounds__(1024) void project_gather_taps_kernel(TapSet t,
                                                                    const float* __restrict__ trans_mat,
                                                                    const float* __restrict__ pts, int B,
@@ -399,19 +392,15 @@ __global__ __launch_bounds__(1024) void project_gather_taps_kernel(TapSet t,
 #undef DISN_ACC
     }
     if (split_amax) {
-      const float sc = split_pow2_scale(feat_split_amax(split_amax[b]));
-      const float xs[4] = {o.x * sc, o.y * sc, o.z * sc, o.w * sc};
-      _Float16 hh[4], ll[4];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        hh[e] = (_Float16)xs[e];
-        ll[e] = (_Float16)(xs[e] - (float)hh[e]);
-      }
+      const float sc = ch2::pow2_scale(feat_split_amax(split_amax[b]), 14);
+      const float x4[4] = {o.x, o.y, o.z, o.w};
+      ch_h4 hh, ll;
+      ch2::split4(x4, sc, hh, ll);
       // Lanes 2i, 2i + 1 hold the two halves (channels c .. c + 3, c + 4 .. c + 7) of ONE 8-channel group (c4_begin and
       // c4_count are even, threads leave the loop in pairs): the even lane sends its l half and takes the partner's h
       // half, the odd lane the other way round -- one 16-byte store per lane (h8 | l8), a wave's store instruction 1 KiB
       // of contiguous bytes, instead of two 8-byte stores at half density
-      const uint2 hv = *reinterpret_cast<const uint2*>(hh), lv = *reinterpret_cast<const uint2*>(ll);
+      const uint2 hv = *reinterpret_cast<const uint2*>(&hh), lv = *reinterpret_cast<const uint2*>(&ll);
       const bool odd = (c & 4) != 0;
       const uint2 send = odd ? hv : lv;
       uint2 recv;
@@ -584,15 +573,11 @@ __global__ __launch_bounds__(256) void project_gather_taps_wave_kernel(TapSet t,
   float img_amax = 0.f;
   auto emit = [&](size_t p, int b, int c, const float4& o) __attribute__((always_inline)) {
     if (SPLIT) {   // (the kernel above's split store: lanes 2i, 2i + 1 are the halves of one 8-channel group)
-      const float sc = split_pow2_scale(feat_split_amax(img_amax));
-      const float xs[4] = {o.x * sc, o.y * sc, o.z * sc, o.w * sc};
-      _Float16 hh[4], ll[4];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        hh[e] = (_Float16)xs[e];
-        ll[e] = (_Float16)(xs[e] - (float)hh[e]);
-      }
-      const uint2 hv = *reinterpret_cast<const uint2*>(hh), lv = *reinterpret_cast<const uint2*>(ll);
+      const float sc = ch2::pow2_scale(feat_split_amax(img_amax), 14);
+      const float x4[4] = {o.x, o.y, o.z, o.w};
+      ch_h4 hh, ll;
+      ch2::split4(x4, sc, hh, ll);
+      const uint2 hv = *reinterpret_cast<const uint2*>(&hh), lv = *reinterpret_cast<const uint2*>(&ll);
       const bool odd = (c & 4) != 0;
       const uint2 send = odd ? hv : lv;
       uint2 recv;
@@ -792,11 +777,7 @@ __global__ __launch_bounds__(256) void gather_fold_kernel(const float* __restric
   // XCD-aware order: hardware workgroup w runs on XCD w % 8; give each XCD a CONTIGUOUS eighth of the
   // blocks, so the pmap rows its points touch (neighbouring points project to neighbouring pixels)
   // fit its 4 MB L2 instead of all eight L2s streaming the whole footprint from the Infinity Cache
-  unsigned lb = blockIdx.x;
-  {
-    const unsigned W = gridDim.x, q = W >> 3, r = W & 7, xcd = lb & 7, idx = lb >> 3;
-    lb = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
+  const unsigned lb = xcd_tile(gridDim.x, blockIdx.x);
   for (size_t i = (size_t)lb * blockDim.x + threadIdx.x; i < total;
        i += (size_t)gridDim.x * blockDim.x) {
     const size_t pt = i >> 7;

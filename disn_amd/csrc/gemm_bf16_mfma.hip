@@ -207,18 +207,14 @@ __global__ __launch_bounds__(256, (BM * BN >= 128 * 128) ? 2 : 3) void gemm_bf16
     // (n-tile, k-split, m-tile): all m-tiles of one (n-tile, k-split) -- the workgroups that read the same
     // weight slice -- sit on one XCD, and with N/BN == 8 an XCD reads one n-tile's columns only: B crosses
     // the fabric once instead of eight times (measured r01: 117 MB fetched per conv4_x layer for 14.2 MB).
-    const int T = gridDim.x * gridDim.y, L = blockIdx.y * gridDim.x + blockIdx.x;
-    const int q = T >> 3, r = T & 7, xcd = L & 7, idx = L >> 3;
-    const int l = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+    const int l = xcd_tile(gridDim.x * gridDim.y, blockIdx.y * gridDim.x + blockIdx.x);
     const int per = d.S * d.mtiles;
     nt = l / per;
     const int rem = l - nt * per;
     ks = rem / d.mtiles;
     mt = rem - ks * d.mtiles;
   } else {  // consecutive tiles (sharing A rows) on the same XCD
-    int w = blockIdx.x;
-    const int W = gridDim.x, q = W >> 3, r = W & 7, xcd = w & 7, idx = w >> 3;
-    w = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+    const int w = xcd_tile(gridDim.x, blockIdx.x);
     mt = w / d.ntiles;
     nt = w - mt * d.ntiles;
     ks = blockIdx.y;

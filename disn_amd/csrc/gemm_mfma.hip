@@ -71,11 +71,7 @@ void gemm_f32_mfma(const GemmDev d) {
 
   // XCD-aware order: block b runs on XCD b%8; give each XCD a contiguous run of logical
   // workgroup ids, i.e. of tiles (neighbouring tiles share A rows / B columns in that XCD's L2).
-  int w = blockIdx.x;
-  {
-    const int q = d.W >> 3, r = d.W & 7, xcd = w & 7, idx = w >> 3;
-    w = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
+  const int w = xcd_tile(d.W, blockIdx.x);
   const int KS = d.ksteps;
   const long u0 = unit_begin(d.units, d.W, w), u1 = unit_begin(d.units, d.W, w + 1);
 

@@ -63,11 +63,7 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_f32_mfma(const TnDev d) {
   const TnParams& p = d.p;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int wm = wave >> 1, wn = wave & 1;
-  int w = blockIdx.x;
-  {
-    const int q = d.W >> 3, r = d.W & 7, xcd = w & 7, idx = w >> 3;
-    w = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
+  int w = xcd_tile(d.W, blockIdx.x);
   const int MS = d.msteps;
   const int KT = d.kt;
   if (KT > 0) w = blockIdx.x;

@@ -31,6 +31,13 @@ __device__ __forceinline__ void nt_store4(float* p, const float4& v) {
   t[0] = v.x; t[1] = v.y; t[2] = v.z; t[3] = v.w;
   __builtin_nontemporal_store(t, reinterpret_cast<nt_v4f*>(p));
 }
+// XCD-aware order of a launch's T workgroups: hardware workgroup L runs on XCD L % 8; the logical index returned gives
+// every XCD a CONTIGUOUS eighth of 0 .. T - 1 (the first T % 8 XCDs one more), so that the workgroups that share an
+// operand (the tiles of one n-tile's weights, neighbouring rows of a map) share one L2
+__device__ __forceinline__ int xcd_tile(int T, int L) {
+  const int q = T >> 3, r = T & 7, xcd = L & 7, idx = L >> 3;
+  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+}
 #endif
 
 // ---- gemm_mfma.hip -------------------------------------------------------
@@ -348,14 +355,15 @@ hipError_t mlp_fused_launch(bool local, const void* image, const float* w1, cons
 // ---- conv_h2.hip: the single-image 3x3 convolution (two-term f16 split, halo in LDS, K parallel inside the workgroup) ----
 size_t conv_h2_image_bytes(int Cin, int Cout);
 size_t h2_image_bytes(int K, int N, int taps);   // payload + inv_sw[N] + column-maximum scratch[N] + pad
-// w: TF HWIO [3][3][Cin][Cout] (taps = 9) or a [K = Cin][N = Cout] matrix (taps = 1, dense_h2.hip); scratch: one
-// device float; the image holds taps * Cin * Cout * 4 + 256 bytes.  flip_t: w is the forward tensor [taps][Cout][Cin]
-// of a layer and the image the one of its data gradient, w'[t][ci][co] = w[taps - 1 - t][co][ci] (train.hip)
-hipError_t conv_h2_pack_launch(const float* w, int Cin, int Cout, void* image, float* scratch, hipStream_t st,
-                               int taps = 9, int flip_t = 0);
-// Many 3x3 weight images in TWO launches (train.hip re-packs 12 forward + 12 data-gradient images per step; as 72
-// separate memset / max / pack launches they were 0.46 ms of serial 5-us kernels): one max |w| pass over all tensors
-// (job k's scale from wmax[slot]; images of one tensor share a slot), one pack pass over all fragments.
+// w: TF HWIO [3][3][Cin][Cout] (taps = 9) or a [K = Cin][N = Cout] matrix (taps = 1, dense_h2.hip); the image holds
+// h2_image_bytes.  flip_t: w is the forward tensor [taps][Cout][Cin] of a layer and the image the one of its data
+// gradient, w'[t][ci][co] = w[taps - 1 - t][co][ci] (train.hip)
+hipError_t conv_h2_pack_launch(const float* w, int Cin, int Cout, void* image, hipStream_t st, int taps = 9,
+                               int flip_t = 0);
+// Many 3x3 weight images in THREE launches (train.hip re-packs 12 forward + 12 data-gradient images per step; as 72
+// separate memset / max / pack launches they were 0.46 ms of serial 5-us kernels): one clearing pass, one column-maximum
+// pass over all tensors (into the tails of the images; images of one tensor share a slot), one pack pass over all
+// fragments.
 struct ConvH2PackJob {
   const float* w;          // forward tensor [9][Cin_fwd][Cout_fwd]
   unsigned char* image;
@@ -366,7 +374,6 @@ struct ConvH2PackJob {
 struct ConvH2PackJobs {
   int n, nslots;
   long total_frags;
-  float* wmax;             // unused since round 4 (column maxima live in the images' tails)
   const float* seg[16];    // tensor of slot s
   int seg_mid[16], seg_inner[16];          // its [9][mid][inner] shape (Cin_fwd, Cout_fwd)
   float *cmax_fwd[16], *cmax_flip[16];     // column-maximum scratch in the tail of the slot's forward / flipped image
@@ -377,19 +384,59 @@ void conv_h2_pack_job_add(ConvH2PackJobs& jobs, const float* w_fwd, int Cin_fwd,
                           int slot);
 hipError_t conv_h2_pack_multi_launch(const ConvH2PackJobs& jobs, hipStream_t st);
 bool conv_h2_supported(int H, int W, int Cin, int Cout);  // Cin, Cout multiples of 64
+
+// Every instantiation of conv_h2_kernel (conv_h2.hip: one image or a few, K parallel inside the workgroup) and of
+// conv_h2w_kernel (conv_h2w.hip: a batch, waves own n-blocks and walk K) that the library launches.  Forms with the
+// same k-waves and segments give the same bits; which one runs is conv_h2_plan()'s business.
+enum ConvForm {
+  // conv_h2_kernel<MB, NW, SEG, TW, D, WK, ABL = 0, OCC = 1, FL = 0>: patch MB * 32 / SEG rows x TW pixels, 32 NW channels
+  CONV_P14_K4 = 0,       // <1, 1, 16, 14, 9, 4>        2 x 14 patches, four k-waves
+  CONV_P14_K8,           // <1, 1, 16, 14, 9, 8>        ... eight k-waves (Cin % 128 == 0)
+  CONV_P14_K8_OCC2,      // <1, 1, 16, 14, 3, 8, 0, 2>  ... cut for two workgroups per CU
+  CONV_P14_K4_OCC2,      // <1, 1, 16, 14, 3, 4, 0, 2>  the 14 x 14 layers of a batched call, two per CU
+  CONV_P14_K4_OCC2_SEG,  // <1, 1, 16, 14, 3, 4, 0, 2, 2>  ... in segments of two chunks
+  CONV_IMG14_K4,         // <7, 1, 16, 14, 3, 4>        the whole 14 x 14 image as one patch
+  CONV_IMG14_K4_SEG,     // <7, 1, 16, 14, 3, 4, 0, 1, 2>  ... in segments of two chunks
+  CONV_P28_N1_K4,        // <2, 1, 32, 28, 9, 4>        2 x 28 patches, one n-block
+  CONV_P28_N1_K8,        // <2, 1, 32, 28, 9, 8>        ... eight k-waves (Cin % 128 == 0)
+  CONV_P28_N2,           // <2, 2, 32, 28, 9, 4>        2 x 28 patches, two n-blocks
+  CONV_P28_N2_OCC2,      // <2, 2, 32, 28, 1, 4, 0, 2>  ... two workgroups per CU
+  CONV_P16_N2,           // <4, 2, 16, 16, 3, 4>        8 x 16 patches, two n-blocks
+  CONV_P16H_N2_OCC2,     // <2, 2, 16, 16, 1, 4, 0, 2>  4 x 16 (half-height) patches, two workgroups per CU
+  // conv_h2w_kernel<MB, MWV, NWV, WK, TH, TW, OCC, SEG = 0, PARK = false>: patch TH x TW, 32 NWV channels
+  CONVW_P32_N2,          // <4, 2, 2, 1, 8, 32, 2>      8 x 32 patches, two m-waves x two n-waves, one k-wave
+  CONVW_N4,              // <7, 1, 4, 1, 8, 28, 2>      8 x 28 patches, four n-waves, one k-wave
+  CONVW_N2,              // <7, 1, 2, 1, 8, 28, 2>      ... two n-waves
+  CONVW_N4_K2,           // <7, 1, 4, 2, 8, 28, 1>      ... four n-waves x two k-waves
+  CONVW_N2_K2,           // <7, 1, 2, 2, 8, 28, 1>      ... two n-waves x two k-waves
+  CONVW_N4_PARK,         // <7, 1, 4, 1, 8, 28, 1, 2, true>  two K halves in segments of two chunks, one k-wave parks p0
+  CONVW_N2_K2_SEG,       // <7, 1, 2, 2, 8, 28, 1, 2>   ... as two k-waves: the same bits
+  CONV_FORMS,
+  CONVW_FIRST = CONVW_P32_N2
+};
+// the private selections among disn_conv3x3_h2's `tiling` numbers (the others force a patch or a form: conv_h2_plan)
+constexpr int kConvTilingAuto = 0;     // by shape and batch: what inference runs
+constexpr int kConvTilingStrict = 11;  // by shape, the single-image forms whatever B (disn_vgg_weights_t.strict_forms = 1)
+constexpr int kConvTilingTrain = 18;   // round 3's batched selection, unsegmented chains: what the training step runs
+constexpr int kConvWideMinImages = 4;  // images per call from which the launchers take their batched forms (one threshold)
+struct ConvPlan {
+  int form;              // ConvForm, or -1: no kernel for this shape and tiling
+  int grid, block;
+  int tiles_x, tiles_y;  // patches per image
+};
+// Which kernel a call runs, with its launch geometry: a pure host function (no HIP call) and the ONE place that holds
+// the selection thresholds and the validity rules of every tiling.
+ConvPlan conv_h2_plan(int B, int H, int W, int Cin, int Cout, int tiling);
 // in_amax: 64 floats whose maximum is max |in|; out_amax (optional, 64 floats zeroed by the caller): atomic
-// max |out| spread over the slots; pool_out
-// (optional, H and W even): the 2x2 max pool of out; tiling 0: by shape
+// max |out| spread over the slots; pool_out (optional, H and W even): the 2x2 max pool of out
 hipError_t conv_h2_launch(const float* in, int B, int H, int W, int Cin, const void* wimg, const float* bias,
                           int Cout, int relu, const float* in_amax, float* out, float* pool_out, float* out_amax,
-                          hipStream_t st, int tiling = 0, int amax_stride = 0);  // amax_stride > 0: slot groups PER IMAGE
+                          hipStream_t st, int tiling = kConvTilingAuto, int amax_stride = 0);  // amax_stride > 0: slot groups PER IMAGE
 
 // ---- conv_h2w.hip: the same convolution for a batch of images (waves own n-blocks, K sequential; see the file) ----
 struct ConvH2Dev;
 bool conv_h2w_supported(int H, int W, int Cin, int Cout);
-int conv_h2w_kwaves(int H, int W, int Cin, int Cout);   // by layer shape only: fixes the summation order
-hipError_t conv_h2w_launch(ConvH2Dev d, hipStream_t st, int variant);  // variant 0: by shape and batch; 1..5 forced
-constexpr int kConvWideMinImages = 4;   // images per call from which the launchers take their batched forms (one threshold)
+hipError_t conv_h2w_launch(const ConvH2Dev& d, const ConvPlan& plan, hipStream_t st);  // plan.form >= CONVW_FIRST
 
 // conv1_1 (Cin = 3, Cout = 64) as a direct fp32 FMA convolution; w_hwio: the TF tensor [3][3][3][64] as is
 hipError_t conv1_1_direct_launch(const float* in, int B, int H, int W, const float* w_hwio, const float* bias, int relu,

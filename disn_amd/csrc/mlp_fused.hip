@@ -39,6 +39,7 @@
 // s_barrier per slot, counted vmcnt (never 0 in steady state), across point-tile boundaries.
 #include "kernels.hpp"
 #include "tuning.hpp"
+#include "h2_common.hpp"
 
 #include <type_traits>
 #include <utility>
@@ -91,13 +92,6 @@ constexpr int kConstFloats = cS5 + 256;
 // ---------------------------------------------------------------------------------------------------
 // packing
 // ---------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float pow2_scale_for(float amax, int target_exp) {
-  // power of two s with amax * s in [2^target_exp, 2^(target_exp+1)); 1 for amax == 0 / non-finite
-  const int e = (int)((__float_as_uint(amax) >> 23) & 0xffu) - 127;
-  if (!(amax > 0.f) || e > 100 || e < -100) return 1.0f;
-  return __uint_as_float((unsigned)(127 + target_exp - e) << 23);
-}
-
 // one workgroup per layer: per-feature (column) amax -> inverse scale; conv3 and fold2/conv1 (point rows) also the
 // largest column 1-norm
 // k4: rows of w4 -- 512 (the point rows) or 1984 (FEAT form: + the 1472 feature rows; their input is not a hidden
@@ -142,7 +136,7 @@ __global__ __launch_bounds__(256) void fm_meta_kernel(const float* __restrict__ 
     const float mfloor = red[0] * fm::kColFloor;
     __syncthreads();
     for (int f = threadIdx.x; f < N; f += 256) {
-      const float cf = pow2_scale_for(fmaxf(c[f], mfloor), 0);   // m cf in [1, 2) (< 1 below the floor); 1 for an all-zero layer
+      const float cf = ch2::pow2_scale(fmaxf(c[f], mfloor), 0);   // m cf in [1, 2) (< 1 below the floor); 1 for an all-zero layer
       c[f] = cf;
       cmax = fmaxf(cmax, cf);
       float a = 0.f, af = 0.f;
@@ -219,9 +213,10 @@ __global__ __launch_bounds__(256) void fm_pack_kernel(const float* __restrict__ 
     // row factor 1 / c_{l-1}[k] of a hidden input feature (layer 0's input and the gathered features have none)
     const float rk = (layer == 0 || k >= 512) ? 1.0f : 1.0f / meta[fm_meta_off(layer - 1) + k];
     const float v = (layer == 2 && k >= k4) ? 0.f : w[(size_t)k * N + 32 * nt + i] * rk * s;
-    const _Float16 h = (_Float16)v;
+    _Float16 h, l;
+    ch2::split(v, h, l);
     hi[t] = h;
-    lo[t] = (_Float16)(v - (float)h);
+    lo[t] = l;
   }
   h8* out = reinterpret_cast<h8*>(image);
   out[((size_t)p * 2) * 64 + lane] = hi;
@@ -548,9 +543,10 @@ __device__ __forceinline__ void fm_tile_to_frags(const f32x16& acc, const float*
     for (int c = 0; c < 4; ++c) {
       const int r = 4 * rq + c;
       const float v = fmaxf(fmaf(acc[r], inv, b4[c]), 0.f) * s;
-      const _Float16 h = (_Float16)v;
+      _Float16 h, l;
+      ch2::split(v, h, l);
       fh[r >> 3][r & 7] = h;
-      fl[r >> 3][r & 7] = (_Float16)(v - (float)h);
+      fl[r >> 3][r & 7] = l;
     }
   }
 }
@@ -738,7 +734,7 @@ __global__ __launch_bounds__(256, 1) void mlp_fused_kernel(const FusedDev P) {
       }
       if (FEAT) {  // every gathered feature is a convex combination of tap values: |feat| <= max |tap| of the image
         const float fmax = feat_split_amax(P.feat_amax[img]);
-        sfeat = pow2_scale_for(fmax, 14);
+        sfeat = ch2::pow2_scale(fmax, 14);
         inv_sfeat = 1.0f / sfeat;
         addmax4 = fmaf(fmax, cw4f, addmax4_bias);
       }
@@ -804,9 +800,10 @@ __global__ __launch_bounds__(256, 1) void mlp_fused_kernel(const FusedDev P) {
 #pragma unroll
         for (int t = 0; t < 8; ++t) {
           const float v = e1[kb][t] * s;
-          const _Float16 h = (_Float16)v;
+          _Float16 h, l;
+          ch2::split(v, h, l);
           x1h[kb][t] = h;
-          x1l[kb][t] = (_Float16)(v - (float)h);
+          x1l[kb][t] = l;
         }
       FM_SETTLE_IN4(x1h[0], x1h[1], x1h[2], x1h[3]);
       FM_SETTLE_IN4(x1l[0], x1l[1], x1l[2], x1l[3]);
@@ -858,9 +855,10 @@ __global__ __launch_bounds__(256, 1) void mlp_fused_kernel(const FusedDev P) {
 #pragma unroll
           for (int t = 0; t < 8; ++t) {
             const float v = z2[nt][8 * hf + t] * s2;
-            const _Float16 h = (_Float16)v;
+            _Float16 h, l;
+            ch2::split(v, h, l);
             x2h[2 * nt + hf][t] = h;
-            x2l[2 * nt + hf][t] = (_Float16)(v - (float)h);
+            x2l[2 * nt + hf][t] = l;
           }
 #pragma unroll
       for (int i = 0; i < 16; i += 2) FM_SETTLE_IN4(x2h[i], x2l[i], x2h[i + 1], x2l[i + 1]);

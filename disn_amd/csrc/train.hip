@@ -204,7 +204,7 @@ int conv_bwd(const float* x, int B, int H, int W, int Cin, const float* w, const
     DISN_TRY(gemm_tn_launch(t, s.tn_ws, st));
   }
   if (dx && h2img) {
-    DISN_TRY(conv_h2_launch(dz, B, H, W, Cout, h2img, s.zero, Cin, 0, amax, dx, nullptr, nullptr, st, 18, 64));
+    DISN_TRY(conv_h2_launch(dz, B, H, W, Cout, h2img, s.zero, Cin, 0, amax, dx, nullptr, nullptr, st, kConvTilingTrain, 64));
   } else if (dx) {
     const float* wt = prepacked;
     if (!wt) {
@@ -239,7 +239,6 @@ struct TrainWs {
   float* conv_h2bT[13];   // the same for the data gradients (mirrored taps, transposed channels)
   float* amax;
   float* amax_bwd;        // [13][B][64]: per-image maxima of every layer gradient (written by the ReLU-mask pass)
-  float* wmax;            // [16]: max |w| of the 12 packed convolution tensors
   BwdWs bw;
   size_t total;
 };
@@ -324,7 +323,6 @@ TrainWs train_layout(void* ws, int B, int N) {
   for (int i = 1; i < 13; ++i) t.conv_h2bT[i] = b.take(conv_h2_image_bytes(kConv[i].cout, kConv[i].cin) / sizeof(float) + 1);
   t.amax = b.take((size_t)27 * B * 64);       // 14 slot sets of the forward chain + 13 of the layer gradients
   t.amax_bwd = t.amax + (size_t)14 * B * 64;  // [13][B][64], zeroed with the others by the resize launch
-  t.wmax = b.take(16);
   t.red_aux = b.take(colsum_ws_bytes(B, 4096) / sizeof(float) + 1);
   size_t red = colsum_ws_bytes(M, 512);
   for (int i = 0; i < 13; ++i)  // bias-gradient partials of every conv layer (chunks x Cout)
@@ -364,7 +362,7 @@ struct CamTrainWs {
   float *conv_p[13], *conv_bT[13], *conv_h2img[13], *conv_h2bT[13];
   float *resized, *act[13], *pooled[13], *h6, *h7, *emb;
   float *demb, *dz7, *dz6, *dpool5, *gA, *gB, *col, *fc_ws, *sumsq_ws, *red_aux;
-  float *amax, *amax_bwd, *wmax;
+  float *amax, *amax_bwd;
   float *rot, *trans, *pred_RT, *save, *dsave, *dRT, *loss_ws;
   BwdWs bw;
   size_t total;
@@ -400,7 +398,6 @@ CamTrainWs cam_train_layout(void* ws, int B, int N) {
   t.red_aux = b.take(colsum_ws_bytes(B, 4096) / sizeof(float) + 1);
   t.amax = b.take((size_t)27 * B * 64);
   t.amax_bwd = t.amax + (size_t)14 * B * 64;
-  t.wmax = b.take(16);
   t.rot = b.take((size_t)B * 9); t.trans = b.take((size_t)B * 3); t.pred_RT = b.take((size_t)B * 12);
   t.save = b.take((size_t)B * CAM_SAVE_STRIDE); t.dsave = b.take((size_t)B * CAM_SAVE_STRIDE);
   t.dRT = b.take((size_t)B * 12);
@@ -491,10 +488,7 @@ int disn_conv3x3_backward(const float* x, int B, int H, int W, int Cin, const fl
   DISN_TRY(relu_bwd_colsum_launch(dy, y, M, Cout, y != nullptr, db, s.red_ws, st));
   // as in disn_train_step: with compute_bf16 != 0 the data gradient runs through conv_h2.hip / conv_h2w.hip
   const bool h2 = compute_bf16 != 0 && dx && Cin != 3 && conv_h2_supported(H, W, Cout, Cin);
-  if (h2) {
-    float* scratch = h2img + (size_t)Cin * 9 * Cout + 2;
-    DISN_TRY(conv_h2_pack_launch(w_hwio, Cout, Cin, h2img, scratch, st, 9, 1));
-  }
+  if (h2) DISN_TRY(conv_h2_pack_launch(w_hwio, Cout, Cin, h2img, st, 9, 1));
   const bool maxima = compute_bf16 != 0 && Cin != 3;   // dz maxima: data gradient and (mode 2) weight gradient
   if (maxima && compute_bf16 == 2) {
     DISN_TRY(hipMemsetAsync(h2amax + (size_t)B * 64, 0, (size_t)B * 64 * sizeof(float), st));
@@ -635,7 +629,6 @@ int disn_train_step(disn_ctx_t* ctx, const float* params, float* grads, const fl
 
   if (h2fwd) {  // 12 forward + 12 data-gradient images (mirrored taps, transposed channels): three launches in all
     ConvH2PackJobs cj{};
-    cj.wmax = t.wmax;
     for (int i = 1; i < 13; ++i) {
       conv_h2_pack_job_add(cj, P(2 * i), kConv[i].cin, kConv[i].cout, t.conv_h2img[i], 0, i - 1);
       conv_h2_pack_job_add(cj, P(2 * i), kConv[i].cin, kConv[i].cout, t.conv_h2bT[i], 1, i - 1);
@@ -652,7 +645,7 @@ int disn_train_step(disn_ctx_t* ctx, const float* params, float* grads, const fl
     } else if (h2fwd) {
       DISN_TRY(conv_h2_launch(x, B, c.hw, c.hw, c.cin, t.conv_h2img[i], P(2 * i + 1), c.cout, 1,
                               t.amax + (size_t)B * 64 * i, t.act[i], c.pool ? t.pooled[i] : nullptr,
-                              t.amax + (size_t)B * 64 * (i + 1), st, 18, 64));
+                              t.amax + (size_t)B * 64 * (i + 1), st, kConvTilingTrain, 64));
     } else {
       DISN_RC(conv_fwd(x, B, c.hw, c.hw, c.cin, t.conv_p[i], P(2 * i + 1), c.cout, 1, t.act[i], gws, gwb, st, bf));
     }
@@ -867,7 +860,6 @@ int disn_cam_train_step(disn_ctx_t* ctx, const float* params, float* grads, cons
   if (ctx) DISN_TRY(hipEventRecord(ctx->ev[1], as));
   if (h2fwd) {
     ConvH2PackJobs cj{};
-    cj.wmax = t.wmax;
     for (int i = 1; i < 13; ++i) {
       conv_h2_pack_job_add(cj, P(2 * i), kConv[i].cin, kConv[i].cout, t.conv_h2img[i], 0, i - 1);
       conv_h2_pack_job_add(cj, P(2 * i), kConv[i].cin, kConv[i].cout, t.conv_h2bT[i], 1, i - 1);
@@ -884,7 +876,7 @@ int disn_cam_train_step(disn_ctx_t* ctx, const float* params, float* grads, cons
     } else if (h2fwd) {
       DISN_TRY(conv_h2_launch(x, B, c.hw, c.hw, c.cin, t.conv_h2img[i], P(2 * i + 1), c.cout, 1,
                               t.amax + (size_t)B * 64 * i, t.act[i], c.pool ? t.pooled[i] : nullptr,
-                              t.amax + (size_t)B * 64 * (i + 1), st, 18, 64));
+                              t.amax + (size_t)B * 64 * (i + 1), st, kConvTilingTrain, 64));
     } else {
       DISN_RC(conv_fwd(x, B, c.hw, c.hw, c.cin, t.conv_p[i], P(2 * i + 1), c.cout, 1, t.act[i], gws, gwb, st, bf));
     }

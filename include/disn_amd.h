@@ -99,6 +99,7 @@ int disn_conv3x3_x3(const float* in, int B, int H, int W, int Cin, const void* w
  * L MFMAs on one fp32 accumulator carries ~0.3 sqrt(L) ulp of rounding noise (tools/ubench/mfma_round.hip: 6.2 ulp rms
  * at 432, 0.9-1.0 with a restart every 27-54); round 3's chains of 216-432 put 2.7 % of trained-like batched requests at
  * 1.0-1.46e-5 of the float64 oracle (profiles/r05k_sweep_full.json), the segmented forms none (profiles/r06w_sweep_full.json: worst 9.5e-6).
+ * WHICH KERNEL RUNS: the rule above, every threshold and the validity of every tiling are the body of conv_h2_plan() (csrc/conv_h2.hip).
  * ws: disn_conv3x3_h2_workspace_bytes(B). */
 size_t disn_pack_conv_h2_bytes(int Cin, int Cout);
 int disn_pack_conv_h2(const float* w_hwio, int Cin, int Cout, void* image, void* stream);
@@ -119,6 +120,10 @@ size_t disn_conv3x3_h2_workspace_bytes(int B);
 int disn_conv3x3_h2(const float* in, int B, int H, int W, int Cin, const void* image, const float* bias, int Cout,
                     int relu, float* out, float* pool_out, float* out_amax, int tiling, void* ws, size_t ws_bytes,
                     void* stream);
+/* Which kernel that call would run (conv_h2_plan(); needs no device): returns the form's id -- the ids are NOT a stable
+ * interface: they name the library's kernel instantiations of this build (enum ConvForm, csrc/kernels.hpp) -- and its
+ * launch geometry in *grid / *block (either may be NULL), or DISN_E_SHAPE where disn_conv3x3_h2 would. */
+int disn_conv3x3_h2_plan(int B, int H, int W, int Cin, int Cout, int tiling, int* grid, int* block);
 
 /* ---------------------------------------------------------------------- *
  * Row A / E: tf.image.resize_bilinear, TF1 legacy (align_corners=False,    *

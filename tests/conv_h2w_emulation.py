@@ -11,7 +11,8 @@ import numpy as np
 
 from conv_h2_emulation import pack, pow2_scale, quad_row, sigma, split  # noqa: F401  (same weight image, same sigma)
 
-# variant -> MB, MWV, NWV, WK, TH, TW   (conv_h2w_launch's switch)
+# variant -> MB, MWV, NWV, WK, TH, TW   (the CONVW_* forms of enum ConvForm, kernels.hpp, in order: 1 = CONVW_P32_N2 ..
+# 7 = CONVW_N2_K2_SEG)
 VARIANTS = {1: (4, 2, 2, 1, 8, 32), 2: (7, 1, 4, 1, 8, 28), 3: (7, 1, 2, 1, 8, 28), 4: (7, 1, 4, 2, 8, 28),
             5: (7, 1, 2, 2, 8, 28), 6: (7, 1, 4, 1, 8, 28), 7: (7, 1, 2, 2, 8, 28)}
 # round 6, the SEGMENTED variants (SEG = 2): the k16 blocks in two halves (lower -> p0, upper -> p1), each half in segments

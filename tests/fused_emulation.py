@@ -51,6 +51,7 @@ def phi(kb: int, g, t):
 
 
 def pow2_scale_for(amax: float, target_exp: int) -> float:
+    """ch2::pow2_scale (h2_common.hpp): the one scale function of every two-term split"""
     if not (amax > 0) or not np.isfinite(amax):
         return 1.0
     e = int(np.floor(np.log2(np.float32(amax))))
@@ -136,7 +137,7 @@ def exp_of(m):
 
 
 def feat_split_scale(featmax: float) -> np.float32:
-    """the image's power-of-two feature scale (elementwise.hip split_pow2_scale o feat_split_amax)"""
+    """the image's power-of-two feature scale (ch2::pow2_scale o feat_split_amax, as elementwise.hip forms it)"""
     return np.float32(pow2_scale_for(max(float(featmax), 2.0 ** -20), 14))
 
 

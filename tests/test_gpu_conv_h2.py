@@ -131,6 +131,20 @@ def test_tilings_agree_bit_for_bit_and_runs_repeat(ops):
         assert np.array_equal(o[0], v)
 
 
+@pytest.mark.parametrize("tiling,H,W,Cin,Cout", [(1, 16, 14, 128, 512), (3, 32, 28, 64, 512), (4, 64, 64, 64, 512)])
+def test_two_workgroups_per_cu_forms_give_their_siblings_bits(ops, tiling, H, W, Cin, Cout):
+    """three images under a forced tiling launch enough workgroups for the form cut for TWO workgroups per CU (grids of
+    384, 384 and 1536: tests/conv_plan_table.json), each image alone its one-per-CU sibling (128, 128, 256): the same
+    k-waves and summation order, so the same bits -- output and pooled output"""
+    x, w, b = case(3, H, W, Cin, Cout, 4100 + tiling)
+    img, bd = ops.pack_conv_h2(dev(w)), dev(b)
+    out, pooled, _ = ops.conv3x3_h2(dev(x), img, bd, Cout, True, pool=True, tiling=tiling)
+    out, pooled = host(out), host(pooled)
+    for k in range(3):
+        o1, p1, _ = ops.conv3x3_h2(dev(x[k:k + 1]), img, bd, Cout, True, pool=True, tiling=tiling)
+        assert np.array_equal(host(o1)[0], out[k]) and np.array_equal(host(p1)[0], pooled[k])
+
+
 def test_14_pixel_layers_of_a_batched_call_run_with_four_k_waves(ops):
     """14-pixel layers (conv5_x) stay on conv_h2.hip; in a call of four images and more they run with FOUR k-waves in
     segments of two chunks (two-row patches, two workgroups per CU, or the whole-image tiling in large calls): the same
