@@ -196,6 +196,8 @@ SIGNATURES = {
     "disn_mesh_udf_grid": (I, [P, L, P, P, P, I, I, I, I, P, P]),
     "disn_mesh_sign_workspace_bytes": (Z, [I, I, I]),
     "disn_mesh_sign": (I, [P, L, P, P, P, I, I, I, P, F, I, F, P, P, P, Z, P]),
+    "disn_mesh_bvh_build_order": (I, [P, L, P, L, P, Z, P]),
+    "disn_render_views": (I, [P, L, P, P, P, I, I, I, I, F, I, P, P, P, P]),
     "disn_mesh_components": (I, [P, L, L, I, P, C.POINTER(C.c_int64)]),
     "disn_voxel_grid_words": (Z, [I]),
     "disn_voxel_surface_workspace_bytes": (Z, [L]),

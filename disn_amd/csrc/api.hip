@@ -1628,6 +1628,19 @@ int disn_mesh_sign(const void* bvh, int64_t nf, const float* xs, const float* ys
                           (hipStream_t)stream);
 }
 
+// ---- view rendering (render.hip) ----
+int disn_render_views(const void* bvh, int64_t nf, const int32_t* order, const float* albedo, const float* cams,
+                      int V, int H, int W, int S, float ambient, int brute, uint8_t* rgba, float* depth,
+                      int32_t* face, void* stream) {
+  if (!bvh || !cams || !rgba || nf < 1 || V < 1 || H < 1 || W < 1 || S < 1) return DISN_E_ARG;
+  if (!(ambient >= 0.0f && ambient <= 1.0f)) return DISN_E_ARG;
+  if (!order && (albedo || face)) return DISN_E_ARG;
+  if (nf > kBvhMaxTris || S > 4 || H > 1024 || W > 1024 || V > 65535) return DISN_E_SHAPE;
+  DISN_TRY(render_views_launch(bvh, nf, order, albedo, cams, V, H, W, S, ambient, brute, rgba, depth, face,
+                               (hipStream_t)stream));
+  return 0;
+}
+
 // ---- voxel IoU (voxel.hip) ----
 static int voxel_axis(int n) { return n < 1 ? DISN_E_ARG : (n > 1024 ? DISN_E_SHAPE : 0); }
 

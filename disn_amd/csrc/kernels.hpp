@@ -295,6 +295,11 @@ int mesh_sign_launch(const void* bvh, int64_t nf, const float* xs, const float* 
                      int nz, const float* u, float tau, int steps, float offset, float* sdf, unsigned char* outside,
                      void* ws, hipStream_t st);
 
+// ---- render.hip (compiled with -ffp-contract=off): V pinhole views of one mesh over the same BVH image ----
+hipError_t render_views_launch(const void* bvh, int64_t nf, const int32_t* order, const float* albedo,
+                               const float* cams, int V, int H, int W, int S, float ambient, int brute,
+                               uint8_t* rgba, float* depth, int32_t* face, hipStream_t st);
+
 // ---- voxel.hip (compiled with -ffp-contract=off): voxel IoU; n^3 bit grids of n*n rows of ceil(n/32) words ----
 size_t voxel_grid_words(int n);
 size_t voxel_surface_ws_bytes(int64_t nf);

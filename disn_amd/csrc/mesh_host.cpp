@@ -2,7 +2,8 @@
 //   disn_read_obj_mesh  -- Wavefront .obj vertices and faces (fan-triangulated polygons), count-then-fill
 //   disn_mesh_components -- connected components of the triangles (edge or vertex connectivity), union-find
 //   disn_mesh_bvh_build -- deterministic BVH over the triangle soup, laid out for the stackless walk of
-//                          mesh_sdf.hip (node format: mesh_bvh.hpp, private to the library)
+//                          mesh_sdf.hip and render.hip (node format: mesh_bvh.hpp, private to the library);
+//                          disn_mesh_bvh_build_order also returns the slot -> face map of the leaf order
 #include "../../include/disn_amd.h"
 #include "mesh_bvh.hpp"
 
@@ -177,8 +178,8 @@ extern "C" size_t disn_mesh_bvh_bytes(int64_t nf) {
   return disn::bvh_bytes(nf);
 }
 
-extern "C" int disn_mesh_bvh_build(const float* verts, int64_t nv, const int32_t* faces, int64_t nf, void* out,
-                                   size_t out_bytes) {
+extern "C" int disn_mesh_bvh_build_order(const float* verts, int64_t nv, const int32_t* faces, int64_t nf,
+                                         void* out, size_t out_bytes, int32_t* order) {
   if (!verts || !faces || !out || nv < 1 || nf < 1) return DISN_E_ARG;
   if (nf > disn::kBvhMaxTris) return DISN_E_SHAPE;
   if (out_bytes < disn::bvh_bytes(nf)) return DISN_E_WS;
@@ -209,7 +210,13 @@ extern "C" int disn_mesh_bvh_build(const float* verts, int64_t nv, const int32_t
     for (int k = 0; k < 3; ++k) std::memcpy(tri + 9 * i + 3 * k, verts + 3 * (int64_t)faces[3 * (int64_t)t + k],
                                             3 * sizeof(float));
   }
+  if (order) std::memcpy(order, b.idx.data(), (size_t)nf * sizeof(int32_t));
   return 0;
+}
+
+extern "C" int disn_mesh_bvh_build(const float* verts, int64_t nv, const int32_t* faces, int64_t nf, void* out,
+                                   size_t out_bytes) {
+  return disn_mesh_bvh_build_order(verts, nv, faces, nf, out, out_bytes, nullptr);
 }
 
 // ---- connected components of a triangle soup (postprocessing/clean_smallparts.py: pymesh.separate_mesh) ----

@@ -52,20 +52,28 @@ def _mesh_arrays(verts, faces) -> Tuple[np.ndarray, np.ndarray]:
     return v, f
 
 
-def build_bvh_host(verts, faces) -> np.ndarray:
-    """the BVH image (uint8, private layout: csrc/mesh_bvh.hpp) of a triangle soup, built on the host;
-    deterministic: the same mesh gives the same bytes"""
+def build_bvh_host_order(verts, faces) -> Tuple[np.ndarray, np.ndarray]:
+    """-> (image, order): the BVH image (uint8, private layout: csrc/mesh_bvh.hpp) of a triangle soup, built on
+    the host, and order int32 [nf], the face stored in each triangle slot of the image (the image keeps the
+    triangles in leaf order); deterministic: the same mesh gives the same bytes"""
     v, f = _mesh_arrays(verts, faces)
     h = lib()
     nbytes = h.disn_mesh_bvh_bytes(f.shape[0])
     if nbytes == 0:
         raise ValueError("unsupported triangle count %d" % f.shape[0])
     out = np.empty(nbytes, np.uint8)
-    rc = h.disn_mesh_bvh_build(v.ctypes.data, v.shape[0], f.ctypes.data, f.shape[0], out.ctypes.data, nbytes)
+    order = np.empty(f.shape[0], np.int32)
+    rc = h.disn_mesh_bvh_build_order(v.ctypes.data, v.shape[0], f.ctypes.data, f.shape[0], out.ctypes.data, nbytes,
+                                     order.ctypes.data)
     if rc == -1:
         raise ValueError("face index out of range (mesh of %d vertices)" % v.shape[0])
-    check("disn_mesh_bvh_build", rc)
-    return out
+    check("disn_mesh_bvh_build_order", rc)
+    return out, order
+
+
+def build_bvh_host(verts, faces) -> np.ndarray:
+    """the BVH image alone (``build_bvh_host_order``)"""
+    return build_bvh_host_order(verts, faces)[0]
 
 
 class MeshBvh:
@@ -74,9 +82,17 @@ class MeshBvh:
     def __init__(self, verts, faces, device=None):
         v, f = _mesh_arrays(verts, faces)
         self.nf = int(f.shape[0])
-        self.host = build_bvh_host(v, f)
+        self.host, self.order_host = build_bvh_host_order(v, f)
         self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
         self.image = torch.from_numpy(self.host).to(self.device)
+        self._order = None
+
+    @property
+    def order(self) -> torch.Tensor:
+        """the slot -> face map on the device (uploaded on first use: only the renderer reads it)"""
+        if self._order is None:
+            self._order = torch.from_numpy(self.order_host).to(self.device)
+        return self._order
 
 
 def _bvh(mesh, faces=None) -> MeshBvh:

@@ -875,6 +875,38 @@ int disn_mesh_sign(const void* bvh, int64_t nf, const float* xs, const float* ys
                    size_t ws_bytes, void* stream);
 
 /* ---------------------------------------------------------------------- *
+ * View rendering (the renders that preprocessing/create_img_h5.py of the   *
+ * reference reads; a ray caster over the BVH above, not Blender).          *
+ *   disn_mesh_bvh_build_order  (host) disn_mesh_bvh_build (the same image, *
+ *       byte for byte) that also writes order_host [nf] int32: the file-   *
+ *       order face stored in triangle slot s of the image.                 *
+ *   disn_render_views  V views of one mesh in one launch.                  *
+ *       cams [V,12] f32 per view: org[3], d0[3], dx[3], dy[3]; the ray of  *
+ *       image point (x, y) is org + t * ((d0 + x*dx) + y*dy), scaled so    *
+ *       that t is the camera-space depth.  Pixel (row i, col j), sample    *
+ *       (sy, sx) of an S x S grid: x = j + (sx+0.5)/S, y = i + (sy+0.5)/S. *
+ *       Nearest hit per sample by Moeller-Trumbore in fp32, two-sided:     *
+ *       det == 0 skipped, u >= 0, v >= 0, u + v <= 1, t > 0; equal t goes  *
+ *       to the lowest file-order face (order[slot]; the slot when order is *
+ *       NULL).  shade = ambient + (1 - ambient) * |n.d| / (|n||d|), times  *
+ *       albedo[face] ([nf,3] f32 in file order; NULL = 0.8 grey).          *
+ *       rgba [V,H,W,4] u8 (4-byte aligned), straight alpha: colour = the   *
+ *       mean over the hit samples, rounded to nearest, alpha = round(255 * *
+ *       hits / S^2), a miss is (0,0,0,0), no gamma.  depth [V,H,W] f32     *
+ *       (optional): the smallest hit t of the pixel's samples, 0 for none. *
+ *       face [V,H,W] i32 (optional): that sample's file-order face, -1.    *
+ *       order (device, [nf] i32) is required with albedo or face.  S 1..4, *
+ *       H, W <= 1024, V <= 65535, 0 <= ambient <= 1.  brute = 1 tests      *
+ *       every triangle: the same bits, for cross-checks.  Deterministic,   *
+ *       no host synchronisation.                                           *
+ * ---------------------------------------------------------------------- */
+int disn_mesh_bvh_build_order(const float* verts_host, int64_t nv, const int32_t* faces_host, int64_t nf,
+                              void* bvh_host, size_t bvh_bytes, int32_t* order_host);
+int disn_render_views(const void* bvh, int64_t nf, const int32_t* order, const float* albedo, const float* cams,
+                      int V, int H, int W, int S, float ambient, int brute, uint8_t* rgba, float* depth,
+                      int32_t* face, void* stream);
+
+/* ---------------------------------------------------------------------- *
  * Small-part cleanup (postprocessing/clean_smallparts.py of the reference; *
  * pymesh.separate_mesh restated).  (host) labels_host[t] = the connected   *
  * component of triangle t: connectivity 0 joins triangles that share an    *
