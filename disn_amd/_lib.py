@@ -188,6 +188,7 @@ SIGNATURES = {
     "disn_mc_count_batch": (I, [P, I, I, F, P, P, Z, P]),
     "disn_mc_emit_batch": (I, [P, P, I, I, F, P, P, P, Z, P]),
     "disn_write_obj": (I, [C.c_char_p, P, L, P, L]),
+    "disn_write_obj_normals": (I, [C.c_char_p, P, L, P, P, L]),
     "disn_read_obj_verts": (L, [C.c_char_p, P, L]),
     "disn_read_obj_mesh": (I, [C.c_char_p, P, L, P, L, P]),
     "disn_mesh_bvh_bytes": (Z, [L]),
@@ -221,6 +222,8 @@ SIGNATURES = {
     "disn_query_folded": (I, [C.POINTER(MlpWeights), P, P, P, P, P, I, I, P, P, Z, P]),
     "disn_query_grid_folded": (I, [C.POINTER(MlpWeights), P, P, P, C.POINTER(C.c_double * 6), I, L, L, F, P,
                                    P, Z, P]),
+    "disn_query_grad_workspace_bytes": (Z, [I, L]),
+    "disn_query_grad": (I, [C.POINTER(MlpWeights), P, P, P, P, I, L, P, P, P, Z, P]),
 }
 
 _LIB: Optional[C.CDLL] = None

@@ -109,9 +109,8 @@ def dense_grid_sdf(engine, enc, image_index: int, trans_mat, sdf_params, sdf_res
     return engine.query_grid(enc, image_index, trans_mat, sdf_params, sdf_res, k0, k1, sdf_weight, out)
 
 
-def create_sdf(engine, imgs, trans_mats, sdf_params, sdf_res: int, sdf_weight: float = SDF_WEIGHT):
-    """``test_one_epoch`` for one batch (test/create_sdf.py:240-285): returns ``result`` --
-    a float32 device tensor [B, (res+1)^3] of pred_sdf / SDF_WEIGHT."""
+def _encode_grids(engine, imgs, trans_mats, sdf_params, sdf_res: int, sdf_weight: float = SDF_WEIGHT):
+    """one ``engine.encode`` call and the grid of every image -> (Encoded, result [B, (res+1)^3])"""
     import torch
     imgs = np.asarray(imgs, np.float32) if not isinstance(imgs, torch.Tensor) else imgs
     B = imgs.shape[0]
@@ -121,18 +120,35 @@ def create_sdf(engine, imgs, trans_mats, sdf_params, sdf_res: int, sdf_weight: f
     sp = np.asarray(sdf_params, dtype=np.float64).reshape(B, 6)
     for b in range(B):
         dense_grid_sdf(engine, enc, b, trans_mats, sp[b], sdf_res, sdf_weight, out=result[b])
-    return result
+    return enc, result
 
 
-def reconstruct(engine, imgs, trans_mats, sdf_params, sdf_res: int, iso: float = 0.0):
+def create_sdf(engine, imgs, trans_mats, sdf_params, sdf_res: int, sdf_weight: float = SDF_WEIGHT):
+    """``test_one_epoch`` for one batch (test/create_sdf.py:240-285): returns ``result`` --
+    a float32 device tensor [B, (res+1)^3] of pred_sdf / SDF_WEIGHT."""
+    return _encode_grids(engine, imgs, trans_mats, sdf_params, sdf_res, sdf_weight)[1]
+
+
+def reconstruct(engine, imgs, trans_mats, sdf_params, sdf_res: int, iso: float = 0.0, refine: int = 0,
+                normals: bool = False):
     """images -> meshes for one group of views: one ``engine.encode`` call, the per-image grids of
     ``create_sdf`` in one [B,(res+1)^3] tensor, ONE batched meshing (one host sync for the group).
     -> B x (verts [nv,3] float32, faces [nf,3] int32) device views; the bits are those of ``create_sdf``
-    followed by ``isosurface.marching_cubes`` image by image."""
+    followed by ``isosurface.marching_cubes`` image by image.
+    ``refine`` > 0: behind the meshing every view's vertices take that many Newton steps onto the network's iso
+    level set (``isosurface.refine_mesh``, from the view's cached folded map); ``normals``: every mesh is a triple
+    (verts, faces, normals [nv,3]) with the unit gradient at its (refined) vertices.  Faces never change."""
     from . import isosurface
-    grids = create_sdf(engine, imgs, trans_mats, sdf_params, sdf_res)
+    enc, grids = _encode_grids(engine, imgs, trans_mats, sdf_params, sdf_res)
     sp = np.asarray(sdf_params, dtype=np.float64).reshape(grids.shape[0], 6)
-    return isosurface.marching_cubes_batch(grids, sp, sdf_res, iso)
+    meshes = isosurface.marching_cubes_batch(grids, sp, sdf_res, iso)
+    if refine <= 0 and not normals:
+        return meshes
+    out = []
+    for b, (verts, faces) in enumerate(meshes):
+        v, f, n = isosurface.refine_mesh(engine, enc, b, trans_mats, verts, faces, sp[b], sdf_res, iso, max(int(refine), 0))
+        out.append((v, f, n) if normals else (v, f))
+    return out
 
 
 # ---- the test-set driver ---------------------------------------------------------------------------
@@ -214,6 +230,9 @@ def parser():
     p.add_argument("--writers", type=int, default=4, help="writer threads, at most %d [default: 4]" % MAX_WRITERS)
     p.add_argument("--num_shards", type=int, default=1)
     p.add_argument("--shard_id", type=int, default=0)
+    p.add_argument("--refine", type=int, default=0, metavar="ITERS",
+                   help="Newton steps that move every vertex onto the network's iso level set [default: 0, none]")
+    p.add_argument("--normals", action="store_true", help="write the unit SDF gradient at every vertex as 'vn' lines")
     return p
 
 
@@ -226,6 +245,8 @@ def check_flags(a) -> None:
         raise ValueError("--writers must be in 1..%d, got %d" % (MAX_WRITERS, a.writers))
     if a.sdf_res < 1:
         raise ValueError("--sdf_res must be positive")
+    if a.refine < 0:
+        raise ValueError("--refine must not be negative")
 
 
 def restore_weights(log_dir: str, random_init: Optional[int]):
@@ -279,7 +300,7 @@ def main(argv=None, reconstruct_fn: Optional[Callable] = None) -> dict:
                            else None, strict=a.strict)
 
         def reconstruct_fn(imgs, trans_mats, sdf_params):
-            return reconstruct(engine, imgs, trans_mats, sdf_params, a.sdf_res, a.iso)
+            return reconstruct(engine, imgs, trans_mats, sdf_params, a.sdf_res, a.iso, a.refine, a.normals)
 
     os.makedirs(out_dir, exist_ok=True)
     logf = open(os.path.join(a.log_dir, "log_test.txt"), "a")
@@ -289,8 +310,8 @@ def main(argv=None, reconstruct_fn: Optional[Callable] = None) -> dict:
         logf.flush()
         print(s)
 
-    def write(path, verts, faces):
-        isosurface.write_obj(path, verts, faces)           # device-to-host copy + file, on a writer thread
+    def write(path, verts, faces, *normals):
+        isosurface.write_obj(path, verts, faces, *normals)  # device-to-host copy + file, on a writer thread
         return path
 
     written = empty = 0
@@ -313,14 +334,14 @@ def main(argv=None, reconstruct_fn: Optional[Callable] = None) -> dict:
                 for f in in_flight:                         # the group before this one: a writer's exception surfaces
                     f.result()
                 in_flight = []
-                for (cat_id, obj, view), (verts, faces) in zip(group, meshes):
+                for (cat_id, obj, view), (verts, faces, *vn) in zip(group, meshes):
                     path = obj_path(out_dir, cat_id, obj, view)
                     if len(verts) == 0 or len(faces) == 0:
                         empty += 1
                         log_string("%d/%d, EMPTY mesh (no surface at iso %s): %s" % (gi, len(work), a.iso, path))
                     else:
                         log_string("%d/%d, submit create_obj %s, %s, %s" % (gi, len(work), cat_id, obj, view))
-                    in_flight.append(writers.submit(write, path, verts, faces))
+                    in_flight.append(writers.submit(write, path, verts, faces, *vn))
                     written += 1
             for f in in_flight:
                 f.result()

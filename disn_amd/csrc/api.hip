@@ -1255,6 +1255,108 @@ int disn_query_folded(const disn_mlp_weights_t* w, const float* pmap, const floa
   return query_impl(w, true, pmap, embedding, trans_mat, pts, pts_rot, B, N, sdf, ws, ws_bytes, (hipStream_t)stream);
 }
 
+// ---- gradient of pred_sdf at the query points (include/disn_amd.h; sdf_grad.hip) ----------------------------
+namespace {
+const int kGradChunk = 16384;  // points per pass: 65536 stacked rows
+
+struct GradWs {
+  float *gbias, *gemv_ws, *zero512;
+  float *e1g, *e1l, *h256, *h512a, *h512b, *g5, *l5;  // [4 chunk][64 | 64 | 256 | 512 | 512 | 256 | 256]
+  size_t total;
+};
+
+GradWs grad_layout(void* ws, int B, int chunk) {
+  Bump b(ws);
+  GradWs g;
+  const size_t rows = (size_t)chunk * 4 * sizeof(float);
+  g.gbias = b.take((size_t)B * 512 * sizeof(float));
+  g.gemv_ws = b.take(gemv_ws_bytes(1, DISN_EMBED_DIM, 512));
+  g.zero512 = b.take(512 * sizeof(float));
+  g.e1g = b.take(rows * 64);
+  g.e1l = b.take(rows * 64);
+  g.h256 = b.take(rows * 256);
+  g.h512a = b.take(rows * 512);
+  g.h512b = b.take(rows * 512);
+  g.g5 = b.take(rows * 256);
+  g.l5 = b.take(rows * 256);
+  g.total = (b.off + 255) & ~size_t(255);
+  return g;
+}
+
+// out [rows][N] = a [rows][K] . W, no bias, no ReLU, on the f32-input MFMA kernel under a FIXED plan: 128 x 128 tiles,
+// one workgroup per tile, the whole K range in ascending order -- a row's sums do not depend on the row count of the
+// call or on the row's position in it (the cost model's stream-K plans cut K by the row count)
+int grad_dense(const float* a, int K, int rows, const float* w_packed, const float* zero_bias, int N, float* out,
+               hipStream_t st) {
+  GemmParams p{};
+  p.a1 = a; p.lda1 = K; p.k1 = K;
+  p.M = rows; p.N = N; p.K = K;
+  p.bp = w_packed; p.bias = zero_bias; p.rows_per_bias = 0;
+  p.out = out; p.ldc = N; p.relu = 0;
+  const int force[3] = {128, 128, -1};
+  const GemmPlan pl = gemm_plan(rows, N, K, 0, force);
+  if (pl.bm != 128 || pl.bn != 128 || pl.ws_bytes != 0 || pl.wgs != ((rows + 127) / 128) * (N / 128)) return DISN_E_SHAPE;
+  DISN_TRY(gemm_launch(p, GEMM_DENSE, pl, nullptr, st));
+  return 0;
+}
+
+// n points of ONE image (gbias_b = its folded bias row)
+int grad_chunk(const disn_mlp_weights_t* w, const float* pmap_b, const float* trans_mat_b, const float* pts, int n,
+               const float* gbias_b, float* sdf, float* grad, const GradWs& s, hipStream_t st) {
+  const int rows = 4 * n;
+  DISN_TRY(grad_embed_launch(pts, n, w->g_w1, w->g_b1, w->l_w1, w->l_b1, s.e1g, s.e1l, st));
+  // global stream: fold1/conv2, conv3, fold2/conv1 (point rows + the image's bias row), fold2/conv2
+  DISN_RC(grad_dense(s.e1g, 64, rows, w->g_w2, s.zero512, 256, s.h256, st));
+  DISN_TRY(grad_act_launch(s.h256, n, 256, w->g_b2, st));
+  DISN_RC(grad_dense(s.h256, 256, rows, w->g_w3, s.zero512, 512, s.h512a, st));
+  DISN_TRY(grad_act_launch(s.h512a, n, 512, w->g_b3, st));
+  DISN_RC(grad_dense(s.h512a, 512, rows, w->g_w4_point, s.zero512, 512, s.h512b, st));
+  DISN_TRY(grad_act_launch(s.h512b, n, 512, gbias_b, st));
+  DISN_RC(grad_dense(s.h512b, 512, rows, w->g_w5, s.zero512, 256, s.g5, st));
+  DISN_TRY(grad_act_launch(s.g5, n, 256, w->g_b5, st));
+  // local stream: the same layers, fold2/conv1 from the folded map
+  DISN_RC(grad_dense(s.e1l, 64, rows, w->l_w2, s.zero512, 256, s.h256, st));
+  DISN_TRY(grad_act_launch(s.h256, n, 256, w->l_b2, st));
+  DISN_RC(grad_dense(s.h256, 256, rows, w->l_w3, s.zero512, 512, s.h512a, st));
+  DISN_TRY(grad_act_launch(s.h512a, n, 512, w->l_b3, st));
+  DISN_RC(grad_dense(s.h512a, 512, rows, w->l_w4_point, s.zero512, 512, s.h512b, st));
+  DISN_TRY(grad_local_seed_launch(pmap_b, trans_mat_b, pts, n, s.h512b, w->l_b4, st));
+  DISN_RC(grad_dense(s.h512b, 512, rows, w->l_w5, s.zero512, 256, s.l5, st));
+  DISN_TRY(grad_act_launch(s.l5, n, 256, w->l_b5, st));
+  DISN_TRY(grad_head_launch(s.g5, s.l5, n, w->g_w6, w->g_b6, w->l_w6, w->l_b6, sdf, grad, st));
+  return 0;
+}
+}  // namespace
+
+size_t disn_query_grad_workspace_bytes(int B, int64_t N) {
+  if (B <= 0 || N <= 0) return 0;
+  return grad_layout(nullptr, B, (int)(N < kGradChunk ? N : kGradChunk)).total;
+}
+
+int disn_query_grad(const disn_mlp_weights_t* w, const float* pmap, const float* embedding,
+                    const float* trans_mat, const float* pts, int B, int64_t N,
+                    float* sdf, float* grad, void* ws, size_t ws_bytes, void* stream) {
+  if (!mlp_weights_ok(w) || !w->l_w4_point || !pmap || !embedding || !trans_mat || !pts || !grad || !ws || B <= 0 ||
+      N <= 0)
+    return DISN_E_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  const int chunk = (int)(N < kGradChunk ? N : kGradChunk);
+  const GradWs s = grad_layout(ws, B, chunk);
+  if (s.total > ws_bytes) return DISN_E_WS;
+  DISN_TRY(hipMemsetAsync(s.zero512, 0, 512 * sizeof(float), st));
+  // one launch per image: the row of image b is the row of a call of one image, whatever B
+  for (int b = 0; b < B; ++b)
+    DISN_RC(gbias_layer(w, embedding + (size_t)b * DISN_EMBED_DIM, 1, s.gbias + (size_t)b * 512, s.gemv_ws, st));
+  for (int b = 0; b < B; ++b)
+    for (int64_t n0 = 0; n0 < N; n0 += chunk) {
+      const int n = (int)((N - n0) < chunk ? (N - n0) : chunk);
+      const size_t o = (size_t)b * (size_t)N + (size_t)n0;
+      DISN_RC(grad_chunk(w, pmap + (size_t)b * kMapPixels * 512, trans_mat + (size_t)b * 12, pts + o * 3, n,
+                         s.gbias + (size_t)b * 512, sdf ? sdf + o : nullptr, grad + o * 3, s, st));
+    }
+  return 0;
+}
+
 int disn_query_grid_folded(const disn_mlp_weights_t* w, const float* pmap, const float* embedding,
                            const float* trans_mat, const double* sdf_params_host, int R,
                            int64_t k0, int64_t k1, float sdf_weight, float* out, void* ws,

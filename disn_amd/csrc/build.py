@@ -33,6 +33,7 @@ SOURCES = {
     "cam_train.hip": ["-ffp-contract=off"],    # fixed-order camera losses and head gradients
     "mlp_small.hip": [],
     "mlp_fused.hip": [],
+    "sdf_grad.hip": ["-ffp-contract=off"],      # the projection rounds as elementwise.hip's: the forward gather's cell
     "conv_h2.hip": ["-mllvm", "-pragma-unroll-threshold=1000000"],
     "conv_h2w.hip": ["-mllvm", "-pragma-unroll-threshold=1000000"],   # the unrolled chunk bodies exceed the default 16 k
     "dense_h2.hip": [],

@@ -50,8 +50,9 @@ extern "C" uint32_t disn_crc32c(const void* data, size_t n, uint32_t crc) {
 #include <cstdlib>
 #include <string>
 
-extern "C" int disn_write_obj(const char* path, const float* verts, int64_t nv, const int32_t* faces,
-                              int64_t nf) {
+// normals == nullptr: the plain file; else nv "vn" lines behind the vertices and faces "f a//a b//b c//c"
+static int write_obj_impl(const char* path, const float* verts, int64_t nv, const float* normals, const int32_t* faces,
+                          int64_t nf) {
   if (!path || (nv > 0 && !verts) || (nf > 0 && !faces) || nv < 0 || nf < 0) return DISN_E_ARG;
   std::FILE* f = std::fopen(path, "wb");
   if (!f) return DISN_E_ARG;
@@ -69,15 +70,33 @@ extern "C" int disn_write_obj(const char* path, const float* verts, int64_t nv, 
     buf.append(line, n);
     if (buf.size() > (1u << 22) - 256) flush();
   }
+  for (int64_t i = 0; normals && i < nv; ++i) {
+    const int n = std::snprintf(line, sizeof line, "vn %.9g %.9g %.9g\n", normals[3 * i], normals[3 * i + 1],
+                                normals[3 * i + 2]);
+    buf.append(line, n);
+    if (buf.size() > (1u << 22) - 256) flush();
+  }
   for (int64_t i = 0; i < nf; ++i) {
-    const int n = std::snprintf(line, sizeof line, "f %d %d %d\n", faces[3 * i] + 1, faces[3 * i + 1] + 1,
-                                faces[3 * i + 2] + 1);
+    const int a = faces[3 * i] + 1, b = faces[3 * i + 1] + 1, c = faces[3 * i + 2] + 1;
+    const int n = normals ? std::snprintf(line, sizeof line, "f %d//%d %d//%d %d//%d\n", a, a, b, b, c, c)
+                          : std::snprintf(line, sizeof line, "f %d %d %d\n", a, b, c);
     buf.append(line, n);
     if (buf.size() > (1u << 22) - 256) flush();
   }
   flush();
   ok = (std::fclose(f) == 0) && ok;
   return ok ? 0 : DISN_E_ARG;
+}
+
+extern "C" int disn_write_obj(const char* path, const float* verts, int64_t nv, const int32_t* faces,
+                              int64_t nf) {
+  return write_obj_impl(path, verts, nv, nullptr, faces, nf);
+}
+
+extern "C" int disn_write_obj_normals(const char* path, const float* verts, int64_t nv, const float* normals,
+                                      const int32_t* faces, int64_t nf) {
+  if (nv > 0 && !normals) return DISN_E_ARG;
+  return write_obj_impl(path, verts, nv, nv > 0 ? normals : nullptr, faces, nf);
 }
 
 // Vertex-only .obj reader for the evaluation driver (a 300 k-vertex mesh in a few tens of ms): the whole file is

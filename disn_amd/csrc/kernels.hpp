@@ -501,6 +501,22 @@ hipError_t final_dot_launch(const float* g5, const float* l5, int64_t M, const f
                             const float* g_b6, const float* l_w6, const float* l_b6, float* sdf,
                             float* sdf_g, float* sdf_l, float out_div, hipStream_t st);
 
+// ---- sdf_grad.hip (compiled with -ffp-contract=off): forward-mode d pred_sdf / d point ------------
+// A point is four stacked rows [value; d/dx; d/dy; d/dz]; every buffer below has 4 n rows.
+// fold1/conv1 of both streams: pts [n][3] -> out_g, out_l [4 n][64] (value row relu'd, tangent rows = rows of w1, masked)
+hipError_t grad_embed_launch(const float* pts, int64_t n, const float* g_w1, const float* g_b1, const float* l_w1,
+                             const float* l_b1, float* out_g, float* out_l, hipStream_t st);
+// in place on x [4 n][C] (a bias-free, ReLU-free product): value row relu(z + bias), tangent rows kept where z + bias > 0
+hipError_t grad_act_launch(float* x, int64_t n, int C, const float* bias, hipStream_t st);
+// the folded local fold2/conv1, in place on pre [4 n][512]: + resample(pmap_b)(project(p)) + bias on the value row,
+// + dg/du du/dp + dg/dv dv/dp on the tangent rows, then ReLU / mask
+hipError_t grad_local_seed_launch(const float* pmap_b, const float* trans_mat_b, const float* pts, int64_t n,
+                                  float* pre, const float* bias, hipStream_t st);
+// g5, l5 [4 n][256] -> sdf [n] (optional) = (g . g_w6 + g_b6) + (l . l_w6 + l_b6) of the value rows, grad [n][3] = the
+// tangent rows' g . g_w6 + l . l_w6
+hipError_t grad_head_launch(const float* g5, const float* l5, int64_t n, const float* g_w6, const float* g_b6,
+                            const float* l_w6, const float* l_b6, float* sdf, float* grad, hipStream_t st);
+
 // ---- cam_head.hip / cam_train.hip ----------------------------------------------
 struct CamK {
   float k[9];

@@ -1,7 +1,7 @@
 """One image to one mesh: the reference's ``demo/demo.py [--cam_est]`` on the HIP engine.
 
     python -m disn_amd.demo --img VIEW.png --log_dir CKPT [--cam_est --cam_log_dir CAM_CKPT]
-                            [--sdf_res 64] [--iso 0.0] [--out demo/result.obj]
+                            [--sdf_res 64] [--iso 0.0] [--out demo/result.obj] [--refine ITERS] [--normals]
 
 The image is read as demo/demo.py:261-279 reads it (``cv2.imread(IMREAD_UNCHANGED)[:, :, :3] / 255``: the
 channels in B, G, R order, alpha dropped) -- through PIL, which is what this project has.  Without ``--cam_est``
@@ -78,6 +78,9 @@ def parser() -> argparse.ArgumentParser:
     p.add_argument("--out", default=os.path.join("demo", "result.obj"), help="the mesh to write")
     p.add_argument("--random_init", type=int, default=None, metavar="SEED",
                    help="run on freshly initialised weights where a checkpoint is missing")
+    p.add_argument("--refine", type=int, default=0, metavar="ITERS",
+                   help="Newton steps that move every vertex onto the network's iso level set [default: 0, none]")
+    p.add_argument("--normals", action="store_true", help="write the unit SDF gradient at every vertex as 'vn' lines")
     return p
 
 
@@ -100,8 +103,10 @@ def main(argv=None) -> dict:
         print("here we use gt cam parameters")
         trans_mat = DEMO_TRANS_MAT
     engine = SdfEngine(store)
-    verts, faces = reconstruct(engine, img, trans_mat, DEMO_SDF_PARAMS, a.sdf_res, a.iso)[0]
-    isosurface.write_obj(a.out, verts, faces)
+    if a.refine < 0:
+        raise ValueError("--refine must not be negative")
+    verts, faces, *vn = reconstruct(engine, img, trans_mat, DEMO_SDF_PARAMS, a.sdf_res, a.iso, a.refine, a.normals)[0]
+    isosurface.write_obj(a.out, verts, faces, *vn)
     print("wrote %s: %d vertices, %d triangles" % (a.out, len(verts), len(faces)))
     tm = trans_mat.cpu().numpy() if hasattr(trans_mat, "cpu") else trans_mat
     return {"out": a.out, "verts": len(verts), "faces": len(faces), "trans_mat": tm}

@@ -324,6 +324,77 @@ class SdfEngine:
                 return ops.query_folded(self.weights.mlp, pm, enc.embedding, trans_mat, pts, pts_rot, ws)
             return ops.query(self.weights.mlp, self.featmap_of(enc), enc.embedding, trans_mat, pts, pts_rot, ws)
 
+    def query_grad(self, enc: Encoded, pts, trans_mat):
+        """pts [B,N,3] -> (pred_sdf [B,N] un-divided, grad [B,N,3] = d pred_sdf / d pts), the same point fed as
+        sample_pc and sample_pc_rot (test/create_sdf.py:268-269).  Forward mode through the folded local stream
+        (pmap_of, built and cached like query(fold=True)'s); fp32-accurate.  A point's results do not
+        depend on B, N or its position in the call, bit for bit."""
+        pts, trans_mat = self._dev(pts), self._dev(trans_mat)
+        with torch.cuda.device(self.device):
+            B = pts.shape[0]
+            pm = self.pmap_of(enc, 0) if B == 1 else torch.stack([self.pmap_of(enc, b) for b in range(B)])
+            ws = self._workspace("grad", lib().disn_query_grad_workspace_bytes(B, pts.shape[1]))
+            return ops.query_grad(self.weights.mlp, pm, enc.embedding, trans_mat, pts, ws)
+
+    # |f| has to fall by more than this for a Newton step to be taken: two fp32 evaluations of pred_sdf may disagree by
+    # the project's 1e-5 bar each, and a vertex must not end worse than it started by ANY of the query forms' measure
+    REFINE_MIN_DECREASE = 2e-5
+
+    def refine_vertices(self, enc: Encoded, image_index: int, trans_mat, verts, iso: float = 0.0, iters: int = 2,
+                        sdf_weight: float = 10.0, cell: Optional[float] = None):
+        """Safeguarded Newton steps p <- p - (f / |grad f|^2) grad f on f = pred_sdf - iso * sdf_weight for the
+        vertices [nv,3] of image ``image_index``'s surface -> (verts' [nv,3], normals [nv,3], residual [nv]).
+        A step is capped at ``cell`` / 2 and a vertex's total displacement at ``cell`` (None: no caps); a step that
+        does not lower |f| (by more than REFINE_MIN_DECREASE) is halved once and otherwise dropped, so no vertex ends
+        worse than it started; a vertex with |grad f|^2 < 1e-12 stays.  normals = grad pred / |grad pred| at the final
+        position (the direction of INCREASING sdf; zero for the degenerate vertex), residual = |f| there.  All of it
+        device work: 1 + 2 * iters query_grad calls, no host round trip."""
+        verts = self._dev(verts).reshape(-1, 3)
+        tm = self._dev(trans_mat).reshape(-1, 4, 3)
+        tm = tm[image_index if tm.shape[0] > 1 else 0].reshape(1, 4, 3).contiguous()
+        nv = verts.shape[0]
+        if nv == 0:
+            return verts, torch.zeros_like(verts), verts.new_zeros((0,))
+        with torch.cuda.device(self.device):
+            pm = self.pmap_of(enc, image_index)
+            emb = enc.embedding[image_index:image_index + 1]
+            ws = self._workspace("grad", lib().disn_query_grad_workspace_bytes(1, nv))
+            target = float(iso) * float(sdf_weight)
+
+            def evaluate(p):
+                sdf, g = ops.query_grad(self.weights.mlp, pm, emb, tm, p.reshape(1, nv, 3).contiguous(), ws)
+                return sdf.reshape(nv) - target, g.reshape(nv, 3)
+
+            def capped(p, step):
+                if cell is None:
+                    return p + step
+                d = (p + step) - verts                      # the total displacement stays within one cell
+                dl = d.norm(dim=1, keepdim=True)
+                return verts + d * torch.clamp(float(cell) / dl.clamp_min(1e-30), max=1.0)
+
+            p = verts.clone()
+            f, g = evaluate(p)
+            for _ in range(int(iters)):
+                g2 = (g * g).sum(dim=1, keepdim=True)
+                step = torch.where(g2 >= 1e-12, -(f[:, None] / g2.clamp_min(1e-12)) * g, torch.zeros_like(g))
+                if cell is not None:
+                    sl = step.norm(dim=1, keepdim=True)
+                    step = step * torch.clamp(0.5 * float(cell) / sl.clamp_min(1e-30), max=1.0)
+                limit = f.abs() - self.REFINE_MIN_DECREASE
+                p1 = capped(p, step)
+                f1, g1 = evaluate(p1)
+                p2 = capped(p, 0.5 * step)
+                f2, g2_ = evaluate(p2)
+                take1 = f1.abs() < limit
+                take2 = ~take1 & (f2.abs() < limit)
+                t1, t2 = take1[:, None], take2[:, None]
+                p = torch.where(t1, p1, torch.where(t2, p2, p))
+                g = torch.where(t1, g1, torch.where(t2, g2_, g))
+                f = torch.where(take1, f1, torch.where(take2, f2, f))
+            gl = g.norm(dim=1, keepdim=True)
+            normals = torch.where(gl * gl >= 1e-12, g / gl.clamp_min(1e-30), torch.zeros_like(g))
+            return p, normals, f.abs()
+
     def query_grid(self, enc: Encoded, image_index: int, trans_mat, sdf_params, res: int,
                    k0: int = 0, k1: Optional[int] = None, sdf_weight: float = 10.0,
                    out: Optional[torch.Tensor] = None, pipelined: bool = False,

@@ -102,12 +102,36 @@ def marching_cubes_batch(sdf: torch.Tensor, sdf_params, res: int, iso: float = 0
     return out
 
 
-def write_obj(path: str, verts, faces) -> None:
-    """Wavefront .obj ("v x y z" / "f a b c", 1-based)."""
-    v = np.ascontiguousarray(verts.detach().cpu().numpy() if isinstance(verts, torch.Tensor) else verts, np.float32)
-    f = np.ascontiguousarray(faces.detach().cpu().numpy() if isinstance(faces, torch.Tensor) else faces, np.int32)
+def write_obj(path: str, verts, faces, normals=None) -> None:
+    """Wavefront .obj ("v x y z" / "f a b c", 1-based).  With ``normals`` [nv,3]: one "vn x y z" line per vertex
+    behind the vertices and faces "f a//a b//b c//c"; without, the plain file."""
+    host = lambda a: a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a
+    v = np.ascontiguousarray(host(verts), np.float32)
+    f = np.ascontiguousarray(host(faces), np.int32)
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-    check("disn_write_obj", lib().disn_write_obj(path.encode(), v.ctypes.data, v.shape[0], f.ctypes.data, f.shape[0]))
+    if normals is None:
+        check("disn_write_obj", lib().disn_write_obj(path.encode(), v.ctypes.data, v.shape[0], f.ctypes.data, f.shape[0]))
+        return
+    n = np.ascontiguousarray(host(normals), np.float32)
+    if n.shape != v.shape:
+        raise ValueError("normals must be [nv,3] like verts, got %s for %s" % (n.shape, v.shape))
+    check("disn_write_obj_normals", lib().disn_write_obj_normals(path.encode(), v.ctypes.data, v.shape[0], n.ctypes.data,
+                                                                 f.ctypes.data, f.shape[0]))
+
+
+def refine_mesh(engine, enc, image_index: int, trans_mat, verts, faces, sdf_params, res: int, iso: float = 0.0,
+                iters: int = 2, sdf_weight: float = 10.0):
+    """The vertices of a ``marching_cubes`` mesh of image ``image_index`` moved onto the network's own ``iso`` level
+    set (``SdfEngine.refine_vertices``; the grid cell of ``sdf_params`` / ``res`` -- its shortest edge -- bounds a
+    step by half and a vertex's way by one cell), with the unit gradient at the new positions as normals.
+    -> (verts' [nv,3], faces (unchanged), normals [nv,3]).  ``iters`` = 0: the vertices as they are, their normals.
+    WINDING: ``marching_cubes`` orders a triangle so that its geometric normal (b - a) x (c - a) points towards
+    larger values (disn_mc_emit), i.e. ALONG +grad pred; the "vn" normals written here point the same way."""
+    p = np.asarray(sdf_params, np.float64).reshape(6)
+    cell = float(np.min((p[3:] - p[:3]) / float(res)))
+    v, n, _ = engine.refine_vertices(enc, image_index, trans_mat, verts, iso=iso, iters=iters, sdf_weight=sdf_weight,
+                                     cell=cell)
+    return v, faces, n
 
 
 def read_obj(path: str):

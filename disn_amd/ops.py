@@ -617,6 +617,24 @@ def query_folded(w: MlpWeights, pmap: torch.Tensor, embedding: torch.Tensor, tra
     return out
 
 
+def query_grad(w: MlpWeights, pmap: torch.Tensor, embedding: torch.Tensor, trans_mat: torch.Tensor,
+               pts: torch.Tensor, ws: Optional[torch.Tensor] = None, want_sdf: bool = True):
+    """disn_query_grad: pmap [B,137*137,512], pts [B,N,3] (fed as sample_pc AND sample_pc_rot) ->
+    (pred_sdf [B,N] un-divided, or None without ``want_sdf``; grad [B,N,3] = d pred_sdf / d pts)"""
+    pts = _chk(pts, "pts")
+    B, N, _ = pts.shape
+    if pmap.numel() != B * MAP_PIXELS * 512:
+        raise ValueError("pmap must be [B,137*137,512]")
+    sdf = torch.empty((B, N), dtype=torch.float32, device=pts.device) if want_sdf else None
+    grad = torch.empty((B, N, 3), dtype=torch.float32, device=pts.device)
+    ws = _fit_ws(ws, lib().disn_query_grad_workspace_bytes(B, N), pts.device)
+    check("disn_query_grad", lib().disn_query_grad(
+        C.byref(w), _chk(pmap, "pmap").data_ptr(), _chk(embedding, "embedding").data_ptr(),
+        _chk(trans_mat, "trans_mat").data_ptr(), pts.data_ptr(), B, N, sdf.data_ptr() if want_sdf else None,
+        grad.data_ptr(), ws.data_ptr(), ws.numel(), _stream()))
+    return sdf, grad
+
+
 def _params6(sdf_params) -> C.Array:
     vals = [float(v) for v in sdf_params]
     if len(vals) != 6:

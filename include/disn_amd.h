@@ -368,6 +368,32 @@ int disn_query_folded(const disn_mlp_weights_t* w, const float* pmap, const floa
                       const float* trans_mat, const float* pts, const float* pts_rot, int B, int N,
                       float* sdf, void* ws, size_t ws_bytes, void* stream);
 
+/* ---------------------------------------------------------------------- *
+ * Gradient of the un-divided pred_sdf with respect to the query point, in  *
+ * forward mode (sdf_grad.hip): the same p is sample_pc and      *
+ * sample_pc_rot (test/create_sdf.py:268-269).  A point carries its value   *
+ * and three tangents as four stacked rows through both streams             *
+ * (models/sdfnet.py:69-92,171-190): every layer is one fp32 MFMA product   *
+ * over the 4 N rows without bias or ReLU, then bias + ReLU on the value    *
+ * row and the value row's sign as a mask on the tangent rows.  The folded  *
+ * local fold2/conv1 adds the resampled pmap rows to the value and          *
+ * dg/du du/dp + dg/dv dv/dp to the tangents                                *
+ * (models/model_normalization.py:172-190,241-251; a clamped coordinate has *
+ * zero derivative; the bilinear cell is the forward gather's).             *
+ * pmap [B][137*137][512] (disn_fold_local), embedding [B,1024], trans_mat  *
+ * [B,4,3], pts [B,N,3] -> sdf [B,N] (un-divided pred_sdf; may be NULL),    *
+ * grad [B,N,3] = d pred_sdf / d pts.  Any N >= 1.                          *
+ * Every product owns whole output tiles and sums K in one fixed order, and *
+ * every image's folded bias row is formed on its own: a point's four       *
+ * results are bit for bit the same in a call of any B and any N, at any    *
+ * position (chunks of 16384 points of one image inside the workspace).     *
+ * sdf agrees with disn_query_folded to fp32 rounding, not bit for bit.     *
+ * ---------------------------------------------------------------------- */
+size_t disn_query_grad_workspace_bytes(int B, int64_t N);
+int disn_query_grad(const disn_mlp_weights_t* w, const float* pmap, const float* embedding,
+                    const float* trans_mat, const float* pts, int B, int64_t N,
+                    float* sdf, float* grad, void* ws, size_t ws_bytes, void* stream);
+
 /* A non-blocking HIP stream for a host that does not link HIP itself (hipStreamCreateWithFlags(hipStreamNonBlocking)
  * on the current device).  disn_amd.engine.StepPipeline creates the streams of its step contexts with it, in a
  * fixed order: ROCm hands out GPU_MAX_HW_QUEUES hardware queues (default 4, the null stream's included) in creation
@@ -829,6 +855,11 @@ int disn_scale_channels(const float* in, int64_t rows, int C, const float* scale
  * reference's output artefact (test/create_sdf.py:311).  Returns 0, or DISN_E_ARG on I/O error. */
 int disn_write_obj(const char* path, const float* verts_host, int64_t nv, const int32_t* faces_host,
                    int64_t nf);
+
+/* The same file with one normal per vertex: "v" lines, then nv "vn x y z" lines (9 significant digits), then faces
+ * "f a//a b//b c//c".  normals_host [nv,3]. */
+int disn_write_obj_normals(const char* path, const float* verts_host, int64_t nv, const float* normals_host,
+                           const int32_t* faces_host, int64_t nf);
 
 /* Host utility: the vertices ("v x y z" lines) of a Wavefront .obj, in file order, into verts_host [cap,3]
  * (NULL / cap 0: count only).  Returns the number of vertices in the file (only the first cap are written),
