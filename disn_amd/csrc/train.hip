@@ -219,29 +219,60 @@ int conv_bwd(const float* x, int B, int H, int W, int Cin, const float* w, const
   return 0;
 }
 
-// ---- the full step ------------------------------------------------------------------
-struct TrainWs {
-  // packed forward weights
-  float* conv_p[13];
-  float *g_p2, *g_p3, *g_p4, *g_p5, *l_p2, *l_p3, *l_p4, *l_p5;
-  // packed weights of the data-gradient GEMMs (flipped conv kernels, transposed MLP weights)
-  float* conv_bT[13];
-  float *g_t2, *g_t3, *g_t4, *g_t5, *l_t2, *l_t3, *l_t4, *l_t4f, *l_t5;
-  // activations
-  float *resized, *act[13], *pooled[13], *h6, *h7, *emb, *gbias, *xy, *feat;
-  float *g1, *l1, *g2, *l2, *g3, *l3, *g4, *l4, *g5, *l5;
-  // gradients
-  float *dpred, *d5, *d4, *d3, *d2, *d1, *dfeat, *dmap, *dgbias, *demb, *dz7, *dz6, *dpool5, *gA, *gB;
+// ---- the VGG-16 encoder's half of a training step ---------------------------------------
+// disn_train_step and disn_cam_train_step fine-tune the same encoder: its workspace, weight re-packs, forward,
+// regularisation segments and backward are written once here, and each step keeps its head, its events and the stream
+// every call below runs on.
+struct EncTrainWs {
+  float* conv_p[13];   // packed forward weights of the implicit-GEMM forward (compute_bf16 == 0)
+  float* conv_bT[13];  // ... of its data-gradient GEMMs (flipped conv kernels)
+  // convolutions through conv_h2.hip / conv_h2w.hip: two-term f16 weight images (re-packed every step), forward and
+  // data gradient (mirrored taps, transposed channels)
+  float *conv_h2img[13], *conv_h2bT[13];
+  float* amax;         // [14][B][64] activation maxima of the forward chain, then
+  float* amax_bwd;     // [13][B][64] per-image maxima of every layer gradient (written by the ReLU-mask pass)
+  float *resized, *act[13], *pooled[13], *h6, *h7, *emb;
+  float *demb, *dz7, *dz6, *dpool5, *gA, *gB;
   float *col, *fc_ws, *sumsq_ws, *red_aux;
-  // forward convolutions through conv_h2.hip / conv_h2w.hip: two-term f16 weight images (re-packed every step) and
-  // the activation-maximum slots [14][B][64] of the layer chain
-  float* conv_h2img[13];
-  float* conv_h2bT[13];   // the same for the data gradients (mirrored taps, transposed channels)
-  float* amax;
-  float* amax_bwd;        // [13][B][64]: per-image maxima of every layer gradient (written by the ReLU-mask pass)
-  BwdWs bw;
-  size_t total;
+  size_t red_bytes;    // bias-gradient partials of the conv and fc layers: the step's BwdWs::red_ws covers them
 };
+
+// extra_fc_ws_bytes: a gemv of the step's own that shares fc_ws
+EncTrainWs enc_train_layout(Bump& b, int B, size_t extra_fc_ws_bytes) {
+  EncTrainWs e;
+  e.conv_bT[0] = e.conv_h2img[0] = e.conv_h2bT[0] = nullptr;
+  for (int i = 0; i < 13; ++i) {
+    const ConvL& L = kConv[i];
+    // (x 3/2: the three-term bf16 image is 6 bytes per weight)
+    e.conv_p[i] = b.take((size_t)conv_kpad(L.cin) * L.cout * 3 / 2);
+    if (i > 0) {
+      e.conv_bT[i] = b.take((size_t)9 * L.cin * L.cout * 3 / 2);
+      e.conv_h2img[i] = b.take(conv_h2_image_bytes(L.cin, L.cout) / sizeof(float) + 1);
+      e.conv_h2bT[i] = b.take(conv_h2_image_bytes(L.cout, L.cin) / sizeof(float) + 1);
+    }
+    e.act[i] = b.take((size_t)B * L.hw * L.hw * L.cout);
+    e.pooled[i] = L.pool ? b.take((size_t)B * (L.hw / 2) * (L.hw / 2) * L.cout) : nullptr;
+  }
+  e.amax = b.take((size_t)27 * B * 64);
+  e.amax_bwd = e.amax + (size_t)14 * B * 64;  // zeroed with the others by the resize launch
+  e.resized = b.take((size_t)B * 224 * 224 * 3);
+  e.h6 = b.take((size_t)B * 4096); e.h7 = b.take((size_t)B * 4096);
+  e.emb = b.take((size_t)B * DISN_EMBED_DIM); e.demb = b.take((size_t)B * DISN_EMBED_DIM);
+  e.dz7 = b.take((size_t)B * 4096); e.dz6 = b.take((size_t)B * 4096);
+  e.dpool5 = b.take((size_t)B * 25088);
+  e.gA = b.take((size_t)B * 224 * 224 * 64); e.gB = b.take((size_t)B * 224 * 224 * 64);
+  e.col = b.take((size_t)B * 224 * 224 * 64);
+  size_t fws = max_sz(gemv_ws_bytes(B, 25088, 4096), extra_fc_ws_bytes);
+  fws = max_sz(fws, gemv_ws_bytes(B, 4096, 4096));
+  fws = max_sz(fws, gemv_ws_bytes(B, 4096, DISN_EMBED_DIM));
+  e.fc_ws = b.take(fws / sizeof(float) + 1);
+  e.sumsq_ws = b.take(32 * 256);
+  e.red_aux = b.take(colsum_ws_bytes(B, 4096) / sizeof(float) + 1);
+  e.red_bytes = colsum_ws_bytes(B, 4096);
+  for (int i = 0; i < 13; ++i)  // chunks x Cout
+    e.red_bytes = max_sz(e.red_bytes, colsum_ws_bytes((long)B * kConv[i].hw * kConv[i].hw, kConv[i].cout));
+  return e;
+}
 
 // forward + backward-data GEMM shapes (rows, N, K) of the convolution stack
 size_t conv_gemm_ws(int B) {
@@ -258,6 +289,164 @@ size_t conv_gemm_ws(int B) {
   }
   return m;
 }
+
+// one step's view of the encoder: variables 0..31 sit at disn_param_layout's offsets in both networks' buffers
+struct EncCall {
+  const EncTrainWs& e;
+  const float* params;
+  float* grads;
+  const disn_param_layout_t& L;
+  const BwdWs& s;  // ns = bf
+  int B, bf;       // bf: planes of the weight images (0 f32-input MFMA, 1 bf16 multiply, 3 fp32-accurate split)
+  bool h2fwd;      // convolutions through conv_h2.hip / conv_h2w.hip (compute_bf16 != 0) instead of the implicit GEMMs
+  float wd;
+  const float* P(int idx) const { return params + L.offset[idx]; }
+  float* G(int idx) const { return grads + L.offset[idx]; }
+};
+
+// the implicit-GEMM forward's re-packs (forward + data-gradient views); the weights change every step
+void enc_pack_jobs(PackJobs& jobs, const EncCall& c) {
+  pack_job_add(jobs, c.P(0), c.e.conv_p[0], 0, 27, 64, 0);  // conv1_1 (K = 27) stays on the fp32 path
+  for (int i = 1; i < 13; ++i) {
+    pack_job_add(jobs, c.P(2 * i), c.e.conv_p[i], 0, 9 * kConv[i].cin, kConv[i].cout, c.bf);
+    pack_job_add(jobs, c.P(2 * i), c.e.conv_bT[i], 2, kConv[i].cin, kConv[i].cout, c.bf);
+  }
+}
+
+// 12 forward + 12 data-gradient images (mirrored taps, transposed channels): three launches in all
+int enc_h2_pack(const EncCall& c, hipStream_t st) {
+  ConvH2PackJobs cj{};
+  for (int i = 1; i < 13; ++i) {
+    conv_h2_pack_job_add(cj, c.P(2 * i), kConv[i].cin, kConv[i].cout, c.e.conv_h2img[i], 0, i - 1);
+    conv_h2_pack_job_add(cj, c.P(2 * i), kConv[i].cin, kConv[i].cout, c.e.conv_h2bT[i], 1, i - 1);
+  }
+  DISN_TRY(conv_h2_pack_multi_launch(cj, st));
+  return 0;
+}
+
+// the 16 VGG weights of the regularisation term; the caller appends its own segments at segs.n
+void enc_vgg_sumsq_segs(SumsqSegs& segs, const disn_param_layout_t& L) {
+  int n = 0;
+  for (int i = 0; i < 13; ++i) { segs.off[n] = L.offset[2 * i]; segs.cnt[n++] = L.count[2 * i]; }
+  for (int i = 0; i < 3; ++i) { segs.off[n] = L.offset[V_FC + 2 * i]; segs.cnt[n++] = L.count[V_FC + 2 * i]; }
+  segs.n = n;
+}
+
+// The resize and the 13 convolutions of the forward (models/CNN/vgg.py:187-196), every activation kept.  h2fwd: through
+// the inference kernels -- conv1_1 direct, conv_h2.hip / conv_h2w.hip (two-term f16 split: fp32-accurate, pools fused)
+// -- in the fp32-accurate and the mixed-precision mode alike: at eight samples 0.8 ms instead of 2.6 (three-term) /
+// ~1.0 ms (bf16 one-term), and the kept activations are the fp32-accurate ones.  Otherwise (every product on the
+// f32-input MFMA) the implicit-GEMM forward.
+int enc_conv_forward(const EncCall& c, const float* img, hipStream_t st, const float** pool5) {
+  const EncTrainWs& e = c.e;
+  const int B = c.B;
+  DISN_TRY(resize_bilinear_launch(img, B, DISN_IMG_H, DISN_IMG_W, 3, e.resized, DISN_VGG_SIZE, DISN_VGG_SIZE, 3, 0, st,
+                                  0, c.h2fwd ? e.amax : nullptr, c.h2fwd ? 27 * B * 64 : 0));
+  const float* x = e.resized;
+  for (int i = 0; i < 13; ++i) {
+    const ConvL& l = kConv[i];
+    if (c.h2fwd && i == 0) {
+      DISN_TRY(conv1_1_direct_launch(x, B, l.hw, l.hw, c.P(0), c.P(1), 1, e.act[0], e.amax + (size_t)B * 64, st, 64));
+    } else if (c.h2fwd) {
+      DISN_TRY(conv_h2_launch(x, B, l.hw, l.hw, l.cin, e.conv_h2img[i], c.P(2 * i + 1), l.cout, 1,
+                              e.amax + (size_t)B * 64 * i, e.act[i], l.pool ? e.pooled[i] : nullptr,
+                              e.amax + (size_t)B * 64 * (i + 1), st, kConvTilingTrain, 64));
+    } else {
+      DISN_RC(conv_fwd(x, B, l.hw, l.hw, l.cin, e.conv_p[i], c.P(2 * i + 1), l.cout, 1, e.act[i], c.s.gemm_ws,
+                       c.s.gemm_ws_bytes, st, c.bf));
+    }
+    x = e.act[i];
+    if (l.pool) {
+      if (!c.h2fwd) DISN_TRY(maxpool2x2_launch(x, B, l.hw, l.hw, l.cout, e.pooled[i], st));
+      x = e.pooled[i];
+    }
+  }
+  *pool5 = x;
+  return 0;
+}
+
+// fc6, fc7, fc8 (HBM-bound: ~0.55 GB of weight traffic), on the stream the step names
+int enc_fc_forward(const EncCall& c, const float* pool5, hipStream_t s) {
+  const EncTrainWs& e = c.e;
+  DISN_TRY(gemv_launch(pool5, c.B, 25088, c.P(V_FC), c.P(V_FC + 1), 4096, 1, e.h6, e.fc_ws, s));
+  DISN_TRY(gemv_launch(e.h6, c.B, 4096, c.P(V_FC + 2), c.P(V_FC + 3), 4096, 1, e.h7, e.fc_ws, s));
+  DISN_TRY(gemv_launch(e.h7, c.B, 4096, c.P(V_FC + 4), c.P(V_FC + 5), DISN_EMBED_DIM, 0, e.emb, e.fc_ws, s));
+  return 0;
+}
+
+// fc8, fc7, fc6 backward from e.demb = d(embedding) to e.dpool5
+int enc_fc_backward(const EncCall& c, const float* pool5, hipStream_t s) {
+  const EncTrainWs& e = c.e;
+  const int B = c.B;
+  float* r2 = e.red_aux;
+  DISN_TRY(relu_bwd_colsum_launch(e.demb, nullptr, B, DISN_EMBED_DIM, 0, c.G(V_FC + 5), r2, s));
+  DISN_TRY(fc_bwd_launch(e.h7, e.demb, B, 4096, DISN_EMBED_DIM, c.P(V_FC + 4), c.wd, c.G(V_FC + 4), e.h7, e.dz7, s));
+  DISN_TRY(relu_bwd_colsum_launch(e.dz7, nullptr, B, 4096, 0, c.G(V_FC + 3), r2, s));
+  DISN_TRY(fc_bwd_launch(e.h6, e.dz7, B, 4096, 4096, c.P(V_FC + 2), c.wd, c.G(V_FC + 2), e.h6, e.dz6, s));
+  DISN_TRY(relu_bwd_colsum_launch(e.dz6, nullptr, B, 4096, 0, c.G(V_FC + 1), r2, s));
+  DISN_TRY(fc_bwd_launch(pool5, e.dz6, B, 25088, 4096, c.P(V_FC), c.wd, c.G(V_FC), nullptr, e.dpool5, s));
+  return 0;
+}
+
+// conv-stack backward from e.dpool5.  dmap [B,137,137,DISN_FEAT_DIM]: the gradient of the sampled feature map, added at
+// the five taps; nullptr: the network samples no features
+int enc_conv_backward(const EncCall& c, const float* dmap, hipStream_t st) {
+  const EncTrainWs& e = c.e;
+  const int B = c.B;
+  const float* dcur = e.dpool5;  // gradient w.r.t. the input of the layer above
+  float* bufs[2] = {e.gA, e.gB};
+  int which = 0;
+  for (int i = 12; i >= 0; --i) {
+    const ConvL& l = kConv[i];
+    float* dy;
+    if (l.pool) {
+      dy = bufs[which];
+      which ^= 1;
+      DISN_TRY(maxpool_bwd_launch(e.act[i], dcur, B, l.hw, l.hw, l.cout, dy, st));
+      // e.col ([B,224,224,64] floats, free until conv1_1) is the row-pass scratch (<= B*56*137*256)
+      if (dmap)
+        DISN_TRY(resize_bwd_launch(dmap, B, l.hw, l.hw, l.cout, DISN_IMG_H, DISN_IMG_W, DISN_FEAT_DIM, kTapOff[l.tap], dy,
+                                   1, e.col, st));
+    } else {
+      dy = const_cast<float*>(dcur);
+    }
+    const long rows = (long)B * l.hw * l.hw;
+    const bool h2 = c.h2fwd && i > 0;
+    float* amax_i = h2 ? e.amax_bwd + (size_t)i * B * 64 : nullptr;
+    bool amax_ready = false;
+    DISN_TRY(relu_bwd_colsum_launch(dy, e.act[i], rows, l.cout, 1, c.G(2 * i + 1), c.s.red_ws, st, amax_i,
+                                    (long)l.hw * l.hw, &amax_ready));
+    const float* xin = i == 0 ? e.resized : (kConv[i - 1].pool ? e.pooled[i - 1] : e.act[i - 1]);
+    float* dx = nullptr;
+    if (i > 0) {
+      dx = bufs[which];
+      if (dx == dy) dx = bufs[which ^ 1];
+    }
+    DISN_RC(conv_bwd(xin, B, l.hw, l.hw, l.cin, c.P(2 * i), dy, l.cout, c.wd, dx, c.G(2 * i), e.col, c.s, st,
+                     e.conv_bT[i], h2 ? e.conv_h2bT[i] : nullptr, amax_i, h2 ? e.amax + (size_t)B * 64 * i : nullptr,
+                     amax_ready));
+    if (dx) {
+      which = (dx == bufs[0]) ? 1 : 0;
+      dcur = dx;
+    }
+  }
+  return 0;
+}
+
+// ---- the SDF network's step --------------------------------------------------------------
+struct TrainWs {
+  EncTrainWs enc;
+  // packed forward weights of the point MLPs, and of their data-gradient GEMMs (transposed)
+  float *g_p2, *g_p3, *g_p4, *g_p5, *l_p2, *l_p3, *l_p4, *l_p5;
+  float *g_t2, *g_t3, *g_t4, *g_t5, *l_t2, *l_t3, *l_t4, *l_t4f, *l_t5;
+  // activations
+  float *gbias, *xy, *feat;
+  float *g1, *l1, *g2, *l2, *g3, *l3, *g4, *l4, *g5, *l5;
+  // gradients
+  float *dpred, *d5, *d4, *d3, *d2, *d1, *dfeat, *dmap, *dgbias;
+  BwdWs bw;
+  size_t total;
+};
 
 size_t train_gemm_ws(int B, long M) {
   size_t m = conv_gemm_ws(B);
@@ -278,23 +467,14 @@ TrainWs train_layout(void* ws, int B, int N) {
   Bump b(ws);
   TrainWs t;
   const long M = (long)B * N;
+  t.enc = enc_train_layout(b, B, gemv_ws_bytes(B, DISN_EMBED_DIM, 512));  // + the folded global block's gemv
   // (x 3/2: the three-term bf16 image is 6 bytes per weight)
-  for (int i = 0; i < 13; ++i) t.conv_p[i] = b.take((size_t)conv_kpad(kConv[i].cin) * kConv[i].cout * 3 / 2);
   t.g_p2 = b.take(64 * 256 * 3 / 2); t.g_p3 = b.take(256 * 512 * 3 / 2); t.g_p4 = b.take(512 * 512 * 3 / 2); t.g_p5 = b.take(512 * 256 * 3 / 2);
   t.l_p2 = b.take(64 * 256 * 3 / 2); t.l_p3 = b.take(256 * 512 * 3 / 2); t.l_p4 = b.take(1984 * 512 * 3 / 2); t.l_p5 = b.take(512 * 256 * 3 / 2);
-  t.conv_bT[0] = nullptr;
-  for (int i = 1; i < 13; ++i) t.conv_bT[i] = b.take((size_t)9 * kConv[i].cin * kConv[i].cout * 3 / 2);
   t.g_t2 = b.take(64 * 256 * 3 / 2); t.g_t3 = b.take(256 * 512 * 3 / 2); t.g_t4 = b.take(512 * 512 * 3 / 2); t.g_t5 = b.take(512 * 256 * 3 / 2);
   t.l_t2 = b.take(64 * 256 * 3 / 2); t.l_t3 = b.take(256 * 512 * 3 / 2); t.l_t4 = b.take(512 * 512 * 3 / 2);
   t.l_t4f = b.take(1472 * 512 * 3 / 2); t.l_t5 = b.take(512 * 256 * 3 / 2);
-  t.resized = b.take((size_t)B * 224 * 224 * 3);
-  for (int i = 0; i < 13; ++i) {
-    const ConvL& L = kConv[i];
-    t.act[i] = b.take((size_t)B * L.hw * L.hw * L.cout);
-    t.pooled[i] = L.pool ? b.take((size_t)B * (L.hw / 2) * (L.hw / 2) * L.cout) : nullptr;
-  }
-  t.h6 = b.take((size_t)B * 4096); t.h7 = b.take((size_t)B * 4096);
-  t.emb = b.take((size_t)B * DISN_EMBED_DIM); t.gbias = b.take((size_t)B * 512);
+  t.gbias = b.take((size_t)B * 512);
   t.xy = b.take((size_t)M * 2); t.feat = b.take((size_t)M * DISN_FEAT_DIM);
   t.g1 = b.take((size_t)M * 64); t.l1 = b.take((size_t)M * 64);
   t.g2 = b.take((size_t)M * 256); t.l2 = b.take((size_t)M * 256);
@@ -306,28 +486,8 @@ TrainWs train_layout(void* ws, int B, int N) {
   t.d2 = b.take((size_t)M * 256); t.d1 = b.take((size_t)M * 64);
   t.dfeat = b.take((size_t)M * DISN_FEAT_DIM);
   t.dmap = b.take((size_t)B * 137 * 137 * DISN_FEAT_DIM);
-  t.dgbias = b.take((size_t)B * 512); t.demb = b.take((size_t)B * DISN_EMBED_DIM);
-  t.dz7 = b.take((size_t)B * 4096); t.dz6 = b.take((size_t)B * 4096);
-  t.dpool5 = b.take((size_t)B * 25088);
-  t.gA = b.take((size_t)B * 224 * 224 * 64); t.gB = b.take((size_t)B * 224 * 224 * 64);
-  t.col = b.take((size_t)B * 224 * 224 * 64);
-  size_t fws = gemv_ws_bytes(B, 25088, 4096);
-  fws = max_sz(fws, gemv_ws_bytes(B, 4096, 4096));
-  fws = max_sz(fws, gemv_ws_bytes(B, 4096, DISN_EMBED_DIM));
-  fws = max_sz(fws, gemv_ws_bytes(B, DISN_EMBED_DIM, 512));
-  t.fc_ws = b.take(fws / sizeof(float) + 1);
-  t.sumsq_ws = b.take(32 * 256);
-  t.conv_h2img[0] = nullptr;
-  for (int i = 1; i < 13; ++i) t.conv_h2img[i] = b.take(conv_h2_image_bytes(kConv[i].cin, kConv[i].cout) / sizeof(float) + 1);
-  t.conv_h2bT[0] = nullptr;
-  for (int i = 1; i < 13; ++i) t.conv_h2bT[i] = b.take(conv_h2_image_bytes(kConv[i].cout, kConv[i].cin) / sizeof(float) + 1);
-  t.amax = b.take((size_t)27 * B * 64);       // 14 slot sets of the forward chain + 13 of the layer gradients
-  t.amax_bwd = t.amax + (size_t)14 * B * 64;  // [13][B][64], zeroed with the others by the resize launch
-  t.red_aux = b.take(colsum_ws_bytes(B, 4096) / sizeof(float) + 1);
-  size_t red = colsum_ws_bytes(M, 512);
-  for (int i = 0; i < 13; ++i)  // bias-gradient partials of every conv layer (chunks x Cout)
-    red = max_sz(red, colsum_ws_bytes((long)B * kConv[i].hw * kConv[i].hw, kConv[i].cout));
-  red = max_sz(red, colsum_ws_bytes(B, 4096));
+  t.dgbias = b.take((size_t)B * 512);
+  size_t red = max_sz(t.enc.red_bytes, colsum_ws_bytes(M, 512));
   red = max_sz(red, max_sz(final_bwd_ws_bytes(M), colsum_ws_bytes(M, DISN_FEAT_DIM)));
   t.bw = bwd_layout(b, (size_t)9 * 512 * 512, M, train_gemm_ws(B, M), red);
   t.total = (b.off + 255) & ~size_t(255);
@@ -359,10 +519,7 @@ void build_cam_layout(disn_cam_param_layout_t* L) {
 }
 
 struct CamTrainWs {
-  float *conv_p[13], *conv_bT[13], *conv_h2img[13], *conv_h2bT[13];
-  float *resized, *act[13], *pooled[13], *h6, *h7, *emb;
-  float *demb, *dz7, *dz6, *dpool5, *gA, *gB, *col, *fc_ws, *sumsq_ws, *red_aux;
-  float *amax, *amax_bwd;
+  EncTrainWs enc;
   float *rot, *trans, *pred_RT, *save, *dsave, *dRT, *loss_ws;
   BwdWs bw;
   size_t total;
@@ -371,41 +528,12 @@ struct CamTrainWs {
 CamTrainWs cam_train_layout(void* ws, int B, int N) {
   Bump b(ws);
   CamTrainWs t;
-  for (int i = 0; i < 13; ++i) t.conv_p[i] = b.take((size_t)conv_kpad(kConv[i].cin) * kConv[i].cout * 3 / 2);
-  t.conv_bT[0] = t.conv_h2img[0] = t.conv_h2bT[0] = nullptr;
-  for (int i = 1; i < 13; ++i) {
-    t.conv_bT[i] = b.take((size_t)9 * kConv[i].cin * kConv[i].cout * 3 / 2);
-    t.conv_h2img[i] = b.take(conv_h2_image_bytes(kConv[i].cin, kConv[i].cout) / sizeof(float) + 1);
-    t.conv_h2bT[i] = b.take(conv_h2_image_bytes(kConv[i].cout, kConv[i].cin) / sizeof(float) + 1);
-  }
-  t.resized = b.take((size_t)B * 224 * 224 * 3);
-  for (int i = 0; i < 13; ++i) {
-    const ConvL& L = kConv[i];
-    t.act[i] = b.take((size_t)B * L.hw * L.hw * L.cout);
-    t.pooled[i] = L.pool ? b.take((size_t)B * (L.hw / 2) * (L.hw / 2) * L.cout) : nullptr;
-  }
-  t.h6 = b.take((size_t)B * 4096); t.h7 = b.take((size_t)B * 4096);
-  t.emb = b.take((size_t)B * DISN_EMBED_DIM); t.demb = b.take((size_t)B * DISN_EMBED_DIM);
-  t.dz7 = b.take((size_t)B * 4096); t.dz6 = b.take((size_t)B * 4096);
-  t.dpool5 = b.take((size_t)B * 25088);
-  t.gA = b.take((size_t)B * 224 * 224 * 64); t.gB = b.take((size_t)B * 224 * 224 * 64);
-  t.col = b.take((size_t)B * 224 * 224 * 64);
-  size_t fws = gemv_ws_bytes(B, 25088, 4096);
-  fws = max_sz(fws, gemv_ws_bytes(B, 4096, 4096));
-  fws = max_sz(fws, gemv_ws_bytes(B, 4096, DISN_EMBED_DIM));
-  t.fc_ws = b.take(fws / sizeof(float) + 1);
-  t.sumsq_ws = b.take(32 * 256);
-  t.red_aux = b.take(colsum_ws_bytes(B, 4096) / sizeof(float) + 1);
-  t.amax = b.take((size_t)27 * B * 64);
-  t.amax_bwd = t.amax + (size_t)14 * B * 64;
+  t.enc = enc_train_layout(b, B, 0);
   t.rot = b.take((size_t)B * 9); t.trans = b.take((size_t)B * 3); t.pred_RT = b.take((size_t)B * 12);
   t.save = b.take((size_t)B * CAM_SAVE_STRIDE); t.dsave = b.take((size_t)B * CAM_SAVE_STRIDE);
   t.dRT = b.take((size_t)B * 12);
   t.loss_ws = b.take(cam_loss_ws_floats(B, N));
-  size_t red = colsum_ws_bytes(B, 4096);
-  for (int i = 0; i < 13; ++i)
-    red = max_sz(red, colsum_ws_bytes((long)B * kConv[i].hw * kConv[i].hw, kConv[i].cout));
-  t.bw = bwd_layout(b, (size_t)9 * 512 * 512, (long)B * 224 * 224, conv_gemm_ws(B), red);
+  t.bw = bwd_layout(b, (size_t)9 * 512 * 512, (long)B * 224 * 224, conv_gemm_ws(B), t.enc.red_bytes);
   t.total = (b.off + 255) & ~size_t(255);
   return t;
 }
@@ -573,23 +701,16 @@ int disn_train_step(disn_ctx_t* ctx, const float* params, float* grads, const fl
   s.ns = bf;
   float* gws = s.gemm_ws;
   const size_t gwb = s.gemm_ws_bytes;
+  const bool h2fwd = compute_bf16 != 0;  // the encoder's convolutions through conv_h2.hip / conv_h2w.hip
+  const EncTrainWs& e = t.enc;
+  const EncCall enc{e, params, grads, L, s, B, bf, h2fwd, wd};
 
   // ---------------- forward ----------------
-  // The 13 convolutions of the forward (models/CNN/vgg.py:187-196) through the inference kernels -- conv1_1 direct,
-  // conv_h2.hip / conv_h2w.hip (two-term f16 split: fp32-accurate, pools fused) -- in the fp32-accurate and the
-  // mixed-precision mode alike: at eight samples 0.8 ms instead of 2.6 (three-term) / ~1.0 ms (bf16 one-term), and the
-  // kept activations are the fp32-accurate ones.  compute_bf16 == 0 (every product on the f32-input MFMA) keeps the
-  // implicit-GEMM forward.  The weight images are re-packed every step (the weights change every step).
-  const bool h2fwd = compute_bf16 != 0;
   // weights in MFMA fragment order (they change every step): fp32, or bf16 in the same storage
   // all 41 re-packs (forward + data-gradient views) in one launch
   {
     PackJobs jobs{};
-    if (!h2fwd) pack_job_add(jobs, P(0), t.conv_p[0], 0, 27, 64, 0);  // conv1_1 (K = 27) stays on the fp32 path
-    for (int i = 1; i < 13; ++i) {
-      if (!h2fwd) pack_job_add(jobs, P(2 * i), t.conv_p[i], 0, 9 * kConv[i].cin, kConv[i].cout, bf);
-      if (!h2fwd) pack_job_add(jobs, P(2 * i), t.conv_bT[i], 2, kConv[i].cin, kConv[i].cout, bf);
-    }
+    if (!h2fwd) enc_pack_jobs(jobs, enc);
     const float* gw4 = P(V_G + 6);  // rows 0..511 point part, 512..1535 global part
     const float* lw4 = P(V_L + 6);  // rows 0..511 point part, 512..1983 image-feature part
     pack_job_add(jobs, P(V_G + 2), t.g_p2, 0, 64, 256, bf);
@@ -618,54 +739,25 @@ int disn_train_step(disn_ctx_t* ctx, const float* params, float* grads, const fl
   }
   {  // regularization loss: depends on the parameters only
     SumsqSegs segs{};
-    int n = 0;
-    for (int i = 0; i < 13; ++i) { segs.off[n] = L.offset[2 * i]; segs.cnt[n++] = L.count[2 * i]; }
-    for (int i = 0; i < 3; ++i) { segs.off[n] = L.offset[V_FC + 2 * i]; segs.cnt[n++] = L.count[V_FC + 2 * i]; }
+    enc_vgg_sumsq_segs(segs, L);
+    int n = segs.n;
     for (int i = 0; i < 6; ++i) { segs.off[n] = L.offset[V_G + 2 * i]; segs.cnt[n++] = L.count[V_G + 2 * i]; }
     for (int i = 0; i < 6; ++i) { segs.off[n] = L.offset[V_L + 2 * i]; segs.cnt[n++] = L.count[V_L + 2 * i]; }
     segs.n = n;
-    DISN_TRY(sumsq_launch(params, segs, 0.5f * wd, losses + 3, t.sumsq_ws, as));
+    DISN_TRY(sumsq_launch(params, segs, 0.5f * wd, losses + 3, e.sumsq_ws, as));
   }
 
-  if (h2fwd) {  // 12 forward + 12 data-gradient images (mirrored taps, transposed channels): three launches in all
-    ConvH2PackJobs cj{};
-    for (int i = 1; i < 13; ++i) {
-      conv_h2_pack_job_add(cj, P(2 * i), kConv[i].cin, kConv[i].cout, t.conv_h2img[i], 0, i - 1);
-      conv_h2_pack_job_add(cj, P(2 * i), kConv[i].cin, kConv[i].cout, t.conv_h2bT[i], 1, i - 1);
-    }
-    DISN_TRY(conv_h2_pack_multi_launch(cj, st));
-  }
-  DISN_TRY(resize_bilinear_launch(img, B, DISN_IMG_H, DISN_IMG_W, 3, t.resized, DISN_VGG_SIZE,
-                                  DISN_VGG_SIZE, 3, 0, st, 0, h2fwd ? t.amax : nullptr, h2fwd ? 27 * B * 64 : 0));
-  const float* x = t.resized;
-  for (int i = 0; i < 13; ++i) {
-    const ConvL& c = kConv[i];
-    if (h2fwd && i == 0) {
-      DISN_TRY(conv1_1_direct_launch(x, B, c.hw, c.hw, P(0), P(1), 1, t.act[0], t.amax + (size_t)B * 64, st, 64));
-    } else if (h2fwd) {
-      DISN_TRY(conv_h2_launch(x, B, c.hw, c.hw, c.cin, t.conv_h2img[i], P(2 * i + 1), c.cout, 1,
-                              t.amax + (size_t)B * 64 * i, t.act[i], c.pool ? t.pooled[i] : nullptr,
-                              t.amax + (size_t)B * 64 * (i + 1), st, kConvTilingTrain, 64));
-    } else {
-      DISN_RC(conv_fwd(x, B, c.hw, c.hw, c.cin, t.conv_p[i], P(2 * i + 1), c.cout, 1, t.act[i], gws, gwb, st, bf));
-    }
-    x = t.act[i];
-    if (c.pool) {
-      if (!h2fwd) DISN_TRY(maxpool2x2_launch(x, B, c.hw, c.hw, c.cout, t.pooled[i], st));
-      x = t.pooled[i];
-    }
-  }
-  const float* pool5 = x;
+  if (h2fwd) DISN_RC(enc_h2_pack(enc, st));
+  const float* pool5;
+  DISN_RC(enc_conv_forward(enc, img, st, &pool5));
   if (ctx) {
     DISN_TRY(hipEventRecord(ctx->ev[1], st));
     DISN_TRY(hipStreamWaitEvent(as, ctx->ev[1], 0));
   }
-  DISN_TRY(gemv_launch(pool5, B, 25088, P(V_FC), P(V_FC + 1), 4096, 1, t.h6, t.fc_ws, as));
-  DISN_TRY(gemv_launch(t.h6, B, 4096, P(V_FC + 2), P(V_FC + 3), 4096, 1, t.h7, t.fc_ws, as));
-  DISN_TRY(gemv_launch(t.h7, B, 4096, P(V_FC + 4), P(V_FC + 5), DISN_EMBED_DIM, 0, t.emb, t.fc_ws, as));
+  DISN_RC(enc_fc_forward(enc, pool5, as));
   // folded global block: gbias[b] = emb[b] . W4[512:1536] + b4
-  DISN_TRY(gemv_launch(t.emb, B, DISN_EMBED_DIM, P(V_G + 6) + (size_t)512 * 512, P(V_G + 7), 512, 0,
-                       t.gbias, t.fc_ws, as));
+  DISN_TRY(gemv_launch(e.emb, B, DISN_EMBED_DIM, P(V_G + 6) + (size_t)512 * 512, P(V_G + 7), 512, 0,
+                       t.gbias, e.fc_ws, as));
   if (ctx) DISN_TRY(hipEventRecord(ctx->ev[2], as));
   DISN_TRY(project_launch(pts, trans_mat, B, N, t.xy, st));
   // rows E + F without the [B,137,137,1472] map (880 MB at B = 8): the five taps are up-sampled at the
@@ -673,7 +765,7 @@ int disn_train_step(disn_ctx_t* ctx, const float* params, float* grads, const fl
   {
     const float* tb[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     for (int i = 0; i < 13; ++i)
-      if (kConv[i].tap >= 0) tb[kConv[i].tap] = t.act[i];
+      if (kConv[i].tap >= 0) tb[kConv[i].tap] = e.act[i];
     DISN_TRY(project_gather_taps_launch(tb, trans_mat, pts, B, N, 0, 5, t.feat, st));
   }
   DISN_TRY(pt_embed_launch(pts_rot, M, P(V_G), P(V_G + 1), P(V_L), P(V_L + 1), t.g1, t.l1, st));
@@ -724,8 +816,8 @@ int disn_train_step(disn_ctx_t* ctx, const float* params, float* grads, const fl
     } else {
       const float* wg = P(V + 6) + (size_t)512 * 512;  // [1024][512]
       DISN_TRY(image_colsum_launch(t.d4, B, N, 512, t.dgbias, s.red_ws, st));
-      DISN_TRY(fc_bwd_launch(t.emb, t.dgbias, B, DISN_EMBED_DIM, 512, wg, wd, G(V + 6) + (size_t)512 * 512, nullptr,
-                             t.demb, st));
+      DISN_TRY(fc_bwd_launch(e.emb, t.dgbias, B, DISN_EMBED_DIM, 512, wg, wd, G(V + 6) + (size_t)512 * 512, nullptr,
+                             e.demb, st));
     }
     DISN_TRY(relu_bwd_colsum_launch(t.d3, h3, M, 512, 1, G(V + 5), s.red_ws, st));
     // fold1/conv3 (256 -> 512), conv2 (64 -> 256), conv1 (3 -> 64)
@@ -741,13 +833,7 @@ int disn_train_step(disn_ctx_t* ctx, const float* params, float* grads, const fl
         DISN_TRY(hipEventRecord(ctx->ev[3], st));
         DISN_TRY(hipStreamWaitEvent(as, ctx->ev[3], 0));
       }
-      float* r2 = t.red_aux;
-      DISN_TRY(relu_bwd_colsum_launch(t.demb, nullptr, B, DISN_EMBED_DIM, 0, G(V_FC + 5), r2, as));
-      DISN_TRY(fc_bwd_launch(t.h7, t.demb, B, 4096, DISN_EMBED_DIM, P(V_FC + 4), wd, G(V_FC + 4), t.h7, t.dz7, as));
-      DISN_TRY(relu_bwd_colsum_launch(t.dz7, nullptr, B, 4096, 0, G(V_FC + 3), r2, as));
-      DISN_TRY(fc_bwd_launch(t.h6, t.dz7, B, 4096, 4096, P(V_FC + 2), wd, G(V_FC + 2), t.h6, t.dz6, as));
-      DISN_TRY(relu_bwd_colsum_launch(t.dz6, nullptr, B, 4096, 0, G(V_FC + 1), r2, as));
-      DISN_TRY(fc_bwd_launch(pool5, t.dz6, B, 25088, 4096, P(V_FC), wd, G(V_FC), nullptr, t.dpool5, as));
+      DISN_RC(enc_fc_backward(enc, pool5, as));
       if (ctx) DISN_TRY(hipEventRecord(ctx->ev[4], as));
     }
   }
@@ -760,43 +846,8 @@ int disn_train_step(disn_ctx_t* ctx, const float* params, float* grads, const fl
   // the caller may start reducing that part while the convolution backward below still runs
   if (head_ready_event) DISN_TRY(hipEventRecord((hipEvent_t)head_ready_event, st));
 
-  // ---------------- backward: conv stack ----------------
-  const float* dcur = t.dpool5;  // gradient w.r.t. the input of the layer above
-  float* bufs[2] = {t.gA, t.gB};
-  int which = 0;
-  for (int i = 12; i >= 0; --i) {
-    const ConvL& c = kConv[i];
-    float* dy;
-    if (c.pool) {
-      dy = bufs[which];
-      which ^= 1;
-      DISN_TRY(maxpool_bwd_launch(t.act[i], dcur, B, c.hw, c.hw, c.cout, dy, st));
-      // t.col ([B,224,224,64] floats, free until conv1_1) is the row-pass scratch (<= B*56*137*256)
-      DISN_TRY(resize_bwd_launch(t.dmap, B, c.hw, c.hw, c.cout, DISN_IMG_H, DISN_IMG_W, DISN_FEAT_DIM,
-                                 kTapOff[c.tap], dy, 1, t.col, st));
-    } else {
-      dy = const_cast<float*>(dcur);
-    }
-    const long rows = (long)B * c.hw * c.hw;
-    float* amax_i = h2fwd && i > 0 ? t.amax_bwd + (size_t)i * B * 64 : nullptr;
-    bool amax_ready = false;
-    DISN_TRY(relu_bwd_colsum_launch(dy, t.act[i], rows, c.cout, 1, G(2 * i + 1), s.red_ws, st, amax_i,
-                                    (long)c.hw * c.hw, &amax_ready));
-    const float* xin = i == 0 ? t.resized : (kConv[i - 1].pool ? t.pooled[i - 1] : t.act[i - 1]);
-    float* dx = nullptr;
-    if (i > 0) {
-      dx = bufs[which];
-      if (dx == dy) dx = bufs[which ^ 1];
-    }
-    DISN_RC(conv_bwd(xin, B, c.hw, c.hw, c.cin, P(2 * i), dy, c.cout, wd, dx, G(2 * i), t.col, s, st,
-                     t.conv_bT[i], h2fwd && i > 0 ? t.conv_h2bT[i] : nullptr, amax_i,
-                     h2fwd && i > 0 ? t.amax + (size_t)B * 64 * i : nullptr, amax_ready));
-    if (dx) {
-      which = (dx == bufs[0]) ? 1 : 0;
-      dcur = dx;
-    }
-  }
-  return 0;
+  // ---------------- backward: conv stack, with the tap gradients of the feature map ----------------
+  return enc_conv_backward(enc, t.dmap, st);
 }
 
 // ---- the camera network's step ------------------------------------------------------
@@ -823,25 +874,21 @@ int disn_cam_train_step(disn_ctx_t* ctx, const float* params, float* grads, cons
   if (ws_bytes < t.total) return DISN_E_WS;
   hipStream_t st = (hipStream_t)stream;
   hipStream_t as = ctx ? ctx->aux : st;
-  disn_cam_param_layout_t L;
+  disn_cam_param_layout_t L;  // the head's variables; the encoder's sit at disn_param_layout's offsets (LE)
   build_cam_layout(&L);
-  auto P = [&](int idx) { return params + L.offset[idx]; };
-  auto G = [&](int idx) { return grads + L.offset[idx]; };
+  disn_param_layout_t LE;
+  build_layout(&LE);
   BwdWs s = t.bw;
   const int bf = compute_bf16 == 2 ? 3 : (compute_bf16 ? 1 : 0);
   s.ns = bf;
-  float* gws = s.gemm_ws;
-  const size_t gwb = s.gemm_ws_bytes;
-
-  // ---------------- VGG forward, every activation kept (as disn_train_step) ----------------
   const bool h2fwd = compute_bf16 != 0;
+  const EncTrainWs& e = t.enc;
+  const EncCall enc{e, params, grads, LE, s, B, bf, h2fwd, wd};
+
+  // ---------------- VGG forward, every activation kept ----------------
   if (!h2fwd) {
     PackJobs jobs{};
-    pack_job_add(jobs, P(0), t.conv_p[0], 0, 27, 64, 0);
-    for (int i = 1; i < 13; ++i) {
-      pack_job_add(jobs, P(2 * i), t.conv_p[i], 0, 9 * kConv[i].cin, kConv[i].cout, bf);
-      pack_job_add(jobs, P(2 * i), t.conv_bT[i], 2, kConv[i].cin, kConv[i].cout, bf);
-    }
+    enc_pack_jobs(jobs, enc);
     DISN_TRY(pack_multi_launch(jobs, st));
   }
   DISN_TRY(hipMemsetAsync(s.zero, 0, 4096 * sizeof(float), st));
@@ -851,102 +898,32 @@ int disn_cam_train_step(disn_ctx_t* ctx, const float* params, float* grads, cons
   }
   {  // regularization: slim's l2_regularizer(wd) on the 16 VGG weights; the camera head has none
     SumsqSegs segs{};
-    int n = 0;
-    for (int i = 0; i < 13; ++i) { segs.off[n] = L.offset[2 * i]; segs.cnt[n++] = L.count[2 * i]; }
-    for (int i = 0; i < 3; ++i) { segs.off[n] = L.offset[V_FC + 2 * i]; segs.cnt[n++] = L.count[V_FC + 2 * i]; }
-    segs.n = n;
-    DISN_TRY(sumsq_launch(params, segs, 0.5f * wd, losses + 5, t.sumsq_ws, as));
+    enc_vgg_sumsq_segs(segs, LE);
+    DISN_TRY(sumsq_launch(params, segs, 0.5f * wd, losses + 5, e.sumsq_ws, as));
   }
   if (ctx) DISN_TRY(hipEventRecord(ctx->ev[1], as));
-  if (h2fwd) {
-    ConvH2PackJobs cj{};
-    for (int i = 1; i < 13; ++i) {
-      conv_h2_pack_job_add(cj, P(2 * i), kConv[i].cin, kConv[i].cout, t.conv_h2img[i], 0, i - 1);
-      conv_h2_pack_job_add(cj, P(2 * i), kConv[i].cin, kConv[i].cout, t.conv_h2bT[i], 1, i - 1);
-    }
-    DISN_TRY(conv_h2_pack_multi_launch(cj, st));
-  }
-  DISN_TRY(resize_bilinear_launch(img, B, DISN_IMG_H, DISN_IMG_W, 3, t.resized, DISN_VGG_SIZE, DISN_VGG_SIZE, 3, 0,
-                                  st, 0, h2fwd ? t.amax : nullptr, h2fwd ? 27 * B * 64 : 0));
-  const float* x = t.resized;
-  for (int i = 0; i < 13; ++i) {
-    const ConvL& c = kConv[i];
-    if (h2fwd && i == 0) {
-      DISN_TRY(conv1_1_direct_launch(x, B, c.hw, c.hw, P(0), P(1), 1, t.act[0], t.amax + (size_t)B * 64, st, 64));
-    } else if (h2fwd) {
-      DISN_TRY(conv_h2_launch(x, B, c.hw, c.hw, c.cin, t.conv_h2img[i], P(2 * i + 1), c.cout, 1,
-                              t.amax + (size_t)B * 64 * i, t.act[i], c.pool ? t.pooled[i] : nullptr,
-                              t.amax + (size_t)B * 64 * (i + 1), st, kConvTilingTrain, 64));
-    } else {
-      DISN_RC(conv_fwd(x, B, c.hw, c.hw, c.cin, t.conv_p[i], P(2 * i + 1), c.cout, 1, t.act[i], gws, gwb, st, bf));
-    }
-    x = t.act[i];
-    if (c.pool) {
-      if (!h2fwd) DISN_TRY(maxpool2x2_launch(x, B, c.hw, c.hw, c.cout, t.pooled[i], st));
-      x = t.pooled[i];
-    }
-  }
-  const float* pool5 = x;
-  DISN_TRY(gemv_launch(pool5, B, 25088, P(V_FC), P(V_FC + 1), 4096, 1, t.h6, t.fc_ws, st));
-  DISN_TRY(gemv_launch(t.h6, B, 4096, P(V_FC + 2), P(V_FC + 3), 4096, 1, t.h7, t.fc_ws, st));
-  DISN_TRY(gemv_launch(t.h7, B, 4096, P(V_FC + 4), P(V_FC + 5), DISN_EMBED_DIM, 0, t.emb, t.fc_ws, st));
+  if (h2fwd) DISN_RC(enc_h2_pack(enc, st));
+  const float* pool5;
+  DISN_RC(enc_conv_forward(enc, img, st, &pool5));
+  DISN_RC(enc_fc_forward(enc, pool5, st));
 
   // ---------------- camera head, losses, head backward (cam_head.hip, cam_train.hip) ----------------
   const disn_cam_weights_t cw = cam_weights_at(params, L);
   const CamK K = cam_k(K_host);
-  DISN_TRY(cam_head_launch(cw, t.emb, K, B, t.rot, t.trans, t.pred_RT, pred_trans_mat, t.save, st));
+  DISN_TRY(cam_head_launch(cw, e.emb, K, B, t.rot, t.trans, t.pred_RT, pred_trans_mat, t.save, st));
   if (ctx) DISN_TRY(hipStreamWaitEvent(st, ctx->ev[1], 0));  // losses[5]
   DISN_TRY(cam_loss_launch(t.pred_RT, pred_trans_mat, pts, RT, trans_mat, K, B, N, loss_mode, losses + 5, losses,
                            dists, t.dRT, t.loss_ws, st));
-  DISN_TRY(cam_head_bwd_launch(cw, t.save, t.dRT, B, t.dsave, t.demb, st));
+  DISN_TRY(cam_head_bwd_launch(cw, t.save, t.dRT, B, t.dsave, e.demb, st));
   {
     CamGrads cg;
-    for (int j = 0; j < 18; ++j) cg.p[j] = G(V_G + j);
-    DISN_TRY(cam_head_wgrad_launch(t.emb, t.save, t.dsave, B, cg, st));
+    for (int j = 0; j < 18; ++j) cg.p[j] = grads + L.offset[V_G + j];
+    DISN_TRY(cam_head_wgrad_launch(e.emb, t.save, t.dsave, B, cg, st));
   }
 
-  // ---------------- backward: fc8, fc7, fc6 ----------------
-  DISN_TRY(relu_bwd_colsum_launch(t.demb, nullptr, B, DISN_EMBED_DIM, 0, G(V_FC + 5), t.red_aux, st));
-  DISN_TRY(fc_bwd_launch(t.h7, t.demb, B, 4096, DISN_EMBED_DIM, P(V_FC + 4), wd, G(V_FC + 4), t.h7, t.dz7, st));
-  DISN_TRY(relu_bwd_colsum_launch(t.dz7, nullptr, B, 4096, 0, G(V_FC + 3), t.red_aux, st));
-  DISN_TRY(fc_bwd_launch(t.h6, t.dz7, B, 4096, 4096, P(V_FC + 2), wd, G(V_FC + 2), t.h6, t.dz6, st));
-  DISN_TRY(relu_bwd_colsum_launch(t.dz6, nullptr, B, 4096, 0, G(V_FC + 1), t.red_aux, st));
-  DISN_TRY(fc_bwd_launch(pool5, t.dz6, B, 25088, 4096, P(V_FC), wd, G(V_FC), nullptr, t.dpool5, st));
-
-  // ---------------- backward: conv stack (no feature-map tap gradient: the camera net samples no features) -------
-  const float* dcur = t.dpool5;
-  float* bufs[2] = {t.gA, t.gB};
-  int which = 0;
-  for (int i = 12; i >= 0; --i) {
-    const ConvL& c = kConv[i];
-    float* dy;
-    if (c.pool) {
-      dy = bufs[which];
-      which ^= 1;
-      DISN_TRY(maxpool_bwd_launch(t.act[i], dcur, B, c.hw, c.hw, c.cout, dy, st));
-    } else {
-      dy = const_cast<float*>(dcur);
-    }
-    const long rows = (long)B * c.hw * c.hw;
-    float* amax_i = h2fwd && i > 0 ? t.amax_bwd + (size_t)i * B * 64 : nullptr;
-    bool amax_ready = false;
-    DISN_TRY(relu_bwd_colsum_launch(dy, t.act[i], rows, c.cout, 1, G(2 * i + 1), s.red_ws, st, amax_i,
-                                    (long)c.hw * c.hw, &amax_ready));
-    const float* xin = i == 0 ? t.resized : (kConv[i - 1].pool ? t.pooled[i - 1] : t.act[i - 1]);
-    float* dx = nullptr;
-    if (i > 0) {
-      dx = bufs[which];
-      if (dx == dy) dx = bufs[which ^ 1];
-    }
-    DISN_RC(conv_bwd(xin, B, c.hw, c.hw, c.cin, P(2 * i), dy, c.cout, wd, dx, G(2 * i), t.col, s, st,
-                     t.conv_bT[i], h2fwd && i > 0 ? t.conv_h2bT[i] : nullptr, amax_i,
-                     h2fwd && i > 0 ? t.amax + (size_t)B * 64 * i : nullptr, amax_ready));
-    if (dx) {
-      which = (dx == bufs[0]) ? 1 : 0;
-      dcur = dx;
-    }
-  }
-  return 0;
+  // ---------------- backward: fc8, fc7, fc6, conv stack (no tap gradient: the camera net samples no features) -------
+  DISN_RC(enc_fc_backward(enc, pool5, st));
+  return enc_conv_backward(enc, nullptr, st);
 }
 
 }  // extern "C"

@@ -16,17 +16,17 @@ Not supported, with a clear error: --shift, --rotation, --optimizer momentum, mu
 from __future__ import annotations
 
 import argparse
-import math
 import os
 import sys
 import time
-from typing import Dict, Optional
+from typing import Dict
 
 import numpy as np
 import torch
 
 from . import ops, posenet
-from .train_sdf import PRECISIONS, adam_step_from_checkpoint, get_learning_rate, schedule_step_from_checkpoint
+from .train_common import PRECISIONS, FlatBuffer, TrainerBase
+from .train_sdf import adam_step_from_checkpoint, schedule_step_from_checkpoint
 from .weights import WeightStore, variable_shapes as sdf_variable_shapes
 
 LOSS_NAMES = ops.CAM_LOSS_NAMES
@@ -49,106 +49,35 @@ def random_init(seed: int = 0) -> Dict[str, np.ndarray]:
     return out
 
 
-class FlatCamParams:
+class FlatCamParams(FlatBuffer):
     """the 50 variables of the camera network in ONE device buffer (disn_cam_param_layout)"""
 
     def __init__(self, device):
-        self.layout = ops.cam_param_layout()
-        self.total = int(self.layout.total)
-        self.device = device
-        self.shapes = variable_shapes()
-        self.index = {n: i for i, n in enumerate(VARIABLE_ORDER)}
-
-    def zeros(self) -> torch.Tensor:
-        return torch.zeros(self.total, dtype=torch.float32, device=self.device)
-
-    def view(self, buf: torch.Tensor, name: str) -> torch.Tensor:
-        i = self.index[name]
-        o, c = int(self.layout.offset[i]), int(self.layout.count[i])
-        return buf[o:o + c].view(self.shapes[name])
+        super().__init__(ops.cam_param_layout(), variable_shapes(), device)
 
     def from_arrays(self, arrays: Dict[str, np.ndarray]) -> torch.Tensor:
-        host = np.zeros(self.total, np.float32)
-        for n, i in self.index.items():
-            if n not in arrays or tuple(np.shape(arrays[n])) != tuple(self.shapes[n]):
-                raise ValueError("camera network variable %s missing or of the wrong shape" % n)
-            o, c = int(self.layout.offset[i]), int(self.layout.count[i])
-            host[o:o + c] = np.asarray(arrays[n], np.float32).reshape(-1)
-        return torch.from_numpy(host).to(self.device)
-
-    def to_arrays(self, buf: torch.Tensor, suffix: str = "") -> Dict[str, np.ndarray]:
-        host = buf.detach().cpu().numpy()
-        out = {}
-        for n, i in self.index.items():
-            o, c = int(self.layout.offset[i]), int(self.layout.count[i])
-            out[n + suffix] = host[o:o + c].reshape(self.shapes[n]).copy()
-        return out
+        return self.fill(arrays.get, check=True)
 
 
-class CamTrainer:
+class CamTrainer(TrainerBase):
     def __init__(self, arrays: Dict[str, np.ndarray], device="cuda:0", batch_size: int = 32, base_lr: float = 1e-4,
                  decay_step: int = 200000, decay_rate: float = 0.9, wd: float = 2e-3, loss_mode="3D",
                  beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8, precision: str = "f32",
                  optimizer: str = "adam"):
         if optimizer != "adam":
             raise NotImplementedError("only the Adam optimizer is supported (the reference's default)")
-        if precision not in PRECISIONS:
-            raise ValueError("precision must be one of %s" % (tuple(PRECISIONS),))
-        self.precision = precision
-        self.compute_bf16 = PRECISIONS[precision]
         self.loss_mode = ops.cam_loss_mode(loss_mode)
-        self.flat = FlatCamParams(torch.device(device))
-        self.params = self.flat.from_arrays(arrays)
-        self.grads = self.flat.zeros()
-        self.m = self.flat.zeros()
-        self.v = self.flat.zeros()
-        self.step_count = 0
-        self.adam_t = 0
-        self.batch_size = batch_size
-        self.base_lr, self.decay_step, self.decay_rate = base_lr, decay_step, decay_rate
-        self.wd = wd
-        self.beta1, self.beta2, self.eps = beta1, beta2, eps
-        self._ws: Optional[torch.Tensor] = None
-        with torch.cuda.device(self.params.device):
-            self.ctx = ops.ctx_create()
-
-    def close(self) -> None:
-        if self.ctx:
-            torch.cuda.synchronize(self.params.device)
-            with torch.cuda.device(self.params.device):
-                ops.ctx_destroy(self.ctx)
-            self.ctx = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # interpreter shutdown
-            pass
+        self._init_state(FlatCamParams(torch.device(device)), arrays.get, True, precision, batch_size, base_lr,
+                         decay_step, decay_rate, wd, beta1, beta2, eps)
 
     def forward_backward(self, feed: Dict[str, torch.Tensor]):
         """gradients into self.grads; -> (pred_trans_mat [B,4,3], losses [7], dists [2,B]) device tensors"""
         B, N = feed["sample_pc"].shape[:2]
-        need = ops.lib().disn_cam_train_workspace_bytes(B, N)
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = None
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.params.device)
+        ws = self._fit_ws(ops.lib().disn_cam_train_workspace_bytes(B, N))
         with torch.cuda.device(self.params.device):
             return ops.cam_train_step(self.params, self.grads, feed["imgs"], feed["sample_pc"], feed["RT"],
                                       feed["trans_mat"], self.wd, self.loss_mode, compute_bf16=self.compute_bf16,
-                                      ws=self._ws, ctx=self.ctx)
-
-    def learning_rate(self) -> float:
-        return get_learning_rate(self.step_count, self.batch_size, self.base_lr, self.decay_step, self.decay_rate)
-
-    def apply_gradients(self) -> float:
-        lr = self.learning_rate()
-        t = self.adam_t + 1
-        lr_t = lr * math.sqrt(1.0 - self.beta2 ** t) / (1.0 - self.beta1 ** t)
-        with torch.cuda.device(self.params.device):
-            ops.adam_update(self.params, self.grads, self.m, self.v, lr_t, self.beta1, self.beta2, self.eps, 1.0)
-        self.adam_t = t
-        self.step_count += 1
-        return lr
+                                      ws=ws, ctx=self.ctx)
 
     def step(self, feed: Dict[str, torch.Tensor]):
         """-> (pred_trans_mat [B,4,3] device, losses dict name -> device scalar, lr)"""
@@ -163,23 +92,8 @@ class CamTrainer:
         return self.forward_backward(feed)
 
     # ---- checkpoints ----------------------------------------------------------------------
-    def state_arrays(self, include_step: bool = False) -> Dict[str, np.ndarray]:
-        out = self.flat.to_arrays(self.params)
-        out.update(self.flat.to_arrays(self.m, "/Adam"))
-        out.update(self.flat.to_arrays(self.v, "/Adam_1"))
-        out["beta1_power"] = np.asarray(self.beta1 ** (self.adam_t + 1), np.float32)
-        out["beta2_power"] = np.asarray(self.beta2 ** (self.adam_t + 1), np.float32)
-        if include_step:
-            out["batch"] = np.asarray(self.step_count, np.int32)
-        return out
-
     def save(self, prefix: str, include_step: bool = True) -> None:
-        from . import tf_checkpoint as tfc
-        tfc.save_checkpoint(prefix, self.state_arrays(include_step))
-        d = os.path.dirname(os.path.abspath(prefix))
-        base = os.path.basename(prefix)
-        paths = [p for p in tfc.all_checkpoint_paths(d) if p != base] + [base]
-        tfc.write_checkpoint_state(d, base, paths[-5:])
+        self._save(prefix, include_step, 5)
 
     def restore(self, prefix: str, prefixes=("",)) -> int:
         """exact-name, exact-shape restore of the variables and their Adam slots whose names start with one of
@@ -187,15 +101,7 @@ class CamTrainer:
         schedule step when the bundle carries them; -> #restored"""
         from . import tf_checkpoint as tfc
         arrays = tfc.load_checkpoint(prefix)
-        n = 0
-        for buf, suffix in ((self.params, ""), (self.m, "/Adam"), (self.v, "/Adam_1")):
-            for name in VARIABLE_ORDER:
-                if not any(name.startswith(p) for p in prefixes):
-                    continue
-                a = arrays.get(name + suffix)
-                if a is not None and tuple(a.shape) == tuple(self.flat.shapes[name]):
-                    self.flat.view(buf, name).copy_(torch.from_numpy(np.ascontiguousarray(a, np.float32)))
-                    n += 1
+        n = self._restore_matching(arrays, slots=True, prefixes=prefixes)
         if "" in prefixes:
             self.adam_t = adam_step_from_checkpoint(arrays, self.beta2, self.adam_t)
             self.step_count = schedule_step_from_checkpoint(arrays)

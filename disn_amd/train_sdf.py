@@ -25,53 +25,22 @@ import torch
 
 from . import ops
 from .parallel import GradientReducer
+from .train_common import PRECISIONS, FlatBuffer, TrainerBase, get_learning_rate  # noqa: F401  (re-exported)
 from .weights import WeightStore, variable_shapes
 
 LOSS_NAMES = ("accuracy", "sdf_loss_realvalue", "sdf_loss", "regularization", "overall_loss")
 VARIABLE_ORDER = tuple(variable_shapes())  # == the order of disn_param_layout
-PRECISIONS = {"f32_mfma": 0, "bf16": 1, "f32": 2}   # -> compute_bf16 of disn_train_step
 HEAD_FIRST_VAR = 26  # vgg_16/fc6/weights: everything from here on is final before the conv backward
 
 
-def get_learning_rate(step: int, batch_size: int, base_lr: float = 1e-4, decay_step: int = 200000,
-                      decay_rate: float = 0.9) -> float:
-    """tf.train.exponential_decay(base, step*batch, decay_step, decay_rate, staircase=True) floored
-    at 1e-6 (train/train_sdf.py:153-161; flags :36-40)"""
-    return max(base_lr * decay_rate ** ((step * batch_size) // decay_step), 1e-6)
-
-
-class FlatParams:
+class FlatParams(FlatBuffer):
     """the 56 variables of the graph in ONE device buffer (include/disn_amd.h, disn_param_layout)"""
 
     def __init__(self, device):
-        self.layout = ops.param_layout()
-        self.total = int(self.layout.total)
-        self.device = device
-        self.shapes = variable_shapes()
-        self.index = {n: i for i, n in enumerate(VARIABLE_ORDER)}
-
-    def zeros(self) -> torch.Tensor:
-        return torch.zeros(self.total, dtype=torch.float32, device=self.device)
-
-    def view(self, buf: torch.Tensor, name: str) -> torch.Tensor:
-        i = self.index[name]
-        o, c = int(self.layout.offset[i]), int(self.layout.count[i])
-        return buf[o:o + c].view(self.shapes[name])
+        super().__init__(ops.param_layout(), variable_shapes(), device)
 
     def from_store(self, store: WeightStore) -> torch.Tensor:
-        host = np.zeros(self.total, np.float32)
-        for n, i in self.index.items():
-            o, c = int(self.layout.offset[i]), int(self.layout.count[i])
-            host[o:o + c] = np.asarray(store[n], np.float32).reshape(-1)
-        return torch.from_numpy(host).to(self.device)
-
-    def to_arrays(self, buf: torch.Tensor, suffix: str = "") -> Dict[str, np.ndarray]:
-        host = buf.detach().cpu().numpy()
-        out = {}
-        for n, i in self.index.items():
-            o, c = int(self.layout.offset[i]), int(self.layout.count[i])
-            out[n + suffix] = host[o:o + c].reshape(self.shapes[n]).copy()
-        return out
+        return self.fill(lambda n: store[n])
 
 
 def adam_step_from_checkpoint(arrays: Dict[str, np.ndarray], beta2: float, current: int = 0,
@@ -104,61 +73,26 @@ def schedule_step_from_checkpoint(arrays: Dict[str, np.ndarray]) -> int:
     return 0
 
 
-class Trainer:
+class Trainer(TrainerBase):
     def __init__(self, store: WeightStore, device="cuda:0", batch_size: int = 20, base_lr: float = 1e-4,
                  decay_step: int = 200000, decay_rate: float = 0.9, wd: float = 1e-5,
                  sdf_weight: float = 10.0, mask_weight: float = 4.0, beta1: float = 0.5,
                  beta2: float = 0.999, eps: float = 1e-8, process_group=None, compute_bf16: bool = False,
                  precision: Optional[str] = None):
-        # precision of the conv / MLP GEMMs (everything else is fp32 in every mode):
-        #   "f32"       fp32-accurate, the reference's precision: forward and data-gradient GEMMs as a
-        #               three-term bf16 split on the bf16 MFMA pipes (same error as the f32-input MFMA,
-        #               faster), weight gradients on the f32-input MFMA            [default]
-        #   "f32_mfma"  every product on the f32-input MFMA
-        #   "bf16"      mixed precision: bf16 multiply, fp32 accumulate / master weights / optimizer
+        # precision: "f32" (default), "f32_mfma" or "bf16" (TrainerBase._init_state); compute_bf16=True: "bf16"
         if precision is None:
             precision = "bf16" if compute_bf16 else "f32"
-        if precision not in PRECISIONS:
-            raise ValueError("precision must be one of %s" % (tuple(PRECISIONS),))
-        self.precision = precision
-        self.compute_bf16 = PRECISIONS[precision]
-        self.flat = FlatParams(torch.device(device))
-        self.params = self.flat.from_store(store)
-        self.grads = self.flat.zeros()
-        self.m = self.flat.zeros()
-        self.v = self.flat.zeros()
-        self.step_count = 0  # the reference's `batch` variable (global step): drives the learning-rate schedule
-        self.adam_t = 0      # Adam's timestep (TF keeps it as beta1_power / beta2_power): drives the bias correction
-        self.batch_size = batch_size  # GLOBAL batch (all ranks), as the LR schedule counts samples
-        self.base_lr, self.decay_step, self.decay_rate = base_lr, decay_step, decay_rate
-        self.wd, self.sdf_weight, self.mask_weight = wd, sdf_weight, mask_weight
-        self.beta1, self.beta2, self.eps = beta1, beta2, eps
+        self._init_state(FlatParams(torch.device(device)), lambda n: store[n], False, precision, batch_size,
+                         base_lr, decay_step, decay_rate, wd, beta1, beta2, eps)
+        self.sdf_weight, self.mask_weight = sdf_weight, mask_weight
         self.pg = process_group
-        self.world = 1
         if process_group is not None or (torch.distributed.is_available() and torch.distributed.is_initialized()):
             self.world = torch.distributed.get_world_size(process_group)
-        self._ws: Optional[torch.Tensor] = None
-        # every stream / event this object owns lives on params.device, and every launch below runs under
-        # torch.cuda.device(params.device): ops._stream() is the CURRENT device's current stream
         with torch.cuda.device(self.params.device):
-            self.ctx = ops.ctx_create()  # auxiliary stream for the HBM-bound side work of the step
             # gradient exchange: fc + MLP bucket under the convolution backward, conv bucket at the end
             self.reducer = GradientReducer(int(self.flat.layout.offset[HEAD_FIRST_VAR]), process_group)
             self.head_ready = torch.cuda.Event()
             self.head_ready.record()  # creates the hipEvent_t handed to the library
-
-    def close(self) -> None:
-        if self.ctx:
-            torch.cuda.synchronize(self.params.device)
-            with torch.cuda.device(self.params.device):
-                ops.ctx_destroy(self.ctx)
-            self.ctx = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # interpreter shutdown
-            pass
 
     # ---- one step ---------------------------------------------------------------------
     def reserve_workspace(self, B: int, N: int) -> int:
@@ -167,41 +101,20 @@ class Trainer:
         need = ops.lib().disn_train_workspace_bytes(B, N)
         if need == 0:
             raise ValueError("unsupported training shape B=%d N=%d (B*N <= 65536)" % (B, N))
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = None
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.params.device)
+        self._fit_ws(need)
         return need
 
     def forward_backward(self, feed: Dict[str, torch.Tensor]):
         """gradients of THIS rank's shard into self.grads; -> (pred, losses tensor[5])"""
         B, N = feed["sample_pc"].shape[:2]
-        need = ops.lib().disn_train_workspace_bytes(B, N)
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = None
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.params.device)
+        ws = self._fit_ws(ops.lib().disn_train_workspace_bytes(B, N))
         with torch.cuda.device(self.params.device):
             out = ops.train_step(self.params, self.grads, feed["imgs"], feed["trans_mat"], feed["sample_pc"],
                                  feed["sample_pc_rot"], feed["sdf"], self.wd, self.sdf_weight,
-                                 self.mask_weight, ws=self._ws, ctx=self.ctx, head_ready=self.head_ready,
+                                 self.mask_weight, ws=ws, ctx=self.ctx, head_ready=self.head_ready,
                                  compute_bf16=self.compute_bf16)
             self.reducer.start_head(self.grads, self.head_ready)
         return out
-
-    def learning_rate(self) -> float:
-        return get_learning_rate(self.step_count, self.batch_size, self.base_lr, self.decay_step,
-                                 self.decay_rate)
-
-    def apply_gradients(self) -> float:
-        lr = self.learning_rate()
-        t = self.adam_t + 1
-        lr_t = lr * math.sqrt(1.0 - self.beta2 ** t) / (1.0 - self.beta1 ** t)
-        with torch.cuda.device(self.params.device):
-            self.reducer.finish(self.grads)
-            ops.adam_update(self.params, self.grads, self.m, self.v, lr_t, self.beta1, self.beta2, self.eps,
-                            1.0 / self.world)
-        self.adam_t = t
-        self.step_count += 1
-        return lr
 
     def step(self, feed: Dict[str, torch.Tensor]):
         """-> (pred [B,N] device, losses dict name -> device scalar, lr)"""
@@ -210,33 +123,13 @@ class Trainer:
         return pred, {n: losses[i] for i, n in enumerate(LOSS_NAMES)}, lr
 
     # ---- checkpoints --------------------------------------------------------------------
-    def state_arrays(self, include_step: bool = False) -> Dict[str, np.ndarray]:
-        """what the reference's Saver writes (train/train_sdf.py:285-286): every variable, the Adam slots and the two
-        beta powers -- NOT `batch` / the learning rate.  include_step: also `batch` (int32, as TF creates it), an
-        extension that lets restore() resume the learning-rate schedule (see schedule_step_from_checkpoint)."""
-        out = self.flat.to_arrays(self.params)
-        out.update(self.flat.to_arrays(self.m, "/Adam"))
-        out.update(self.flat.to_arrays(self.v, "/Adam_1"))
-        out["beta1_power"] = np.asarray(self.beta1 ** (self.adam_t + 1), np.float32)
-        out["beta2_power"] = np.asarray(self.beta2 ** (self.adam_t + 1), np.float32)
-        if include_step:
-            out["batch"] = np.asarray(self.step_count, np.int32)
-        return out
-
     def weight_store(self) -> WeightStore:
         return WeightStore(self.flat.to_arrays(self.params))
 
     def save(self, prefix: str, include_step: bool = False, max_to_keep: int = 5) -> None:
-        """variables + Adam slots + beta powers as a TF Saver-V2 bundle, and the `checkpoint` state file next to it
-        (what saver.save writes, train/train_sdf.py:285-286,322-328), so that restore_latest / get_checkpoint_state
-        find it.  The state file keeps the last ``max_to_keep`` prefixes in all_model_checkpoint_paths, as
-        tf.train.Saver does (older bundles stay on disk here; TF would delete them)."""
-        from . import tf_checkpoint as tfc
-        tfc.save_checkpoint(prefix, self.state_arrays(include_step))
-        d = os.path.dirname(os.path.abspath(prefix))
-        base = os.path.basename(prefix)
-        paths = [p for p in tfc.all_checkpoint_paths(d) if p != base] + [base]
-        tfc.write_checkpoint_state(d, base, paths[-max(1, int(max_to_keep)):])
+        """variables + Adam slots + beta powers as a TF Saver-V2 bundle with its `checkpoint` state file
+        (TrainerBase._save)"""
+        self._save(prefix, include_step, max_to_keep)
 
     def restore(self, prefix: str, underflow_step: Optional[int] = None, prefixes=None) -> int:
         """prefix + exact-shape match, as load_model (train/train_sdf.py:190-219); -> #restored.  Adam's timestep comes
@@ -248,21 +141,9 @@ class Trainer:
         variables -- the Adam slots, Adam's timestep and the schedule are left alone."""
         from . import tf_checkpoint as tfc
         arrays = tfc.load_checkpoint(prefix)
-        n = 0
         if prefixes is not None:
-            for name in VARIABLE_ORDER:
-                a = arrays.get(name)
-                if any(name.startswith(p) for p in prefixes) and a is not None \
-                        and tuple(a.shape) == tuple(self.flat.shapes[name]):
-                    self.flat.view(self.params, name).copy_(torch.from_numpy(np.ascontiguousarray(a, np.float32)))
-                    n += 1
-            return n
-        for buf, suffix in ((self.params, ""), (self.m, "/Adam"), (self.v, "/Adam_1")):
-            for name in VARIABLE_ORDER:
-                a = arrays.get(name + suffix)
-                if a is not None and tuple(a.shape) == tuple(self.flat.shapes[name]):
-                    self.flat.view(buf, name).copy_(torch.from_numpy(np.ascontiguousarray(a, np.float32)))
-                    n += 1
+            return self._restore_matching(arrays, slots=False, prefixes=prefixes)
+        n = self._restore_matching(arrays, slots=True)
         self.adam_t = adam_step_from_checkpoint(arrays, self.beta2, self.adam_t, underflow_step)
         self.step_count = schedule_step_from_checkpoint(arrays)
         if "batch" not in arrays and self.adam_t > 0:
