@@ -138,6 +138,12 @@ SIGNATURES = {
     "disn_query_grid_fused_workspace_bytes": (Z, [L]),
     "disn_query_grid_fused": (I, [C.POINTER(MlpWeights), P, P, P, P, C.POINTER(C.c_double * 6), I, L, L, F, P,
                                   P, Z, P]),
+    "disn_query_grid_listed_workspace_bytes": (Z, [L]),
+    "disn_query_grid_listed": (I, [C.POINTER(MlpWeights), P, P, P, P, C.POINTER(C.c_double * 6), I, P, I, L, L, F, P,
+                                   P, Z, P]),
+    "disn_grid_band_select_workspace_bytes": (Z, [I, I]),
+    "disn_grid_band_select": (I, [P, I, I, F, F, I, P, P, L, P, P, Z, P]),
+    "disn_grid_band_fill": (I, [P, I, I, P, P]),
     "disn_sdf_mlp_workspace_bytes": (Z, [I, I]),
     "disn_sdf_mlp": (I, [C.POINTER(MlpWeights), P, P, P, I, I, P, P, P, P, Z, P]),
     "disn_query_workspace_bytes": (Z, [I, I]),

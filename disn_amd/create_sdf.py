@@ -15,6 +15,7 @@ The test-set driver (``python -m disn_amd.create_sdf``, the reference's ``test/c
 
     python -m disn_amd.create_sdf --log_dir CKPT --test_lst_dir LSTS --sdf_dir SDF --rendered_dir VIEWS
                                   [--category all] [--sdf_res 64] [--iso 0.0] [--view_num 24] [--cam_est]
+                                  [--band STRIDE --band_margin 0.5 --band_dilate 1]
 
 walks ``<test_lst_dir>/<cat_id>_test.lst``, encodes ``--batch_size`` views per call, fills their grids, meshes
 the whole group with one read-back (``isosurface.marching_cubes_batch``) and writes
@@ -31,7 +32,9 @@ the whole group with one read-back (``isosurface.marching_cubes_batch``) and wri
     (never an object's views) after the views were drawn, so shards write what one run writes;
   * an empty mesh is written (and logged), not skipped; a writer thread's exception fails the run;
   * ``--skip_existing`` drops entries whose file exists with more than 200 bytes (the size filter of
-    ``evaluate.build_file_dict(min_size=200)``) before the groups are formed.
+    ``evaluate.build_file_dict(min_size=200)``) before the groups are formed;
+  * ``--band STRIDE`` (2, 4 or 8; default 0 = the dense grid) evaluates the network on every STRIDE-th grid point and
+    then only near the ``--iso`` surface, the rest of the grid interpolated (``SdfEngine.query_grid_band``).
 """
 from __future__ import annotations
 
@@ -109,6 +112,41 @@ def dense_grid_sdf(engine, enc, image_index: int, trans_mat, sdf_params, sdf_res
     return engine.query_grid(enc, image_index, trans_mat, sdf_params, sdf_res, k0, k1, sdf_weight, out)
 
 
+def band_args(band, sdf_res: int) -> Optional[Tuple[int, float, int]]:
+    """``band`` = None or (stride, margin, dilate) checked against the resolution (ValueError; no device work):
+    the narrow-band evaluation of ``SdfEngine.query_grid_band``"""
+    if band is None:
+        return None
+    stride, margin, dilate = band
+    stride, margin, dilate = int(stride), float(margin), int(dilate)
+    if stride not in (2, 4, 8):
+        raise ValueError("--band must be 0 (dense) or one of 2, 4, 8, got %d" % stride)
+    if sdf_res < stride or sdf_res % stride or sdf_res > 1289:
+        raise ValueError("--band %d needs --sdf_res to be a multiple of it (at most 1289), got %d" % (stride, sdf_res))
+    if not margin >= 0.0:
+        raise ValueError("--band_margin must not be negative")
+    if dilate < 0:
+        raise ValueError("--band_dilate must not be negative")
+    return stride, margin, dilate
+
+
+def add_band_flags(p) -> None:
+    p.add_argument("--band", type=int, default=0, metavar="STRIDE",
+                   help="narrow-band grid: evaluate every STRIDE-th point (2, 4 or 8), then only near the surface "
+                        "[default: 0, the dense grid]")
+    p.add_argument("--band_margin", type=float, default=0.5,
+                   help="a coarse cell is active when iso lies within its corner range widened by this share of it "
+                        "[default: 0.5]")
+    p.add_argument("--band_dilate", type=int, default=1, help="rounds of dilation of the active cells [default: 1]")
+
+
+def band_from_flags(a) -> Optional[Tuple[int, float, int]]:
+    """None for --band 0, else the checked (stride, margin, dilate)"""
+    if a.band == 0:
+        return None
+    return band_args((a.band, a.band_margin, a.band_dilate), a.sdf_res)
+
+
 def _encode_grids(engine, imgs, trans_mats, sdf_params, sdf_res: int, sdf_weight: float = SDF_WEIGHT):
     """one ``engine.encode`` call and the grid of every image -> (Encoded, result [B, (res+1)^3])"""
     import torch
@@ -123,23 +161,62 @@ def _encode_grids(engine, imgs, trans_mats, sdf_params, sdf_res: int, sdf_weight
     return enc, result
 
 
-def create_sdf(engine, imgs, trans_mats, sdf_params, sdf_res: int, sdf_weight: float = SDF_WEIGHT):
+def _encode_grids_band(engine, imgs, trans_mats, sdf_params, sdf_res: int, iso: float, band,
+                       sdf_weight: float = SDF_WEIGHT):
+    """``_encode_grids`` through the narrow band: all coarse passes, then all selections, ONE copy of the B pairs of
+    data-dependent counts, then the band passes and fills -> (Encoded, result [B, (res+1)^3], stats per image).  Every
+    image's grid is bit for bit ``engine.query_grid_band``'s."""
+    import torch
+    stride, margin, dilate = band
+    imgs = np.asarray(imgs, np.float32) if not isinstance(imgs, torch.Tensor) else imgs
+    B = imgs.shape[0]
+    enc = engine.encode(imgs)
+    total = (sdf_res + 1) ** 3
+    result = torch.empty((B, total), dtype=torch.float32, device=engine.device)
+    counts = torch.zeros((B, 2), dtype=torch.int64, device=engine.device)
+    sp = np.asarray(sdf_params, dtype=np.float64).reshape(B, 6)
+    for b in range(B):
+        engine.band_coarse(enc, b, trans_mats, sp[b], sdf_res, stride, sdf_weight, out=result[b])
+    picked = [engine.band_select(result[b], sdf_res, iso, stride, margin, dilate, counts=counts[b]) for b in range(B)]
+    sizes = counts.cpu().numpy()                      # the one host sync of the group's grids
+    stats = []
+    for b in range(B):
+        mask, idx, _ = picked[b]
+        engine.band_finish(enc, b, trans_mats, sp[b], sdf_res, result[b], mask, idx, int(sizes[b, 0]), stride,
+                           sdf_weight)
+        stats.append({"coarse_points": (sdf_res // stride + 1) ** 3, "band_points": int(sizes[b, 0]),
+                      "active_cells": int(sizes[b, 1]), "total_points": total})
+    return enc, result, stats
+
+
+def create_sdf(engine, imgs, trans_mats, sdf_params, sdf_res: int, sdf_weight: float = SDF_WEIGHT, band=None,
+               iso: float = 0.0):
     """``test_one_epoch`` for one batch (test/create_sdf.py:240-285): returns ``result`` --
-    a float32 device tensor [B, (res+1)^3] of pred_sdf / SDF_WEIGHT."""
-    return _encode_grids(engine, imgs, trans_mats, sdf_params, sdf_res, sdf_weight)[1]
+    a float32 device tensor [B, (res+1)^3] of pred_sdf / SDF_WEIGHT.  ``band`` = (stride, margin, dilate): the
+    narrow-band evaluation around ``iso`` (``SdfEngine.query_grid_band``; points away from the surface interpolated)."""
+    band = band_args(band, sdf_res)
+    if band is None:
+        return _encode_grids(engine, imgs, trans_mats, sdf_params, sdf_res, sdf_weight)[1]
+    return _encode_grids_band(engine, imgs, trans_mats, sdf_params, sdf_res, iso, band, sdf_weight)[1]
 
 
 def reconstruct(engine, imgs, trans_mats, sdf_params, sdf_res: int, iso: float = 0.0, refine: int = 0,
-                normals: bool = False):
+                normals: bool = False, band=None):
     """images -> meshes for one group of views: one ``engine.encode`` call, the per-image grids of
     ``create_sdf`` in one [B,(res+1)^3] tensor, ONE batched meshing (one host sync for the group).
     -> B x (verts [nv,3] float32, faces [nf,3] int32) device views; the bits are those of ``create_sdf``
     followed by ``isosurface.marching_cubes`` image by image.
     ``refine`` > 0: behind the meshing every view's vertices take that many Newton steps onto the network's iso
     level set (``isosurface.refine_mesh``, from the view's cached folded map); ``normals``: every mesh is a triple
-    (verts, faces, normals [nv,3]) with the unit gradient at its (refined) vertices.  Faces never change."""
+    (verts, faces, normals [nv,3]) with the unit gradient at its (refined) vertices.  Faces never change.
+    ``band`` = (stride, margin, dilate): the grids come from the narrow-band evaluation (one more host sync for the
+    group: the band sizes); the bits are those of ``engine.query_grid_band`` and ``marching_cubes`` image by image."""
     from . import isosurface
-    enc, grids = _encode_grids(engine, imgs, trans_mats, sdf_params, sdf_res)
+    band = band_args(band, sdf_res)
+    if band is None:
+        enc, grids = _encode_grids(engine, imgs, trans_mats, sdf_params, sdf_res)
+    else:
+        enc, grids, _ = _encode_grids_band(engine, imgs, trans_mats, sdf_params, sdf_res, iso, band)
     sp = np.asarray(sdf_params, dtype=np.float64).reshape(grids.shape[0], 6)
     meshes = isosurface.marching_cubes_batch(grids, sp, sdf_res, iso)
     if refine <= 0 and not normals:
@@ -233,6 +310,7 @@ def parser():
     p.add_argument("--refine", type=int, default=0, metavar="ITERS",
                    help="Newton steps that move every vertex onto the network's iso level set [default: 0, none]")
     p.add_argument("--normals", action="store_true", help="write the unit SDF gradient at every vertex as 'vn' lines")
+    add_band_flags(p)
     return p
 
 
@@ -247,6 +325,7 @@ def check_flags(a) -> None:
         raise ValueError("--sdf_res must be positive")
     if a.refine < 0:
         raise ValueError("--refine must not be negative")
+    band_from_flags(a)
 
 
 def restore_weights(log_dir: str, random_init: Optional[int]):
@@ -299,8 +378,12 @@ def main(argv=None, reconstruct_fn: Optional[Callable] = None) -> dict:
         engine = SdfEngine(store, torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available()
                            else None, strict=a.strict)
 
+        band = band_from_flags(a)
+
         def reconstruct_fn(imgs, trans_mats, sdf_params):
-            return reconstruct(engine, imgs, trans_mats, sdf_params, a.sdf_res, a.iso, a.refine, a.normals)
+            if band is None:
+                return reconstruct(engine, imgs, trans_mats, sdf_params, a.sdf_res, a.iso, a.refine, a.normals)
+            return reconstruct(engine, imgs, trans_mats, sdf_params, a.sdf_res, a.iso, a.refine, a.normals, band=band)
 
     os.makedirs(out_dir, exist_ok=True)
     logf = open(os.path.join(a.log_dir, "log_test.txt"), "a")

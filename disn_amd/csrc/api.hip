@@ -1523,6 +1523,81 @@ int disn_query_grid_fused(const disn_mlp_weights_t* w, const float* pmap, const 
                        sdf_weight, st);
 }
 
+// ---- narrow-band grid evaluation (grid_band.hip) ----
+namespace {
+// R <= 1289: (R+1)^3 < 2^31, a flat index fits the int32 list and the 32-bit scan
+bool band_shape_ok(int R, int s) { return (s == 2 || s == 4 || s == 8) && R >= s && R <= 1289 && R % s == 0; }
+
+struct ListedWs {
+  float *gbias, *gemv_ws, *gsum, *pts, *vals;
+  size_t total;
+};
+ListedWs listed_layout(void* ws, int64_t n) {
+  Bump b(ws);
+  ListedWs f;
+  f.gbias = b.take((size_t)512 * sizeof(float));
+  f.gemv_ws = b.take(gemv_ws_bytes(1, DISN_EMBED_DIM, 512));
+  f.gsum = b.take((size_t)n * sizeof(float));
+  f.pts = b.take((size_t)n * 3 * sizeof(float));
+  f.vals = b.take((size_t)n * sizeof(float));
+  f.total = (b.off + 255) & ~size_t(255);
+  return f;
+}
+}  // namespace
+
+size_t disn_grid_band_select_workspace_bytes(int R, int stride) {
+  return band_shape_ok(R, stride) ? band_select_ws_bytes(R, stride) : 0;
+}
+
+int disn_grid_band_select(const float* grid, int R, int stride, float iso, float margin, int dilate,
+                          int32_t* cell_mask, int32_t* idx, int64_t idx_capacity, uint64_t* counts, void* ws,
+                          size_t ws_bytes, void* stream) {
+  if (!grid || !cell_mask || !idx || !counts || !ws || !band_shape_ok(R, stride) || dilate < 0 || idx_capacity < 0 ||
+      !(margin >= 0.0f))
+    return DISN_E_ARG;
+  if (ws_bytes < band_select_ws_bytes(R, stride)) return DISN_E_WS;
+  DISN_TRY(band_select_launch(grid, R, stride, iso, margin, dilate, cell_mask, idx, (size_t)idx_capacity,
+                              reinterpret_cast<unsigned long long*>(counts), ws, (hipStream_t)stream));
+  return 0;
+}
+
+int disn_grid_band_fill(float* grid, int R, int stride, const int32_t* cell_mask, void* stream) {
+  if (!grid || !cell_mask || !band_shape_ok(R, stride)) return DISN_E_ARG;
+  DISN_TRY(band_fill_launch(grid, R, stride, cell_mask, (hipStream_t)stream));
+  return 0;
+}
+
+size_t disn_query_grid_listed_workspace_bytes(int64_t max_points) {
+  if (max_points <= 0) return 0;
+  return listed_layout(nullptr, max_points).total;
+}
+
+int disn_query_grid_listed(const disn_mlp_weights_t* w, const float* pmap, const float* pmap_amax,
+                           const float* embedding, const float* trans_mat, const double* sdf_params_host, int R,
+                           const int32_t* idx, int stride, int64_t first, int64_t n, float sdf_weight, float* grid,
+                           void* ws, size_t ws_bytes, void* stream) {
+  GridSpec g;
+  if (!fused_ok(w) || !pmap || !pmap_amax || !embedding || !trans_mat || !grid || !ws ||
+      !grid_spec(sdf_params_host, R, &g) || R > 1289 || first < 0 || n < 0 || sdf_weight == 0.0f)
+    return DISN_E_ARG;
+  if (idx ? stride != 0 : !band_shape_ok(R, stride)) return DISN_E_ARG;
+  if (!idx) {  // a run of the lattice
+    const int64_t c1 = R / stride + 1;
+    if (first + n > c1 * c1 * c1) return DISN_E_ARG;
+  }
+  if (n == 0) return 0;
+  hipStream_t st = (hipStream_t)stream;
+  const ListedWs f = listed_layout(ws, n);
+  if (f.total > ws_bytes) return DISN_E_WS;
+  DISN_RC(gbias_layer(w, embedding, 1, f.gbias, f.gemv_ws, st));
+  DISN_TRY(band_coords_launch(g, idx, stride, (size_t)first, (size_t)n, f.pts, st));
+  // point mode with pts = pts_rot and the grid path's own division: the bits of disn_query_grid_fused at these points
+  DISN_RC(fused_streams(w, f.gbias, pmap, pmap_amax, trans_mat, f.pts, f.pts, nullptr, 0, n, f.gsum, f.vals,
+                        sdf_weight, st));
+  DISN_TRY(band_scatter_launch(f.vals, idx, R, stride, (size_t)first, (size_t)n, grid, st));
+  return 0;
+}
+
 int disn_grid_points(const double* sdf_params_host, int R, int64_t k0, int64_t k1, float* pts,
                      void* stream) {
   GridSpec g;

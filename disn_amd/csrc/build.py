@@ -40,6 +40,7 @@ SOURCES = {
     "dense_h2w.hip": [],
     "elementwise.hip": ["-ffp-contract=off"],
     "marching_cubes.hip": ["-ffp-contract=off"],
+    "grid_band.hip": ["-ffp-contract=off"],     # the rule and the fill bit-identical to their float32 restatement
     "metrics.hip": ["-ffp-contract=off"],       # nn_distance bit-identical to a float32 restatement
     "mesh_sdf.hip": ["-ffp-contract=off"],      # distances and crossings bit-identical to their restatements
     "render.hip": ["-ffp-contract=off"],        # hits, depth and shading bit-identical to their float32 restatement

@@ -273,6 +273,26 @@ hipError_t mc_verts_batch_launch(const float* vol, const GridSpec* g, int b0, in
                                  float* verts, void* ws, hipStream_t st);
 hipError_t mc_faces_batch_launch(const float* vol, int B, int R, float iso, int* faces, void* ws, hipStream_t st);
 
+// exclusive scan of n < 2^32 uint32 (three passes); bsum: one uint32 per kScanBlockItems items and one more; *total
+// (device memory) = the grand total
+constexpr int kScanBlockItems = 4096;
+hipError_t exclusive_scan(const unsigned* in, unsigned* out, size_t n, unsigned* bsum, unsigned long long* total,
+                          hipStream_t st);
+
+// ---- grid_band.hip (compiled with -ffp-contract=off): narrow-band grid evaluation around a dense tensor ----
+// R % s == 0, s in {2, 4, 8}, R <= 1289 are the caller's to check (api.hip).  cell_mask [(R/s)^3] 0 / 1; idx: the band
+// points' flat indices in ascending order (entries beyond idx_capacity are dropped); counts (device) = {band points,
+// active cells}
+size_t band_select_ws_bytes(int R, int s);
+hipError_t band_select_launch(const float* grid, int R, int s, float iso, float margin, int dilate, int* cell_mask,
+                              int* idx, size_t idx_capacity, unsigned long long* counts, void* ws, hipStream_t st);
+// entries first .. first + count - 1 of a point list: idx, or (idx == nullptr) the lattice of stride s in flat order
+hipError_t band_coords_launch(const GridSpec& g, const int* idx, int s, size_t first, size_t count, float* pts,
+                              hipStream_t st);
+hipError_t band_scatter_launch(const float* vals, const int* idx, int R, int s, size_t first, size_t count, float* grid,
+                               hipStream_t st);
+hipError_t band_fill_launch(float* grid, int R, int s, const int* cell_mask, hipStream_t st);
+
 // ---- metrics.hip (compiled with -ffp-contract=off): evaluation metrics, one workspace for every entry ----
 size_t metrics_ws_bytes(int b, int n, int m);
 hipError_t nn_distance_launch(const float* xyz1, const float* xyz2, int b, int n, int m, float* dist1, int* idx1,

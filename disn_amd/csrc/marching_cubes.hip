@@ -97,8 +97,9 @@ __global__ __launch_bounds__(256) void scan_add_kernel(unsigned* __restrict__ ou
     if (base + i < n) out[base + i] += add;
 }
 
-static hipError_t exclusive_scan(const unsigned* in, unsigned* out, size_t n, unsigned* bsum,
-                                 unsigned long long* total, hipStream_t st) {
+static_assert(kScanBlock == kScanBlockItems, "kernels.hpp sizes the callers' block sums");
+hipError_t exclusive_scan(const unsigned* in, unsigned* out, size_t n, unsigned* bsum,
+                          unsigned long long* total, hipStream_t st) {
   const int nb = (int)((n + kScanBlock - 1) / kScanBlock);
   hipLaunchKernelGGL(scan_block_kernel, dim3(nb), dim3(256), 0, st, in, out, n, bsum);
   hipLaunchKernelGGL(scan_sums_kernel, dim3(1), dim3(1024), 0, st, bsum, nb, total);

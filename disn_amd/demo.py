@@ -2,6 +2,7 @@
 
     python -m disn_amd.demo --img VIEW.png --log_dir CKPT [--cam_est --cam_log_dir CAM_CKPT]
                             [--sdf_res 64] [--iso 0.0] [--out demo/result.obj] [--refine ITERS] [--normals]
+                            [--band STRIDE --band_margin 0.5 --band_dilate 1]
 
 The image is read as demo/demo.py:261-279 reads it (``cv2.imread(IMREAD_UNCHANGED)[:, :, :3] / 255``: the
 channels in B, G, R order, alpha dropped) -- through PIL, which is what this project has.  Without ``--cam_est``
@@ -81,6 +82,8 @@ def parser() -> argparse.ArgumentParser:
     p.add_argument("--refine", type=int, default=0, metavar="ITERS",
                    help="Newton steps that move every vertex onto the network's iso level set [default: 0, none]")
     p.add_argument("--normals", action="store_true", help="write the unit SDF gradient at every vertex as 'vn' lines")
+    from .create_sdf import add_band_flags
+    add_band_flags(p)
     return p
 
 
@@ -88,7 +91,8 @@ def main(argv=None) -> dict:
     """-> {"out", "verts", "faces", "trans_mat"}"""
     a = parser().parse_args(argv)
     from . import isosurface
-    from .create_sdf import reconstruct, restore_weights
+    from .create_sdf import band_from_flags, reconstruct, restore_weights
+    band = band_from_flags(a)                                          # a bad stride / resolution: before anything else
     img = read_image(a.img)
     if img.shape[1:3] != (137, 137):
         raise ValueError("%s is %dx%d; the network reads 137x137 renderings" % (a.img, img.shape[2], img.shape[1]))
@@ -105,7 +109,9 @@ def main(argv=None) -> dict:
     engine = SdfEngine(store)
     if a.refine < 0:
         raise ValueError("--refine must not be negative")
-    verts, faces, *vn = reconstruct(engine, img, trans_mat, DEMO_SDF_PARAMS, a.sdf_res, a.iso, a.refine, a.normals)[0]
+    extra = {} if band is None else {"band": band}
+    verts, faces, *vn = reconstruct(engine, img, trans_mat, DEMO_SDF_PARAMS, a.sdf_res, a.iso, a.refine, a.normals,
+                                    **extra)[0]
     isosurface.write_obj(a.out, verts, faces, *vn)
     print("wrote %s: %d vertices, %d triangles" % (a.out, len(verts), len(faces)))
     tm = trans_mat.cpu().numpy() if hasattr(trans_mat, "cpu") else trans_mat

@@ -431,6 +431,75 @@ class SdfEngine:
             return ops.query_grid(self.weights.mlp, self.featmap_of(enc)[image_index], enc.embedding[image_index:image_index + 1],
                                   tm.contiguous(), sdf_params, res, k0, k1, sdf_weight, ws, out, ctx)
 
+    # ---- narrow-band grid: coarse lattice, selection, band points, fill ------------------------------
+    BAND_CHUNK = 1 << 21      # listed points per disn_query_grid_listed call (40 MB of workspace)
+
+    def _band_image(self, enc: Encoded, image_index: int, trans_mat):
+        """(pmap, max |pmap|, embedding row, trans_mat [4,3]) of one image: what a listed query reads"""
+        if not self.fused:
+            raise ValueError("query_grid_band runs the fused point-MLP kernels: build the engine with fused=True")
+        tm = self._dev(trans_mat).reshape(-1, 4, 3)
+        tm = tm[image_index if tm.shape[0] > 1 else 0].contiguous()
+        return (self.pmap_of(enc, image_index), self.pmap_amax_of(enc, image_index),
+                enc.embedding[image_index:image_index + 1], tm)
+
+    def _band_listed(self, image, sdf_params, res: int, grid, idx, stride: int, n: int, sdf_weight: float) -> None:
+        pm, am, emb, tm = image
+        for first in range(0, n, self.BAND_CHUNK):
+            m = min(self.BAND_CHUNK, n - first)
+            ws = self._workspace("band_listed", lib().disn_query_grid_listed_workspace_bytes(m))
+            ops.query_grid_listed(self.weights.mlp, pm, am, emb, tm, sdf_params, res, grid, idx, stride, first, m,
+                                  sdf_weight, ws)
+
+    def band_coarse(self, enc: Encoded, image_index: int, trans_mat, sdf_params, res: int, stride: int = 4,
+                    sdf_weight: float = 10.0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """step 1 of query_grid_band: the network at the fine grid's points whose indices are multiples of ``stride``,
+        written to their places in the dense tensor (every other element is left as it is)"""
+        ops.band_check(res, stride)
+        with torch.cuda.device(self.device):
+            image = self._band_image(enc, image_index, trans_mat)
+            if out is None:
+                out = torch.empty((res + 1) ** 3, dtype=torch.float32, device=self.device)
+            self._band_listed(image, sdf_params, res, out, None, stride, ops.band_sizes(res, stride)[0], sdf_weight)
+        return out
+
+    def band_select(self, grid: torch.Tensor, res: int, iso: float = 0.0, stride: int = 4, margin: float = 0.5,
+                    dilate: int = 1, counts: Optional[torch.Tensor] = None):
+        """step 2: (cell_mask, idx, counts) of ops.grid_band_select; ``counts``: where the two sizes go (a row of a
+        group's [B,2] tensor, so that the group reads all of them back at once)"""
+        with torch.cuda.device(self.device):
+            ws = self._workspace("band_select", lib().disn_grid_band_select_workspace_bytes(res, stride))
+            return ops.grid_band_select(grid, res, stride, iso, margin, dilate, counts, ws)
+
+    def band_finish(self, enc: Encoded, image_index: int, trans_mat, sdf_params, res: int, grid: torch.Tensor,
+                    cell_mask: torch.Tensor, idx: torch.Tensor, band_points: int, stride: int = 4,
+                    sdf_weight: float = 10.0) -> torch.Tensor:
+        """steps 3 and 4: the network at the first ``band_points`` listed points (in chunks of BAND_CHUNK), then the
+        fill of everything that was not evaluated"""
+        with torch.cuda.device(self.device):
+            if band_points:
+                image = self._band_image(enc, image_index, trans_mat)
+                self._band_listed(image, sdf_params, res, grid, idx, 0, int(band_points), sdf_weight)
+            return ops.grid_band_fill(grid, res, stride, cell_mask)
+
+    def query_grid_band(self, enc: Encoded, image_index: int, trans_mat, sdf_params, res: int, iso: float = 0.0,
+                        stride: int = 4, margin: float = 0.5, dilate: int = 1, sdf_weight: float = 10.0,
+                        out: Optional[torch.Tensor] = None):
+        """The dense grid of query_grid(fused=True) with the network evaluated only near the ``iso`` surface
+        -> (grid [(res+1)^3], stats).  The coarse lattice of ``stride`` (2, 4 or 8; res % stride == 0) is evaluated
+        first; a coarse cell whose corner values lo .. hi satisfy lo - t < iso <= hi + t, t = margin * (hi - lo), is
+        active, then ``dilate`` rounds of 26-neighbourhood dilation; every fine point of an active cell's closed box
+        is evaluated; every other point is the trilinear interpolant of its cell's corners.  Evaluated points carry
+        the dense grid's bits; when no surface cell lies outside the active cells, marching cubes gives the dense
+        grid's mesh.  stats: {"coarse_points", "band_points", "active_cells", "total_points"}; one
+        device-to-host copy (the two data-dependent counts)."""
+        grid = self.band_coarse(enc, image_index, trans_mat, sdf_params, res, stride, sdf_weight, out)
+        mask, idx, counts = self.band_select(grid, res, iso, stride, margin, dilate)
+        nband, ncell = (int(v) for v in counts.tolist())
+        self.band_finish(enc, image_index, trans_mat, sdf_params, res, grid, mask, idx, nband, stride, sdf_weight)
+        return grid, {"coarse_points": ops.band_sizes(res, stride)[0], "band_points": nband, "active_cells": ncell,
+                      "total_points": (res + 1) ** 3}
+
 
 class StepPipeline:
     """``in_flight`` independent encode + query steps at a time on one GPU.

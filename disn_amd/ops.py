@@ -676,6 +676,94 @@ def query_grid(w: MlpWeights, featmap: torch.Tensor, embedding: torch.Tensor, tr
 
 
 # ---------------------------------------------------------------------------
+# narrow-band grid evaluation (grid_band.hip)
+# ---------------------------------------------------------------------------
+BAND_STRIDES = (2, 4, 8)
+BAND_MAX_RES = 1289          # (res+1)^3 < 2^31: a flat index fits the int32 point list
+
+
+def band_check(res: int, stride: int) -> None:
+    """ValueError for a stride or a resolution the narrow band does not take (host arithmetic, no device work)"""
+    if stride not in BAND_STRIDES:
+        raise ValueError("the band stride must be one of %s, got %r" % (BAND_STRIDES, stride))
+    if res < stride or res % stride or res > BAND_MAX_RES:
+        raise ValueError("the band needs a grid resolution that is a multiple of the stride %d and at most %d, got %d"
+                         % (stride, BAND_MAX_RES, res))
+
+
+def band_sizes(res: int, stride: int) -> Tuple[int, int, int]:
+    """(points of the coarse lattice, coarse cells, capacity of the band list) of a grid"""
+    band_check(res, stride)
+    c = res // stride
+    return (c + 1) ** 3, c ** 3, (res + 1) ** 3 - (c + 1) ** 3
+
+
+def query_grid_listed(w: MlpWeights, pmap: torch.Tensor, pmap_amax: torch.Tensor, embedding: torch.Tensor,
+                      trans_mat: torch.Tensor, sdf_params, res: int, grid: torch.Tensor,
+                      idx: Optional[torch.Tensor] = None, stride: int = 0, first: int = 0, n: Optional[int] = None,
+                      sdf_weight: float = 10.0, ws: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """disn_query_grid_listed: grid[p] = pred_sdf / sdf_weight at ``n`` listed points of the dense tensor ``grid``
+    [(res+1)^3] -- entries first.. of ``idx`` (int32 flat indices), or of the lattice of ``stride`` when idx is None"""
+    grid = _chk(grid, "grid")
+    if grid.numel() != (res + 1) ** 3:
+        raise ValueError("grid must hold (res+1)^3 = %d values, got %d" % ((res + 1) ** 3, grid.numel()))
+    if idx is not None:
+        if not (idx.is_cuda and idx.dtype == torch.int32 and idx.is_contiguous()):
+            raise TypeError("idx must be a contiguous int32 CUDA tensor")
+        n = idx.numel() - first if n is None else n
+        if first < 0 or n < 0 or first + n > idx.numel():
+            raise ValueError("entries %d..%d lie outside the list of %d" % (first, first + n, idx.numel()))
+        stride = 0
+    else:
+        n = band_sizes(res, stride)[0] - first if n is None else n
+    if n == 0:
+        return grid
+    ws = _fit_ws(ws, lib().disn_query_grid_listed_workspace_bytes(n), grid.device)
+    p6 = _params6(sdf_params)
+    check("disn_query_grid_listed", lib().disn_query_grid_listed(
+        C.byref(w), _chk(pmap, "pmap").data_ptr(), _chk(pmap_amax, "pmap_amax").data_ptr(),
+        _chk(embedding, "embedding").data_ptr(), _chk(trans_mat, "trans_mat").data_ptr(), C.byref(p6), res,
+        idx.data_ptr() if idx is not None else None, stride, first, n, float(sdf_weight), grid.data_ptr(),
+        ws.data_ptr(), ws.numel(), _stream()))
+    return grid
+
+
+def grid_band_select(grid: torch.Tensor, res: int, stride: int, iso: float = 0.0, margin: float = 0.5,
+                     dilate: int = 1, counts: Optional[torch.Tensor] = None, ws: Optional[torch.Tensor] = None):
+    """disn_grid_band_select on a dense tensor whose coarse lattice is evaluated -> (cell_mask [(res/stride)^3] int32,
+    idx [capacity] int32 -- its first counts[0] entries are the band points, ascending --, counts [2] int64 on the
+    device = (band points, active cells): data dependent, the caller reads them back)"""
+    grid = _chk(grid, "grid")
+    _, cells, cap = band_sizes(res, stride)
+    if grid.numel() != (res + 1) ** 3:
+        raise ValueError("grid must hold (res+1)^3 = %d values, got %d" % ((res + 1) ** 3, grid.numel()))
+    if dilate < 0 or not margin >= 0:
+        raise ValueError("the band margin and dilation must not be negative")
+    dev = grid.device
+    mask = torch.empty(cells, dtype=torch.int32, device=dev)
+    idx = torch.empty(cap, dtype=torch.int32, device=dev)
+    if counts is None:
+        counts = torch.zeros(2, dtype=torch.int64, device=dev)
+    ws = _fit_ws(ws, lib().disn_grid_band_select_workspace_bytes(res, stride), dev)
+    check("disn_grid_band_select", lib().disn_grid_band_select(
+        grid.data_ptr(), res, stride, float(iso), float(margin), int(dilate), mask.data_ptr(), idx.data_ptr(), cap,
+        counts.data_ptr(), ws.data_ptr(), ws.numel(), _stream()))
+    return mask, idx, counts
+
+
+def grid_band_fill(grid: torch.Tensor, res: int, stride: int, cell_mask: torch.Tensor) -> torch.Tensor:
+    """disn_grid_band_fill: in place, every point that is neither a lattice nor a band point of ``cell_mask``"""
+    grid = _chk(grid, "grid")
+    _, cells, _ = band_sizes(res, stride)
+    if grid.numel() != (res + 1) ** 3 or cell_mask.numel() != cells or cell_mask.dtype != torch.int32 \
+            or not cell_mask.is_cuda or not cell_mask.is_contiguous():
+        raise ValueError("grid must hold (res+1)^3 values and cell_mask (res/stride)^3 int32 flags on the device")
+    check("disn_grid_band_fill", lib().disn_grid_band_fill(grid.data_ptr(), res, stride, cell_mask.data_ptr(),
+                                                           _stream()))
+    return grid
+
+
+# ---------------------------------------------------------------------------
 # training step (SURVEY 8f #3)
 # ---------------------------------------------------------------------------
 def param_layout() -> _lib.ParamLayout:

@@ -561,6 +561,47 @@ int disn_query_grid_fused(const disn_mlp_weights_t* w, const float* pmap, const 
                           int64_t k0, int64_t k1, float sdf_weight, float* out, void* ws, size_t ws_bytes,
                           void* stream);
 
+/* ---------------------------------------------------------------------- *
+ * Narrow-band grid evaluation (grid_band.hip): the network runs on the     *
+ * coarse lattice of the fine grid (every index a multiple of `stride`, one *
+ * of 2, 4, 8; R % stride == 0, R <= 1289) and on the fine points near the  *
+ * surface; the rest of the dense tensor is filled by interpolation.  All   *
+ * three entries work on the tensor disn_query_grid_fused fills,            *
+ * grid [(R+1)^3] of pred_sdf / sdf_weight, "inside" = value < iso as in    *
+ * disn_mc_count.  A bad stride or R is DISN_E_ARG.                         *
+ *   disn_query_grid_listed -> grid[p] = pred_sdf(point p) / sdf_weight for *
+ *       the n listed points p, bit for bit what disn_query_grid_fused      *
+ *       writes there; no other element is touched.  The list: idx[first .. *
+ *       first + n) (int32 flat indices, DEVICE; stride = 0), or with idx = *
+ *       NULL points first .. first + n - 1 of the lattice of `stride` in   *
+ *       flat order over (R/stride + 1)^3 -- the coarse pass.  n = 0 is a   *
+ *       no-op.  Workspace: disn_query_grid_listed_workspace_bytes(n); call *
+ *       it in chunks to bound it.                                          *
+ *   disn_grid_band_select  -> from the lattice values in `grid`:           *
+ *       cell_mask [(R/stride)^3] int32 0 / 1: a coarse cell with corner    *
+ *       minimum lo and maximum hi is active iff lo - t < iso && hi + t >=  *
+ *       iso, t = margin * (hi - lo) in float32 (margin >= 0), then         *
+ *       `dilate` rounds of 26-neighbourhood dilation; idx: the fine points *
+ *       in the closed box of an active cell, lattice points left out, in   *
+ *       ascending order (at most (R+1)^3 - (R/stride+1)^3; entries beyond  *
+ *       idx_capacity are dropped); counts[0] = #band points, counts[1] =   *
+ *       #active cells (uint64, DEVICE: data dependent, read them back).    *
+ *   disn_grid_band_fill    -> every point that is neither a lattice nor a  *
+ *       band point gets the trilinear interpolant of the 8 corners of its  *
+ *       coarse cell min(i / stride, R/stride - 1), clamped to [lo, hi]     *
+ *       (float32, fixed order); needs no workspace.                        *
+ * ---------------------------------------------------------------------- */
+size_t disn_query_grid_listed_workspace_bytes(int64_t max_points);
+int disn_query_grid_listed(const disn_mlp_weights_t* w, const float* pmap, const float* pmap_amax,
+                           const float* embedding, const float* trans_mat, const double* sdf_params_host, int R,
+                           const int32_t* idx, int stride, int64_t first, int64_t n, float sdf_weight, float* grid,
+                           void* ws, size_t ws_bytes, void* stream);
+size_t disn_grid_band_select_workspace_bytes(int R, int stride);
+int disn_grid_band_select(const float* grid, int R, int stride, float iso, float margin, int dilate,
+                          int32_t* cell_mask, int32_t* idx, int64_t idx_capacity, uint64_t* counts, void* ws,
+                          size_t ws_bytes, void* stream);
+int disn_grid_band_fill(float* grid, int R, int stride, const int32_t* cell_mask, void* stream);
+
 /* disn_query_grid, chunk-pipelined over the context's two streams: the HBM-bound front of chunk
  * i+1 (grid points, projection, gather) runs under the MFMA-bound MLP of chunk i.  Same result. */
 size_t disn_query_grid_ctx_workspace_bytes(int64_t max_points);
