@@ -205,6 +205,11 @@ SIGNATURES = {
     "disn_mesh_sign": (I, [P, L, P, P, P, I, I, I, P, F, I, F, P, P, P, Z, P]),
     "disn_mesh_bvh_build_order": (I, [P, L, P, L, P, Z, P]),
     "disn_render_views": (I, [P, L, P, P, P, I, I, I, I, F, I, P, P, P, P]),
+    "disn_trace_state_bytes": (Z, [L]),
+    "disn_trace_setup": (I, [P, I, I, I, C.POINTER(C.c_double * 6), F, P, Z, P, P]),
+    "disn_trace_advance": (I, [P, I, I, I, P, L, I, F, F, F, F, F, F, I, I, P, Z, P, P]),
+    "disn_trace_collect": (I, [P, I, I, I, P, Z, P, P]),
+    "disn_trace_shade": (I, [P, I, I, I, P, Z, P, P, L, F, F, F, P, P, P, P, P, P]),
     "disn_mesh_components": (I, [P, L, L, I, P, C.POINTER(C.c_int64)]),
     "disn_voxel_grid_words": (Z, [I]),
     "disn_voxel_surface_workspace_bytes": (Z, [L]),

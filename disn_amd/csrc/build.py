@@ -44,6 +44,7 @@ SOURCES = {
     "metrics.hip": ["-ffp-contract=off"],       # nn_distance bit-identical to a float32 restatement
     "mesh_sdf.hip": ["-ffp-contract=off"],      # distances and crossings bit-identical to their restatements
     "render.hip": ["-ffp-contract=off"],        # hits, depth and shading bit-identical to their float32 restatement
+    "sdf_trace.hip": ["-ffp-contract=off"],     # the ray state machine bit-identical to its float32 restatement
     "voxel.hip": ["-ffp-contract=off"],         # the overlap test bit-identical to its float32 restatement
     "batch_assemble.hip": ["-ffp-contract=off"],   # sample_pc_rot in the order its bound is derived for
     "api.hip": [],

@@ -320,6 +320,24 @@ hipError_t render_views_launch(const void* bvh, int64_t nf, const int32_t* order
                                const float* cams, int V, int H, int W, int S, float ambient, int brute,
                                uint8_t* rgba, float* depth, int32_t* face, hipStream_t st);
 
+// ---- sdf_trace.hip (compiled with -ffp-contract=off): sphere tracing of an implicit field, V views of H x W rays ----
+// the state machine, the lists and the counts live in the caller's state (trace_state_bytes); `pts` takes one point per
+// listed ray (room for every ray at setup and collect, for n_active at advance); list `in` (0 / 1) is read, the other
+// one written; the sizes are the caller's to check (api.hip)
+struct TraceMarch {
+  float sdf_weight, iso, eps, step_scale, min_step, max_step;
+  int max_steps, refine;
+};
+size_t trace_state_bytes(size_t n_rays);
+hipError_t trace_setup_launch(const float* cams, int V, int H, int W, const float box[6], float t_min, void* state,
+                              float* pts, hipStream_t st);
+hipError_t trace_advance_launch(const float* cams, int V, int H, int W, const float* values, size_t n_active, int in,
+                                const TraceMarch& p, void* state, float* pts, hipStream_t st);
+hipError_t trace_collect_launch(const float* cams, int V, int H, int W, void* state, float* pts, hipStream_t st);
+hipError_t trace_shade_launch(const float* cams, int V, int H, int W, const void* state, const float* pred,
+                              const float* grad, size_t n_hits, float sdf_weight, float iso, float ambient, float* depth,
+                              float* normal, float* residual, uint8_t* status, uint8_t* rgba, hipStream_t st);
+
 // ---- voxel.hip (compiled with -ffp-contract=off): voxel IoU; n^3 bit grids of n*n rows of ceil(n/32) words ----
 size_t voxel_grid_words(int n);
 size_t voxel_surface_ws_bytes(int64_t nf);

@@ -3,6 +3,7 @@
     python -m disn_amd.demo --img VIEW.png --log_dir CKPT [--cam_est --cam_log_dir CAM_CKPT]
                             [--sdf_res 64] [--iso 0.0] [--out demo/result.obj] [--refine ITERS] [--normals]
                             [--band STRIDE --band_margin 0.5 --band_dilate 1]
+                            [--preview OUT.png [--preview_size 137]]
 
 The image is read as demo/demo.py:261-279 reads it (``cv2.imread(IMREAD_UNCHANGED)[:, :, :3] / 255``: the
 channels in B, G, R order, alpha dropped) -- through PIL, which is what this project has.  Without ``--cam_est``
@@ -11,6 +12,10 @@ matrix is ``pred_trans_mat`` of ``posenet.CameraEstimator``, restored from ``--c
 [-1,-1,-1,1,1,1] (:278), and the mesh comes from ONE ``create_sdf.reconstruct`` call.  As everywhere in this
 project a missing checkpoint is an error unless ``--random_init SEED`` asks for initialised weights (the
 reference goes on silently).
+
+``--preview OUT.png`` also writes the predicted surface as seen by the camera in use, sphere-traced from the network
+without a grid or a mesh (``SdfEngine.trace``), prints the trace's statistics and, when the input PNG has
+an alpha channel, the 2-D IoU of the predicted silhouette with it: low with a good mesh means a camera failure.
 """
 from __future__ import annotations
 
@@ -82,9 +87,41 @@ def parser() -> argparse.ArgumentParser:
     p.add_argument("--refine", type=int, default=0, metavar="ITERS",
                    help="Newton steps that move every vertex onto the network's iso level set [default: 0, none]")
     p.add_argument("--normals", action="store_true", help="write the unit SDF gradient at every vertex as 'vn' lines")
+    p.add_argument("--preview", default=None, metavar="OUT.png",
+                   help="also write the sphere-traced view of the predicted surface from the camera in use")
+    p.add_argument("--preview_size", type=int, default=137, metavar="N", help="the preview is N x N [default: 137]")
     from .create_sdf import add_band_flags
     add_band_flags(p)
     return p
+
+
+def read_alpha(path: str) -> Optional[np.ndarray]:
+    """-> [H,W] uint8 alpha channel of a PNG, None when it has none"""
+    from PIL import Image
+    with Image.open(path) as im:
+        if im.mode not in ("RGBA", "LA"):
+            return None
+        return np.asarray(im.getchannel("A"), dtype=np.uint8)
+
+
+def write_preview(engine, img: np.ndarray, trans_mat, path: str, size: int, iso: float,
+                  alpha: Optional[np.ndarray] = None) -> dict:
+    """the traced view of image 0 from its own camera -> ``path``; returns {"stats", "iou" (None without alpha)}"""
+    from . import render
+    from .create_img_h5 import _write_png
+    if size < 1:
+        raise ValueError("--preview_size must be positive")
+    out = engine.trace(engine.encode(img), 0, trans_mat, size=(size, size), sdf_params=DEMO_SDF_PARAMS[0], iso=iso)
+    rgba = out["rgba"][0].cpu().numpy()
+    _write_png(path, rgba)
+    print("preview %s: %s" % (path, out["stats"]))
+    iou = None
+    if alpha is not None:
+        rows = ((np.arange(size) + 0.5) * alpha.shape[0] / size).astype(np.int64)     # the alpha at the rays' pixels
+        cols = ((np.arange(size) + 0.5) * alpha.shape[1] / size).astype(np.int64)
+        iou = render.silhouette_iou(rgba[:, :, 3], alpha[rows][:, cols])
+        print("silhouette IoU with the input's alpha channel: %.4f" % iou)
+    return {"stats": out["stats"], "iou": iou}
 
 
 def main(argv=None) -> dict:
@@ -115,7 +152,10 @@ def main(argv=None) -> dict:
     isosurface.write_obj(a.out, verts, faces, *vn)
     print("wrote %s: %d vertices, %d triangles" % (a.out, len(verts), len(faces)))
     tm = trans_mat.cpu().numpy() if hasattr(trans_mat, "cpu") else trans_mat
-    return {"out": a.out, "verts": len(verts), "faces": len(faces), "trans_mat": tm}
+    res = {"out": a.out, "verts": len(verts), "faces": len(faces), "trans_mat": tm}
+    if a.preview:
+        res["preview"] = write_preview(engine, img, trans_mat, a.preview, a.preview_size, a.iso, read_alpha(a.img))
+    return res
 
 
 if __name__ == "__main__":

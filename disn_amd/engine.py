@@ -500,6 +500,56 @@ class SdfEngine:
         return grid, {"coarse_points": ops.band_sizes(res, stride)[0], "band_points": nband, "active_cells": ncell,
                       "total_points": (res + 1) ** 3}
 
+    # ---- direct rendering of the predicted surface: sphere tracing, no grid and no mesh ----------------
+    TRACE_CHUNK = 1 << 20     # points per disn_query_fused / disn_query_grad call of a trace
+
+    def trace(self, enc: Encoded, image_index: int, trans_mat, cams=None, size=(137, 137),
+              sdf_params=(-1.0, -1.0, -1.0, 1.0, 1.0, 1.0), iso: float = 0.0, sdf_weight: float = 10.0,
+              want=("rgba",), **march):
+        """Views of image ``image_index``'s predicted surface pred_sdf / sdf_weight == iso by sphere tracing
+        (render.trace_field with the network as the field) -> its dict: "rgba", "depth", "normal", "residual", "status"
+        as named in ``want``, and "stats".  ``cams`` [V,12]: None is the input's own camera
+        (render.sdf_ray_cameras(trans_mat), size = (W, H) rays); any other cameras give novel views -- the feature
+        projection inside the network always uses the image's ``trans_mat``.  Every iteration's values come from the
+        fused folded point kernels (query(fold=True, fused=True)'s, in chunks of TRACE_CHUNK) whatever the number of
+        active rays, so a ray's result does not depend on the other rays; pred and grad at the hits come from one
+        query_grad pass.  ``march``: render.trace_field's eps, step_scale, min_step, max_step, max_steps, refine,
+        ambient, t_min."""
+        from . import render
+        if not self.fused:
+            raise ValueError("trace runs the fused point-MLP kernels: build the engine with fused=True")
+        tm_all = self._dev(trans_mat).reshape(-1, 4, 3)
+        tm = tm_all[image_index if tm_all.shape[0] > 1 else 0].reshape(1, 4, 3).contiguous()
+        if cams is None:
+            cams = render.sdf_ray_cameras(tm.cpu().numpy(), int(size[0]), int(size[1]))
+        with torch.cuda.device(self.device):
+            pm, am = self.pmap_of(enc, image_index), self.pmap_amax_of(enc, image_index)
+            emb = enc.embedding[image_index:image_index + 1]
+            mlp = self.weights.mlp
+
+            def chunks(pts):
+                for first in range(0, pts.shape[0], self.TRACE_CHUNK):
+                    yield first, pts[first:first + self.TRACE_CHUNK].reshape(1, -1, 3)
+
+            def field(pts):
+                out = torch.empty(pts.shape[0], dtype=torch.float32, device=self.device)
+                for first, p in chunks(pts):
+                    ws = self._workspace("fused", lib().disn_query_fused_workspace_bytes(1, p.shape[1]))
+                    ops.query_fused(mlp, pm, am, emb, tm, p, p, ws, out[first:first + p.shape[1]].reshape(1, -1))
+                return out
+
+            def grad(pts):
+                pred, g = [], []
+                for _, p in chunks(pts):
+                    ws = self._workspace("grad", lib().disn_query_grad_workspace_bytes(1, p.shape[1]))
+                    s, d = ops.query_grad(mlp, pm, emb, tm, p, ws)
+                    pred.append(s.reshape(-1))
+                    g.append(d.reshape(-1, 3))
+                return (pred[0], g[0]) if len(g) == 1 else (torch.cat(pred), torch.cat(g))
+
+            return render.trace_field(field, cams, size, sdf_params, iso=iso, grad=grad, sdf_weight=sdf_weight,
+                                      want=want, device=self.device, **march)
+
 
 class StepPipeline:
     """``in_flight`` independent encode + query steps at a time on one GPU.

@@ -764,6 +764,111 @@ def grid_band_fill(grid: torch.Tensor, res: int, stride: int, cell_mask: torch.T
 
 
 # ---------------------------------------------------------------------------
+# sphere tracing of an implicit field (sdf_trace.hip)
+# ---------------------------------------------------------------------------
+TRACE_FIELDS = ("t", "t1", "len", "t_lo", "f_lo", "t_hi", "f_hi", "phase", "status", "march_evals", "bracket_evals",
+                "have_lo", "hit_slot")                        # DISN_TRACE_* of include/disn_amd.h, in order
+TRACE_FLOAT_FIELDS = TRACE_FIELDS[:7]
+TRACE_MARCH, TRACE_BRACKET, TRACE_DONE = 0, 1, 2
+
+
+def _trace_cams(cams, size):
+    W, H = int(size[0]), int(size[1])
+    if not (isinstance(cams, torch.Tensor) and cams.is_cuda and cams.dtype == torch.float32 and cams.is_contiguous()
+            and cams.dim() == 2 and cams.shape[1] == 12):
+        raise TypeError("cams must be a contiguous float32 CUDA tensor [V,12]")
+    return cams.shape[0], H, W
+
+
+def trace_state(n_rays: int, device) -> torch.Tensor:
+    """the caller-owned state of ``n_rays`` rays: an int32 tensor of disn_trace_state_bytes / 4 words"""
+    nbytes = lib().disn_trace_state_bytes(int(n_rays))
+    if nbytes == 0:
+        raise ValueError("a trace takes 1 .. 2^27 rays, got %d" % n_rays)
+    return torch.empty(nbytes // 4, dtype=torch.int32, device=device)
+
+
+def trace_state_view(state: torch.Tensor, n_rays: int) -> dict:
+    """views into a state: every field of TRACE_FIELDS [n_rays] (float32 or int32), "lists" [3, n_rays] int32 (active 0,
+    active 1, hits) and "counts" [3] int32"""
+    n4 = (int(n_rays) + 63) // 64 * 64
+    nf = len(TRACE_FIELDS)
+    rows = state[:(nf + 3) * n4].view(nf + 3, n4)[:, :n_rays]
+    out = {name: (rows[k].view(torch.float32) if name in TRACE_FLOAT_FIELDS else rows[k])
+           for k, name in enumerate(TRACE_FIELDS)}
+    out["lists"] = rows[nf:]
+    out["counts"] = state[(nf + 3) * n4:(nf + 3) * n4 + 3]
+    return out
+
+
+def trace_setup(cams: torch.Tensor, size, sdf_params, state: torch.Tensor, pts: torch.Tensor,
+                t_min: float = 0.0) -> None:
+    """disn_trace_setup: cams [V,12], size = (W, H) -> the state of V*H*W rays, active list 0, its count and its points
+    in ``pts`` [>= V*H*W, 3]"""
+    V, H, W = _trace_cams(cams, size)
+    pts = _chk(pts, "pts")
+    if pts.numel() < 3 * V * H * W:
+        raise ValueError("pts must have room for every ray's point")
+    p6 = _params6(sdf_params)
+    check("disn_trace_setup", lib().disn_trace_setup(
+        cams.data_ptr(), V, H, W, C.byref(p6), float(t_min), state.data_ptr(), state.numel() * state.element_size(),
+        pts.data_ptr(), _stream()))
+
+
+def trace_advance(cams: torch.Tensor, size, state: torch.Tensor, values: torch.Tensor, n_active: int, list_in: int,
+                  pts: torch.Tensor, iso: float = 0.0, sdf_weight: float = 1.0, eps: float = 1e-4,
+                  step_scale: float = 0.8, min_step: float = 1e-3, max_step: float = 0.1, max_steps: int = 96,
+                  refine: int = 8) -> None:
+    """disn_trace_advance: ``values`` [>= n_active] of the points of active list ``list_in`` (f = value / sdf_weight -
+    iso) -> the other list, its count and its points in ``pts`` [>= n_active, 3]"""
+    V, H, W = _trace_cams(cams, size)
+    values, pts = _chk(values, "values"), _chk(pts, "pts")
+    if values.numel() < n_active or pts.numel() < 3 * n_active:
+        raise ValueError("values and pts must hold n_active = %d entries" % n_active)
+    check("disn_trace_advance", lib().disn_trace_advance(
+        cams.data_ptr(), V, H, W, values.data_ptr(), int(n_active), int(list_in), float(sdf_weight), float(iso),
+        float(eps), float(step_scale), float(min_step), float(max_step), int(max_steps), int(refine), state.data_ptr(),
+        state.numel() * state.element_size(), pts.data_ptr(), _stream()))
+
+
+def trace_collect(cams: torch.Tensor, size, state: torch.Tensor, pts: torch.Tensor) -> None:
+    """disn_trace_collect: the hit list (list 2), its count, every ray's hit slot and the hits' points in ``pts``"""
+    V, H, W = _trace_cams(cams, size)
+    pts = _chk(pts, "pts")
+    if pts.numel() < 3 * V * H * W:
+        raise ValueError("pts must have room for every ray's point")
+    check("disn_trace_collect", lib().disn_trace_collect(
+        cams.data_ptr(), V, H, W, state.data_ptr(), state.numel() * state.element_size(), pts.data_ptr(), _stream()))
+
+
+def trace_shade(cams: torch.Tensor, size, state: torch.Tensor, pred: Optional[torch.Tensor],
+                grad: Optional[torch.Tensor], n_hits: int, iso: float = 0.0, sdf_weight: float = 1.0,
+                ambient: float = 0.3, want: Sequence[str] = ("rgba", "depth", "normal", "residual", "status")) -> dict:
+    """disn_trace_shade: pred [n_hits] (un-divided) and grad [n_hits,3] at the collected points -> the outputs named in
+    ``want``: depth [V,H,W], normal [V,H,W,3], residual [V,H,W] float32, status [V,H,W], rgba [V,H,W,4] uint8"""
+    V, H, W = _trace_cams(cams, size)
+    unknown = set(want) - {"rgba", "depth", "normal", "residual", "status"}
+    if unknown:
+        raise ValueError("unknown trace outputs %r" % (sorted(unknown),))
+    if n_hits:
+        pred, grad = _chk(pred, "pred"), _chk(grad, "grad")
+        if pred.numel() < n_hits or grad.numel() < 3 * n_hits:
+            raise ValueError("pred and grad must hold n_hits = %d entries" % n_hits)
+    dev = cams.device
+    shapes = {"rgba": ((V, H, W, 4), torch.uint8), "depth": ((V, H, W), torch.float32),
+              "normal": ((V, H, W, 3), torch.float32), "residual": ((V, H, W), torch.float32),
+              "status": ((V, H, W), torch.uint8)}
+    out = {k: torch.empty(shapes[k][0], dtype=shapes[k][1], device=dev) for k in shapes if k in want}
+    ptr = {k: (out[k].data_ptr() if k in out else None) for k in shapes}
+    check("disn_trace_shade", lib().disn_trace_shade(
+        cams.data_ptr(), V, H, W, state.data_ptr(), state.numel() * state.element_size(),
+        pred.data_ptr() if n_hits else None, grad.data_ptr() if n_hits else None, int(n_hits), float(sdf_weight),
+        float(iso), float(ambient), ptr["depth"], ptr["normal"], ptr["residual"], ptr["status"], ptr["rgba"],
+        _stream()))
+    return out
+
+
+# ---------------------------------------------------------------------------
 # training step (SURVEY 8f #3)
 # ---------------------------------------------------------------------------
 def param_layout() -> _lib.ParamLayout:

@@ -979,6 +979,72 @@ int disn_render_views(const void* bvh, int64_t nf, const int32_t* order, const f
                       int32_t* face, void* stream);
 
 /* ---------------------------------------------------------------------- *
+ * Sphere tracing of an implicit field (sdf_trace.hip): for V    *
+ * views of H x W rays (cams [V,12] as disn_render_views', one sample per   *
+ * pixel at x = j + 0.5, y = i + 0.5, in the frame of the query points),    *
+ * the first point of a ray where value / sdf_weight - iso changes sign.    *
+ * The field is the caller's: these entries keep a per-ray state machine,   *
+ * hand out the compacted list of points to evaluate and take the values    *
+ * back.  n = V*H*W <= 2^27; H, W <= 8192.                                  *
+ * state: caller-owned, disn_trace_state_bytes(n) bytes of 4-byte words;    *
+ *   field f (DISN_TRACE_*) of ray r is word f*n4 + r, n4 = n rounded up to *
+ *   a multiple of 64; three int32 lists of ray indices at fields           *
+ *   DISN_TRACE_FIELDS + l (l = 0, 1: the active lists; 2: the hits) and    *
+ *   their uint32 counts at words (DISN_TRACE_FIELDS + 3)*n4 + l.           *
+ *   phase: 0 MARCH, 1 BRACKET, 2 DONE.  status of a DONE ray: 0 miss,      *
+ *   1 hit with |f| <= eps, 2 hit at the first sample (f < 0 before any     *
+ *   f > 0: the box clips the shape or the camera is inside), 3 hit after   *
+ *   `refine` bracket evaluations (|f| > eps; see residual), 4 miss after   *
+ *   `max_steps` march evaluations.                                         *
+ *   disn_trace_setup    [t0, t1] of the box sdf_params_host (6 doubles,    *
+ *       cast to f32) clipped to t >= t_min, by a slab test in which an     *
+ *       axis with |dir| < 2^-100 is a containment test; an empty interval  *
+ *       is a miss, every other ray starts in MARCH at t0.  Writes list 0,  *
+ *       count 0 and pts [count,3] = org + t*dir (room for n points).       *
+ *   disn_trace_advance  values [n_active] of the points of list `list_in`  *
+ *       (0 / 1) -> every listed ray moves by the rules at the head of      *
+ *       sdf_trace.hip; writes the other list, its count and its points     *
+ *       (room for n_active).  1 <= n_active <= n.                          *
+ *   disn_trace_collect  list 2, count 2, the hit slot of every ray and     *
+ *       pts [count,3]: the rays of status 1..3 (room for n points).        *
+ *   disn_trace_shade    pred [n_hits] (un-divided), grad [n_hits,3] at the *
+ *       collected points -> depth [V,H,W] f32 = t, normal [V,H,W,3] f32 =  *
+ *       grad/|grad| (0 when |grad|^2 < 1e-12), residual [V,H,W] f32 =      *
+ *       |pred/sdf_weight - iso|, status [V,H,W] u8, rgba [V,H,W,4] u8      *
+ *       (4-byte aligned): disn_render_views' headlight on 0.8 grey with    *
+ *       n = grad, alpha 255; everything 0 where there is no hit.  Each     *
+ *       output may be NULL.                                                *
+ * The order of a list is unspecified; a ray's results depend neither on    *
+ * it nor on the other rays.  No host synchronisation: the caller reads a   *
+ * count back when it needs one.                                            *
+ * ---------------------------------------------------------------------- */
+#define DISN_TRACE_T 0
+#define DISN_TRACE_T1 1
+#define DISN_TRACE_LEN 2
+#define DISN_TRACE_T_LO 3
+#define DISN_TRACE_F_LO 4
+#define DISN_TRACE_T_HI 5
+#define DISN_TRACE_F_HI 6
+#define DISN_TRACE_PHASE 7
+#define DISN_TRACE_STATUS 8
+#define DISN_TRACE_MARCH_EVALS 9
+#define DISN_TRACE_BRACKET_EVALS 10
+#define DISN_TRACE_HAVE_LO 11
+#define DISN_TRACE_HIT_SLOT 12
+#define DISN_TRACE_FIELDS 13
+size_t disn_trace_state_bytes(int64_t n_rays);
+int disn_trace_setup(const float* cams, int V, int H, int W, const double* sdf_params_host, float t_min, void* state,
+                     size_t state_bytes, float* pts, void* stream);
+int disn_trace_advance(const float* cams, int V, int H, int W, const float* values, int64_t n_active, int list_in,
+                       float sdf_weight, float iso, float eps, float step_scale, float min_step, float max_step,
+                       int max_steps, int refine, void* state, size_t state_bytes, float* pts, void* stream);
+int disn_trace_collect(const float* cams, int V, int H, int W, void* state, size_t state_bytes, float* pts,
+                       void* stream);
+int disn_trace_shade(const float* cams, int V, int H, int W, const void* state, size_t state_bytes, const float* pred,
+                     const float* grad, int64_t n_hits, float sdf_weight, float iso, float ambient, float* depth,
+                     float* normal, float* residual, uint8_t* status, uint8_t* rgba, void* stream);
+
+/* ---------------------------------------------------------------------- *
  * Small-part cleanup (postprocessing/clean_smallparts.py of the reference; *
  * pymesh.separate_mesh restated).  (host) labels_host[t] = the connected   *
  * component of triangle t: connectivity 0 joins triangles that share an    *
