@@ -233,6 +233,13 @@ SIGNATURES = {
     "disn_query_folded": (I, [C.POINTER(MlpWeights), P, P, P, P, P, I, I, P, P, Z, P]),
     "disn_query_grid_folded": (I, [C.POINTER(MlpWeights), P, P, P, C.POINTER(C.c_double * 6), I, L, L, F, P,
                                    P, Z, P]),
+    "disn_gather_taps_pool": (I, [C.POINTER(C.c_void_p * 5), I, P, P, I, P, I, P, P]),
+    "disn_pool_embedding": (I, [P, I, P, I, P, P]),
+    "disn_query_views_workspace_bytes": (Z, [I]),
+    "disn_query_views": (I, [C.POINTER(MlpWeights), C.POINTER(C.c_void_p * 5), I, P, P, P, I, P, I, P, P, Z, P]),
+    "disn_query_grid_views_workspace_bytes": (Z, [I]),
+    "disn_query_grid_views": (I, [C.POINTER(MlpWeights), C.POINTER(C.c_void_p * 5), I, P, P, P, I,
+                                  C.POINTER(C.c_double * 6), I, L, L, F, P, P, Z, P]),
     "disn_query_grad_workspace_bytes": (Z, [I, L]),
     "disn_query_grad": (I, [C.POINTER(MlpWeights), P, P, P, P, I, L, P, P, P, Z, P]),
 }

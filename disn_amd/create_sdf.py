@@ -34,7 +34,11 @@ the whole group with one read-back (``isosurface.marching_cubes_batch``) and wri
   * ``--skip_existing`` drops entries whose file exists with more than 200 bytes (the size filter of
     ``evaluate.build_file_dict(min_size=200)``) before the groups are formed;
   * ``--band STRIDE`` (2, 4 or 8; default 0 = the dense grid) evaluates the network on every STRIDE-th grid point and
-    then only near the ``--iso`` surface, the rest of the grid interpolated (``SdfEngine.query_grid_band``).
+    then only near the ``--iso`` surface, the rest of the grid interpolated (``SdfEngine.query_grid_band``, DESIGN 4w);
+  * ``--fuse_views V [--fuse_pool max|mean]`` (multi-view) fuses every run of V chosen views of an object
+    into ONE mesh, the features pooled over the views (``reconstruct_fused``): view_num / V meshes per object, each
+    named after the first view of its run, in ``test_objs/[camest_]fuse<V><pool>_<res+1>_<iso>`` -- score them with
+    ``disn_amd.evaluate --view_num view_num/V``.  Not combinable with ``--band``, ``--refine`` or ``--normals``.
 """
 from __future__ import annotations
 
@@ -228,6 +232,61 @@ def reconstruct(engine, imgs, trans_mats, sdf_params, sdf_res: int, iso: float =
     return out
 
 
+def fuse_args(fuse, pool: str = "max") -> Optional[Tuple[int, str]]:
+    """``fuse`` = None / 0 (off) or the number of views fused into one mesh -> None or the checked (V, pool)
+    (ValueError; no device work): what ``reconstruct_fused`` and ``--fuse_views`` take"""
+    if not fuse:
+        return None
+    V = int(fuse)
+    if V == 1:
+        raise ValueError("--fuse_views 1 fuses nothing: use the normal path")
+    if not 2 <= V <= 24:
+        raise ValueError("--fuse_views must be in 2..24, got %d" % V)
+    if pool not in ("max", "mean"):
+        raise ValueError("--fuse_pool must be max or mean, got %r" % (pool,))
+    return V, pool
+
+
+def reconstruct_fused(engine, imgs, trans_mats, sdf_params, sdf_res: int, iso: float = 0.0, fuse: int = 2,
+                      pool: str = "max"):
+    """multi-view ``reconstruct``: the B images are B / ``fuse`` runs of ``fuse`` consecutive views of one object each
+    (cameras trans_mats [B,4,3] in the object's frame, the run's grid box = its first view's sdf_params).  One
+    ``engine.encode`` call, one ``engine.query_grid_views`` grid per run (features pooled over the run's views,
+    ``pool`` = "max" or "mean"), ONE batched meshing -> B / fuse x (verts, faces); a run's bits are those of
+    ``query_grid_views`` followed by ``isosurface.marching_cubes`` on that run alone."""
+    import torch
+
+    from . import isosurface
+    checked = fuse_args(fuse, pool)
+    if checked is None:
+        raise ValueError("reconstruct_fused needs the number of views to fuse")
+    V, pool = checked
+    imgs = np.asarray(imgs, np.float32) if not isinstance(imgs, torch.Tensor) else imgs
+    B = imgs.shape[0]
+    if B % V:
+        raise ValueError("%d images are no whole number of runs of %d views" % (B, V))
+    tm = np.asarray(trans_mats, np.float32).reshape(B, 4, 3) if not isinstance(trans_mats, torch.Tensor) \
+        else trans_mats.reshape(B, 4, 3)
+    sp = np.asarray(sdf_params, dtype=np.float64).reshape(B, 6)[::V]
+    enc = engine.encode(imgs)
+    grids = torch.empty((B // V, (sdf_res + 1) ** 3), dtype=torch.float32, device=engine.device)
+    for r in range(B // V):
+        engine.query_grid_views(enc, (r * V, V), tm[r * V:(r + 1) * V], sp[r], sdf_res, pool, out=grids[r])
+    return isosurface.marching_cubes_batch(grids, sp, sdf_res, iso)
+
+
+def fuse_runs(entries: Sequence, fuse: int) -> List[List]:
+    """the listed views in runs of ``fuse`` consecutive entries, each run the views of ONE object (ValueError
+    otherwise: ``view_num`` must be a multiple of ``fuse``)"""
+    if len(entries) % fuse:
+        raise ValueError("%d views are no whole number of runs of %d" % (len(entries), fuse))
+    runs = [list(entries[i:i + fuse]) for i in range(0, len(entries), fuse)]
+    for run in runs:
+        if any(e[:2] != run[0][:2] for e in run):
+            raise ValueError("a run of %d views spans two objects: %s" % (fuse, run))
+    return runs
+
+
 # ---- the test-set driver ---------------------------------------------------------------------------
 MIN_OBJ_BYTES = 200          # evaluate.build_file_dict(min_size=200) / test_iou.py:124
 MAX_WRITERS = 16
@@ -261,9 +320,11 @@ def groups(entries: Sequence, batch_size: int) -> List[List]:
     return [list(entries[i:i + batch_size]) for i in range(0, len(entries), batch_size)]
 
 
-def result_obj_path(log_dir: str, sdf_res: int, iso: float, cam_est: bool = False) -> str:
-    """test/create_sdf.py:88-93: <log_dir>/test_objs/[camest_]<res+1>_<str(iso)>"""
-    return os.path.join(log_dir, "test_objs", ("camest_" if cam_est else "") + str(sdf_res + 1) + "_" + str(iso))
+def result_obj_path(log_dir: str, sdf_res: int, iso: float, cam_est: bool = False, fuse=None) -> str:
+    """test/create_sdf.py:88-93: <log_dir>/test_objs/[camest_]<res+1>_<str(iso)>; ``fuse`` = (V, pool): the fused
+    meshes' own directory [camest_]fuse<V><pool>_<res+1>_<str(iso)>"""
+    prefix = ("camest_" if cam_est else "") + ("fuse%d%s_" % tuple(fuse) if fuse else "")
+    return os.path.join(log_dir, "test_objs", prefix + str(sdf_res + 1) + "_" + str(iso))
 
 
 def obj_path(out_dir: str, cat_id: str, obj: str, view: int) -> str:
@@ -311,10 +372,34 @@ def parser():
                    help="Newton steps that move every vertex onto the network's iso level set [default: 0, none]")
     p.add_argument("--normals", action="store_true", help="write the unit SDF gradient at every vertex as 'vn' lines")
     add_band_flags(p)
+    p.add_argument("--fuse_views", type=int, default=0, metavar="V",
+                   help="multi-view: fuse every run of V chosen views of an object into ONE mesh (features pooled "
+                        "over the views); view_num and batch_size must be multiples of V [default: 0, one mesh per view]")
+    p.add_argument("--fuse_pool", default="max", choices=("max", "mean"), help="how --fuse_views pools [default: max]")
     return p
 
 
-def check_flags(a) -> None:
+def fuse_from_flags(a) -> Optional[Tuple[int, str]]:
+    """None without --fuse_views, else the checked (V, pool): ValueError for V = 1, a view_num or batch_size that is
+    no multiple of V, or a combination with --band / --refine / --normals (those read ONE image's folded map)"""
+    fuse = fuse_args(a.fuse_views, a.fuse_pool)
+    if fuse is None:
+        return None
+    V = fuse[0]
+    if a.view_num % V:
+        raise ValueError("--view_num %d is no multiple of --fuse_views %d" % (a.view_num, V))
+    batch_size = a.view_num if a.batch_size is None else a.batch_size
+    if batch_size < V or batch_size % V:
+        raise ValueError("--batch_size %d is no multiple of --fuse_views %d" % (batch_size, V))
+    for flag, on in (("--band", a.band != 0), ("--refine", a.refine > 0), ("--normals", a.normals)):
+        if on:
+            raise ValueError("--fuse_views cannot be combined with %s: that path reads one image's folded feature "
+                             "map, and max pooling has none" % flag)
+    return fuse
+
+
+def check_flags(a) -> Optional[Tuple[int, str]]:
+    """every flag rule, before any list, checkpoint or device is touched -> the checked --fuse_views (V, pool) or None"""
     from . import model_normalization as model
     F = model._flags(a)
     F.img_feat_twostream = True
@@ -326,6 +411,7 @@ def check_flags(a) -> None:
     if a.refine < 0:
         raise ValueError("--refine must not be negative")
     band_from_flags(a)
+    return fuse_from_flags(a)
 
 
 def restore_weights(log_dir: str, random_init: Optional[int]):
@@ -363,12 +449,18 @@ def main(argv=None, reconstruct_fn: Optional[Callable] = None) -> dict:
     from . import isosurface
     from .evaluate import categories
     a = parser().parse_args(argv)
-    check_flags(a)
+    fuse = check_flags(a)
     batch_size = a.view_num if a.batch_size is None else a.batch_size
-    out_dir = result_obj_path(a.log_dir, a.sdf_res, a.iso, a.cam_est)
+    per_mesh = fuse[0] if fuse else 1            # views that make one mesh; a mesh is named after the first of them
+    out_dir = result_obj_path(a.log_dir, a.sdf_res, a.iso, a.cam_est, fuse)
     entries = sample_list(categories(a.category), a.test_lst_dir, a.view_num, a.seed, a.num_shards, a.shard_id)
-    todo = pending(entries, out_dir) if a.skip_existing else entries
-    work = groups(todo, batch_size)
+    if fuse:
+        runs = fuse_runs(entries, per_mesh)
+        heads = set(pending([r[0] for r in runs], out_dir)) if a.skip_existing else None
+        todo = [e for r in runs if heads is None or r[0] in heads for e in r]
+    else:
+        todo = pending(entries, out_dir) if a.skip_existing else entries
+    work = groups(todo, batch_size)              # (batch_size is a multiple of per_mesh: a group holds whole runs)
     note = "device work replaced by the caller"
     if reconstruct_fn is None and work:
         store, note = restore_weights(a.log_dir, a.random_init)       # before any device work
@@ -381,6 +473,8 @@ def main(argv=None, reconstruct_fn: Optional[Callable] = None) -> dict:
         band = band_from_flags(a)
 
         def reconstruct_fn(imgs, trans_mats, sdf_params):
+            if fuse:
+                return reconstruct_fused(engine, imgs, trans_mats, sdf_params, a.sdf_res, a.iso, fuse[0], fuse[1])
             if band is None:
                 return reconstruct(engine, imgs, trans_mats, sdf_params, a.sdf_res, a.iso, a.refine, a.normals)
             return reconstruct(engine, imgs, trans_mats, sdf_params, a.sdf_res, a.iso, a.refine, a.normals, band=band)
@@ -412,12 +506,12 @@ def main(argv=None, reconstruct_fn: Optional[Callable] = None) -> dict:
                 batch = nxt.result()
                 nxt = fetch(work[gi + 1]) if gi + 1 < len(work) else None
                 meshes = reconstruct_fn(batch["img"], batch["trans_mat"], batch["sdf_params"])
-                if len(meshes) != len(group):
+                if len(meshes) * per_mesh != len(group):
                     raise RuntimeError("group %d: %d meshes for %d views" % (gi, len(meshes), len(group)))
                 for f in in_flight:                         # the group before this one: a writer's exception surfaces
                     f.result()
                 in_flight = []
-                for (cat_id, obj, view), (verts, faces, *vn) in zip(group, meshes):
+                for (cat_id, obj, view), (verts, faces, *vn) in zip(group[::per_mesh], meshes):
                     path = obj_path(out_dir, cat_id, obj, view)
                     if len(verts) == 0 or len(faces) == 0:
                         empty += 1

@@ -1619,6 +1619,103 @@ int disn_query_grid(const disn_mlp_weights_t* w, const float* featmap, const flo
                          ws_bytes, (hipStream_t)stream);
 }
 
+// ---- multi-view: pooled features (include/disn_amd.h) -----------------------------------------------------------------
+static int pool_status(int V, int pool) {
+  return (V < 1 || V > DISN_MAX_VIEWS || (pool != DISN_POOL_MAX && pool != DISN_POOL_MEAN)) ? DISN_E_SHAPE : 0;
+}
+
+int disn_gather_taps_pool(const float* const taps[5], int V, const float* trans_mat, const float* weights, int pool,
+                          const float* pts, int N, float* feat, void* stream) {
+  if (!taps_ok(taps) || !trans_mat || !pts || !feat || N <= 0) return DISN_E_ARG;
+  DISN_RC(pool_status(V, pool));
+  DISN_TRY(gather_taps_pool_launch(taps, V, trans_mat, weights, pool == DISN_POOL_MEAN, pts, N, feat,
+                                   (hipStream_t)stream));
+  return 0;
+}
+
+int disn_pool_embedding(const float* emb, int V, const float* weights, int pool, float* out, void* stream) {
+  if (!emb || !out) return DISN_E_ARG;
+  DISN_RC(pool_status(V, pool));
+  DISN_TRY(pool_rows_launch(emb, V, DISN_EMBED_DIM, weights, pool == DISN_POOL_MEAN, out, (hipStream_t)stream));
+  return 0;
+}
+
+size_t disn_query_views_workspace_bytes(int N) {
+  if (N <= 0) return 0;
+  return query_layout(nullptr, 1, chunk_for(N), true, false).total;
+}
+
+int disn_query_views(const disn_mlp_weights_t* w, const float* const taps[5], int V, const float* embedding_pooled,
+                     const float* trans_mat, const float* weights, int pool, const float* pts, int N, float* sdf,
+                     void* ws, size_t ws_bytes, void* stream) {
+  if (!mlp_weights_ok(w) || !taps_ok(taps) || !embedding_pooled || !trans_mat || !pts || !sdf || !ws || N <= 0)
+    return DISN_E_ARG;
+  DISN_RC(pool_status(V, pool));
+  hipStream_t st = (hipStream_t)stream;
+  const int chunk = chunk_for(N);
+  const QueryWs q = query_layout(ws, 1, chunk, true, false);
+  if (q.total > ws_bytes) return DISN_E_WS;
+  DISN_RC(gbias_layer(w, embedding_pooled, 1, q.gbias, q.gemv_ws, st));
+  for (int n0 = 0; n0 < N; n0 += chunk) {
+    const int n = (N - n0) < chunk ? (N - n0) : chunk;
+    const float* p = pts + (size_t)n0 * 3;
+    DISN_TRY(gather_taps_pool_launch(taps, V, trans_mat, weights, pool == DISN_POOL_MEAN, p, n, q.feat, st));
+    DISN_RC(mlp_chunk(w, p, n, q.gbias, q.feat, sdf + n0, nullptr, nullptr, 1.0f, q.mlp, st));
+  }
+  return 0;
+}
+
+// The grid is cut into chunks at FIXED grid indices (multiples of the chunk size counted from point 0), and a range
+// evaluates every chunk it touches WHOLE: the layers of a chunk scale activations by the maxima over its rows and plan
+// their GEMMs by its row count, so only a chunk of the same points gives the same bits.  Any range k0..k1 is then bit for
+// bit that slice of the whole grid; a range pays for at most one chunk of points it does not return at either end.
+struct GridViewsWs { QueryWs q; float* part; size_t total; int chunk; };
+static GridViewsWs grid_views_layout(void* ws, int R) {
+  GridViewsWs v;
+  const int64_t res = (int64_t)R + 1;
+  v.chunk = chunk_for((long)(res * res * res));
+  v.q = query_layout(ws, 1, v.chunk, true, true);
+  v.part = ws ? reinterpret_cast<float*>(static_cast<char*>(ws) + v.q.total) : nullptr;   // a partly wanted chunk's values
+  v.total = v.q.total + (((size_t)v.chunk * sizeof(float) + 255) & ~size_t(255));
+  return v;
+}
+
+size_t disn_query_grid_views_workspace_bytes(int R) {
+  if (R < 1 || R > 1290) return 0;
+  return grid_views_layout(nullptr, R).total;
+}
+
+int disn_query_grid_views(const disn_mlp_weights_t* w, const float* const taps[5], int V, const float* embedding_pooled,
+                          const float* trans_mat, const float* weights, int pool, const double* sdf_params_host, int R,
+                          int64_t k0, int64_t k1, float sdf_weight, float* out, void* ws, size_t ws_bytes,
+                          void* stream) {
+  GridSpec g;
+  if (!mlp_weights_ok(w) || !taps_ok(taps) || !embedding_pooled || !trans_mat || !out || !ws ||
+      !grid_range(sdf_params_host, R, k0, k1, &g) || sdf_weight == 0.0f)
+    return DISN_E_ARG;
+  if (R > 1290) return DISN_E_SHAPE;
+  DISN_RC(pool_status(V, pool));
+  hipStream_t st = (hipStream_t)stream;
+  const GridViewsWs v = grid_views_layout(ws, R);
+  if (v.total > ws_bytes) return DISN_E_WS;
+  const QueryWs& q = v.q;
+  const int64_t total = (int64_t)g.res * g.res * g.res;
+  DISN_RC(gbias_layer(w, embedding_pooled, 1, q.gbias, q.gemv_ws, st));
+  for (int64_t kc = k0 / v.chunk * v.chunk; kc < k1; kc += v.chunk) {
+    const int n = (int)((total - kc) < v.chunk ? (total - kc) : v.chunk);
+    const int64_t lo = kc > k0 ? kc : k0, hi = (kc + n) < k1 ? (kc + n) : k1;
+    const bool whole = lo == kc && hi == kc + n;
+    DISN_TRY(grid_points_launch(g, kc, kc + n, q.pts, st));
+    DISN_TRY(gather_taps_pool_launch(taps, V, trans_mat, weights, pool == DISN_POOL_MEAN, q.pts, n, q.feat, st));
+    DISN_RC(mlp_chunk(w, q.pts, n, q.gbias, q.feat, whole ? out + (kc - k0) : v.part, nullptr, nullptr, sdf_weight, q.mlp,
+                      st));
+    if (!whole)
+      DISN_TRY(hipMemcpyAsync(out + (lo - k0), v.part + (lo - kc), (size_t)(hi - lo) * sizeof(float),
+                              hipMemcpyDeviceToDevice, st));
+  }
+  return 0;
+}
+
 // Same result as disn_query_grid, chunk-pipelined over two streams: the HBM-bound front of chunk
 // i+1 (grid points, projection, gather: ~0.3 ms per 65536 points) runs on ctx->aux into the other
 // half of a double buffer while the MFMA-bound MLP of chunk i (~2 ms) runs on `stream`.

@@ -486,6 +486,24 @@ struct PointGeom {
   bool ok, ff, cc, fc, cf;
   int ify, icy, ifx, icx;
 };
+// sample4's range test, corners, weights and validity for the projected pixel (x, y).  A NaN projection (degenerate
+// camera) fails `ok`: zeros, as sample4; the int conversions are then unused.
+__device__ __forceinline__ PointGeom point_geom(float x, float y) {
+  PointGeom pg;
+  pg.ok = x > -1.0f && y > -1.0f && x < (float)DISN_IMG && y < (float)DISN_IMG;
+  const float fx = floorf(x), fy = floorf(y);
+  const float cx = fx + 1.0f, cy = fy + 1.0f;
+  const float dx = cx - x, dy = cy - y;
+  pg.ifx = (int)fx; pg.ify = (int)fy; pg.icx = (int)cx; pg.icy = (int)cy;
+  pg.w_ff = dx * dy;
+  pg.w_cc = (1.0f - dx) * (1.0f - dy);
+  pg.w_fc = dx * (1.0f - dy);
+  pg.w_cf = (1.0f - dx) * dy;
+  const bool xf = pg.ifx >= 0 && pg.ifx < DISN_IMG, xc = pg.icx >= 0 && pg.icx < DISN_IMG;
+  const bool yf = pg.ify >= 0 && pg.ify < DISN_IMG, yc = pg.icy >= 0 && pg.icy < DISN_IMG;
+  pg.ff = xf && yf; pg.cc = xc && yc; pg.fc = xf && yc; pg.cf = xc && yf;
+  return pg;
+}
 
 // the four up-sampled map pixels of this lane's 4 channels, then the resampler's sum.  RC / CC: how the tap rows (columns)
 // of the map's second row icy (column icx) relate to those of the first -- 0: the same two (case a), 1: they start at the
@@ -608,22 +626,7 @@ __global__ __launch_bounds__(256) void project_gather_taps_wave_kernel(TapSet t,
     }
     float x, y;
     project_point(trans_mat + (size_t)b * 12, pts[pt * 3], pts[pt * 3 + 1], pts[pt * 3 + 2], x, y);
-    PointGeom pg;
-    pg.ok = x > -1.0f && y > -1.0f && x < (float)DISN_IMG && y < (float)DISN_IMG;
-    {
-      const float fx = floorf(x), fy = floorf(y);
-      const float cx = fx + 1.0f, cy = fy + 1.0f;
-      const float dx = cx - x, dy = cy - y;
-      pg.ifx = (int)fx; pg.ify = (int)fy; pg.icx = (int)cx; pg.icy = (int)cy;
-      pg.w_ff = dx * dy;
-      pg.w_cc = (1.0f - dx) * (1.0f - dy);
-      pg.w_fc = dx * (1.0f - dy);
-      pg.w_cf = (1.0f - dx) * dy;
-      const bool xf = pg.ifx >= 0 && pg.ifx < DISN_IMG, xc = pg.icx >= 0 && pg.icx < DISN_IMG;
-      const bool yf = pg.ify >= 0 && pg.ify < DISN_IMG, yc = pg.icy >= 0 && pg.icy < DISN_IMG;
-      pg.ff = xf && yf; pg.cc = xc && yc; pg.fc = xf && yc; pg.cf = xc && yf;
-    }
-    // a NaN projection (degenerate camera) fails `ok`: zeros, as sample4.  The int conversions above are then unused.
+    const PointGeom pg = point_geom(x, y);
     const bool okw = __builtin_amdgcn_readfirstlane((int)pg.ok) != 0;
     // ---- taps 4, 3 (two passes each), tap 2: wave-uniform geometry
 #pragma unroll 1
@@ -709,12 +712,7 @@ int project_gather_taps_amax_blocks(int n, int feat_ld, int tap_begin, int tap_e
   return (int)(g < 1 ? 1 : (g > cap ? cap : g));
 }
 
-hipError_t project_gather_taps_launch(const float* const taps[5], const float* trans_mat,
-                                      const float* pts, int B, int n, int tap_begin, int tap_end,
-                                      float* feat, hipStream_t st, int feat_ld, float* amax,
-                                      size_t amax_stride, int amax_cap, const float* split_amax,
-                                      const float* const* tap_slots, size_t slot_stride) {
-  static const int c4_off[6] = {0, 16, 48, 112, 240, DISN_FEAT4};
+static TapSet tap_set(const float* const taps[5]) {
   static const int ch[5] = {64, 128, 256, 512, 512};
   TapSet t;
   for (int k = 0; k < 5; ++k) {
@@ -722,6 +720,16 @@ hipError_t project_gather_taps_launch(const float* const taps[5], const float* t
     t.s[k] = (float)(224 >> k) / (float)DISN_IMG;
     t.stride[k] = (size_t)(224 >> k) * (224 >> k) * ch[k];
   }
+  return t;
+}
+
+hipError_t project_gather_taps_launch(const float* const taps[5], const float* trans_mat,
+                                      const float* pts, int B, int n, int tap_begin, int tap_end,
+                                      float* feat, hipStream_t st, int feat_ld, float* amax,
+                                      size_t amax_stride, int amax_cap, const float* split_amax,
+                                      const float* const* tap_slots, size_t slot_stride) {
+  static const int c4_off[6] = {0, 16, 48, 112, 240, DISN_FEAT4};
+  const TapSet t = tap_set(taps);
   if (feat_ld <= 0) feat_ld = DISN_FEAT;
   // all five taps into rows of 1472 .. 1536 floats, from 10 240 points on: one wave per point (round 6; the SAME BITS, so
   // the choice is free).  Its six passes per point are six dependent memory round trips: below ~5 x 2048 points, where
@@ -759,6 +767,158 @@ hipError_t project_gather_taps_launch(const float* const taps[5], const float* t
   }
   hipLaunchKernelGGL(project_gather_taps_kernel, dim3(grid_for(total, 16384)), dim3(256), 0, st, t,
                      trans_mat, pts, B, n, c4_begin, c4_count, feat, feat_ld, amax, amax_stride, split_amax);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// Multi-view: the rows of project_gather_taps_wave_kernel for V views of ONE object, pooled over the views before they
+// are written.  View v's taps lie at t.p[k] + v * t.stride[k], its camera at trans_mat + 12 v; per view the value is that
+// kernel's, expression by expression (project_point, point_geom, tap_geom, tap_resample*), a view whose projection fails
+// the resampler's range test (NaN included) contributing zeros.  Then, in view order and never fused (-ffp-contract=off),
+//     max :  p = f_0;        p = fmaxf(p, f_v)
+//     mean:  p = w_0 * f_0;  p = p + w_v * f_v          (w_v = weights[v], or 1 / V rounded to fp32 without weights)
+// One wave per point, a lane owning 4 channels as there.  Lane v < V projects the point into view v once per point; the
+// passes read a view's geometry from its lane (v_readlane: wave-uniform again, the branches scalar).  Views are the INNER
+// loop of a pass, so the running pool is one float4 per lane and a row is written once: n * 5888 bytes out whatever V is,
+// V * ~36 KB requested per point.  A pass is V dependent memory round trips: at a few hundred points the kernel is
+// latency-bound like its single-view parent; one form for every n.
+// Units: taps and rows are in the engine's equalised units (channel c times a POSITIVE power of two s_c, the same for
+// every view).  max(s a, s b) = s max(a, b) for s > 0 and w (s a) = s (w a), s a + s b = s (a + b) exactly for a power of
+// two (no over- or underflow at these magnitudes), so both pools commute with the factors: the pooled row is the pooled
+// true feature times s_c, what the equalised MLP weights expect.  The kernel relies on it and never converts.
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ int lane_value(int v, int l) { return __builtin_amdgcn_readlane(v, l); }
+__device__ __forceinline__ float lane_value(float v, int l) {
+  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l));
+}
+
+template <bool MEAN>
+__device__ __forceinline__ void pool_step(float4& p, const float4& f, bool first, float w) {
+  if (MEAN) {
+    if (first) { p.x = w * f.x; p.y = w * f.y; p.z = w * f.z; p.w = w * f.w; }
+    else { p.x = p.x + w * f.x; p.y = p.y + w * f.y; p.z = p.z + w * f.z; p.w = p.w + w * f.w; }
+  } else {
+    if (first) p = f;
+    else { p.x = fmaxf(p.x, f.x); p.y = fmaxf(p.y, f.y); p.z = fmaxf(p.z, f.z); p.w = fmaxf(p.w, f.w); }
+  }
+}
+
+template <bool MEAN>
+__global__ __launch_bounds__(256) void gather_taps_pool_kernel(TapSet t, int V, const float* __restrict__ trans_mat,
+                                                               const float* __restrict__ weights, float w_default,
+                                                               const float* __restrict__ pts, int n,
+                                                               float* __restrict__ feat) {
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), nw = blockDim.x >> 6;
+  const int lv = lane < V ? lane : 0;   // (lanes V .. 63 repeat view 0; nobody reads them)
+  const float w_mine = MEAN ? (weights ? weights[lv] : w_default) : 0.f;
+  for (size_t pt = (size_t)blockIdx.x * nw + wave; pt < (size_t)n; pt += (size_t)gridDim.x * nw) {
+    float x, y;
+    project_point(trans_mat + (size_t)lv * 12, pts[pt * 3], pts[pt * 3 + 1], pts[pt * 3 + 2], x, y);
+    const PointGeom mine = point_geom(x, y);
+    const int mine_flags = (int)mine.ok | (int)mine.ff << 1 | (int)mine.cc << 2 | (int)mine.fc << 3 | (int)mine.cf << 4;
+    auto view_geom = [&](int v) __attribute__((always_inline)) {
+      PointGeom pg;
+      const int fl = lane_value(mine_flags, v);
+      pg.ok = fl & 1; pg.ff = fl & 2; pg.cc = fl & 4; pg.fc = fl & 8; pg.cf = fl & 16;
+      pg.w_ff = lane_value(mine.w_ff, v); pg.w_cc = lane_value(mine.w_cc, v);
+      pg.w_fc = lane_value(mine.w_fc, v); pg.w_cf = lane_value(mine.w_cf, v);
+      pg.ify = lane_value(mine.ify, v); pg.icy = lane_value(mine.icy, v);
+      pg.ifx = lane_value(mine.ifx, v); pg.icx = lane_value(mine.icx, v);
+      return pg;
+    };
+    float* row = feat + pt * DISN_FEAT;
+    // ---- taps 4, 3 (two passes each), tap 2: wave-uniform geometry.  The two halves of taps 4 and 3 are passes of their
+    // own, so a view's geometry (13 readlanes, tap_geom, 8 readfirstlanes) is derived twice for them: a few dozen scalar /
+    // VALU operations per view next to a pass's loads, against a second float4 of running pool and a second call site of
+    // the nine resample bodies if the halves shared one view loop
+#pragma unroll 1
+    for (int pass = 0; pass < 5; ++pass) {
+      const int k = 4 - (pass >> 1), half = pass & 1;
+      const int hw = 224 >> k, ch = k == 2 ? 256 : 512, coff0 = k == 2 ? 192 : (k == 3 ? 448 : 960);
+      const int cl = 4 * lane + 256 * half;
+      float4 p = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll 1
+      for (int v = 0; v < V; ++v) {
+        const PointGeom pg = view_geom(v);
+        float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (pg.ok) {
+          TapGeom g = tap_geom(hw, ch, t.s[k], pg.ify, pg.icy, pg.ifx, pg.icx);
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            g.roff[i] = __builtin_amdgcn_readfirstlane(g.roff[i]);
+            g.coff[i] = __builtin_amdgcn_readfirstlane(g.coff[i]);
+          }
+          o = tap_resample_uniform(t.p[k] + (size_t)v * t.stride[k] + cl, g, pg);
+        }
+        pool_step<MEAN>(p, o, v == 0, MEAN ? lane_value(w_mine, v) : 0.f);
+      }
+      *reinterpret_cast<float4*>(row + coff0 + cl) = p;
+    }
+    // ---- tap 1 (lanes 0..31), tap 0 (32..47): per-lane geometry, no skipping; lanes 48..63 idle (rows of 1472 floats)
+    {
+      const bool is1 = lane < 32, is0 = lane >= 32 && lane < 48;
+      const int cl = is1 ? 4 * lane : 4 * (lane - 32);
+      float4 p = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll 1
+      for (int v = 0; v < V; ++v) {
+        const PointGeom pg = view_geom(v);
+        float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (pg.ok && (is1 || is0)) {
+          const TapGeom g1 = tap_geom(112, 128, t.s[1], pg.ify, pg.icy, pg.ifx, pg.icx);
+          const TapGeom g0 = tap_geom(224, 64, t.s[0], pg.ify, pg.icy, pg.ifx, pg.icx);
+          TapGeom g;
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            g.roff[i] = is1 ? g1.roff[i] : g0.roff[i];
+            g.coff[i] = is1 ? g1.coff[i] : g0.coff[i];
+          }
+#pragma unroll
+          for (int i = 0; i < 2; ++i) {
+            g.xl[i] = is1 ? g1.xl[i] : g0.xl[i];
+            g.yl[i] = is1 ? g1.yl[i] : g0.yl[i];
+          }
+          const float* tap = (is1 ? t.p[1] + (size_t)v * t.stride[1] : t.p[0] + (size_t)v * t.stride[0]) + cl;
+          o = tap_resample<2, 2>(tap, g, pg);
+        }
+        pool_step<MEAN>(p, o, v == 0, MEAN ? lane_value(w_mine, v) : 0.f);
+      }
+      if (is1 || is0) *reinterpret_cast<float4*>(row + (is1 ? 64 + cl : cl)) = p;
+    }
+  }
+}
+
+hipError_t gather_taps_pool_launch(const float* const taps[5], int V, const float* trans_mat, const float* weights,
+                                   bool mean, const float* pts, int n, float* feat, hipStream_t st) {
+  const TapSet t = tap_set(taps);
+  const unsigned grid = (unsigned)(((size_t)n + 3) / 4 < 32768 ? ((size_t)n + 3) / 4 : 32768);
+  const float w_default = 1.0f / (float)V;
+  if (mean) hipLaunchKernelGGL(gather_taps_pool_kernel<true>, dim3(grid), dim3(256), 0, st, t, V, trans_mat, weights, w_default, pts, n, feat);
+  else hipLaunchKernelGGL(gather_taps_pool_kernel<false>, dim3(grid), dim3(256), 0, st, t, V, trans_mat, weights, w_default, pts, n, feat);
+  return hipGetLastError();
+}
+
+// the same two rules over the rows of x [V][C] -> out [C] (the views' embeddings: signed, so max is the plain maximum)
+template <bool MEAN>
+__global__ __launch_bounds__(256) void pool_rows_kernel(const float* __restrict__ x, int V, int C,
+                                                        const float* __restrict__ weights, float w_default,
+                                                        float* __restrict__ out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= C) return;
+  float p = x[i];
+  if (MEAN) p = (weights ? weights[0] : w_default) * p;
+  for (int v = 1; v < V; ++v) {
+    const float f = x[(size_t)v * C + i];
+    if (MEAN) p = p + (weights ? weights[v] : w_default) * f;
+    else p = fmaxf(p, f);
+  }
+  out[i] = p;
+}
+
+hipError_t pool_rows_launch(const float* x, int V, int C, const float* weights, bool mean, float* out, hipStream_t st) {
+  const float w_default = 1.0f / (float)V;
+  if (mean) hipLaunchKernelGGL(pool_rows_kernel<true>, dim3((C + 255) / 256), dim3(256), 0, st, x, V, C, weights, w_default, out);
+  else hipLaunchKernelGGL(pool_rows_kernel<false>, dim3((C + 255) / 256), dim3(256), 0, st, x, V, C, weights, w_default, out);
   return hipGetLastError();
 }
 

@@ -152,6 +152,13 @@ bool project_gather_taps_takes_slots(int B, int n, int feat_ld);   // whether th
 // image's power-of-two scale, [h8 | l8] per 8 channels) -- the operand of mlp_fused_small_launch(local)
 // amax != nullptr (all five taps): max |feat| per workgroup at amax[b * amax_stride + (0 .. blocks - 1)]
 int project_gather_taps_amax_blocks(int n, int feat_ld, int tap_begin = 0, int tap_end = 5);  // feat_ld > 1472: zero-padded rows
+// multi-view: the rows of project_gather_taps_launch for V views (1 .. 24) of ONE object -- view v's tap k at
+// taps[k] + v * (floats of one image of tap k), its camera at trans_mat + 12 v -- pooled over the views in view order:
+// max (p = f_0; p = fmaxf(p, f_v)) or mean (p = w_0 f_0; p = p + w_v f_v, never fused; weights == nullptr: every
+// w_v = 1 / V) -> feat [n][1472].  pool_rows_launch: the same rules over the rows of x [V][C] -> out [C].
+hipError_t gather_taps_pool_launch(const float* const taps[5], int V, const float* trans_mat, const float* weights,
+                                   bool mean, const float* pts, int n, float* feat, hipStream_t st);
+hipError_t pool_rows_launch(const float* x, int V, int C, const float* weights, bool mean, float* out, hipStream_t st);
 // folded local fold2/conv1 (disn_fold_local): h = relu(pre + resample(pmap_b)(pts) + bias), [n,512]
 hipError_t gather_fold_launch(const float* pmap_b, const float* trans_mat_b, const float* pts, int n,
                               const float* pre, const float* bias, float* h, hipStream_t st);

@@ -431,6 +431,50 @@ class SdfEngine:
             return ops.query_grid(self.weights.mlp, self.featmap_of(enc)[image_index], enc.embedding[image_index:image_index + 1],
                                   tm.contiguous(), sdf_params, res, k0, k1, sdf_weight, ws, out, ctx)
 
+    # ---- multi-view: one object from V views, features pooled over the views ---------------------------
+    def _views(self, enc: Encoded, views, trans_mat, pool: str, weights):
+        """(taps of the range, pooled embedding [1,1024], trans_mat [V,4,3], weights [V] or None) of the images
+        ``views`` = (v0, V) of ``enc``; ValueError before any device work for a bad range, pool or weight count.
+        The embedding is pooled here, on every call (a [1,1024] tensor, one launch): nothing is cached per range."""
+        v0, V = int(views[0]), int(views[1])
+        ops.pool_check(pool, V, weights)
+        if v0 < 0 or v0 + V > enc.embedding.shape[0]:
+            raise ValueError("views (%d, %d) of %d encoded images" % (v0, V, enc.embedding.shape[0]))
+        tm = self._dev(trans_mat).reshape(-1, 4, 3)
+        if tm.shape[0] != V:
+            raise ValueError("trans_mat holds %d cameras for %d views" % (tm.shape[0], V))
+        w = None if weights is None else self._dev(weights).reshape(V)
+        taps = [t[v0:v0 + V] for t in enc.taps]        # contiguous slices: view v at tap + v * stride
+        emb = ops.pool_embedding(enc.embedding[v0:v0 + V], pool, w)
+        return taps, emb, tm, w
+
+    def query_views(self, enc: Encoded, views, trans_mat, pts, pool: str = "max", weights=None) -> torch.Tensor:
+        """pts [N,3] in the object's frame -> pred_sdf [N] (un-divided) of ONE object seen in the images ``views`` =
+        (v0, V) of ``enc`` with the cameras trans_mat [V,4,3]: the per-point local feature and the embedding are
+        pooled over the views (``pool``: "max", or "mean" with ``weights`` [V], default 1/V each -- weights
+        (1-t, t) over two objects' views interpolate their shapes), then the two decoder streams run as in
+        query(fold=False).  Max pooling is not linear, so there is no folded form."""
+        pts = self._dev(pts).reshape(-1, 3)
+        with torch.cuda.device(self.device):
+            taps, emb, tm, w = self._views(enc, views, trans_mat, pool, weights)
+            ws = self._workspace("query", lib().disn_query_views_workspace_bytes(pts.shape[0]))
+            return ops.query_views(self.weights.mlp, taps, emb, tm, pts, pool, w, ws)
+
+    def query_grid_views(self, enc: Encoded, views, trans_mat, sdf_params, res: int, pool: str = "max", weights=None,
+                         k0: int = 0, k1: Optional[int] = None, sdf_weight: float = 10.0,
+                         out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """query_views on the grid points k0..k1-1 of query_grid (generated on the device), / sdf_weight
+        -> [(res+1)^3] for the whole grid.  Any range is bit for bit that slice of the whole grid: the chunks of 65536
+        points sit at fixed grid indices and a range evaluates the ones it touches whole (up to one chunk of extra
+        points at either end).  Every call pools the views' embeddings again (one short launch): a caller that walks a
+        grid in many small ranges pays it each time."""
+        k1 = (res + 1) ** 3 if k1 is None else k1
+        with torch.cuda.device(self.device):
+            taps, emb, tm, w = self._views(enc, views, trans_mat, pool, weights)
+            ws = self._workspace("grid", lib().disn_query_grid_views_workspace_bytes(res))
+            return ops.query_grid_views(self.weights.mlp, taps, emb, tm, sdf_params, res, k0, k1, pool, w, sdf_weight,
+                                        ws, out)
+
     # ---- narrow-band grid (DESIGN 4w): coarse lattice, selection, band points, fill ------------------------------
     BAND_CHUNK = 1 << 21      # listed points per disn_query_grid_listed call (40 MB of workspace)
 

@@ -676,6 +676,102 @@ def query_grid(w: MlpWeights, featmap: torch.Tensor, embedding: torch.Tensor, tr
 
 
 # ---------------------------------------------------------------------------
+# multi-view: features pooled over V views of one object
+# ---------------------------------------------------------------------------
+POOLS = {"max": 0, "mean": 1}      # DISN_POOL_MAX, DISN_POOL_MEAN
+MAX_VIEWS = 24                     # DISN_MAX_VIEWS
+
+
+def pool_check(pool: str, views: int, weights=None) -> int:
+    """the DISN_POOL_* value of ``pool``; ValueError for an unknown pool, a view count outside 1..24 or weights that
+    are not one per view (host arithmetic, no device work)"""
+    if pool not in POOLS:
+        raise ValueError("pool must be one of %s, got %r" % (sorted(POOLS), pool))
+    if not 1 <= int(views) <= MAX_VIEWS:
+        raise ValueError("1..%d views can be pooled, got %d" % (MAX_VIEWS, views))
+    if weights is not None and len(weights) != views:
+        raise ValueError("%d weights for %d views" % (len(weights), views))
+    return POOLS[pool]
+
+
+def _view_args(taps: Sequence[torch.Tensor], trans_mat: torch.Tensor, pool: str, weights: Optional[torch.Tensor]):
+    """shared prologue of the pooled wrappers -> (tap pointers, V, trans_mat, weights pointer or None, pool value).
+    taps: five [V,hw,hw,ch] tensors (a slice ``enc.taps[k][v0:v0+V]`` is contiguous); weights [V]: only mean reads
+    them, None = 1/V each"""
+    trans_mat = _chk(trans_mat, "trans_mat")
+    V = trans_mat.numel() // 12
+    code = pool_check(pool, V, weights)
+    for t, (hw, ch) in zip(taps, TAP_SHAPES):
+        if tuple(t.shape) != (V, hw, hw, ch):
+            raise ValueError("tap of shape %s for %d views of [%d,%d,%d]" % (tuple(t.shape), V, hw, hw, ch))
+    wp = None if weights is None else _chk(weights, "weights")
+    return _tap_ptrs(taps), V, trans_mat, wp, code
+
+
+def gather_taps_pool(taps: Sequence[torch.Tensor], trans_mat: torch.Tensor, pts: torch.Tensor, pool: str = "max",
+                     weights: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """disn_gather_taps_pool: the taps of V views of one object [V,...], trans_mat [V,4,3], pts [N,3] -> the rows of
+    gather_taps view by view, pooled over the views in view order -> feat [N,1472] (``out``: its first N rows)"""
+    pts = _chk(pts, "pts")
+    N = pts.shape[0]
+    arr, V, trans_mat, wp, code = _view_args(taps, trans_mat, pool, weights)
+    if out is None:
+        out = torch.empty((N, FEAT_DIM), dtype=torch.float32, device=pts.device)
+    check("disn_gather_taps_pool", lib().disn_gather_taps_pool(
+        C.byref(arr), V, trans_mat.data_ptr(), wp.data_ptr() if wp is not None else None, code, pts.data_ptr(), N,
+        _chk(out, "out").data_ptr(), _stream()))
+    return out
+
+
+def pool_embedding(embedding: torch.Tensor, pool: str = "max", weights: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """disn_pool_embedding: [V,1024] -> [1,1024] by gather_taps_pool's rules"""
+    embedding = _chk(embedding, "embedding")
+    V = embedding.shape[0]
+    code = pool_check(pool, V, weights)
+    wp = None if weights is None else _chk(weights, "weights")
+    out = torch.empty((1, embedding.shape[1]), dtype=torch.float32, device=embedding.device)
+    check("disn_pool_embedding", lib().disn_pool_embedding(
+        embedding.data_ptr(), V, wp.data_ptr() if wp is not None else None, code, out.data_ptr(), _stream()))
+    return out
+
+
+def query_views(w: MlpWeights, taps: Sequence[torch.Tensor], embedding_pooled: torch.Tensor, trans_mat: torch.Tensor,
+                pts: torch.Tensor, pool: str = "max", weights: Optional[torch.Tensor] = None,
+                ws: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """disn_query_views: pts [N,3] -> pred_sdf [N] (un-divided) of the two decoder streams on the pooled features"""
+    pts = _chk(pts, "pts")
+    N = pts.shape[0]
+    arr, V, trans_mat, wp, code = _view_args(taps, trans_mat, pool, weights)
+    if out is None:
+        out = torch.empty((N,), dtype=torch.float32, device=pts.device)
+    ws = _fit_ws(ws, lib().disn_query_views_workspace_bytes(N), pts.device)
+    check("disn_query_views", lib().disn_query_views(
+        C.byref(w), C.byref(arr), V, _chk(embedding_pooled, "embedding").data_ptr(), trans_mat.data_ptr(),
+        wp.data_ptr() if wp is not None else None, code, pts.data_ptr(), N, out.data_ptr(), ws.data_ptr(), ws.numel(),
+        _stream()))
+    return out
+
+
+def query_grid_views(w: MlpWeights, taps: Sequence[torch.Tensor], embedding_pooled: torch.Tensor,
+                     trans_mat: torch.Tensor, sdf_params, res: int, k0: int, k1: int, pool: str = "max",
+                     weights: Optional[torch.Tensor] = None, sdf_weight: float = 10.0,
+                     ws: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """disn_query_grid_views: query_grid's points k0..k1-1 on the pooled features -> pred_sdf / sdf_weight [k1-k0];
+    any range is bit for bit that slice of the whole grid (chunks at fixed grid indices, evaluated whole)"""
+    arr, V, trans_mat, wp, code = _view_args(taps, trans_mat, pool, weights)
+    dev = trans_mat.device
+    if out is None:
+        out = torch.empty((k1 - k0,), dtype=torch.float32, device=dev)
+    p6 = _params6(sdf_params)
+    ws = _fit_ws(ws, lib().disn_query_grid_views_workspace_bytes(res), dev)
+    check("disn_query_grid_views", lib().disn_query_grid_views(
+        C.byref(w), C.byref(arr), V, _chk(embedding_pooled, "embedding").data_ptr(), trans_mat.data_ptr(),
+        wp.data_ptr() if wp is not None else None, code, C.byref(p6), res, k0, k1, float(sdf_weight), out.data_ptr(),
+        ws.data_ptr(), ws.numel(), _stream()))
+    return out
+
+
+# ---------------------------------------------------------------------------
 # narrow-band grid evaluation (grid_band.hip; DESIGN 4w)
 # ---------------------------------------------------------------------------
 BAND_STRIDES = (2, 4, 8)

@@ -509,6 +509,48 @@ int disn_query_grid_folded(const disn_mlp_weights_t* w, const float* pmap, const
                            size_t ws_bytes, void* stream);
 
 /* ---------------------------------------------------------------------- *
+ * Multi-view: ONE object seen in V views (1 .. DISN_MAX_VIEWS), all in the *
+ * object's frame.  The per-point local feature and the per-view embedding  *
+ * are pooled over the views, then the two decoder streams run on the       *
+ * pooled features (the paper's multi-view form).  View v's tap k*
+ * lies at taps[k] + v * (floats of one image of tap k) -- a contiguous     *
+ * slice of an encoded batch -- and its camera at trans_mat + 12 v.         *
+ * pool, in view order, fp32, never fused:                                  *
+ *   DISN_POOL_MAX : p = f_0;       p = fmaxf(p, f_v)                       *
+ *   DISN_POOL_MEAN: p = w_0 f_0;   p = p + w_v f_v      (w = weights [V];  *
+ *                   NULL: every w_v = 1 / V rounded to float32; only the   *
+ *                   mean reads them; (1 - t, t) interpolates two shapes)   *
+ * f_v is disn_gather_taps's row of view v, bit for bit; a view whose       *
+ * projection leaves the resampler's range (or is NaN) contributes zeros.   *
+ * An unknown pool or a V outside 1 .. DISN_MAX_VIEWS is DISN_E_SHAPE.      *
+ * ---------------------------------------------------------------------- */
+#define DISN_POOL_MAX 0
+#define DISN_POOL_MEAN 1
+#define DISN_MAX_VIEWS 24
+/* pts [N,3] -> feat [N,1472]: rows D + E + F of every view, pooled; each row is written once */
+int disn_gather_taps_pool(const float* const taps[5], int V, const float* trans_mat, const float* weights, int pool,
+                          const float* pts, int N, float* feat, void* stream);
+/* emb [V,1024] -> out [1,1024] by the same rules (the embedding is signed: max is the plain element-wise maximum) */
+int disn_pool_embedding(const float* emb, int V, const float* weights, int pool, float* out, void* stream);
+/* Rows D..H on pooled features: pts [N,3] go in chunks through disn_gather_taps_pool and the layers of disn_sdf_mlp
+ * (B = 1, pts_rot = pts) with embedding_pooled [1,1024] -> sdf [N], un-divided.  The pooled rows only ever exist
+ * chunk-wise inside `ws`. */
+size_t disn_query_views_workspace_bytes(int N);
+int disn_query_views(const disn_mlp_weights_t* w, const float* const taps[5], int V, const float* embedding_pooled,
+                     const float* trans_mat, const float* weights, int pool, const float* pts, int N, float* sdf,
+                     void* ws, size_t ws_bytes, void* stream);
+/* disn_query_grid on pooled features: grid points k0..k1-1 generated on the device, out[k-k0] = pred_sdf / sdf_weight.
+ * Grid order and arguments as disn_query_grid.  The grid is cut into chunks of 65536 points at fixed grid indices and a
+ * range evaluates every chunk it touches whole (a chunk's layers scale by maxima over its rows), so ANY range is bit for
+ * bit that slice of the whole grid; a range pays for at most one chunk of points it does not return at either end.
+ * The workspace depends on R alone (R <= 1290). */
+size_t disn_query_grid_views_workspace_bytes(int R);
+int disn_query_grid_views(const disn_mlp_weights_t* w, const float* const taps[5], int V, const float* embedding_pooled,
+                          const float* trans_mat, const float* weights, int pool, const double* sdf_params_host, int R,
+                          int64_t k0, int64_t k1, float sdf_weight, float* out, void* ws, size_t ws_bytes,
+                          void* stream);
+
+/* ---------------------------------------------------------------------- *
  * Fused point MLP (mlp_fused.hip): rows D, F (folded), G, H of one stream  *
  * in ONE persistent kernel -- models/sdfnet.py:71-88 ('sdfprediction') and *
  * :173-186 ('sdfprediction_imgfeat'), sum models/model_normalization.py:204*
