@@ -242,6 +242,10 @@ SIGNATURES = {
                                   C.POINTER(C.c_double * 6), I, L, L, F, P, P, Z, P]),
     "disn_query_grad_workspace_bytes": (Z, [I, L]),
     "disn_query_grad": (I, [C.POINTER(MlpWeights), P, P, P, P, I, L, P, P, P, Z, P]),
+    "disn_mesh_clean_workspace_bytes": (Z, [I, L, L]),
+    "disn_mesh_components_device": (I, [P, P, P, P, I, I, P, P, P, P, Z, P]),
+    "disn_mesh_clean_count_batch": (I, [P, P, P, P, I, I, C.c_double, C.c_double, P, P, Z, P]),
+    "disn_mesh_clean_emit_batch": (I, [P, P, P, P, P, I, P, P, P, P, P, Z, P]),
 }
 
 _LIB: Optional[C.CDLL] = None

@@ -38,7 +38,13 @@ the whole group with one read-back (``isosurface.marching_cubes_batch``) and wri
   * ``--fuse_views V [--fuse_pool max|mean]`` (multi-view) fuses every run of V chosen views of an object
     into ONE mesh, the features pooled over the views (``reconstruct_fused``): view_num / V meshes per object, each
     named after the first view of its run, in ``test_objs/[camest_]fuse<V><pool>_<res+1>_<iso>`` -- score them with
-    ``disn_amd.evaluate --view_num view_num/V``.  Not combinable with ``--band``, ``--refine`` or ``--normals``.
+    ``disn_amd.evaluate --view_num view_num/V``.  Not combinable with ``--band``, ``--refine`` or ``--normals``;
+  * ``--clean CATS [--clean_dist_thresh 0.5 --clean_num_thresh 0.3 --clean_connectivity face]`` drops the small and
+    the far parts (``postprocess.clean_meshes_device``) of every mesh of the listed categories (``clean`` =
+    the reference's five, ``all``, or names separated by commas) while the group still lies on the device, before
+    ``--refine``; the other categories are written as they are, and the tree goes to ``<...>_comb``: it is the
+    ``_comb`` tree of the two-step route.  A mesh of which nothing is kept is written uncleaned,
+    logged and counted as "unclean".  Composes with ``--band``, ``--refine``, ``--normals`` and ``--fuse_views``.
 """
 from __future__ import annotations
 
@@ -204,8 +210,51 @@ def create_sdf(engine, imgs, trans_mats, sdf_params, sdf_res: int, sdf_weight: f
     return _encode_grids_band(engine, imgs, trans_mats, sdf_params, sdf_res, iso, band, sdf_weight)[1]
 
 
+def clean_args(clean) -> Optional[Tuple[float, float, str]]:
+    """``clean`` = None or (dist_thresh, num_thresh, connectivity) checked (ValueError; no device work): what
+    ``reconstruct`` / ``reconstruct_fused`` hand to ``postprocess.clean_meshes_device``"""
+    if clean is None:
+        return None
+    from .postprocess import CONNECTIVITY
+    dist_thresh, num_thresh, connectivity = clean
+    dist_thresh, num_thresh = float(dist_thresh), float(num_thresh)
+    if not dist_thresh >= 0.0:
+        raise ValueError("--clean_dist_thresh must not be negative")
+    if not num_thresh >= 0.0:
+        raise ValueError("--clean_num_thresh must not be negative")
+    if connectivity not in CONNECTIVITY:
+        raise ValueError("--clean_connectivity must be one of %s, got %r" % (", ".join(sorted(CONNECTIVITY)),
+                                                                             connectivity))
+    return dist_thresh, num_thresh, connectivity
+
+
+def clean_group(meshes, clean, select=None, strict: bool = True):
+    """the small-part cleanup of one group right behind its meshing: the meshes ``select`` marks (None: all) that
+    have triangles go through ONE ``clean_meshes_device`` call.  -> (meshes, unclean [B] bool).  ``strict``: a mesh
+    of which nothing is kept raises; otherwise it stays as it is and is marked in ``unclean``."""
+    from .postprocess import clean_meshes_device
+    meshes = list(meshes)
+    unclean = [False] * len(meshes)
+    picked = [b for b, m in enumerate(meshes) if (select is None or select[b]) and len(m[1])]
+    if clean is None or not picked:
+        return meshes, unclean
+    cleaned, _ = clean_meshes_device([meshes[b] for b in picked], clean[0], clean[1], clean[2], strict=strict)
+    for b, m in zip(picked, cleaned):
+        if m is None:
+            unclean[b] = True
+        else:
+            meshes[b] = m
+    return meshes, unclean
+
+
 def reconstruct(engine, imgs, trans_mats, sdf_params, sdf_res: int, iso: float = 0.0, refine: int = 0,
-                normals: bool = False, band=None):
+                normals: bool = False, band=None, clean=None):
+    """``reconstruct_select`` for callers that clean every mesh or none (see there); -> the meshes"""
+    return reconstruct_select(engine, imgs, trans_mats, sdf_params, sdf_res, iso, refine, normals, band, clean)[0]
+
+
+def reconstruct_select(engine, imgs, trans_mats, sdf_params, sdf_res: int, iso: float = 0.0, refine: int = 0,
+                       normals: bool = False, band=None, clean=None, select=None, strict: bool = True):
     """images -> meshes for one group of views: one ``engine.encode`` call, the per-image grids of
     ``create_sdf`` in one [B,(res+1)^3] tensor, ONE batched meshing (one host sync for the group).
     -> B x (verts [nv,3] float32, faces [nf,3] int32) device views; the bits are those of ``create_sdf``
@@ -214,22 +263,29 @@ def reconstruct(engine, imgs, trans_mats, sdf_params, sdf_res: int, iso: float =
     level set (``isosurface.refine_mesh``, from the view's cached folded map); ``normals``: every mesh is a triple
     (verts, faces, normals [nv,3]) with the unit gradient at its (refined) vertices.  Faces never change.
     ``band`` = (stride, margin, dilate): the grids come from the narrow-band evaluation (one more host sync for the
-    group: the band sizes); the bits are those of ``engine.query_grid_band`` and ``marching_cubes`` image by image."""
+    group: the band sizes); the bits are those of ``engine.query_grid_band`` and ``marching_cubes`` image by image.
+    ``clean`` = (dist_thresh, num_thresh, connectivity): right behind the meshing and BEFORE the refinement the small
+    and the far parts are dropped on the device (``clean_group``: one more host sync for the group, the cleaned
+    sizes), so the rule sees the vertices the reference's rule sees and dropped parts are never refined; the bits are
+    those of ``postprocess.clean_arrays`` on the uncleaned mesh.  ``select`` [B] bool: only those meshes are cleaned.
+    A mesh of which nothing is kept raises ValueError (``strict``; False: it stays uncleaned).
+    -> (meshes, unclean [B] bool)"""
     from . import isosurface
     band = band_args(band, sdf_res)
+    clean = clean_args(clean)
     if band is None:
         enc, grids = _encode_grids(engine, imgs, trans_mats, sdf_params, sdf_res)
     else:
         enc, grids, _ = _encode_grids_band(engine, imgs, trans_mats, sdf_params, sdf_res, iso, band)
     sp = np.asarray(sdf_params, dtype=np.float64).reshape(grids.shape[0], 6)
-    meshes = isosurface.marching_cubes_batch(grids, sp, sdf_res, iso)
+    meshes, unclean = clean_group(isosurface.marching_cubes_batch(grids, sp, sdf_res, iso), clean, select, strict)
     if refine <= 0 and not normals:
-        return meshes
+        return meshes, unclean
     out = []
     for b, (verts, faces) in enumerate(meshes):
         v, f, n = isosurface.refine_mesh(engine, enc, b, trans_mats, verts, faces, sp[b], sdf_res, iso, max(int(refine), 0))
         out.append((v, f, n) if normals else (v, f))
-    return out
+    return out, unclean
 
 
 def fuse_args(fuse, pool: str = "max") -> Optional[Tuple[int, str]]:
@@ -248,12 +304,19 @@ def fuse_args(fuse, pool: str = "max") -> Optional[Tuple[int, str]]:
 
 
 def reconstruct_fused(engine, imgs, trans_mats, sdf_params, sdf_res: int, iso: float = 0.0, fuse: int = 2,
-                      pool: str = "max"):
+                      pool: str = "max", clean=None):
+    """``reconstruct_fused_select`` for callers that clean every mesh or none (see there); -> the meshes"""
+    return reconstruct_fused_select(engine, imgs, trans_mats, sdf_params, sdf_res, iso, fuse, pool, clean)[0]
+
+
+def reconstruct_fused_select(engine, imgs, trans_mats, sdf_params, sdf_res: int, iso: float = 0.0, fuse: int = 2,
+                             pool: str = "max", clean=None, select=None, strict: bool = True):
     """multi-view ``reconstruct``: the B images are B / ``fuse`` runs of ``fuse`` consecutive views of one object each
     (cameras trans_mats [B,4,3] in the object's frame, the run's grid box = its first view's sdf_params).  One
     ``engine.encode`` call, one ``engine.query_grid_views`` grid per run (features pooled over the run's views,
     ``pool`` = "max" or "mean"), ONE batched meshing -> B / fuse x (verts, faces); a run's bits are those of
-    ``query_grid_views`` followed by ``isosurface.marching_cubes`` on that run alone."""
+    ``query_grid_views`` followed by ``isosurface.marching_cubes`` on that run alone.  ``clean``, ``select`` (one
+    entry per RUN) and ``strict`` as in ``reconstruct_select``.  -> (meshes, unclean [B / fuse] bool)"""
     import torch
 
     from . import isosurface
@@ -261,6 +324,7 @@ def reconstruct_fused(engine, imgs, trans_mats, sdf_params, sdf_res: int, iso: f
     if checked is None:
         raise ValueError("reconstruct_fused needs the number of views to fuse")
     V, pool = checked
+    clean = clean_args(clean)
     imgs = np.asarray(imgs, np.float32) if not isinstance(imgs, torch.Tensor) else imgs
     B = imgs.shape[0]
     if B % V:
@@ -272,7 +336,7 @@ def reconstruct_fused(engine, imgs, trans_mats, sdf_params, sdf_res: int, iso: f
     grids = torch.empty((B // V, (sdf_res + 1) ** 3), dtype=torch.float32, device=engine.device)
     for r in range(B // V):
         engine.query_grid_views(enc, (r * V, V), tm[r * V:(r + 1) * V], sp[r], sdf_res, pool, out=grids[r])
-    return isosurface.marching_cubes_batch(grids, sp, sdf_res, iso)
+    return clean_group(isosurface.marching_cubes_batch(grids, sp, sdf_res, iso), clean, select, strict)
 
 
 def fuse_runs(entries: Sequence, fuse: int) -> List[List]:
@@ -320,11 +384,13 @@ def groups(entries: Sequence, batch_size: int) -> List[List]:
     return [list(entries[i:i + batch_size]) for i in range(0, len(entries), batch_size)]
 
 
-def result_obj_path(log_dir: str, sdf_res: int, iso: float, cam_est: bool = False, fuse=None) -> str:
+def result_obj_path(log_dir: str, sdf_res: int, iso: float, cam_est: bool = False, fuse=None,
+                    clean: bool = False) -> str:
     """test/create_sdf.py:88-93: <log_dir>/test_objs/[camest_]<res+1>_<str(iso)>; ``fuse`` = (V, pool): the fused
-    meshes' own directory [camest_]fuse<V><pool>_<res+1>_<str(iso)>"""
+    meshes' own directory [camest_]fuse<V><pool>_<res+1>_<str(iso)>; ``clean``: the tree with the cleaned categories,
+    <...>_comb (the name INTEGRATION 3e gives the combined tree)"""
     prefix = ("camest_" if cam_est else "") + ("fuse%d%s_" % tuple(fuse) if fuse else "")
-    return os.path.join(log_dir, "test_objs", prefix + str(sdf_res + 1) + "_" + str(iso))
+    return os.path.join(log_dir, "test_objs", prefix + str(sdf_res + 1) + "_" + str(iso) + ("_comb" if clean else ""))
 
 
 def obj_path(out_dir: str, cat_id: str, obj: str, view: int) -> str:
@@ -376,7 +442,41 @@ def parser():
                    help="multi-view: fuse every run of V chosen views of an object into ONE mesh (features pooled "
                         "over the views); view_num and batch_size must be multiples of V [default: 0, one mesh per view]")
     p.add_argument("--fuse_pool", default="max", choices=("max", "mean"), help="how --fuse_views pools [default: max]")
+    p.add_argument("--clean", default=None, metavar="CATS",
+                   help="drop the small and the far parts of the meshes of these categories on the device: clean (the "
+                        "reference's five), all, or names separated by commas; results go to <...>_comb")
+    add_clean_flags(p)
     return p
+
+
+def add_clean_flags(p) -> None:
+    p.add_argument("--clean_dist_thresh", type=float, default=None,
+                   help="largest centroid distance of a kept part [default: 0.5]")
+    p.add_argument("--clean_num_thresh", type=float, default=None,
+                   help="smallest share of the largest part's vertices [default: 0.3]")
+    p.add_argument("--clean_connectivity", default=None, help="face or vertex [default: face]")
+
+
+def clean_from_flags(a, on: bool) -> Optional[Tuple[float, float, str]]:
+    """the checked (dist_thresh, num_thresh, connectivity) when cleaning is ``on``; ValueError for a --clean_* option
+    without it, a negative threshold or an unknown connectivity"""
+    given = [f for f in ("clean_dist_thresh", "clean_num_thresh", "clean_connectivity") if getattr(a, f) is not None]
+    if not on:
+        if given:
+            raise ValueError("--%s needs --clean" % given[0])
+        return None
+    return clean_args((0.5 if a.clean_dist_thresh is None else a.clean_dist_thresh,
+                       0.3 if a.clean_num_thresh is None else a.clean_num_thresh,
+                       a.clean_connectivity or "face"))
+
+
+def clean_cats_from_flags(a):
+    """None without --clean, else ((dist_thresh, num_thresh, connectivity), the set of category ids to clean)"""
+    from .evaluate import categories
+    clean = clean_from_flags(a, a.clean is not None)
+    if clean is None:
+        return None
+    return clean, set(categories(a.clean).values())      # ValueError for an unknown category
 
 
 def fuse_from_flags(a) -> Optional[Tuple[int, str]]:
@@ -411,6 +511,7 @@ def check_flags(a) -> Optional[Tuple[int, str]]:
     if a.refine < 0:
         raise ValueError("--refine must not be negative")
     band_from_flags(a)
+    clean_cats_from_flags(a)
     return fuse_from_flags(a)
 
 
@@ -441,8 +542,10 @@ def load_group(group: Sequence, sdf_dir: str, rendered_dir: str, backcolorwhite:
 
 
 def main(argv=None, reconstruct_fn: Optional[Callable] = None) -> dict:
-    """-> {"written", "skipped", "empty", "out_dir"}.  ``reconstruct_fn(imgs, trans_mats, sdf_params)`` replaces
-    the device work (engine + ``reconstruct``) -- for host-side tests of the driver."""
+    """-> {"written", "skipped", "empty", "out_dir"} and, with ``--clean``, "unclean".  ``reconstruct_fn(imgs, trans_mats, sdf_params)``
+    replaces the device work (engine + ``reconstruct``) -- for host-side tests of the driver.  With ``--clean`` it is
+    called as ``reconstruct_fn(imgs, trans_mats, sdf_params, select)`` -- ``select``: one bool per mesh, True for the
+    listed categories -- and returns (meshes, unclean): ``unclean`` marks the meshes of which nothing was kept."""
     from concurrent.futures import ThreadPoolExecutor
     from datetime import datetime
 
@@ -452,7 +555,8 @@ def main(argv=None, reconstruct_fn: Optional[Callable] = None) -> dict:
     fuse = check_flags(a)
     batch_size = a.view_num if a.batch_size is None else a.batch_size
     per_mesh = fuse[0] if fuse else 1            # views that make one mesh; a mesh is named after the first of them
-    out_dir = result_obj_path(a.log_dir, a.sdf_res, a.iso, a.cam_est, fuse)
+    cleaning = clean_cats_from_flags(a)
+    out_dir = result_obj_path(a.log_dir, a.sdf_res, a.iso, a.cam_est, fuse, clean=cleaning is not None)
     entries = sample_list(categories(a.category), a.test_lst_dir, a.view_num, a.seed, a.num_shards, a.shard_id)
     if fuse:
         runs = fuse_runs(entries, per_mesh)
@@ -472,7 +576,13 @@ def main(argv=None, reconstruct_fn: Optional[Callable] = None) -> dict:
 
         band = band_from_flags(a)
 
-        def reconstruct_fn(imgs, trans_mats, sdf_params):
+        def reconstruct_fn(imgs, trans_mats, sdf_params, select=None):
+            if cleaning is not None:
+                if fuse:
+                    return reconstruct_fused_select(engine, imgs, trans_mats, sdf_params, a.sdf_res, a.iso, fuse[0],
+                                                    fuse[1], cleaning[0], select, strict=False)
+                return reconstruct_select(engine, imgs, trans_mats, sdf_params, a.sdf_res, a.iso, a.refine, a.normals,
+                                          band, cleaning[0], select, strict=False)
             if fuse:
                 return reconstruct_fused(engine, imgs, trans_mats, sdf_params, a.sdf_res, a.iso, fuse[0], fuse[1])
             if band is None:
@@ -491,7 +601,7 @@ def main(argv=None, reconstruct_fn: Optional[Callable] = None) -> dict:
         isosurface.write_obj(path, verts, faces, *normals)  # device-to-host copy + file, on a writer thread
         return path
 
-    written = empty = 0
+    written = empty = unclean = 0
     try:
         log_string(str(a))
         log_string("%s; %d views listed, %d to do in %d groups -> %s  (%s)"
@@ -505,14 +615,22 @@ def main(argv=None, reconstruct_fn: Optional[Callable] = None) -> dict:
             for gi, group in enumerate(work):
                 batch = nxt.result()
                 nxt = fetch(work[gi + 1]) if gi + 1 < len(work) else None
-                meshes = reconstruct_fn(batch["img"], batch["trans_mat"], batch["sdf_params"])
+                if cleaning is None:
+                    meshes = reconstruct_fn(batch["img"], batch["trans_mat"], batch["sdf_params"])
+                    left = [False] * len(meshes)
+                else:
+                    meshes, left = reconstruct_fn(batch["img"], batch["trans_mat"], batch["sdf_params"],
+                                                  [e[0] in cleaning[1] for e in group[::per_mesh]])
                 if len(meshes) * per_mesh != len(group):
                     raise RuntimeError("group %d: %d meshes for %d views" % (gi, len(meshes), len(group)))
                 for f in in_flight:                         # the group before this one: a writer's exception surfaces
                     f.result()
                 in_flight = []
-                for (cat_id, obj, view), (verts, faces, *vn) in zip(group[::per_mesh], meshes):
+                for (cat_id, obj, view), (verts, faces, *vn), as_it_is in zip(group[::per_mesh], meshes, left):
                     path = obj_path(out_dir, cat_id, obj, view)
+                    if as_it_is:
+                        unclean += 1
+                        log_string("%d/%d, UNCLEAN mesh (no part is kept, written as it is): %s" % (gi, len(work), path))
                     if len(verts) == 0 or len(faces) == 0:
                         empty += 1
                         log_string("%d/%d, EMPTY mesh (no surface at iso %s): %s" % (gi, len(work), a.iso, path))
@@ -526,7 +644,10 @@ def main(argv=None, reconstruct_fn: Optional[Callable] = None) -> dict:
                    % (written, empty, len(entries) - len(todo), datetime.now()))
     finally:
         logf.close()
-    return {"written": written, "skipped": len(entries) - len(todo), "empty": empty, "out_dir": out_dir}
+    res = {"written": written, "skipped": len(entries) - len(todo), "empty": empty, "out_dir": out_dir}
+    if cleaning is not None:
+        res["unclean"] = unclean
+    return res
 
 
 if __name__ == "__main__":

@@ -46,6 +46,7 @@ SOURCES = {
     "render.hip": ["-ffp-contract=off"],        # hits, depth and shading bit-identical to their float32 restatement
     "sdf_trace.hip": ["-ffp-contract=off"],     # the ray state machine bit-identical to its float32 restatement
     "voxel.hip": ["-ffp-contract=off"],         # the overlap test bit-identical to its float32 restatement
+    "mesh_clean.hip": ["-ffp-contract=off"],    # the keep rule's float64 arithmetic as clean_arrays states it
     "batch_assemble.hip": ["-ffp-contract=off"],   # sample_pc_rot in the order its bound is derived for
     "api.hip": [],
     "host_util.cpp": ["-msse4.2"],

@@ -286,6 +286,11 @@ constexpr int kScanBlockItems = 4096;
 hipError_t exclusive_scan(const unsigned* in, unsigned* out, size_t n, unsigned* bsum, unsigned long long* total,
                           hipStream_t st);
 
+// ---- mesh_clean.hip (compiled with -ffp-contract=off) ----------------------------
+// small-part cleanup of the batch disn_mc_emit_batch leaves: disn_mesh_components_device, disn_mesh_clean_count_batch,
+// disn_mesh_clean_emit_batch are defined there whole (checks, workspace layout, launches); its ranks and its stable
+// sort run on exclusive_scan above
+
 // ---- grid_band.hip (compiled with -ffp-contract=off): narrow-band grid evaluation around a dense tensor ----
 // R % s == 0, s in {2, 4, 8}, R <= 1289 are the caller's to check (api.hip).  cell_mask [(R/s)^3] 0 / 1; idx: the band
 // points' flat indices in ascending order (entries beyond idx_capacity are dropped); counts (device) = {band points,

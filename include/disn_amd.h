@@ -1098,6 +1098,54 @@ int disn_mesh_components(const int32_t* faces_host, int64_t nf, int64_t nv, int 
                          int64_t* ncomp);
 
 /* ---------------------------------------------------------------------- *
+ * Small-part cleanup on the device: B meshes back to back as               *
+ * disn_mc_emit_batch leaves them -- verts [sum nv][3], faces [sum nf][3]   *
+ * int32 with indices LOCAL to their mesh, v_off_host / f_off_host [B+1]    *
+ * int64 ascending from 0.  Limits as disn_mesh_components: sum nf <=       *
+ * INT32_MAX/3, sum nv <= INT32_MAX (disn_mesh_clean_workspace_bytes is 0   *
+ * beyond them).  Labels, component ids and connectivity as                 *
+ * disn_mesh_components, mesh by mesh; components never span meshes.        *
+ *   disn_mesh_components_device  labels [sum nf] (local component ids),    *
+ *       ncomp [B] int64; comp_verts (optional, int64 [sum nf] capacity,    *
+ *       needs verts): the number of distinct vertices of every component,  *
+ *       the meshes' components back to back.  A mesh with a status (below) *
+ *       has labels -1 and ncomp = -status.                                 *
+ *   disn_mesh_clean_count_batch  the rule of clean_smallparts.py:38-54: a  *
+ *       part is kept when (double)count > (double)biggest * num_thresh and *
+ *       sqrt(sum centroid^2) < dist_thresh, count = its distinct vertices, *
+ *       biggest = its mesh's largest count, centroid = the float64 sum of  *
+ *       their coordinates / count (the sum's order is not fixed: a         *
+ *       decision can differ from another order's only when the distance is *
+ *       within rounding of dist_thresh).  counts [B][5] int64 (device) =   *
+ *       ncomp, nkept, nv', nf', status per mesh.  status: 0 ok; 1 nothing  *
+ *       kept (nv' = nf' = 0); 2 a face index outside [0, nv_b): the first  *
+ *       kernel compares every index with its mesh's size and every later   *
+ *       one skips that mesh, nothing is addressed through an unchecked     *
+ *       index; 3 internal table full.  An empty mesh: ncomp 0, status 0.   *
+ *   disn_mesh_clean_emit_batch  after the caller read `counts` back        *
+ *       (counts_host; same ws, untouched in between -- the contract of     *
+ *       disn_mc_count / disn_mc_emit): verts_out [sum nv'][3], faces_out   *
+ *       [sum nf'][3] (local again), vmap_out [sum nv'] = the source vertex *
+ *       (local) of every output vertex, kept_out [sum nkept] = the kept    *
+ *       component ids.  Kept parts in component order, a part's vertices   *
+ *       in ascending source index (a vertex of two kept parts once per     *
+ *       part, unreferenced ones dropped), its faces in source order.       *
+ * No kernel waits for another workgroup; no host synchronisation.  The     *
+ * offset arrays must stay valid until the stream has passed the call.      *
+ * ---------------------------------------------------------------------- */
+size_t disn_mesh_clean_workspace_bytes(int B, int64_t nv_total, int64_t nf_total);
+int disn_mesh_components_device(const float* verts, const int32_t* faces, const int64_t* v_off_host,
+                                const int64_t* f_off_host, int B, int connectivity, int32_t* labels, int64_t* ncomp,
+                                int64_t* comp_verts, void* ws, size_t ws_bytes, void* stream);
+int disn_mesh_clean_count_batch(const float* verts, const int32_t* faces, const int64_t* v_off_host,
+                                const int64_t* f_off_host, int B, int connectivity, double dist_thresh,
+                                double num_thresh, int64_t* counts, void* ws, size_t ws_bytes, void* stream);
+int disn_mesh_clean_emit_batch(const float* verts, const int32_t* faces, const int64_t* v_off_host,
+                               const int64_t* f_off_host, const int64_t* counts_host, int B, float* verts_out,
+                               int32_t* faces_out, int32_t* vmap_out, int32_t* kept_out, void* ws, size_t ws_bytes,
+                               void* stream);
+
+/* ---------------------------------------------------------------------- *
  * Voxel IoU (test/test_iou.py of the reference; pymesh.VoxelGrid restated, *
  * parity with PyMesh itself unpinned).  Bit grids: an n^3 grid is n*n rows *
  * of ceil(n/32) uint32 words, cell (x, y, z) = bit (x & 31) of word        *
