@@ -105,7 +105,9 @@ __global__ __launch_bounds__(256) void fm_meta_kernel(const float* __restrict__ 
   __shared__ float red[256];
   __shared__ float rrow[512];   // 1 / c_{l-1}[k] of the hidden input features (1 for layer 0)
   for (int i = threadIdx.x; i < 512; i += 256) rrow[i] = 1.0f;
-  if (threadIdx.x < 16) meta[threadIdx.x] = 0.f;
+  // the whole 64-float header and the 64 bytes behind the meta block: an image is the same bytes whatever its buffer held
+  if (threadIdx.x < 64) meta[threadIdx.x] = 0.f;
+  if (threadIdx.x < 16) meta[fm::kMetaFloats + threadIdx.x] = 0.f;
   __syncthreads();
   for (int layer = 0; layer < 4; ++layer) {
     const float* w = layer == 0 ? w2 : (layer == 1 ? w3 : (layer == 2 ? w4 : w5));
@@ -754,6 +756,10 @@ __global__ __launch_bounds__(256, 1) void mlp_fused_kernel(const FusedDev P) {
       float c[3];
 #pragma unroll
       for (int a = 0; a < 3; ++a) {
+        // product and sum rounded separately, as elementwise.hip / grid_band.hip (compiled with -ffp-contract=off) and
+        // numpy do: fused into one fma, a node whose coordinate cancels to zero (R = 12, index 6 of [-1, 1]) comes
+        // out as -5.6e-17 and the grid is no longer bit for bit the point query on disn_grid_points
+#pragma clang fp contract(off)
         double v = (double)idx[a] * P.grid.step[a];
         v = v + P.grid.start[a];
         if (idx[a] == P.grid.res - 1 && P.grid.res > 1) v = P.grid.stop[a];
