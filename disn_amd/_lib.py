@@ -1,4 +1,4 @@
-"""ctypes binding of libdisn_amd.so (include/disn_amd.h).
+"""ctypes binding of libdisn_amd.so (include/disn_amd.h and, for the mesh simplification, include/disn_amd_simplify.h).
 
 The HIP library is the product: there is NO CPU fallback.  ``lib()`` raises
 ``DisnLibraryError`` when the shared object is missing or does not export the
@@ -248,6 +248,14 @@ SIGNATURES = {
     "disn_mesh_clean_emit_batch": (I, [P, P, P, P, P, I, P, P, P, P, P, Z, P]),
 }
 
+# name -> (restype, argtypes); every symbol declared in include/disn_amd_simplify.h (the second header of the same
+# library: include/disn_amd.h, SIGNATURES and the ABI version stay as they are)
+SIGNATURES_SIMPLIFY = {
+    "disn_mesh_simplify_workspace_bytes": (Z, [I, L, L]),
+    "disn_mesh_simplify_count_batch": (I, [P, P, P, P, P, P, I, I, P, P, Z, P]),
+    "disn_mesh_simplify_emit_batch": (I, [P, P, P, P, I, P, P, P, P, P, P, Z, P]),
+}
+
 _LIB: Optional[C.CDLL] = None
 
 
@@ -264,7 +272,7 @@ def lib() -> C.CDLL:
         h = C.CDLL(LIB_PATH)
     except OSError as e:  # pragma: no cover - depends on the box
         raise DisnLibraryError("cannot load %s: %s" % (LIB_PATH, e)) from e
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_SIMPLIFY.items()):
         try:
             fn = getattr(h, name)
         except AttributeError as e:

@@ -45,6 +45,13 @@ the whole group with one read-back (``isosurface.marching_cubes_batch``) and wri
     ``--refine``; the other categories are written as they are, and the tree goes to ``<...>_comb``: it is the
     ``_comb`` tree of the two-step route.  A mesh of which nothing is kept is written uncleaned,
     logged and counted as "unclean".  Composes with ``--band``, ``--refine``, ``--normals`` and ``--fuse_views``.
+  * ``--simplify CELLS`` (1..1024; the reference does not simplify) clusters every mesh's vertices on a lattice of
+    CELLS cells along the longest side of the view's ``sdf_params`` box and places each cluster by its faces' quadric
+    (``postprocess.simplify_meshes_device``) while the group still lies on the device: behind ``--clean``
+    and BEFORE ``--refine`` and ``--normals``, so the refinement pulls the moved vertices back onto the network's
+    level set and the normals are the gradients at the final vertices.  The tree goes to ``<...>[_comb]_s<CELLS>``.
+    ``evaluate``'s cd_emd and f_score sample VERTICES, as the reference's do: the scores of a simplified tree are
+    not the reference's numbers.  Composes with every flag above.
 """
 from __future__ import annotations
 
@@ -247,14 +254,46 @@ def clean_group(meshes, clean, select=None, strict: bool = True):
     return meshes, unclean
 
 
+def simplify_args(simplify) -> Optional[int]:
+    """``simplify`` = None or the number of lattice cells along the box's longest side, checked (ValueError; no device
+    work): what ``reconstruct`` / ``reconstruct_fused`` hand to ``postprocess.simplify_meshes_device``"""
+    if simplify is None:
+        return None
+    from .postprocess import MAX_CELLS
+    try:
+        cells = int(simplify)
+    except (TypeError, ValueError):
+        cells = None
+    if cells is None or cells != simplify or not 1 <= cells <= MAX_CELLS:
+        raise ValueError("--simplify must be a number of cells in 1..%d, got %r" % (MAX_CELLS, simplify))
+    return cells
+
+
+def simplify_group(meshes, simplify, boxes):
+    """the simplification of one group behind its meshing and cleanup: the meshes that have triangles go through ONE
+    ``simplify_meshes_device`` call, each on the lattice of its own box (``boxes`` [B,6]) -> the meshes"""
+    from .postprocess import simplify_meshes_device
+    meshes = list(meshes)
+    picked = [b for b, m in enumerate(meshes) if len(m[1])]
+    if simplify is None or not picked:
+        return meshes
+    boxes = np.asarray(boxes, np.float64).reshape(len(meshes), 6)
+    simplified, _ = simplify_meshes_device([meshes[b] for b in picked], boxes[picked], simplify)
+    for b, m in zip(picked, simplified):
+        meshes[b] = m
+    return meshes
+
+
 def reconstruct(engine, imgs, trans_mats, sdf_params, sdf_res: int, iso: float = 0.0, refine: int = 0,
-                normals: bool = False, band=None, clean=None):
+                normals: bool = False, band=None, clean=None, simplify=None):
     """``reconstruct_select`` for callers that clean every mesh or none (see there); -> the meshes"""
-    return reconstruct_select(engine, imgs, trans_mats, sdf_params, sdf_res, iso, refine, normals, band, clean)[0]
+    return reconstruct_select(engine, imgs, trans_mats, sdf_params, sdf_res, iso, refine, normals, band, clean,
+                              simplify=simplify)[0]
 
 
 def reconstruct_select(engine, imgs, trans_mats, sdf_params, sdf_res: int, iso: float = 0.0, refine: int = 0,
-                       normals: bool = False, band=None, clean=None, select=None, strict: bool = True):
+                       normals: bool = False, band=None, clean=None, select=None, strict: bool = True,
+                       simplify=None):
     """images -> meshes for one group of views: one ``engine.encode`` call, the per-image grids of
     ``create_sdf`` in one [B,(res+1)^3] tensor, ONE batched meshing (one host sync for the group).
     -> B x (verts [nv,3] float32, faces [nf,3] int32) device views; the bits are those of ``create_sdf``
@@ -269,16 +308,23 @@ def reconstruct_select(engine, imgs, trans_mats, sdf_params, sdf_res: int, iso: 
     sizes), so the rule sees the vertices the reference's rule sees and dropped parts are never refined; the bits are
     those of ``postprocess.clean_arrays`` on the uncleaned mesh.  ``select`` [B] bool: only those meshes are cleaned.
     A mesh of which nothing is kept raises ValueError (``strict``; False: it stays uncleaned).
+    ``simplify`` = CELLS: behind the cleanup and BEFORE the refinement every mesh with triangles is simplified on the
+    lattice of CELLS cells along the longest side of its view's ``sdf_params`` box (``simplify_group``: one more host
+    sync for the group, the simplified sizes); the bits are those of ``postprocess.simplify_arrays`` on the (cleaned)
+    mesh.  The refinement then pulls the moved vertices back onto the network's level set, and the normals are the
+    gradients at the final vertices.
     -> (meshes, unclean [B] bool)"""
     from . import isosurface
     band = band_args(band, sdf_res)
     clean = clean_args(clean)
+    simplify = simplify_args(simplify)
     if band is None:
         enc, grids = _encode_grids(engine, imgs, trans_mats, sdf_params, sdf_res)
     else:
         enc, grids, _ = _encode_grids_band(engine, imgs, trans_mats, sdf_params, sdf_res, iso, band)
     sp = np.asarray(sdf_params, dtype=np.float64).reshape(grids.shape[0], 6)
     meshes, unclean = clean_group(isosurface.marching_cubes_batch(grids, sp, sdf_res, iso), clean, select, strict)
+    meshes = simplify_group(meshes, simplify, sp)
     if refine <= 0 and not normals:
         return meshes, unclean
     out = []
@@ -304,19 +350,21 @@ def fuse_args(fuse, pool: str = "max") -> Optional[Tuple[int, str]]:
 
 
 def reconstruct_fused(engine, imgs, trans_mats, sdf_params, sdf_res: int, iso: float = 0.0, fuse: int = 2,
-                      pool: str = "max", clean=None):
+                      pool: str = "max", clean=None, simplify=None):
     """``reconstruct_fused_select`` for callers that clean every mesh or none (see there); -> the meshes"""
-    return reconstruct_fused_select(engine, imgs, trans_mats, sdf_params, sdf_res, iso, fuse, pool, clean)[0]
+    return reconstruct_fused_select(engine, imgs, trans_mats, sdf_params, sdf_res, iso, fuse, pool, clean,
+                                    simplify=simplify)[0]
 
 
 def reconstruct_fused_select(engine, imgs, trans_mats, sdf_params, sdf_res: int, iso: float = 0.0, fuse: int = 2,
-                             pool: str = "max", clean=None, select=None, strict: bool = True):
+                             pool: str = "max", clean=None, select=None, strict: bool = True, simplify=None):
     """multi-view ``reconstruct``: the B images are B / ``fuse`` runs of ``fuse`` consecutive views of one object each
     (cameras trans_mats [B,4,3] in the object's frame, the run's grid box = its first view's sdf_params).  One
     ``engine.encode`` call, one ``engine.query_grid_views`` grid per run (features pooled over the run's views,
     ``pool`` = "max" or "mean"), ONE batched meshing -> B / fuse x (verts, faces); a run's bits are those of
     ``query_grid_views`` followed by ``isosurface.marching_cubes`` on that run alone.  ``clean``, ``select`` (one
-    entry per RUN) and ``strict`` as in ``reconstruct_select``.  -> (meshes, unclean [B / fuse] bool)"""
+    entry per RUN), ``strict`` and ``simplify`` (on the lattice of the run's box) as in ``reconstruct_select``.
+    -> (meshes, unclean [B / fuse] bool)"""
     import torch
 
     from . import isosurface
@@ -325,6 +373,7 @@ def reconstruct_fused_select(engine, imgs, trans_mats, sdf_params, sdf_res: int,
         raise ValueError("reconstruct_fused needs the number of views to fuse")
     V, pool = checked
     clean = clean_args(clean)
+    simplify = simplify_args(simplify)
     imgs = np.asarray(imgs, np.float32) if not isinstance(imgs, torch.Tensor) else imgs
     B = imgs.shape[0]
     if B % V:
@@ -336,7 +385,8 @@ def reconstruct_fused_select(engine, imgs, trans_mats, sdf_params, sdf_res: int,
     grids = torch.empty((B // V, (sdf_res + 1) ** 3), dtype=torch.float32, device=engine.device)
     for r in range(B // V):
         engine.query_grid_views(enc, (r * V, V), tm[r * V:(r + 1) * V], sp[r], sdf_res, pool, out=grids[r])
-    return clean_group(isosurface.marching_cubes_batch(grids, sp, sdf_res, iso), clean, select, strict)
+    meshes, unclean = clean_group(isosurface.marching_cubes_batch(grids, sp, sdf_res, iso), clean, select, strict)
+    return simplify_group(meshes, simplify, sp), unclean
 
 
 def fuse_runs(entries: Sequence, fuse: int) -> List[List]:
@@ -385,12 +435,14 @@ def groups(entries: Sequence, batch_size: int) -> List[List]:
 
 
 def result_obj_path(log_dir: str, sdf_res: int, iso: float, cam_est: bool = False, fuse=None,
-                    clean: bool = False) -> str:
+                    clean: bool = False, simplify=None) -> str:
     """test/create_sdf.py:88-93: <log_dir>/test_objs/[camest_]<res+1>_<str(iso)>; ``fuse`` = (V, pool): the fused
     meshes' own directory [camest_]fuse<V><pool>_<res+1>_<str(iso)>; ``clean``: the tree with the cleaned categories,
-    <...>_comb (the name INTEGRATION 3e gives the combined tree)"""
+    <...>_comb (the name INTEGRATION 3e gives the combined tree); ``simplify`` = CELLS: the simplified meshes' tree,
+    <...>[_comb]_s<CELLS>"""
     prefix = ("camest_" if cam_est else "") + ("fuse%d%s_" % tuple(fuse) if fuse else "")
-    return os.path.join(log_dir, "test_objs", prefix + str(sdf_res + 1) + "_" + str(iso) + ("_comb" if clean else ""))
+    return os.path.join(log_dir, "test_objs", prefix + str(sdf_res + 1) + "_" + str(iso) + ("_comb" if clean else "")
+                        + ("_s%d" % simplify if simplify is not None else ""))
 
 
 def obj_path(out_dir: str, cat_id: str, obj: str, view: int) -> str:
@@ -446,7 +498,19 @@ def parser():
                    help="drop the small and the far parts of the meshes of these categories on the device: clean (the "
                         "reference's five), all, or names separated by commas; results go to <...>_comb")
     add_clean_flags(p)
+    add_simplify_flag(p)
     return p
+
+
+def add_simplify_flag(p) -> None:
+    p.add_argument("--simplify", type=int, default=None, metavar="CELLS",
+                   help="simplify every mesh on the device: cluster its vertices on a lattice of CELLS cells (1..1024) "
+                        "along the box's longest side, one quadric-placed vertex per cell; results go to <...>_s<CELLS>")
+
+
+def simplify_from_flags(a) -> Optional[int]:
+    """None without --simplify, else the checked number of cells (ValueError outside 1..1024)"""
+    return simplify_args(a.simplify)
 
 
 def add_clean_flags(p) -> None:
@@ -512,6 +576,7 @@ def check_flags(a) -> Optional[Tuple[int, str]]:
         raise ValueError("--refine must not be negative")
     band_from_flags(a)
     clean_cats_from_flags(a)
+    simplify_from_flags(a)
     return fuse_from_flags(a)
 
 
@@ -542,7 +607,8 @@ def load_group(group: Sequence, sdf_dir: str, rendered_dir: str, backcolorwhite:
 
 
 def main(argv=None, reconstruct_fn: Optional[Callable] = None) -> dict:
-    """-> {"written", "skipped", "empty", "out_dir"} and, with ``--clean``, "unclean".  ``reconstruct_fn(imgs, trans_mats, sdf_params)``
+    """-> {"written", "skipped", "empty", "out_dir"}, with ``--clean`` also "unclean", with ``--simplify`` also "simplified" (the
+    meshes with triangles: those that went through the stage).  ``reconstruct_fn(imgs, trans_mats, sdf_params)``
     replaces the device work (engine + ``reconstruct``) -- for host-side tests of the driver.  With ``--clean`` it is
     called as ``reconstruct_fn(imgs, trans_mats, sdf_params, select)`` -- ``select``: one bool per mesh, True for the
     listed categories -- and returns (meshes, unclean): ``unclean`` marks the meshes of which nothing was kept."""
@@ -556,7 +622,9 @@ def main(argv=None, reconstruct_fn: Optional[Callable] = None) -> dict:
     batch_size = a.view_num if a.batch_size is None else a.batch_size
     per_mesh = fuse[0] if fuse else 1            # views that make one mesh; a mesh is named after the first of them
     cleaning = clean_cats_from_flags(a)
-    out_dir = result_obj_path(a.log_dir, a.sdf_res, a.iso, a.cam_est, fuse, clean=cleaning is not None)
+    simplify = simplify_from_flags(a)
+    more = {} if simplify is None else {"simplify": simplify}     # (without the flag every call below is as it was)
+    out_dir = result_obj_path(a.log_dir, a.sdf_res, a.iso, a.cam_est, fuse, clean=cleaning is not None, **more)
     entries = sample_list(categories(a.category), a.test_lst_dir, a.view_num, a.seed, a.num_shards, a.shard_id)
     if fuse:
         runs = fuse_runs(entries, per_mesh)
@@ -580,14 +648,16 @@ def main(argv=None, reconstruct_fn: Optional[Callable] = None) -> dict:
             if cleaning is not None:
                 if fuse:
                     return reconstruct_fused_select(engine, imgs, trans_mats, sdf_params, a.sdf_res, a.iso, fuse[0],
-                                                    fuse[1], cleaning[0], select, strict=False)
+                                                    fuse[1], cleaning[0], select, strict=False, **more)
                 return reconstruct_select(engine, imgs, trans_mats, sdf_params, a.sdf_res, a.iso, a.refine, a.normals,
-                                          band, cleaning[0], select, strict=False)
+                                          band, cleaning[0], select, strict=False, **more)
             if fuse:
-                return reconstruct_fused(engine, imgs, trans_mats, sdf_params, a.sdf_res, a.iso, fuse[0], fuse[1])
+                return reconstruct_fused(engine, imgs, trans_mats, sdf_params, a.sdf_res, a.iso, fuse[0], fuse[1],
+                                         **more)
             if band is None:
-                return reconstruct(engine, imgs, trans_mats, sdf_params, a.sdf_res, a.iso, a.refine, a.normals)
-            return reconstruct(engine, imgs, trans_mats, sdf_params, a.sdf_res, a.iso, a.refine, a.normals, band=band)
+                return reconstruct(engine, imgs, trans_mats, sdf_params, a.sdf_res, a.iso, a.refine, a.normals, **more)
+            return reconstruct(engine, imgs, trans_mats, sdf_params, a.sdf_res, a.iso, a.refine, a.normals, band=band,
+                               **more)
 
     os.makedirs(out_dir, exist_ok=True)
     logf = open(os.path.join(a.log_dir, "log_test.txt"), "a")
@@ -647,6 +717,8 @@ def main(argv=None, reconstruct_fn: Optional[Callable] = None) -> dict:
     res = {"written": written, "skipped": len(entries) - len(todo), "empty": empty, "out_dir": out_dir}
     if cleaning is not None:
         res["unclean"] = unclean
+    if simplify is not None:
+        res["simplified"] = written - empty
     return res
 
 

@@ -4,6 +4,7 @@
                             [--sdf_res 64] [--iso 0.0] [--out demo/result.obj] [--refine ITERS] [--normals]
                             [--band STRIDE --band_margin 0.5 --band_dilate 1]
                             [--clean --clean_dist_thresh 0.5 --clean_num_thresh 0.3 --clean_connectivity face]
+                            [--simplify CELLS]
                             [--preview OUT.png [--preview_size 137]]
 
 The image is read as demo/demo.py:261-279 reads it (``cv2.imread(IMREAD_UNCHANGED)[:, :, :3] / 255``: the
@@ -17,6 +18,10 @@ reference goes on silently).
 ``--preview OUT.png`` also writes the predicted surface as seen by the camera in use, sphere-traced from the network
 without a grid or a mesh (``SdfEngine.trace``), prints the trace's statistics and, when the input PNG has
 an alpha channel, the 2-D IoU of the predicted silhouette with it: low with a good mesh means a camera failure.
+
+``--simplify CELLS`` simplifies the mesh on the device before it is written (``postprocess.simplify_meshes_device``,
+DESIGN §4za): one quadric-placed vertex per cell of a lattice of CELLS cells per side of the box, behind ``--clean`` and
+before ``--refine`` / ``--normals``.
 """
 from __future__ import annotations
 
@@ -91,11 +96,12 @@ def parser() -> argparse.ArgumentParser:
     p.add_argument("--preview", default=None, metavar="OUT.png",
                    help="also write the sphere-traced view of the predicted surface from the camera in use")
     p.add_argument("--preview_size", type=int, default=137, metavar="N", help="the preview is N x N [default: 137]")
-    from .create_sdf import add_band_flags, add_clean_flags
+    from .create_sdf import add_band_flags, add_clean_flags, add_simplify_flag
     add_band_flags(p)
     p.add_argument("--clean", action="store_true",
                    help="drop the mesh's small and far parts on the device (postprocess.clean_meshes_device)")
     add_clean_flags(p)
+    add_simplify_flag(p)
     return p
 
 
@@ -132,9 +138,10 @@ def main(argv=None) -> dict:
     """-> {"out", "verts", "faces", "trans_mat"}"""
     a = parser().parse_args(argv)
     from . import isosurface
-    from .create_sdf import band_from_flags, clean_from_flags, reconstruct, restore_weights
+    from .create_sdf import band_from_flags, clean_from_flags, reconstruct, restore_weights, simplify_from_flags
     band = band_from_flags(a)                                          # a bad stride / resolution: before anything else
     clean = clean_from_flags(a, a.clean)
+    simplify = simplify_from_flags(a)
     img = read_image(a.img)
     if img.shape[1:3] != (137, 137):
         raise ValueError("%s is %dx%d; the network reads 137x137 renderings" % (a.img, img.shape[2], img.shape[1]))
@@ -154,6 +161,8 @@ def main(argv=None) -> dict:
     extra = {} if band is None else {"band": band}
     if clean is not None:
         extra["clean"] = clean
+    if simplify is not None:
+        extra["simplify"] = simplify
     verts, faces, *vn = reconstruct(engine, img, trans_mat, DEMO_SDF_PARAMS, a.sdf_res, a.iso, a.refine, a.normals,
                                     **extra)[0]
     isosurface.write_obj(a.out, verts, faces, *vn)
