@@ -1,4 +1,5 @@
-"""ctypes binding of libdisn_amd.so (include/disn_amd.h and, for the mesh simplification, include/disn_amd_simplify.h).
+"""ctypes binding of libdisn_amd.so (include/disn_amd.h and, for the mesh simplification and the vertex colours,
+include/disn_amd_simplify.h and include/disn_amd_colour.h).
 
 The HIP library is the product: there is NO CPU fallback.  ``lib()`` raises
 ``DisnLibraryError`` when the shared object is missing or does not export the
@@ -256,6 +257,14 @@ SIGNATURES_SIMPLIFY = {
     "disn_mesh_simplify_emit_batch": (I, [P, P, P, P, I, P, P, P, P, P, P, Z, P]),
 }
 
+# name -> (restype, argtypes); every symbol declared in include/disn_amd_colour.h (the third header, added the same way)
+SIGNATURES_COLOUR = {
+    "disn_mesh_colour_workspace_bytes": (Z, [I, I, L, L, I]),
+    "disn_mesh_zbuffer_batch": (I, [P, P, P, P, I, P, I, I, P, P, P, Z, P]),
+    "disn_mesh_colour_batch": (I, [P, P, P, P, I, P, P, P, I, I, F, I, I, I, P, P, P, P, Z, P]),
+    "disn_write_obj_colours": (I, [C.c_char_p, P, L, P, P, P, L]),
+}
+
 _LIB: Optional[C.CDLL] = None
 
 
@@ -272,7 +281,7 @@ def lib() -> C.CDLL:
         h = C.CDLL(LIB_PATH)
     except OSError as e:  # pragma: no cover - depends on the box
         raise DisnLibraryError("cannot load %s: %s" % (LIB_PATH, e)) from e
-    for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_SIMPLIFY.items()):
+    for name, (res, args) in [kv for t in (SIGNATURES, SIGNATURES_SIMPLIFY, SIGNATURES_COLOUR) for kv in t.items()]:
         try:
             fn = getattr(h, name)
         except AttributeError as e:

@@ -284,16 +284,74 @@ def simplify_group(meshes, simplify, boxes):
     return meshes
 
 
+MIRROR_AXES = {"x": 0, "y": 1, "z": 2, "0": 0, "1": 1, "2": 2, 0: 0, 1: 1, 2: 2}
+COLOUR_DEFAULTS = {"S": 2, "rel_tol": 1e-3, "mirror_axis": None, "fill_iters": 32, "bgr": True}
+
+
+def colour_args(colour) -> Optional[dict]:
+    """``colour`` = None / False (off), True (the defaults) or a dict with some of S, rel_tol, mirror_axis (None, 0, 1,
+    2 or "x", "y", "z"), fill_iters, bgr -> None or the checked, complete dict (ValueError; no device work): the keyword
+    arguments ``reconstruct`` / ``reconstruct_fused`` hand to ``postprocess.colour_meshes_device``"""
+    if colour is None or colour is False:
+        return None
+    from .postprocess import _colour_params
+    given = {} if colour is True else dict(colour)
+    unknown = sorted(set(given) - set(COLOUR_DEFAULTS))
+    if unknown:
+        raise ValueError("--colour takes S, rel_tol, mirror_axis, fill_iters and bgr, not %s" % ", ".join(unknown))
+    c = dict(COLOUR_DEFAULTS, **given)
+    if c["mirror_axis"] is not None:
+        if isinstance(c["mirror_axis"], bool) or c["mirror_axis"] not in MIRROR_AXES:
+            raise ValueError("--colour_mirror must be x, y or z (or 0, 1, 2), got %r" % (c["mirror_axis"],))
+        c["mirror_axis"] = MIRROR_AXES[c["mirror_axis"]]
+    _colour_params(c["S"], c["rel_tol"], c["mirror_axis"], c["fill_iters"])
+    c["bgr"] = bool(c["bgr"])
+    return c
+
+
+def colour_group(meshes, colour, imgs, trans_mats, views_per_mesh: int = 1, alpha=None):
+    """the colouring of one group behind every other stage: ONE ``colour_meshes_device`` call for the meshes that have
+    vertices, mesh b from views b V .. (b + 1) V - 1 of ``imgs`` [B V,137,137,3] and ``trans_mats`` [B V,4,3] (V =
+    ``views_per_mesh``; ``alpha`` None or [B V,137,137] uint8) -> the meshes, each with ``colours`` uint8 [nv,3] as its
+    last element (empty for an empty mesh); vertices, faces and normals are not touched"""
+    import torch
+
+    from .postprocess import IMG, colour_meshes_device
+    meshes = [tuple(m) for m in meshes]
+    if colour is None:
+        return meshes
+    V = int(views_per_mesh)
+    picked = [b for b, m in enumerate(meshes) if len(m[0])]
+    out = [m + (torch.zeros((0, 3), dtype=torch.uint8, device=m[0].device),) for m in meshes]
+    if not picked:
+        return out
+    dev = meshes[picked[0]][0].device
+    on_dev = lambda a, dt: (a if isinstance(a, torch.Tensor) else torch.from_numpy(np.array(a))).to(dev, dt)
+    im = on_dev(imgs, torch.float32).reshape(len(meshes), V, IMG, IMG, 3)
+    tm = trans_mats.detach().cpu().numpy() if isinstance(trans_mats, torch.Tensor) else trans_mats
+    tm = np.asarray(tm, np.float32).reshape(len(meshes), V, 4, 3)
+    al = None if alpha is None else on_dev(alpha, torch.uint8).reshape(len(meshes), V, IMG, IMG)
+    idx = torch.as_tensor(picked, device=dev)
+    whole = len(picked) == len(meshes)
+    cs, _ = colour_meshes_device([meshes[b][:2] for b in picked], im if whole else im.index_select(0, idx), tm[picked],
+                                 views_per_mesh=V, alpha=al if al is None or whole else al.index_select(0, idx),
+                                 **colour)
+    for b, c in zip(picked, cs):
+        out[b] = meshes[b] + (c,)
+    return out
+
+
 def reconstruct(engine, imgs, trans_mats, sdf_params, sdf_res: int, iso: float = 0.0, refine: int = 0,
-                normals: bool = False, band=None, clean=None, simplify=None):
+                normals: bool = False, band=None, clean=None, simplify=None, colour=None, alpha=None):
     """``reconstruct_select`` for callers that clean every mesh or none (see there); -> the meshes"""
+    more = {} if colour is None or colour is False else {"colour": colour, "alpha": alpha}
     return reconstruct_select(engine, imgs, trans_mats, sdf_params, sdf_res, iso, refine, normals, band, clean,
-                              simplify=simplify)[0]
+                              simplify=simplify, **more)[0]
 
 
 def reconstruct_select(engine, imgs, trans_mats, sdf_params, sdf_res: int, iso: float = 0.0, refine: int = 0,
                        normals: bool = False, band=None, clean=None, select=None, strict: bool = True,
-                       simplify=None):
+                       simplify=None, colour=None, alpha=None):
     """images -> meshes for one group of views: one ``engine.encode`` call, the per-image grids of
     ``create_sdf`` in one [B,(res+1)^3] tensor, ONE batched meshing (one host sync for the group).
     -> B x (verts [nv,3] float32, faces [nf,3] int32) device views; the bits are those of ``create_sdf``
@@ -313,11 +371,16 @@ def reconstruct_select(engine, imgs, trans_mats, sdf_params, sdf_res: int, iso: 
     sync for the group, the simplified sizes); the bits are those of ``postprocess.simplify_arrays`` on the (cleaned)
     mesh.  The refinement then pulls the moved vertices back onto the network's level set, and the normals are the
     gradients at the final vertices.
+    ``colour`` = True or a dict (``colour_args``): behind every other stage each mesh is coloured from its own view
+    (``colour_group``; ``alpha`` None or [B,137,137] uint8 masks the background) and gains ``colours`` uint8 [nv,3] as
+    its last element: (verts, faces[, normals], colours).  Vertices, faces and normals are bit for bit those of the
+    call without it; the bytes are those of ``postprocess.colour_arrays`` on the final mesh.
     -> (meshes, unclean [B] bool)"""
     from . import isosurface
     band = band_args(band, sdf_res)
     clean = clean_args(clean)
     simplify = simplify_args(simplify)
+    colour = colour_args(colour)
     if band is None:
         enc, grids = _encode_grids(engine, imgs, trans_mats, sdf_params, sdf_res)
     else:
@@ -326,12 +389,12 @@ def reconstruct_select(engine, imgs, trans_mats, sdf_params, sdf_res: int, iso: 
     meshes, unclean = clean_group(isosurface.marching_cubes_batch(grids, sp, sdf_res, iso), clean, select, strict)
     meshes = simplify_group(meshes, simplify, sp)
     if refine <= 0 and not normals:
-        return meshes, unclean
+        return (meshes if colour is None else colour_group(meshes, colour, imgs, trans_mats, 1, alpha)), unclean
     out = []
     for b, (verts, faces) in enumerate(meshes):
         v, f, n = isosurface.refine_mesh(engine, enc, b, trans_mats, verts, faces, sp[b], sdf_res, iso, max(int(refine), 0))
         out.append((v, f, n) if normals else (v, f))
-    return out, unclean
+    return (out if colour is None else colour_group(out, colour, imgs, trans_mats, 1, alpha)), unclean
 
 
 def fuse_args(fuse, pool: str = "max") -> Optional[Tuple[int, str]]:
@@ -350,20 +413,23 @@ def fuse_args(fuse, pool: str = "max") -> Optional[Tuple[int, str]]:
 
 
 def reconstruct_fused(engine, imgs, trans_mats, sdf_params, sdf_res: int, iso: float = 0.0, fuse: int = 2,
-                      pool: str = "max", clean=None, simplify=None):
+                      pool: str = "max", clean=None, simplify=None, colour=None, alpha=None):
     """``reconstruct_fused_select`` for callers that clean every mesh or none (see there); -> the meshes"""
+    more = {} if colour is None or colour is False else {"colour": colour, "alpha": alpha}
     return reconstruct_fused_select(engine, imgs, trans_mats, sdf_params, sdf_res, iso, fuse, pool, clean,
-                                    simplify=simplify)[0]
+                                    simplify=simplify, **more)[0]
 
 
 def reconstruct_fused_select(engine, imgs, trans_mats, sdf_params, sdf_res: int, iso: float = 0.0, fuse: int = 2,
-                             pool: str = "max", clean=None, select=None, strict: bool = True, simplify=None):
+                             pool: str = "max", clean=None, select=None, strict: bool = True, simplify=None,
+                             colour=None, alpha=None):
     """multi-view ``reconstruct``: the B images are B / ``fuse`` runs of ``fuse`` consecutive views of one object each
     (cameras trans_mats [B,4,3] in the object's frame, the run's grid box = its first view's sdf_params).  One
     ``engine.encode`` call, one ``engine.query_grid_views`` grid per run (features pooled over the run's views,
     ``pool`` = "max" or "mean"), ONE batched meshing -> B / fuse x (verts, faces); a run's bits are those of
     ``query_grid_views`` followed by ``isosurface.marching_cubes`` on that run alone.  ``clean``, ``select`` (one
-    entry per RUN), ``strict`` and ``simplify`` (on the lattice of the run's box) as in ``reconstruct_select``.
+    entry per RUN), ``strict`` and ``simplify`` (on the lattice of the run's box) as in ``reconstruct_select``;
+    ``colour``: every run's mesh is coloured from ALL ``fuse`` views of the run (``alpha`` None or [B,137,137]).
     -> (meshes, unclean [B / fuse] bool)"""
     import torch
 
@@ -374,6 +440,7 @@ def reconstruct_fused_select(engine, imgs, trans_mats, sdf_params, sdf_res: int,
     V, pool = checked
     clean = clean_args(clean)
     simplify = simplify_args(simplify)
+    colour = colour_args(colour)
     imgs = np.asarray(imgs, np.float32) if not isinstance(imgs, torch.Tensor) else imgs
     B = imgs.shape[0]
     if B % V:
@@ -386,7 +453,8 @@ def reconstruct_fused_select(engine, imgs, trans_mats, sdf_params, sdf_res: int,
     for r in range(B // V):
         engine.query_grid_views(enc, (r * V, V), tm[r * V:(r + 1) * V], sp[r], sdf_res, pool, out=grids[r])
     meshes, unclean = clean_group(isosurface.marching_cubes_batch(grids, sp, sdf_res, iso), clean, select, strict)
-    return simplify_group(meshes, simplify, sp), unclean
+    meshes = simplify_group(meshes, simplify, sp)
+    return (meshes if colour is None else colour_group(meshes, colour, imgs, tm, V, alpha)), unclean
 
 
 def fuse_runs(entries: Sequence, fuse: int) -> List[List]:
@@ -435,14 +503,14 @@ def groups(entries: Sequence, batch_size: int) -> List[List]:
 
 
 def result_obj_path(log_dir: str, sdf_res: int, iso: float, cam_est: bool = False, fuse=None,
-                    clean: bool = False, simplify=None) -> str:
+                    clean: bool = False, simplify=None, colour: bool = False) -> str:
     """test/create_sdf.py:88-93: <log_dir>/test_objs/[camest_]<res+1>_<str(iso)>; ``fuse`` = (V, pool): the fused
     meshes' own directory [camest_]fuse<V><pool>_<res+1>_<str(iso)>; ``clean``: the tree with the cleaned categories,
     <...>_comb (the name INTEGRATION 3e gives the combined tree); ``simplify`` = CELLS: the simplified meshes' tree,
-    <...>[_comb]_s<CELLS>"""
+    <...>[_comb]_s<CELLS>; ``colour``: the coloured meshes' tree, <...>[_comb][_s<CELLS>]_col"""
     prefix = ("camest_" if cam_est else "") + ("fuse%d%s_" % tuple(fuse) if fuse else "")
     return os.path.join(log_dir, "test_objs", prefix + str(sdf_res + 1) + "_" + str(iso) + ("_comb" if clean else "")
-                        + ("_s%d" % simplify if simplify is not None else ""))
+                        + ("_s%d" % simplify if simplify is not None else "") + ("_col" if colour else ""))
 
 
 def obj_path(out_dir: str, cat_id: str, obj: str, view: int) -> str:
@@ -499,7 +567,27 @@ def parser():
                         "reference's five), all, or names separated by commas; results go to <...>_comb")
     add_clean_flags(p)
     add_simplify_flag(p)
+    add_colour_flags(p)
     return p
+
+
+def add_colour_flags(p) -> None:
+    p.add_argument("--colour", "--color", dest="colour", action="store_true",
+                   help="colour every mesh's vertices on the device from the view(s) it was reconstructed from "
+                        "('v x y z r g b' lines); results go to <...>_col")
+    p.add_argument("--colour_mirror", "--color_mirror", dest="colour_mirror", default=None, metavar="AXIS",
+                   help="with --colour: a vertex no view sees takes the colour of its reflection in the plane AXIS = 0 "
+                        "(x, y or z) of the object frame when that is seen [default: off]")
+
+
+def colour_from_flags(a) -> Optional[dict]:
+    """None without --colour, else the checked keyword arguments (ValueError for --colour_mirror without --colour or
+    with an axis that is none)"""
+    if not a.colour:
+        if a.colour_mirror is not None:
+            raise ValueError("--colour_mirror needs --colour")
+        return None
+    return colour_args(True if a.colour_mirror is None else {"mirror_axis": a.colour_mirror})
 
 
 def add_simplify_flag(p) -> None:
@@ -577,6 +665,7 @@ def check_flags(a) -> Optional[Tuple[int, str]]:
     band_from_flags(a)
     clean_cats_from_flags(a)
     simplify_from_flags(a)
+    colour_from_flags(a)
     return fuse_from_flags(a)
 
 
@@ -608,7 +697,8 @@ def load_group(group: Sequence, sdf_dir: str, rendered_dir: str, backcolorwhite:
 
 def main(argv=None, reconstruct_fn: Optional[Callable] = None) -> dict:
     """-> {"written", "skipped", "empty", "out_dir"}, with ``--clean`` also "unclean", with ``--simplify`` also "simplified" (the
-    meshes with triangles: those that went through the stage).  ``reconstruct_fn(imgs, trans_mats, sdf_params)``
+    meshes with triangles: those that went through the stage), with ``--colour`` also "coloured" (likewise; every mesh
+    then ends in ``colours`` uint8 [nv,3], behind the normals when there are any).  ``reconstruct_fn(imgs, trans_mats, sdf_params)``
     replaces the device work (engine + ``reconstruct``) -- for host-side tests of the driver.  With ``--clean`` it is
     called as ``reconstruct_fn(imgs, trans_mats, sdf_params, select)`` -- ``select``: one bool per mesh, True for the
     listed categories -- and returns (meshes, unclean): ``unclean`` marks the meshes of which nothing was kept."""
@@ -623,8 +713,12 @@ def main(argv=None, reconstruct_fn: Optional[Callable] = None) -> dict:
     per_mesh = fuse[0] if fuse else 1            # views that make one mesh; a mesh is named after the first of them
     cleaning = clean_cats_from_flags(a)
     simplify = simplify_from_flags(a)
+    colour = colour_from_flags(a)
     more = {} if simplify is None else {"simplify": simplify}     # (without the flag every call below is as it was)
-    out_dir = result_obj_path(a.log_dir, a.sdf_res, a.iso, a.cam_est, fuse, clean=cleaning is not None, **more)
+    out_dir = result_obj_path(a.log_dir, a.sdf_res, a.iso, a.cam_est, fuse, clean=cleaning is not None, **more,
+                              **({} if colour is None else {"colour": True}))
+    if colour is not None:
+        more["colour"] = colour
     entries = sample_list(categories(a.category), a.test_lst_dir, a.view_num, a.seed, a.num_shards, a.shard_id)
     if fuse:
         runs = fuse_runs(entries, per_mesh)
@@ -667,8 +761,11 @@ def main(argv=None, reconstruct_fn: Optional[Callable] = None) -> dict:
         logf.flush()
         print(s)
 
-    def write(path, verts, faces, *normals):
-        isosurface.write_obj(path, verts, faces, *normals)  # device-to-host copy + file, on a writer thread
+    def write(path, verts, faces, *extras):
+        if colour is None:
+            isosurface.write_obj(path, verts, faces, *extras)  # device-to-host copy + file, on a writer thread
+        else:                                                  # (verts, faces[, normals], colours)
+            isosurface.write_obj(path, verts, faces, *extras[:-1], colours=extras[-1])
         return path
 
     written = empty = unclean = 0
@@ -719,6 +816,8 @@ def main(argv=None, reconstruct_fn: Optional[Callable] = None) -> dict:
         res["unclean"] = unclean
     if simplify is not None:
         res["simplified"] = written - empty
+    if colour is not None:
+        res["coloured"] = written - empty
     return res
 
 

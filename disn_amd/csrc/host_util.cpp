@@ -2,6 +2,7 @@
 //   disn_crc32c -- CRC-32C (Castagnoli) as used by TensorFlow's table / tensor-bundle files
 //                  (disn_amd/tf_checkpoint.py); SSE4.2 crc32 instruction, table fallback.
 #include "../../include/disn_amd.h"
+#include "../../include/disn_amd_colour.h"
 
 #include <cstdint>
 #include <cstring>
@@ -50,9 +51,10 @@ extern "C" uint32_t disn_crc32c(const void* data, size_t n, uint32_t crc) {
 #include <cstdlib>
 #include <string>
 
-// normals == nullptr: the plain file; else nv "vn" lines behind the vertices and faces "f a//a b//b c//c"
+// normals == nullptr: the plain file; else nv "vn" lines behind the vertices and faces "f a//a b//b c//c";
+// colours != nullptr: "v x y z r g b" with r, g, b = c / 255 in four decimals (steps of 1/255 stay apart)
 static int write_obj_impl(const char* path, const float* verts, int64_t nv, const float* normals, const int32_t* faces,
-                          int64_t nf) {
+                          int64_t nf, const uint8_t* colours = nullptr) {
   if (!path || (nv > 0 && !verts) || (nf > 0 && !faces) || nv < 0 || nf < 0) return DISN_E_ARG;
   std::FILE* f = std::fopen(path, "wb");
   if (!f) return DISN_E_ARG;
@@ -65,8 +67,11 @@ static int write_obj_impl(const char* path, const float* verts, int64_t nv, cons
     buf.clear();
   };
   for (int64_t i = 0; i < nv; ++i) {
-    const int n = std::snprintf(line, sizeof line, "v %.9g %.9g %.9g\n", verts[3 * i], verts[3 * i + 1],
-                                verts[3 * i + 2]);
+    const int n = colours ? std::snprintf(line, sizeof line, "v %.9g %.9g %.9g %.4f %.4f %.4f\n", verts[3 * i],
+                                          verts[3 * i + 1], verts[3 * i + 2], colours[3 * i] / 255.0,
+                                          colours[3 * i + 1] / 255.0, colours[3 * i + 2] / 255.0)
+                          : std::snprintf(line, sizeof line, "v %.9g %.9g %.9g\n", verts[3 * i], verts[3 * i + 1],
+                                          verts[3 * i + 2]);
     buf.append(line, n);
     if (buf.size() > (1u << 22) - 256) flush();
   }
@@ -97,6 +102,12 @@ extern "C" int disn_write_obj_normals(const char* path, const float* verts, int6
                                       const int32_t* faces, int64_t nf) {
   if (nv > 0 && !normals) return DISN_E_ARG;
   return write_obj_impl(path, verts, nv, nv > 0 ? normals : nullptr, faces, nf);
+}
+
+extern "C" int disn_write_obj_colours(const char* path, const float* verts, int64_t nv, const uint8_t* colours,
+                                      const float* normals, const int32_t* faces, int64_t nf) {
+  if (nv > 0 && !colours) return DISN_E_ARG;
+  return write_obj_impl(path, verts, nv, nv > 0 ? normals : nullptr, faces, nf, nv > 0 ? colours : nullptr);
 }
 
 // Vertex-only .obj reader for the evaluation driver (a 300 k-vertex mesh in a few tens of ms): the whole file is

@@ -102,21 +102,47 @@ def marching_cubes_batch(sdf: torch.Tensor, sdf_params, res: int, iso: float = 0
     return out
 
 
-def write_obj(path: str, verts, faces, normals=None) -> None:
+def write_obj(path: str, verts, faces, normals=None, colours=None) -> None:
     """Wavefront .obj ("v x y z" / "f a b c", 1-based).  With ``normals`` [nv,3]: one "vn x y z" line per vertex
-    behind the vertices and faces "f a//a b//b c//c"; without, the plain file."""
+    behind the vertices and faces "f a//a b//b c//c"; without, the plain file.  With ``colours`` uint8 [nv,3] (R G B):
+    "v x y z r g b", r, g, b = c / 255 in four decimals (``read_obj_colours``; the readers of plain files stop after
+    the third number of a "v" line and read these as they read the others)."""
     host = lambda a: a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a
     v = np.ascontiguousarray(host(verts), np.float32)
     f = np.ascontiguousarray(host(faces), np.int32)
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-    if normals is None:
+    if normals is None and colours is None:
         check("disn_write_obj", lib().disn_write_obj(path.encode(), v.ctypes.data, v.shape[0], f.ctypes.data, f.shape[0]))
         return
-    n = np.ascontiguousarray(host(normals), np.float32)
-    if n.shape != v.shape:
-        raise ValueError("normals must be [nv,3] like verts, got %s for %s" % (n.shape, v.shape))
-    check("disn_write_obj_normals", lib().disn_write_obj_normals(path.encode(), v.ctypes.data, v.shape[0], n.ctypes.data,
-                                                                 f.ctypes.data, f.shape[0]))
+    n = None
+    if normals is not None:
+        n = np.ascontiguousarray(host(normals), np.float32)
+        if n.shape != v.shape:
+            raise ValueError("normals must be [nv,3] like verts, got %s for %s" % (n.shape, v.shape))
+    if colours is None:
+        check("disn_write_obj_normals", lib().disn_write_obj_normals(path.encode(), v.ctypes.data, v.shape[0],
+                                                                     n.ctypes.data, f.ctypes.data, f.shape[0]))
+        return
+    c = host(colours)
+    if c.dtype != np.uint8 or c.shape != v.shape:
+        raise ValueError("colours must be uint8 [nv,3] like verts, got %s %s for %s" % (c.dtype, c.shape, v.shape))
+    c = np.ascontiguousarray(c)
+    check("disn_write_obj_colours", lib().disn_write_obj_colours(path.encode(), v.ctypes.data, v.shape[0], c.ctypes.data,
+                                                                 None if n is None else n.ctypes.data, f.ctypes.data,
+                                                                 f.shape[0]))
+
+
+def read_obj_colours(path: str) -> np.ndarray:
+    """the colours of a coloured .obj as uint8 [nv,3]: rint(255 c) of the three numbers behind x y z on every "v" line
+    (ValueError for a "v" line without them)"""
+    cs = []
+    for line in open(path):
+        if line.startswith("v "):
+            t = line.split()
+            if len(t) < 7:
+                raise ValueError("%s: a vertex without colour: %r" % (path, line.rstrip()))
+            cs.append([float(x) for x in t[4:7]])
+    return np.rint(np.asarray(cs, np.float64).reshape(-1, 3) * 255.0).astype(np.uint8)
 
 
 def refine_mesh(engine, enc, image_index: int, trans_mat, verts, faces, sdf_params, res: int, iso: float = 0.0,

@@ -20,6 +20,11 @@ the [B,5] sizes per group.
 Not in the reference: simplification by quadric vertex clustering (``--simplify CELLS`` of ``create_sdf`` and ``demo``,
 DESIGN 4za).  ``simplify_arrays`` is the rule, on the host; ``simplify_meshes_device`` / ``simplify_arrays_device``
 (mesh_simplify.hip) give its integers and its position bits for meshes that lie on the device.
+
+Not in the reference either: vertex colours from the input views (``--colour`` of ``create_sdf`` and ``demo``, DESIGN
+4zb).  ``zbuffer_arrays`` / ``colour_arrays`` are the rule, on the host; ``zbuffer_meshes_device``,
+``colour_meshes_device`` and ``colour_arrays_device`` (mesh_colour.hip) give its depth bits and its colour bytes for
+meshes that lie on the device.
 """
 from __future__ import annotations
 
@@ -229,6 +234,269 @@ def simplify_arrays(verts, faces, box, cells: int, dedup: bool = True, placement
         keep = np.zeros(nf, bool)
         keep[ids[lowest]] = True
     return out_v, g[keep].astype(np.int32).reshape(-1, 3), vmap.astype(np.int32), first.astype(np.int32)
+
+
+# ---- vertex colours from the input views: the rule (the device restates it, mesh_colour.hip) ----------
+IMG = 137                                   # the views are IMG x IMG, pixel centres at integer (u, v)
+COLOUR_SAMPLES = (1, 2, 4)                  # z-buffer samples per image pixel and axis
+COLOUR_MAX_VIEWS, COLOUR_MAX_FILL = 256, 4096
+CLASS_FALLBACK, CLASS_SEEN, CLASS_MIRROR, CLASS_FILL = 0, 1, 2, 3
+MIRROR_FRONT = 32                           # a reflection may lie this many rel_tol in FRONT of the stored surface
+_UNCOLOURED = 255                           # the working state of ``seen`` before the fallback
+_GREY16 = 32768                             # mid grey: 128 of 255
+_TINY = np.float32(1.17549435e-38)          # the smallest positive normal float32
+_F32_0, _F32_1, _F32_HALF = np.float32(0.0), np.float32(1.0), np.float32(0.5)
+
+
+def _colour_params(S, rel_tol, mirror_axis, fill_iters):
+    if S not in COLOUR_SAMPLES:
+        raise ValueError("S must be one of %s, got %r" % (COLOUR_SAMPLES, S))
+    if mirror_axis not in (None, 0, 1, 2):
+        raise ValueError("mirror_axis must be None, 0, 1 or 2, got %r" % (mirror_axis,))
+    if int(fill_iters) != fill_iters or not 0 <= int(fill_iters) <= COLOUR_MAX_FILL:
+        raise ValueError("fill_iters must be in 0..%d, got %r" % (COLOUR_MAX_FILL, fill_iters))
+    tol = np.float32(rel_tol)
+    if not (tol >= 0.0 and tol < 1.0):
+        raise ValueError("rel_tol must be in [0, 1), got %r" % (rel_tol,))
+    return int(S), tol, -1 if mirror_axis is None else int(mirror_axis), int(fill_iters)
+
+
+def _colour_mesh(verts, faces):
+    v, f = _host(verts, faces)
+    if f.shape[0] and (f.min() < 0 or f.max() >= v.shape[0]):
+        raise ValueError("face index out of range (mesh of %d vertices)" % v.shape[0])
+    if not np.isfinite(v).all():
+        raise ValueError("a vertex coordinate is not finite")
+    return v, f
+
+
+def _colour_views(trans_mats) -> np.ndarray:
+    T = np.ascontiguousarray(trans_mats, np.float32)
+    if T.ndim == 2:
+        T = T[None]
+    if T.ndim != 3 or T.shape[1:] != (4, 3) or not 1 <= T.shape[0] <= COLOUR_MAX_VIEWS:
+        raise ValueError("trans_mats must be [V,4,3] with 1 <= V <= %d, got %s" % (COLOUR_MAX_VIEWS, T.shape))
+    return T
+
+
+def _screen(v: np.ndarray, T: np.ndarray, S: int):
+    """float32, the gather's projection [p, 1] . T = (u w, v w, w) in its order of operations -> sub-pixel position
+    (x, y) = ((u + 1/2) S, (v + 1/2) S), q = 1/w, (u, v), and ok = w > 0 with x, y, q finite"""
+    with np.errstate(all="ignore"):
+        p = []
+        for j in range(3):
+            a = v[:, 0] * T[0, j] + v[:, 1] * T[1, j]
+            a = a + v[:, 2] * T[2, j]
+            p.append(a + T[3, j])
+        w = p[2]
+        u, vv, q = p[0] / w, p[1] / w, _F32_1 / w
+        x, y = (u + _F32_HALF) * np.float32(S), (vv + _F32_HALF) * np.float32(S)
+        ok = (w > 0.0) & np.isfinite(x) & np.isfinite(y) & np.isfinite(q)
+    return x, y, q, u, vv, ok
+
+
+def _cover(t, cx, cy):
+    """the sub-pixels with centres (cx, cy) against the triangles ``t`` (a dict of float32 arrays that broadcast with
+    cx, cy) -> (inside, value): conservative coverage and the biased, clamped plane of q"""
+    inside = None
+    for k in range(3):
+        a, b, xi, yi = t["a"][k], t["b"][k], t["ex"][k], t["ey"][k]
+        e = ((a * (cx - xi) + b * (cy - yi)) + _F32_HALF * (np.abs(a) + np.abs(b))) >= 0.0
+        inside = e if inside is None else inside & e
+    val = t["q0"] + (t["gx"] * (cx - t["x0"]) + t["gy"] * (cy - t["y0"]))
+    val = np.where(val > t["qmax"], t["qmax"], val)
+    val = np.where(val < t["qmin"], t["qmin"], val)
+    val = val - (np.abs(t["gx"]) + np.abs(t["gy"]))
+    return inside, np.where(val >= _TINY, val, _TINY).astype(np.float32)
+
+
+def _raster_view(v: np.ndarray, f: np.ndarray, T: np.ndarray, S: int) -> np.ndarray:
+    N = IMG * S
+    zb = np.zeros(N * N, np.uint32)               # positive floats order as their bits do
+    x, y, q, _, _, ok = _screen(v, T, S)
+    keep = np.nonzero(ok[f[:, 0]] & ok[f[:, 1]] & ok[f[:, 2]])[0] if f.shape[0] else np.zeros(0, np.int64)
+    if keep.size == 0:
+        return zb.view(np.float32).reshape(N, N)
+    c = f[keep]
+    with np.errstate(all="ignore"):
+        X, Y, Q = [x[c[:, k]] for k in range(3)], [y[c[:, k]] for k in range(3)], [q[c[:, k]] for k in range(3)]
+        area = (X[1] - X[0]) * (Y[2] - Y[0]) - (X[2] - X[0]) * (Y[1] - Y[0])
+        dq1, dq2 = Q[1] - Q[0], Q[2] - Q[0]
+        gx = (dq1 * (Y[2] - Y[0]) - dq2 * (Y[1] - Y[0])) / area
+        gy = (dq2 * (X[1] - X[0]) - dq1 * (X[2] - X[0])) / area
+        fi0, fi1 = np.floor(np.minimum(np.minimum(X[0], X[1]), X[2])), np.floor(np.maximum(np.maximum(X[0], X[1]), X[2]))
+        fj0, fj1 = np.floor(np.minimum(np.minimum(Y[0], Y[1]), Y[2])), np.floor(np.maximum(np.maximum(Y[0], Y[1]), Y[2]))
+        good = (np.isfinite(area) & (area != 0.0) & np.isfinite(gx) & np.isfinite(gy)
+                & (fi1 >= 0.0) & (fi0 <= N - 1.0) & (fj1 >= 0.0) & (fj0 <= N - 1.0))
+    g = np.nonzero(good)[0]
+    if g.size == 0:
+        return zb.view(np.float32).reshape(N, N)
+    X, Y, Q = [a[g] for a in X], [a[g] for a in Y], [a[g] for a in Q]
+    s = np.where(area[g] > 0.0, _F32_1, -_F32_1).astype(np.float32)
+    t = {"a": [s * (Y[i] - Y[j]) for i, j in ((1, 2), (2, 0), (0, 1))],
+         "b": [s * (X[j] - X[i]) for i, j in ((1, 2), (2, 0), (0, 1))],
+         "ex": [X[1], X[2], X[0]], "ey": [Y[1], Y[2], Y[0]], "x0": X[0], "y0": Y[0], "q0": Q[0], "gx": gx[g], "gy": gy[g],
+         "qmin": np.minimum(np.minimum(Q[0], Q[1]), Q[2]), "qmax": np.maximum(np.maximum(Q[0], Q[1]), Q[2])}
+    i0 = np.maximum(fi0[g], _F32_0).astype(np.int64)
+    i1 = np.minimum(fi1[g], np.float32(N - 1)).astype(np.int64)
+    j0 = np.maximum(fj0[g], _F32_0).astype(np.int64)
+    j1 = np.minimum(fj1[g], np.float32(N - 1)).astype(np.int64)
+    bw, bh = i1 - i0 + 1, j1 - j0 + 1
+    pick = lambda m: {k: ([a[m] for a in val] if isinstance(val, list) else val[m]) for k, val in t.items()}
+    # (how the triangles are grouped is the host's business: the buffer keeps a maximum, whatever the order)
+    small = np.nonzero((bw <= 8) & (bh <= 8))[0]
+    if small.size:
+        ts = pick(small)
+        for dj in range(int(bh[small].max())):
+            for di in range(int(bw[small].max())):
+                m = (di < bw[small]) & (dj < bh[small])
+                if not m.any():
+                    continue
+                ii, jj = i0[small] + di, j0[small] + dj
+                inside, val = _cover(ts, ii.astype(np.float32) + _F32_HALF, jj.astype(np.float32) + _F32_HALF)
+                m &= inside
+                np.maximum.at(zb, (jj * N + ii)[m], val.view(np.uint32)[m])
+    for n in np.nonzero((bw > 8) | (bh > 8))[0]:
+        tn = pick(n)
+        ii, jj = np.arange(i0[n], i1[n] + 1), np.arange(j0[n], j1[n] + 1)
+        inside, val = _cover(tn, (ii.astype(np.float32) + _F32_HALF)[None, :], (jj.astype(np.float32) + _F32_HALF)[:, None])
+        idx = (jj[:, None] * N + ii[None, :])[inside]
+        np.maximum.at(zb, idx, val.view(np.uint32)[inside])
+    return zb.view(np.float32).reshape(N, N)
+
+
+def zbuffer_arrays(verts, faces, trans_mats, S: int = 2) -> np.ndarray:
+    """Depth maps of a mesh from its views, on the host: THE SPECIFICATION of ``zbuffer_meshes_device`` (same bits).
+    -> [V, 137 S, 137 S] float32 of q = 1/w, larger is nearer, 0 is empty.  Everything is float32, operation by operation.
+
+    A vertex goes to x = (u + 1/2) S, y = (v + 1/2) S with [p, 1] . trans_mat = (u w, v w, w); sub-pixel (i, j) covers
+    [i, i+1) x [j, j+1) and is stored at [j, i].  A triangle with a vertex at w <= 0 (or x, y, 1/w not finite), of zero
+    screen area, or whose plane of q has no finite gradient, is skipped.  Coverage is conservative: a sub-pixel of the
+    bounding box, clipped to the image, belongs to the triangle when its three edge functions at the centre, oriented by
+    the sign of the area and each raised by (|a| + |b|) / 2, are >= 0.  The value is the plane of q at the centre,
+    clamped to the vertices' [min q, max q], THEN lowered by |dq/dx| + |dq/dy| and floored at the smallest positive
+    normal float; the buffer keeps the maximum (of the bits: positive floats order as their bits do).
+    ValueError for a face index out of range or a coordinate that is not finite."""
+    if S not in COLOUR_SAMPLES:
+        raise ValueError("S must be one of %s, got %r" % (COLOUR_SAMPLES, S))
+    v, f = _colour_mesh(verts, faces)
+    T = _colour_views(trans_mats)
+    return np.stack([_raster_view(v, f, T[k], int(S)) for k in range(T.shape[0])])
+
+
+def _seen_view(v, T, zb, alpha, S: int, tol, reflected: bool):
+    """-> (seen bool [n], u, v): w > 0, the sub-pixel inside the image, 1/w >= (1 - tol) zbuf there (and, for a
+    reflection, 1/w <= (1 + 32 tol) zbuf: on the visible surface), alpha > 0 at the nearest image pixel"""
+    N = IMG * S
+    x, y, q, u, vv, ok = _screen(v, T, S)
+    with np.errstate(all="ignore"):
+        fi, fj = np.floor(x), np.floor(y)
+        ok = ok & (fi >= 0.0) & (fi <= N - 1.0) & (fj >= 0.0) & (fj <= N - 1.0)
+        i, j = np.where(ok, fi, _F32_0).astype(np.int64), np.where(ok, fj, _F32_0).astype(np.int64)
+        z = zb[j, i]
+        ok &= q >= (_F32_1 - tol) * z
+        if reflected:
+            ok &= q <= (_F32_1 + np.float32(MIRROR_FRONT) * tol) * z
+        u, vv = np.where(ok, u, _F32_0), np.where(ok, vv, _F32_0)
+        if alpha is not None:
+            top = np.float32(IMG - 1)
+            pu = np.rint(np.minimum(np.maximum(u, _F32_0), top)).astype(np.int64)
+            pv = np.rint(np.minimum(np.maximum(vv, _F32_0), top)).astype(np.int64)
+            ok &= alpha[pv, pu] > 0
+    return ok, u, vv
+
+
+def _sample16(image, u, vv, bgr: bool) -> np.ndarray:
+    """bilinear at (u, v) clamped to [0, 136], float32 lerps in the gather's form -> rint(c 65535) int64 [n,3]"""
+    top = np.float32(IMG - 1)
+    uc, vc = np.minimum(np.maximum(u, _F32_0), top), np.minimum(np.maximum(vv, _F32_0), top)
+    fx0, fy0 = np.floor(uc), np.floor(vc)
+    x0, y0 = fx0.astype(np.int64), fy0.astype(np.int64)
+    x1, y1 = np.minimum(x0 + 1, IMG - 1), np.minimum(y0 + 1, IMG - 1)
+    xl, yl = (uc - fx0)[:, None], (vc - fy0)[:, None]
+    tl, tr, bl, br = image[y0, x0], image[y0, x1], image[y1, x0], image[y1, x1]
+    with np.errstate(all="ignore"):
+        t = tl + (tr - tl) * xl
+        b = bl + (br - bl) * xl
+        val = t + (b - t) * yl
+        val = np.where(val > 0.0, val, _F32_0)
+        val = np.where(val < 1.0, val, _F32_1)
+        c = np.rint(val * np.float32(65535.0)).astype(np.int64)
+    return c[:, ::-1] if bgr else c
+
+
+def _mean_half_up(total: np.ndarray, n: np.ndarray) -> np.ndarray:
+    return (2 * total + n) // (2 * n)
+
+
+def colour_arrays(verts, faces, images, trans_mats, alpha=None, S: int = 2, rel_tol: float = 1e-3, mirror_axis=None,
+                  fill_iters: int = 32, bgr: bool = True) -> Tuple[np.ndarray, np.ndarray]:
+    """Vertex colours of a mesh from its V input views, on the host: THE SPECIFICATION of ``colour_meshes_device`` (same
+    bytes).  images [V,137,137,3] float32 in [0,1], trans_mats [V,4,3], alpha [V,137,137] uint8 or None.
+    -> (colours uint8 [nv,3], R G B; seen uint8 [nv], the class).
+
+    seen      vertex p is seen by view k when w > 0, its sub-pixel lies inside the image, 1/w >= (1 - rel_tol) zbuf
+              there (``zbuffer_arrays``; an empty cell hides nothing) and, with ``alpha``, alpha > 0 at the nearest
+              image pixel rint(clamp(u)), rint(clamp(v))
+    sample    bilinear at (u, v) clamped to [0, 136] in float32, clamped to [0, 1]; a channel is rint(c 65535), an integer;
+              ``bgr``: the images are in cv2 order, channel 2 is written first
+    class 1   seen by >= 1 view: the integer mean over those views, (2 sum + n) // (2 n)
+    class 2   ``mirror_axis``: an unseen vertex whose reflection in that coordinate plane passes the same test and also
+              1/w <= (1 + 32 rel_tol) zbuf (it lies ON the visible surface, not in front of it; the stored value is
+              lowered by a sub-pixel's extent of its plane, 0.3 to 2 % of q on a 32 x 16 sphere, so the bound on this
+              side is ``MIRROR_FRONT`` = 32 times wider) takes the mean of the reflection's samples
+    class 3   up to ``fill_iters`` rounds: a still uncoloured vertex that shares a face with coloured ones takes the
+              integer mean of those corners (once per shared face) as they were before the round
+    class 0   what is left: the integer mean of the mesh's coloured vertices, or mid grey (128) when there are none
+    colours = (c16 255 + 32767) // 65535.  Every sum is an integer sum: no result depends on an order of additions.
+    ValueError for a face index out of range or a coordinate that is not finite."""
+    S, tol, axis, fill_iters = _colour_params(S, rel_tol, mirror_axis, fill_iters)
+    v, f = _colour_mesh(verts, faces)
+    T = _colour_views(trans_mats)
+    V, nv = T.shape[0], v.shape[0]
+    img = np.ascontiguousarray(images, np.float32).reshape(V, IMG, IMG, 3)
+    al = None if alpha is None else np.ascontiguousarray(alpha, np.uint8).reshape(V, IMG, IMG)
+    zb = [_raster_view(v, f, T[k], S) for k in range(V)]
+    c16, cls = np.zeros((nv, 3), np.int64), np.full(nv, _UNCOLOURED, np.uint8)
+    if nv == 0:
+        return np.zeros((0, 3), np.uint8), np.zeros(0, np.uint8)
+
+    def gather(p, reflected):
+        total, n = np.zeros((nv, 3), np.int64), np.zeros(nv, np.int64)
+        for k in range(V):
+            ok, u, vv = _seen_view(p, T[k], zb[k], None if al is None else al[k], S, tol, reflected)
+            total[ok] += _sample16(img[k], u[ok], vv[ok], bgr)
+            n += ok
+        return total, n
+
+    total, n = gather(v, False)
+    hit = n > 0
+    c16[hit], cls[hit] = _mean_half_up(total[hit], n[hit, None]), CLASS_SEEN
+    if axis >= 0:
+        r = v.copy()
+        r[:, axis] = -r[:, axis]
+        total, n = gather(r, True)
+        hit = (n > 0) & (cls == _UNCOLOURED)
+        c16[hit], cls[hit] = _mean_half_up(total[hit], n[hit, None]), CLASS_MIRROR
+    for _ in range(fill_iters):
+        done = cls != _UNCOLOURED
+        total, n = np.zeros((nv, 3), np.int64), np.zeros(nv, np.int64)
+        for k in range(3):
+            for m in range(3):
+                if m != k:
+                    sel = ~done[f[:, k]] & done[f[:, m]]
+                    np.add.at(total, f[sel, k], c16[f[sel, m]])
+                    np.add.at(n, f[sel, k], 1)
+        new = ~done & (n > 0)
+        if not new.any():
+            break
+        c16[new], cls[new] = _mean_half_up(total[new], n[new, None]), CLASS_FILL
+    done = cls != _UNCOLOURED
+    if not done.all():
+        k = int(done.sum())
+        c16[~done] = _mean_half_up(c16[done].sum(0), np.int64(k)) if k else _GREY16
+        cls[~done] = CLASS_FALLBACK
+    return ((c16 * 255 + 32767) // 65535).astype(np.uint8), cls
 
 
 # ---- the device path (mesh_clean.hip) --------------------------------------------------------------------------
@@ -463,6 +731,127 @@ def simplify_arrays_device(verts, faces, box, cells: int, dedup: bool = True):
         msg = str(e)
         raise ValueError(msg[len("mesh 0: "):] if msg.startswith("mesh 0: ") else msg) from e
     return simplified[0][0], simplified[0][1], maps[0][0], maps[0][1]
+
+
+# ---- vertex colours on the device (mesh_colour.hip) -------------------------------------------------------------
+def _colour_inputs(meshes, trans_mats, views_per_mesh: int, S: int):
+    """-> (B, V, verts, v_off, faces, f_off, trans_mat [B,V,4,3] device, workspace)"""
+    import torch
+
+    from . import ops
+    if S not in COLOUR_SAMPLES:
+        raise ValueError("S must be one of %s, got %r" % (COLOUR_SAMPLES, S))
+    V, B = int(views_per_mesh), len(meshes)
+    if not 1 <= V <= COLOUR_MAX_VIEWS:
+        raise ValueError("views_per_mesh must be in 1..%d, got %r" % (COLOUR_MAX_VIEWS, views_per_mesh))
+    (v, v_off), (f, f_off) = (_pack([m[0] for m in meshes], torch.float32, "verts"),
+                              _pack([m[1] for m in meshes], torch.int32, "faces"))
+    dev = v.device
+    tm = torch.as_tensor(np.ascontiguousarray(trans_mats.detach().cpu().numpy() if hasattr(trans_mats, "detach")
+                                              else trans_mats, np.float32))
+    if tm.numel() != B * V * 12:
+        raise ValueError("trans_mats must hold %d meshes x %d views x [4,3], got %s" % (B, V, tuple(tm.shape)))
+    tm_d = torch.empty((B, V, 4, 3), dtype=torch.float32, device=dev)
+    tm_d.copy_(tm.reshape(B, V, 4, 3))
+    need = lib().disn_mesh_colour_workspace_bytes(B, V, int(v_off[-1]), int(f_off[-1]), int(S))
+    if need == 0:
+        raise ValueError("unsupported batch: %d meshes, %d views, %d vertices, %d triangles"
+                         % (B, V, v_off[-1], f_off[-1]))
+    return B, V, v, v_off, f, f_off, tm_d, ops._ws(need, dev)
+
+
+def _colour_status(status, v_off, strict: bool) -> np.ndarray:
+    st = status.cpu().numpy()
+    for b in np.nonzero(st)[0] if strict else ():
+        if st[b] == STATUS_INDEX:
+            raise ValueError("mesh %d: face index out of range (mesh of %d vertices)" % (b, v_off[b + 1] - v_off[b]))
+        if st[b] == STATUS_FINITE:
+            raise ValueError("mesh %d: a vertex coordinate is not finite" % b)
+        raise RuntimeError("mesh %d: status %d" % (b, st[b]))
+    return st
+
+
+def zbuffer_meshes_device(meshes, trans_mats, views_per_mesh: int = 1, S: int = 2, strict: bool = True):
+    """``zbuffer_arrays`` for a group of meshes that lie on the device: depth maps without a BVH.  ``meshes``: B x
+    (verts [nv,3] float32, faces [nf,3] int32, ...) device tensors; ``trans_mats`` [B, V, 4, 3] (host or device), V =
+    ``views_per_mesh``.  -> [B, V, 137 S, 137 S] float32 device tensor with the bits of ``zbuffer_arrays`` (q = 1/w, 0
+    empty).  ValueError for a face index out of range or a coordinate that is not finite -- with ``strict=False`` such
+    a mesh gets empty maps and the call returns (zbuf, status int32 [B] on the host)."""
+    import torch
+
+    from . import ops
+    from ._lib import check
+    meshes = [tuple(m) for m in meshes]
+    if not meshes:
+        return torch.zeros((0, int(views_per_mesh), IMG * S, IMG * S)) if strict else (None, np.zeros(0, np.int32))
+    B, V, v, v_off, f, f_off, tm, ws = _colour_inputs(meshes, trans_mats, views_per_mesh, S)
+    dev = v.device
+    with torch.cuda.device(dev):
+        zbuf = torch.empty((B, V, IMG * S, IMG * S), dtype=torch.float32, device=dev)
+        status = torch.empty(B, dtype=torch.int32, device=dev)
+        check("disn_mesh_zbuffer_batch", lib().disn_mesh_zbuffer_batch(
+            v.data_ptr(), f.data_ptr(), v_off.ctypes.data, f_off.ctypes.data, B, tm.data_ptr(), V, int(S),
+            zbuf.data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel(), ops._stream()))
+        st = _colour_status(status, v_off, strict)
+    return zbuf if strict else (zbuf, st)
+
+
+def colour_meshes_device(meshes, imgs, trans_mats, views_per_mesh: int = 1, alpha=None, S: int = 2,
+                         rel_tol: float = 1e-3, mirror_axis=None, fill_iters: int = 32, bgr: bool = True,
+                         strict: bool = True):
+    """``colour_arrays`` for a group of meshes that lie on the device.  ``meshes``: B x (verts [nv,3] float32, faces
+    [nf,3] int32, ...) device tensors (the views the earlier stages return are used in place); ``imgs`` [B, V, 137, 137,
+    3] float32 device tensor in [0,1] (or anything with that many elements), ``trans_mats`` [B, V, 4, 3], ``alpha`` None
+    or [B, V, 137, 137] uint8; V = ``views_per_mesh``.  ONE call, no read-back but the B status words.
+    -> (colours, seen): B x uint8 [nv,3] (R G B) and B x uint8 [nv] (the class) device views, the bytes of
+    ``colour_arrays``.  An empty mesh gives empty arrays.  ValueError for a face index out of range or a coordinate that
+    is not finite -- with ``strict=False`` such a mesh is mid grey, class 0, and the call returns (colours, seen,
+    status int32 [B] on the host)."""
+    import torch
+
+    from . import ops
+    from ._lib import check
+    S, tol, axis, fill_iters = _colour_params(S, rel_tol, mirror_axis, fill_iters)
+    meshes = [tuple(m) for m in meshes]
+    if not meshes:
+        return ([], []) if strict else ([], [], np.zeros(0, np.int32))
+    B, V, v, v_off, f, f_off, tm, ws = _colour_inputs(meshes, trans_mats, views_per_mesh, S)
+    dev, nv = v.device, int(v_off[-1])
+    if not (isinstance(imgs, torch.Tensor) and imgs.is_cuda and imgs.dtype == torch.float32
+            and imgs.numel() == B * V * IMG * IMG * 3):
+        raise TypeError("imgs must be a float32 CUDA tensor of %d x %d x 137 x 137 x 3 values (the HIP path has no CPU "
+                        "fallback)" % (B, V))
+    imgs = imgs.contiguous()
+    if alpha is not None:
+        if not (isinstance(alpha, torch.Tensor) and alpha.is_cuda and alpha.dtype == torch.uint8
+                and alpha.numel() == B * V * IMG * IMG):
+            raise TypeError("alpha must be a uint8 CUDA tensor of %d x %d x 137 x 137 values" % (B, V))
+        alpha = alpha.contiguous()
+    with torch.cuda.device(dev):
+        colours = torch.empty((nv, 3), dtype=torch.uint8, device=dev)
+        seen = torch.empty(nv, dtype=torch.uint8, device=dev)
+        status = torch.empty(B, dtype=torch.int32, device=dev)
+        check("disn_mesh_colour_batch", lib().disn_mesh_colour_batch(
+            v.data_ptr(), f.data_ptr(), v_off.ctypes.data, f_off.ctypes.data, B, imgs.data_ptr(),
+            None if alpha is None else alpha.data_ptr(), tm.data_ptr(), V, S, float(tol), axis, fill_iters,
+            1 if bgr else 0, colours.data_ptr(), seen.data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel(),
+            ops._stream()))
+        st = _colour_status(status, v_off, strict)
+    cs = [colours[int(v_off[b]):int(v_off[b + 1])] for b in range(B)]
+    ss = [seen[int(v_off[b]):int(v_off[b + 1])] for b in range(B)]
+    return (cs, ss) if strict else (cs, ss, st)
+
+
+def colour_arrays_device(verts, faces, images, trans_mats, alpha=None, **kw):
+    """``colour_arrays`` for one mesh on the device: images [V,137,137,3] device float32, trans_mats [V,4,3], alpha None
+    or [V,137,137] device uint8 -> (colours uint8 [nv,3], seen uint8 [nv]) device tensors; the same ValueErrors"""
+    V = int(np.asarray(trans_mats.shape if hasattr(trans_mats, "shape") else np.shape(trans_mats))[:-2].prod())
+    try:
+        cs, ss = colour_meshes_device([(verts, faces)], images, trans_mats, views_per_mesh=max(V, 1), alpha=alpha, **kw)
+    except ValueError as e:
+        msg = str(e)
+        raise ValueError(msg[len("mesh 0: "):] if msg.startswith("mesh 0: ") else msg) from e
+    return cs[0], ss[0]
 
 
 def clean_single_mesh(src: str, tar: str, dist_thresh: float = 0.5, num_thresh: float = 0.3,
