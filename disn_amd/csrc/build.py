@@ -55,7 +55,8 @@ SOURCES = {
     "mesh_host.cpp": [],
 }
 COMMON = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
-HEADERS = ["kernels.hpp", "tuning.hpp", "h2_common.hpp", "mc_tables.h", "mesh_bvh.hpp", os.path.join(ROOT, "include", "disn_amd.h"),
+HEADERS = ["kernels.hpp", "tuning.hpp", "h2_common.hpp", "mc_tables.h", "mesh_bvh.hpp", "mesh_batch.hpp",
+           os.path.join(ROOT, "include", "disn_amd.h"),
            os.path.join(ROOT, "include", "disn_amd_simplify.h"), os.path.join(ROOT, "include", "disn_amd_colour.h")]
 
 

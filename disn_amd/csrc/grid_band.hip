@@ -203,21 +203,14 @@ struct BandWs {
 
 BandWs band_layout(void* ws, int R, int s) {
   const size_t n = (size_t)R + 1, np = n * n * n, C = (size_t)(R / s), nc = C * C * C;
-  char* base = static_cast<char*>(ws);
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    off = (off + 255) & ~size_t(255);
-    unsigned* p = base ? reinterpret_cast<unsigned*>(base + off) : nullptr;
-    off += bytes;
-    return p;
-  };
+  WsCursor c(ws);
   BandWs w;
-  w.flag = take(np * 4);
-  w.off = take(np * 4);
-  w.bsum = take(((np + kScanBlockItems - 1) / kScanBlockItems + 1) * 4);
-  w.mtmp = take(nc * 4);
-  w.coff = take(nc * 4);
-  w.total = (off + 255) & ~size_t(255);
+  w.flag = c.take<unsigned>(np);
+  w.off = c.take<unsigned>(np);
+  w.bsum = c.take<unsigned>(scan_bsum_items(np));
+  w.mtmp = c.take<unsigned>(nc);
+  w.coff = c.take<unsigned>(nc);
+  w.total = c.next();
   return w;
 }
 

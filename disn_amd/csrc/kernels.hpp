@@ -285,6 +285,23 @@ hipError_t mc_faces_batch_launch(const float* vol, int B, int R, float iso, int*
 constexpr int kScanBlockItems = 4096;
 hipError_t exclusive_scan(const unsigned* in, unsigned* out, size_t n, unsigned* bsum, unsigned long long* total,
                           hipStream_t st);
+inline size_t scan_bsum_items(size_t n) { return (n + kScanBlockItems - 1) / kScanBlockItems + 1; }   // bsum's uint32s
+
+// Hands out a caller's workspace piece by piece: every piece starts at a multiple of 256 bytes.  With ws == nullptr
+// the pieces are null and only the offsets count (the *_workspace_bytes queries).
+struct WsCursor {
+  char* base;
+  size_t off = 0;
+  explicit WsCursor(void* ws) : base(static_cast<char*>(ws)) {}
+  size_t next() const { return (off + 255) & ~size_t(255); }     // where the next piece starts; at the end, the total
+  template <typename T>
+  T* take(size_t count) {
+    off = next();
+    T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
+    off += count * sizeof(T);
+    return p;
+  }
+};
 
 // ---- mesh_clean.hip (compiled with -ffp-contract=off) ----------------------------
 // small-part cleanup of the batch disn_mc_emit_batch leaves: disn_mesh_components_device, disn_mesh_clean_count_batch,

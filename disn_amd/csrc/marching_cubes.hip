@@ -308,21 +308,14 @@ struct McWs {
 
 static McWs mc_layout(void* ws, int R) {
   const size_t n = (size_t)R + 1, ne = 3 * n * n * n, nc = (size_t)R * R * R;
-  char* base = static_cast<char*>(ws);
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    off = (off + 255) & ~size_t(255);
-    unsigned* p = base ? reinterpret_cast<unsigned*>(base + off) : nullptr;
-    off += bytes;
-    return p;
-  };
+  WsCursor c(ws);
   McWs w;
-  w.eflag = take(ne * 4);
-  w.eidx = take(ne * 4);
-  w.ccount = take(nc * 4);
-  w.coff = take(nc * 4);
-  w.bsum = take(((ne + kScanBlock - 1) / kScanBlock + 1) * 4);
-  w.total = (off + 255) & ~size_t(255);
+  w.eflag = c.take<unsigned>(ne);
+  w.eidx = c.take<unsigned>(ne);
+  w.ccount = c.take<unsigned>(nc);
+  w.coff = c.take<unsigned>(nc);
+  w.bsum = c.take<unsigned>(scan_bsum_items(ne));
+  w.total = c.next();
   return w;
 }
 
@@ -336,22 +329,15 @@ struct McBatchWs {
 
 static McBatchWs mc_batch_layout(void* ws, int B, int R) {
   const size_t n = (size_t)R + 1, ne = (size_t)B * 3 * n * n * n, nc = (size_t)B * R * R * R;
-  char* base = static_cast<char*>(ws);
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    off = (off + 255) & ~size_t(255);
-    unsigned* p = base ? reinterpret_cast<unsigned*>(base + off) : nullptr;
-    off += bytes;
-    return p;
-  };
+  WsCursor c(ws);
   McBatchWs w;
-  w.eflag = take(ne * 4);
-  w.eidx = take(ne * 4);
-  w.ccount = take(nc * 4);
-  w.coff = take(nc * 4);
-  w.bsum = take(((ne + kScanBlock - 1) / kScanBlock + 1) * 4);
-  w.totals = reinterpret_cast<unsigned long long*>(take(2 * sizeof(unsigned long long)));
-  w.total = (off + 255) & ~size_t(255);
+  w.eflag = c.take<unsigned>(ne);
+  w.eidx = c.take<unsigned>(ne);
+  w.ccount = c.take<unsigned>(nc);
+  w.coff = c.take<unsigned>(nc);
+  w.bsum = c.take<unsigned>(scan_bsum_items(ne));
+  w.totals = c.take<unsigned long long>(2);
+  w.total = c.next();
   return w;
 }
 

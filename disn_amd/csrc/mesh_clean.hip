@@ -16,61 +16,15 @@
 //   claim/find  a probe index that advances once per step, at most `mask + 1` steps; a full table raises status 3
 // Everything the emit writes is a function of integers alone; the one order-dependent quantity is the float64
 // coordinate sum behind the centroid test (hardware float64 atomic add), DESIGN 4z.  Compiled with -ffp-contract=off.
-#include "kernels.hpp"
+// (mesh_of, the tables, the face validator and the host-side helpers are those of mesh_batch.hpp.)
+#include "mesh_batch.hpp"
 
 #include <vector>
 
 namespace disn {
 namespace {
 
-constexpr unsigned long long kEmptyKey = ~0ull;
-constexpr unsigned kNone = 0xFFFFFFFFu;
-constexpr int kThreads = 256;
-
-// the mesh of flat element i: the largest b with off[b] <= i (empty meshes are stepped over)
-__device__ __forceinline__ int mesh_of(const long long* __restrict__ off, int B, long long i) {
-  int lo = 0, hi = B - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (off[mid] <= i) lo = mid;
-    else hi = mid - 1;
-  }
-  return lo;
-}
-
-__device__ __forceinline__ unsigned long long mix64(unsigned long long x) {
-  x ^= x >> 30; x *= 0xbf58476d1ce4e5b9ull;
-  x ^= x >> 27; x *= 0x94d049bb133111ebull;
-  return x ^ (x >> 31);
-}
-
-// the slot of `key`, claiming an empty one; -1 when `mask + 1` probes found neither (table full)
-__device__ __forceinline__ long long table_claim(unsigned long long* keys, unsigned long long mask,
-                                                 unsigned long long key, bool* is_new) {
-  unsigned long long h = mix64(key) & mask;
-  for (unsigned long long probe = 0; probe <= mask; ++probe) {
-    const unsigned long long prev = atomicCAS(&keys[h], kEmptyKey, key);
-    if (prev == kEmptyKey || prev == key) {
-      *is_new = prev == kEmptyKey;
-      return (long long)h;
-    }
-    h = (h + 1) & mask;
-  }
-  return -1;
-}
-
-// the slot of `key` in a table no one writes any more; -1 when it is not there
-__device__ __forceinline__ long long table_find(const unsigned long long* __restrict__ keys, unsigned long long mask,
-                                                unsigned long long key) {
-  unsigned long long h = mix64(key) & mask;
-  for (unsigned long long probe = 0; probe <= mask; ++probe) {
-    const unsigned long long k = keys[h];
-    if (k == key) return (long long)h;
-    if (k == kEmptyKey) return -1;
-    h = (h + 1) & mask;
-  }
-  return -1;
-}
+enum { ST_NOTHING_KEPT = 1 };
 
 __device__ __forceinline__ int find_root(int* parent, int x) {
   int p;
@@ -90,28 +44,8 @@ __device__ __forceinline__ void unite(int* parent, int a, int b) {
   }
 }
 
-#define GRID_STRIDE(i, n) \
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < (n); i += (long long)gridDim.x * blockDim.x)
-
 __global__ __launch_bounds__(kThreads) void init_parent_kernel(int* __restrict__ parent, long long nf) {
   GRID_STRIDE(f, nf) parent[f] = (int)f;
-}
-
-// status 2 for a mesh with an index outside [0, nv_b): the ONLY kernel that looks at an index before it is checked
-__global__ __launch_bounds__(kThreads) void validate_kernel(const int* __restrict__ faces,
-                                                            const long long* __restrict__ voff,
-                                                            const long long* __restrict__ foff, int B, long long nf,
-                                                            int* __restrict__ status) {
-  GRID_STRIDE(f, nf) {
-    const int b = mesh_of(foff, B, f);
-    const long long nvb = voff[b + 1] - voff[b];
-    bool bad = false;
-    for (int k = 0; k < 3; ++k) {
-      const int i = faces[3 * f + k];
-      bad |= i < 0 || (long long)i >= nvb;
-    }
-    if (bad) atomicMax(&status[b], 2);
-  }
 }
 
 __device__ __forceinline__ unsigned long long edge_key(const int* __restrict__ faces, long long f, int k,
@@ -132,7 +66,7 @@ __global__ __launch_bounds__(kThreads) void edge_insert_kernel(const int* __rest
     for (int k = 0; k < 3; ++k) {
       bool is_new;
       const long long s = table_claim(keys, mask, edge_key(faces, f, k, voff[b]), &is_new);
-      if (s < 0) { atomicMax(&status[b], 3); break; }
+      if (s < 0) { atomicMax(&status[b], (int)ST_TABLE); break; }
       atomicMin(&minface[s], (int)f);
     }
   }
@@ -241,7 +175,7 @@ __global__ __launch_bounds__(kThreads) void pair_kernel(const float* __restrict_
     const long long gv = voff[b] + faces[q];
     bool is_new;
     const long long s = table_claim(keys, mask, (unsigned long long)gc << 32 | (unsigned long long)gv, &is_new);
-    if (s < 0) { atomicMax(&status[b], 3); continue; }
+    if (s < 0) { atomicMax(&status[b], (int)ST_TABLE); continue; }
     if (!is_new) continue;
     rep[q] = 1;
     atomicAdd(&ccount[gc], 1u);
@@ -301,7 +235,7 @@ __global__ void finish_kernel(const long long* __restrict__ foff, int B, long lo
   const long long ncomp = (long long)cbase[b + 1] - (long long)cbase[b];
   int st = status[b];
   const bool ok = st == 0;
-  if (ok && foff[b + 1] > foff[b] && meshcnt[3 * b] == 0) st = 1;
+  if (ok && foff[b + 1] > foff[b] && meshcnt[3 * b] == 0) st = ST_NOTHING_KEPT;
   counts[5 * b + 0] = ok ? ncomp : 0;
   counts[5 * b + 1] = ok ? (long long)meshcnt[3 * b] : 0;
   counts[5 * b + 2] = ok ? (long long)meshcnt[3 * b + 1] : 0;
@@ -501,72 +435,36 @@ struct CleanWs {
 };
 
 CleanWs clean_layout(void* ws, int B, long long nv, long long nf) {
-  char* base = static_cast<char*>(ws);
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    off = (off + 255) & ~size_t(255);
-    char* p = base ? base + off : nullptr;
-    off += bytes;
-    return p;
-  };
+  WsCursor c(ws);
   const size_t b1 = (size_t)B + 1, f = (size_t)(nf > 0 ? nf : 1), v = (size_t)(nv > 0 ? nv : 1);
   CleanWs w;
-  w.voff = (long long*)take(b1 * 8); w.foff = (long long*)take(b1 * 8);
-  w.vseg = (long long*)take(b1 * 8); w.fseg = (long long*)take(b1 * 8); w.kseg = (long long*)take(b1 * 8);
-  const size_t z0 = (off + 255) & ~size_t(255);
-  w.status = (int*)take(b1 * 4);
-  w.biggest = (unsigned*)take(b1 * 4);
-  w.meshcnt = (unsigned long long*)take(3 * b1 * 8);
-  w.ccount = (unsigned*)take(f * 4); w.cfaces = (unsigned*)take(f * 4);
-  w.csum = (double*)take(3 * f * 8);
-  w.rep = (unsigned char*)take(3 * f);
-  w.zero_bytes = off - z0;
-  w.cbase = (unsigned*)take(b1 * 4); w.kbase = (unsigned*)take(b1 * 4);
-  w.parent = (int*)take(f * 4); w.root = (int*)take(f * 4);
-  w.flag = (unsigned*)take(f * 4); w.fscan = (unsigned*)take(f * 4); w.glabel = (unsigned*)take(f * 4);
-  w.croot = (unsigned*)take(f * 4); w.keep = (unsigned*)take(f * 4); w.kscan = (unsigned*)take(f * 4);
-  w.vmin = (int*)take(v * 4);
-  w.kdeg = (unsigned*)take(v * 4); w.koff = (unsigned*)take(v * 4); w.cursor = (unsigned*)take(v * 4);
+  w.voff = c.take<long long>(b1); w.foff = c.take<long long>(b1);
+  w.vseg = c.take<long long>(b1); w.fseg = c.take<long long>(b1); w.kseg = c.take<long long>(b1);
+  const size_t z0 = c.next();
+  w.status = c.take<int>(b1);
+  w.biggest = c.take<unsigned>(b1);
+  w.meshcnt = c.take<unsigned long long>(3 * b1);
+  w.ccount = c.take<unsigned>(f); w.cfaces = c.take<unsigned>(f);
+  w.csum = c.take<double>(3 * f);
+  w.rep = c.take<unsigned char>(3 * f);
+  w.zero_bytes = c.off - z0;
+  w.cbase = c.take<unsigned>(b1); w.kbase = c.take<unsigned>(b1);
+  w.parent = c.take<int>(f); w.root = c.take<int>(f);
+  w.flag = c.take<unsigned>(f); w.fscan = c.take<unsigned>(f); w.glabel = c.take<unsigned>(f);
+  w.croot = c.take<unsigned>(f); w.keep = c.take<unsigned>(f); w.kscan = c.take<unsigned>(f);
+  w.vmin = c.take<int>(v);
+  w.kdeg = c.take<unsigned>(v); w.koff = c.take<unsigned>(v); w.cursor = c.take<unsigned>(v);
   unsigned long long T = 16;
   while (T < 6ull * f) T <<= 1;          // 3 nf entries at most (edges, then pairs): at most half full
   w.T = T;
-  w.keys = (unsigned long long*)take(T * 8);
-  w.slotval = (unsigned*)take(T * 4);
-  for (int i = 0; i < 2; ++i) { w.key[i] = (unsigned*)take(3 * f * 4); w.val[i] = (unsigned*)take(3 * f * 4); }
-  w.z = (unsigned*)take(3 * f * 4); w.zs = (unsigned*)take(3 * f * 4);
-  const size_t longest = 3 * f > v ? 3 * f : v;
-  w.bsum = (unsigned*)take(((longest + kScanBlockItems - 1) / kScanBlockItems + 1) * 4);
-  w.totals = (unsigned long long*)take(4 * 8);
-  w.total = (off + 255) & ~size_t(255);
+  w.keys = c.take<unsigned long long>(T);
+  w.slotval = c.take<unsigned>(T);
+  for (int i = 0; i < 2; ++i) { w.key[i] = c.take<unsigned>(3 * f); w.val[i] = c.take<unsigned>(3 * f); }
+  w.z = c.take<unsigned>(3 * f); w.zs = c.take<unsigned>(3 * f);
+  w.bsum = c.take<unsigned>(scan_bsum_items(3 * f > v ? 3 * f : v));
+  w.totals = c.take<unsigned long long>(4);
+  w.total = c.next();
   return w;
-}
-
-inline int blocks_for(long long n) {
-  long long b = (n + kThreads - 1) / kThreads;
-  if (b > 16384) b = 16384;
-  return (int)(b < 1 ? 1 : b);
-}
-
-#define CLEAN_TRY(expr)                   \
-  do {                                    \
-    hipError_t _e = (expr);               \
-    if (_e != hipSuccess) return (int)_e; \
-  } while (0)
-#define LAUNCH(kernel, n, ...)                                                                    \
-  do {                                                                                            \
-    hipLaunchKernelGGL(kernel, dim3(blocks_for(n)), dim3(kThreads), 0, st, __VA_ARGS__);          \
-    CLEAN_TRY(hipGetLastError());                                                                 \
-  } while (0)
-
-// the offsets a caller hands in: ascending from 0, within the limits of disn_mesh_components
-bool offsets_ok(const int64_t* v_off, const int64_t* f_off, int B) {
-  if (!v_off || !f_off || B < 1 || v_off[0] != 0 || f_off[0] != 0) return false;
-  for (int b = 0; b < B; ++b)
-    if (v_off[b + 1] < v_off[b] || f_off[b + 1] < f_off[b]) return false;
-  return true;
-}
-bool batch_ok(int B, int64_t nv, int64_t nf) {
-  return B >= 1 && nv >= 0 && nf >= 0 && nf <= INT32_MAX / 3 && nv <= INT32_MAX;
 }
 
 // labels (and, with verts, the statistics and the rule); leaves everything disn_mesh_clean_emit_batch reads in ws
@@ -575,51 +473,49 @@ int count_run(const float* verts, const int* faces, const int64_t* v_off, const 
               long long* counts, void* ws_ptr, hipStream_t st) {
   const long long nv = v_off[B], nf = f_off[B];
   const CleanWs w = clean_layout(ws_ptr, B, nv, nf);
-  static_assert(sizeof(long long) == sizeof(int64_t), "offsets travel as int64");
-  CLEAN_TRY(hipMemcpyAsync(w.voff, v_off, ((size_t)B + 1) * 8, hipMemcpyHostToDevice, st));
-  CLEAN_TRY(hipMemcpyAsync(w.foff, f_off, ((size_t)B + 1) * 8, hipMemcpyHostToDevice, st));
-  CLEAN_TRY(hipMemsetAsync(w.status, 0, w.zero_bytes, st));
-  CLEAN_TRY(hipMemsetAsync(w.totals, 0, 4 * 8, st));
+  MESH_TRY(upload_offsets(w.voff, w.foff, v_off, f_off, B, st));
+  MESH_TRY(hipMemsetAsync(w.status, 0, w.zero_bytes, st));
+  MESH_TRY(hipMemsetAsync(w.totals, 0, 4 * 8, st));
   const int bb = (B + 1 + kThreads - 1) / kThreads;
   if (nf > 0) {
     const unsigned long long mask = w.T - 1;
-    LAUNCH(init_parent_kernel, nf, w.parent, nf);
-    LAUNCH(validate_kernel, nf, faces, w.voff, w.foff, B, nf, w.status);
-    CLEAN_TRY(hipMemsetAsync(w.keys, 0xFF, w.T * 8, st));
+    MESH_LAUNCH(init_parent_kernel, nf, w.parent, nf);
+    MESH_LAUNCH(validate_faces_kernel, nf, faces, w.voff, w.foff, B, nf, w.status);
+    MESH_TRY(hipMemsetAsync(w.keys, 0xFF, w.T * 8, st));
     if (connectivity == 0) {
-      CLEAN_TRY(hipMemsetAsync(w.slotval, 0x7F, w.T * 4, st));
-      LAUNCH(edge_insert_kernel, nf, faces, w.voff, w.foff, B, nf, w.status, w.keys, mask, (int*)w.slotval);
-      LAUNCH(edge_union_kernel, nf, faces, w.voff, w.foff, B, nf, w.status, w.keys, mask, (const int*)w.slotval,
+      MESH_TRY(hipMemsetAsync(w.slotval, 0x7F, w.T * 4, st));
+      MESH_LAUNCH(edge_insert_kernel, nf, faces, w.voff, w.foff, B, nf, w.status, w.keys, mask, (int*)w.slotval);
+      MESH_LAUNCH(edge_union_kernel, nf, faces, w.voff, w.foff, B, nf, w.status, w.keys, mask, (const int*)w.slotval,
              w.parent);
-      CLEAN_TRY(hipMemsetAsync(w.keys, 0xFF, w.T * 8, st));
+      MESH_TRY(hipMemsetAsync(w.keys, 0xFF, w.T * 8, st));
     } else {
-      CLEAN_TRY(hipMemsetAsync(w.vmin, 0x7F, (size_t)(nv > 0 ? nv : 1) * 4, st));
-      LAUNCH(vertex_min_kernel, nf, faces, w.voff, w.foff, B, nf, w.status, w.vmin);
-      LAUNCH(vertex_union_kernel, nf, faces, w.voff, w.foff, B, nf, w.status, w.vmin, w.parent);
+      MESH_TRY(hipMemsetAsync(w.vmin, 0x7F, (size_t)(nv > 0 ? nv : 1) * 4, st));
+      MESH_LAUNCH(vertex_min_kernel, nf, faces, w.voff, w.foff, B, nf, w.status, w.vmin);
+      MESH_LAUNCH(vertex_union_kernel, nf, faces, w.voff, w.foff, B, nf, w.status, w.vmin, w.parent);
     }
-    LAUNCH(compress_kernel, nf, w.foff, B, nf, w.status, w.parent, w.root, w.flag);
-    CLEAN_TRY(exclusive_scan(w.flag, w.fscan, (size_t)nf, w.bsum, w.totals, st));
+    MESH_LAUNCH(compress_kernel, nf, w.foff, B, nf, w.status, w.parent, w.root, w.flag);
+    MESH_TRY(exclusive_scan(w.flag, w.fscan, (size_t)nf, w.bsum, w.totals, st));
   }
   hipLaunchKernelGGL(comp_base_kernel, dim3(bb), dim3(kThreads), 0, st, w.foff, B, nf, w.fscan, w.totals, w.cbase,
                      ncomp, w.status);
-  CLEAN_TRY(hipGetLastError());
+  MESH_TRY(hipGetLastError());
   if (nf > 0) {
-    LAUNCH(label_kernel, nf, w.foff, B, nf, w.root, w.fscan, w.cbase, w.glabel, labels, w.cfaces, w.croot);
+    MESH_LAUNCH(label_kernel, nf, w.foff, B, nf, w.root, w.fscan, w.cbase, w.glabel, labels, w.cfaces, w.croot);
     if (verts) {
-      LAUNCH(pair_kernel, 3 * nf, verts, faces, w.voff, w.foff, B, nf, w.status, w.glabel, w.keys, w.T - 1, w.rep,
+      MESH_LAUNCH(pair_kernel, 3 * nf, verts, faces, w.voff, w.foff, B, nf, w.status, w.glabel, w.keys, w.T - 1, w.rep,
              w.ccount, w.csum);
-      LAUNCH(biggest_kernel, nf, w.foff, B, w.totals, w.croot, w.ccount, w.biggest, comp_verts);
+      MESH_LAUNCH(biggest_kernel, nf, w.foff, B, w.totals, w.croot, w.ccount, w.biggest, comp_verts);
     }
     if (counts) {
-      LAUNCH(keep_kernel, nf, w.foff, B, nf, w.totals, w.status, w.croot, w.ccount, w.cfaces, w.csum, w.biggest,
+      MESH_LAUNCH(keep_kernel, nf, w.foff, B, nf, w.totals, w.status, w.croot, w.ccount, w.cfaces, w.csum, w.biggest,
              dist_thresh, num_thresh, w.keep, w.meshcnt);
-      CLEAN_TRY(exclusive_scan(w.keep, w.kscan, (size_t)nf, w.bsum, w.totals + 1, st));
+      MESH_TRY(exclusive_scan(w.keep, w.kscan, (size_t)nf, w.bsum, w.totals + 1, st));
     }
   }
   if (counts) {
     hipLaunchKernelGGL(finish_kernel, dim3(bb), dim3(kThreads), 0, st, w.foff, B, nf, w.cbase, w.kscan, w.status,
                        w.meshcnt, w.kbase, counts);
-    CLEAN_TRY(hipGetLastError());
+    MESH_TRY(hipGetLastError());
   }
   return 0;
 }
@@ -628,9 +524,9 @@ int count_run(const float* verts, const int* faces, const int64_t* v_off, const 
 int sort_run(const CleanWs& w, long long n, int bits, const long long* seg, int B, hipStream_t st, int* where) {
   int cur = 0;
   for (int bit = 0; bit < bits; ++bit, cur ^= 1) {
-    LAUNCH(split_flag_kernel, n, w.key[cur], n, bit, w.z);
-    CLEAN_TRY(exclusive_scan(w.z, w.zs, (size_t)n, w.bsum, w.totals + 2, st));
-    LAUNCH(split_scatter_kernel, n, w.key[cur], w.val[cur], n, w.z, w.zs, w.totals + 2, seg, B, w.key[cur ^ 1],
+    MESH_LAUNCH(split_flag_kernel, n, w.key[cur], n, bit, w.z);
+    MESH_TRY(exclusive_scan(w.z, w.zs, (size_t)n, w.bsum, w.totals + 2, st));
+    MESH_LAUNCH(split_scatter_kernel, n, w.key[cur], w.val[cur], n, w.z, w.zs, w.totals + 2, seg, B, w.key[cur ^ 1],
            w.val[cur ^ 1]);
   }
   *where = cur;
@@ -643,7 +539,7 @@ int sort_run(const CleanWs& w, long long n, int bits, const long long* seg, int 
 using namespace disn;
 
 extern "C" size_t disn_mesh_clean_workspace_bytes(int B, int64_t nv_total, int64_t nf_total) {
-  return batch_ok(B, nv_total, nf_total) ? clean_layout(nullptr, B, nv_total, nf_total).total : 0;
+  return mesh_limits_ok(B, nv_total, nf_total) ? clean_layout(nullptr, B, nv_total, nf_total).total : 0;
 }
 
 extern "C" int disn_mesh_components_device(const float* verts, const int32_t* faces, const int64_t* v_off_host,
@@ -655,7 +551,7 @@ extern "C" int disn_mesh_components_device(const float* verts, const int32_t* fa
   const int64_t nv = v_off_host[B], nf = f_off_host[B];
   if (nf > 0 && (!faces || !labels)) return DISN_E_ARG;
   if (comp_verts && nf > 0 && !verts) return DISN_E_ARG;
-  if (!batch_ok(B, nv, nf)) return DISN_E_SHAPE;
+  if (!mesh_limits_ok(B, nv, nf)) return DISN_E_SHAPE;
   if (ws_bytes < clean_layout(nullptr, B, nv, nf).total) return DISN_E_WS;
   return count_run(comp_verts ? verts : nullptr, faces, v_off_host, f_off_host, B, connectivity, 0.0, 0.0, labels,
                    reinterpret_cast<long long*>(ncomp), reinterpret_cast<long long*>(comp_verts), nullptr, ws,
@@ -670,7 +566,7 @@ extern "C" int disn_mesh_clean_count_batch(const float* verts, const int32_t* fa
     return DISN_E_ARG;
   const int64_t nv = v_off_host[B], nf = f_off_host[B];
   if (nf > 0 && (!faces || !verts)) return DISN_E_ARG;
-  if (!batch_ok(B, nv, nf)) return DISN_E_SHAPE;
+  if (!mesh_limits_ok(B, nv, nf)) return DISN_E_SHAPE;
   if (ws_bytes < clean_layout(nullptr, B, nv, nf).total) return DISN_E_WS;
   return count_run(verts, faces, v_off_host, f_off_host, B, connectivity, dist_thresh, num_thresh, nullptr, nullptr,
                    nullptr, reinterpret_cast<long long*>(counts), ws, (hipStream_t)stream);
@@ -682,7 +578,7 @@ extern "C" int disn_mesh_clean_emit_batch(const float* verts, const int32_t* fac
                                           void* ws, size_t ws_bytes, void* stream) {
   if (!offsets_ok(v_off_host, f_off_host, B) || !counts_host || !ws) return DISN_E_ARG;
   const int64_t nv = v_off_host[B], nf = f_off_host[B];
-  if (!batch_ok(B, nv, nf)) return DISN_E_SHAPE;
+  if (!mesh_limits_ok(B, nv, nf)) return DISN_E_SHAPE;
   if (ws_bytes < clean_layout(nullptr, B, nv, nf).total) return DISN_E_WS;
   hipStream_t st = (hipStream_t)stream;
   const CleanWs w = clean_layout(ws, B, nv, nf);
@@ -708,26 +604,26 @@ extern "C" int disn_mesh_clean_emit_batch(const float* verts, const int32_t* fac
   int bits = 0;
   while ((1ll << bits) < most) ++bits;
   hipLaunchKernelGGL(segments_kernel, dim3(1), dim3(1), 0, st, B, w.meshcnt, w.kseg, w.vseg, w.fseg);
-  CLEAN_TRY(hipGetLastError());
+  MESH_TRY(hipGetLastError());
   const unsigned long long mask = w.T - 1;
   int at = 0;
   // vertices
-  CLEAN_TRY(hipMemsetAsync(w.kdeg, 0, (size_t)nv * 4, st));
-  CLEAN_TRY(hipMemsetAsync(w.cursor, 0, (size_t)nv * 4, st));
-  LAUNCH(pair_degree_kernel, 3 * nf, faces, w.voff, w.foff, B, nf, w.rep, w.glabel, w.keep, w.kdeg);
-  CLEAN_TRY(exclusive_scan(w.kdeg, w.koff, (size_t)nv, w.bsum, w.totals + 3, st));
-  LAUNCH(pair_list_kernel, 3 * nf, faces, w.voff, w.foff, B, nf, w.rep, w.glabel, w.keep, w.kscan, w.kbase, w.koff,
+  MESH_TRY(hipMemsetAsync(w.kdeg, 0, (size_t)nv * 4, st));
+  MESH_TRY(hipMemsetAsync(w.cursor, 0, (size_t)nv * 4, st));
+  MESH_LAUNCH(pair_degree_kernel, 3 * nf, faces, w.voff, w.foff, B, nf, w.rep, w.glabel, w.keep, w.kdeg);
+  MESH_TRY(exclusive_scan(w.kdeg, w.koff, (size_t)nv, w.bsum, w.totals + 3, st));
+  MESH_LAUNCH(pair_list_kernel, 3 * nf, faces, w.voff, w.foff, B, nf, w.rep, w.glabel, w.keep, w.kscan, w.kbase, w.koff,
          w.cursor, nvo, w.key[0], w.val[0]);
   if (int rc = sort_run(w, nvo, bits, w.vseg, B, st, &at)) return rc;
-  LAUNCH(emit_verts_kernel, nvo, verts, faces, w.voff, w.foff, w.vseg, B, nf, w.val[at], nvo, w.glabel, w.keys, mask,
+  MESH_LAUNCH(emit_verts_kernel, nvo, verts, faces, w.voff, w.foff, w.vseg, B, nf, w.val[at], nvo, w.glabel, w.keys, mask,
          w.slotval, verts_out, vmap_out);
   // faces
-  LAUNCH(face_flag_kernel, nf, nf, w.glabel, w.keep, w.flag);
-  CLEAN_TRY(exclusive_scan(w.flag, w.fscan, (size_t)nf, w.bsum, w.totals + 3, st));
-  LAUNCH(face_list_kernel, nf, w.foff, B, nf, w.flag, w.fscan, w.glabel, w.kscan, w.kbase, nfo, w.key[0], w.val[0]);
+  MESH_LAUNCH(face_flag_kernel, nf, nf, w.glabel, w.keep, w.flag);
+  MESH_TRY(exclusive_scan(w.flag, w.fscan, (size_t)nf, w.bsum, w.totals + 3, st));
+  MESH_LAUNCH(face_list_kernel, nf, w.foff, B, nf, w.flag, w.fscan, w.glabel, w.kscan, w.kbase, nfo, w.key[0], w.val[0]);
   if (int rc = sort_run(w, nfo, bits, w.fseg, B, st, &at)) return rc;
-  LAUNCH(emit_faces_kernel, nfo, faces, w.voff, w.foff, B, nf, w.val[at], nfo, w.glabel, w.keys, mask, w.slotval,
+  MESH_LAUNCH(emit_faces_kernel, nfo, faces, w.voff, w.foff, B, nf, w.val[at], nfo, w.glabel, w.keys, mask, w.slotval,
          faces_out);
-  LAUNCH(emit_kept_kernel, nf, w.foff, w.kseg, B, w.totals, w.croot, w.keep, w.kscan, w.kbase, w.cbase, nk, kept_out);
+  MESH_LAUNCH(emit_kept_kernel, nf, w.foff, w.kseg, B, w.totals, w.croot, w.keep, w.kscan, w.kbase, w.cbase, nk, kept_out);
   return 0;
 }

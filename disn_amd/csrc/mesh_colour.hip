@@ -14,15 +14,14 @@
 // box of at most (137 S)^2 sub-pixels.  NO FLOATING-POINT ATOMIC: the sums are integer sums, the maximum an integer
 // maximum.  No host read-back: progress[r] says whether fill round r has anything to do, and a round without returns
 // at once.  Compiled with -ffp-contract=off: the float32 arithmetic rounds as numpy's does.
-// (mesh_of and the launch helpers are those of mesh_simplify.hip, which keeps them to itself.)
-#include "kernels.hpp"
+// (mesh_of, the two validators and the host-side helpers are those of mesh_batch.hpp.)
+#include "mesh_batch.hpp"
 
 #include "../../include/disn_amd_colour.h"
 
 namespace disn {
 namespace {
 
-constexpr int kThreads = 256;
 constexpr int kImg = DISN_COLOUR_IMG;
 constexpr int kSmallBox = 64;                  // sub-pixels a thread rasterises itself
 constexpr int kBigBlocks = 1024;               // of 4 waves each, striding over the queue of large faces
@@ -32,51 +31,8 @@ constexpr int kGrey16 = 32768;
 constexpr float kMirrorFront = 32.0f;          // postprocess.MIRROR_FRONT
 constexpr float kTiny = 1.17549435e-38f;
 constexpr float kBig = 3.4028234663852886e38f;
-enum { ST_INDEX = 2, ST_FINITE = 4 };
-
-// the mesh of flat element i: the largest b with off[b] <= i (empty meshes are stepped over)
-__device__ __forceinline__ int mesh_of(const long long* __restrict__ off, int B, long long i) {
-  int lo = 0, hi = B - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (off[mid] <= i) lo = mid;
-    else hi = mid - 1;
-  }
-  return lo;
-}
-
-#define GRID_STRIDE(i, n) \
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < (n); i += (long long)gridDim.x * blockDim.x)
 
 __device__ __forceinline__ bool finite_f(float x) { return fabsf(x) <= kBig; }
-
-// status 2 for a mesh with an index outside [0, nv_b): the ONLY kernel that looks at an index before it is checked
-__global__ __launch_bounds__(kThreads) void validate_faces_kernel(const int* __restrict__ faces,
-                                                                  const long long* __restrict__ voff,
-                                                                  const long long* __restrict__ foff, int B,
-                                                                  long long nf, int* status) {
-  GRID_STRIDE(f, nf) {
-    const int b = mesh_of(foff, B, f);
-    const long long nvb = voff[b + 1] - voff[b];
-    bool bad = false;
-    for (int k = 0; k < 3; ++k) {
-      const int i = faces[3 * f + k];
-      bad |= i < 0 || (long long)i >= nvb;
-    }
-    if (bad) atomicMax(&status[b], (int)ST_INDEX);
-  }
-}
-
-// status 4 for a mesh with a coordinate that is not finite
-__global__ __launch_bounds__(kThreads) void validate_verts_kernel(const float* __restrict__ verts,
-                                                                  const long long* __restrict__ voff, int B,
-                                                                  long long nv, int* status) {
-  GRID_STRIDE(v, nv) {
-    const float s = (verts[3 * v] - verts[3 * v]) + (verts[3 * v + 1] - verts[3 * v + 1]) +
-                    (verts[3 * v + 2] - verts[3 * v + 2]);          // 0 for finite coordinates, NaN otherwise
-    if (!(s == 0.0f)) atomicMax(&status[mesh_of(voff, B, v)], (int)ST_FINITE);
-  }
-}
 
 // _screen: the gather's projection in its order of operations; false unless w > 0 and x, y, q are finite
 __device__ __forceinline__ bool screen(const float* __restrict__ T, float px, float py, float pz, int S, float& x,
@@ -408,57 +364,27 @@ struct ColourWs {
 };
 
 ColourWs colour_layout(void* ws, int B, int V, long long nv, long long nf, int S) {
-  char* base = static_cast<char*>(ws);
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    off = (off + 255) & ~size_t(255);
-    char* p = base ? base + off : nullptr;
-    off += bytes;
-    return p;
-  };
+  WsCursor c(ws);
   const size_t b1 = (size_t)B + 1, f = (size_t)(nf > 0 ? nf : 1), v = (size_t)(nv > 0 ? nv : 1);
   ColourWs w;
-  w.voff = (long long*)take(b1 * 8); w.foff = (long long*)take(b1 * 8);
-  const size_t z0 = (off + 255) & ~size_t(255);
-  w.qcount = (unsigned long long*)take(8);
-  w.progress = (int*)take((DISN_COLOUR_MAX_FILL + 2) * 4);
-  w.meshacc = (unsigned long long*)take(4 * b1 * 8);
-  w.acc = (unsigned long long*)take(4 * v * 8);
-  w.zero_bytes = off - z0;
-  w.c16 = (int*)take(3 * v * 4);
-  w.queue = (long long*)take(f * (size_t)V * 8);
+  w.voff = c.take<long long>(b1); w.foff = c.take<long long>(b1);
+  const size_t z0 = c.next();
+  w.qcount = c.take<unsigned long long>(1);
+  w.progress = c.take<int>(DISN_COLOUR_MAX_FILL + 2);
+  w.meshacc = c.take<unsigned long long>(4 * b1);
+  w.acc = c.take<unsigned long long>(4 * v);
+  w.zero_bytes = c.off - z0;
+  w.c16 = c.take<int>(3 * v);
+  w.queue = c.take<long long>(f * (size_t)V);
   w.zbuf_bytes = (size_t)B * V * (kImg * S) * (kImg * S) * 4;
-  w.zbuf = (float*)take(w.zbuf_bytes);
-  w.total = (off + 255) & ~size_t(255);
+  w.zbuf = c.take<float>(w.zbuf_bytes / 4);
+  w.total = c.next();
   return w;
 }
 
-inline int blocks_for(long long n) {
-  long long b = (n + kThreads - 1) / kThreads;
-  if (b > 16384) b = 16384;
-  return (int)(b < 1 ? 1 : b);
-}
-
-#define COLOUR_TRY(expr)                  \
-  do {                                    \
-    hipError_t _e = (expr);               \
-    if (_e != hipSuccess) return (int)_e; \
-  } while (0)
-#define LAUNCH(kernel, n, ...)                                                                    \
-  do {                                                                                            \
-    hipLaunchKernelGGL(kernel, dim3(blocks_for(n)), dim3(kThreads), 0, st, __VA_ARGS__);          \
-    COLOUR_TRY(hipGetLastError());                                                                \
-  } while (0)
-
-bool offsets_ok(const int64_t* v_off, const int64_t* f_off, int B) {
-  if (!v_off || !f_off || B < 1 || v_off[0] != 0 || f_off[0] != 0) return false;
-  for (int b = 0; b < B; ++b)
-    if (v_off[b + 1] < v_off[b] || f_off[b + 1] < f_off[b]) return false;
-  return true;
-}
 bool batch_ok(int B, int V, int64_t nv, int64_t nf, int S) {
-  return B >= 1 && B <= 65535 && V >= 1 && V <= DISN_COLOUR_MAX_VIEWS && (S == 1 || S == 2 || S == 4) && nv >= 0 &&
-         nf >= 0 && nf <= INT32_MAX / 3 && nv <= INT32_MAX;
+  return mesh_limits_ok(B, nv, nf) && B <= 65535 && V >= 1 && V <= DISN_COLOUR_MAX_VIEWS &&
+         (S == 1 || S == 2 || S == 4);
 }
 
 // offsets to the device, the zeroed block, the statuses, the z-buffers of every (mesh, view) into `zbuf`
@@ -466,20 +392,18 @@ int zbuffer_run(const ColourWs& w, const float* verts, const int32_t* faces, con
                 const int64_t* f_off_host, int B, const float* tm, int V, int S, float* zbuf, int32_t* status,
                 hipStream_t st) {
   const int64_t nv = v_off_host[B], nf = f_off_host[B];
-  static_assert(sizeof(long long) == sizeof(int64_t), "offsets travel as int64");
-  COLOUR_TRY(hipMemcpyAsync(w.voff, v_off_host, ((size_t)B + 1) * 8, hipMemcpyHostToDevice, st));
-  COLOUR_TRY(hipMemcpyAsync(w.foff, f_off_host, ((size_t)B + 1) * 8, hipMemcpyHostToDevice, st));
-  COLOUR_TRY(hipMemsetAsync(w.qcount, 0, w.zero_bytes, st));
-  COLOUR_TRY(hipMemsetAsync(status, 0, (size_t)B * 4, st));
-  COLOUR_TRY(hipMemsetAsync(zbuf, 0, w.zbuf_bytes, st));
-  if (nf > 0) LAUNCH(validate_faces_kernel, nf, faces, w.voff, w.foff, B, nf, status);
-  if (nv > 0) LAUNCH(validate_verts_kernel, nv, verts, w.voff, B, nv, status);
+  MESH_TRY(upload_offsets(w.voff, w.foff, v_off_host, f_off_host, B, st));
+  MESH_TRY(hipMemsetAsync(w.qcount, 0, w.zero_bytes, st));
+  MESH_TRY(hipMemsetAsync(status, 0, (size_t)B * 4, st));
+  MESH_TRY(hipMemsetAsync(zbuf, 0, w.zbuf_bytes, st));
+  if (nf > 0) MESH_LAUNCH(validate_faces_kernel, nf, faces, w.voff, w.foff, B, nf, status);
+  if (nv > 0) MESH_LAUNCH(validate_verts_kernel, nv, verts, w.voff, B, nv, status);
   if (nf > 0 && nv > 0) {
     const long long items = (long long)nf * V;
-    LAUNCH(raster_kernel, items, verts, faces, w.voff, w.foff, B, items, status, tm, V, S, zbuf, w.qcount, w.queue);
+    MESH_LAUNCH(raster_kernel, items, verts, faces, w.voff, w.foff, B, items, status, tm, V, S, zbuf, w.qcount, w.queue);
     hipLaunchKernelGGL(raster_big_kernel, dim3(kBigBlocks), dim3(kThreads), 0, st, verts, faces, w.voff, w.foff, B,
                        items, status, tm, V, S, zbuf, w.qcount, w.queue);
-    COLOUR_TRY(hipGetLastError());
+    MESH_TRY(hipGetLastError());
   }
   return 0;
 }
@@ -521,18 +445,18 @@ extern "C" int disn_mesh_colour_batch(const float* verts, const int32_t* faces, 
   const ColourWs w = colour_layout(ws, B, V, nv, nf, S);
   const int rc = zbuffer_run(w, verts, faces, v_off_host, f_off_host, B, trans_mat, V, S, w.zbuf, status, st);
   if (rc != 0 || nv == 0) return rc;
-  LAUNCH(vertex_kernel, nv, verts, w.voff, B, nv, status, images, alpha, trans_mat, V, S, rel_tol, mirror_axis,
+  MESH_LAUNCH(vertex_kernel, nv, verts, w.voff, B, nv, status, images, alpha, trans_mat, V, S, rel_tol, mirror_axis,
          bgr ? 1 : 0, w.zbuf, w.c16, seen);
   if (nf > 0 && fill_iters > 0) {
-    COLOUR_TRY(hipMemsetAsync(w.progress, 1, 4, st));             // round 0 always runs (any non-zero word)
+    MESH_TRY(hipMemsetAsync(w.progress, 1, 4, st));             // round 0 always runs (any non-zero word)
     for (int r = 0; r < fill_iters; ++r) {
-      LAUNCH(fill_scatter_kernel, nf, faces, w.voff, w.foff, B, nf, status, w.progress, r, w.c16, seen, w.acc);
-      LAUNCH(fill_apply_kernel, nv, nv, w.progress, r, w.c16, seen, w.acc);
+      MESH_LAUNCH(fill_scatter_kernel, nf, faces, w.voff, w.foff, B, nf, status, w.progress, r, w.c16, seen, w.acc);
+      MESH_LAUNCH(fill_apply_kernel, nv, nv, w.progress, r, w.c16, seen, w.acc);
     }
   }
   hipLaunchKernelGGL(mesh_mean_kernel, dim3(kMeanSlices, B), dim3(kThreads), 0, st, w.voff, status, w.c16, seen,
                      w.meshacc);
-  COLOUR_TRY(hipGetLastError());
-  LAUNCH(finish_kernel, nv, w.voff, B, nv, status, w.meshacc, w.c16, seen, colours);
+  MESH_TRY(hipGetLastError());
+  MESH_LAUNCH(finish_kernel, nv, w.voff, B, nv, status, w.meshacc, w.c16, seen, colours);
   return 0;
 }

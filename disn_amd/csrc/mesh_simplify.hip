@@ -15,53 +15,18 @@
 // NO FLOATING-POINT ATOMIC: every real that is summed has magnitude <= 1 and is added as rint(x 2^32) to an int64 with a
 // 64-bit integer atomic add, so the sums, and with them every output bit, do not depend on the order of execution.
 // Compiled with -ffp-contract=off: the float32 cell and the float64 arithmetic round as numpy's do.
-// (mesh_of, mix64, table_claim and the launch helpers are those of mesh_clean.hip, which keeps them to itself.)
-#include "kernels.hpp"
+// (mesh_of, the tables, the two validators and the host-side helpers are those of mesh_batch.hpp.)
+#include "mesh_batch.hpp"
 
 #include "../../include/disn_amd_simplify.h"
 
 namespace disn {
 namespace {
 
-constexpr unsigned long long kEmptyKey = ~0ull;
-constexpr unsigned kNone = 0xFFFFFFFFu;
-constexpr int kThreads = 256;
 constexpr int kAcc = 14;                       // per cluster: 10 quadric entries, 3 sums of rel, the member count
 constexpr unsigned kTripleLimit = 1u << 21;    // cluster numbers a face key holds: 3 x 21 bits (status 5 beyond)
 constexpr double kFix = 4294967296.0;          // 2^32
-enum { ST_INDEX = 2, ST_TABLE = 3, ST_FINITE = 4, ST_CAPACITY = 5 };
-
-// the mesh of flat element i: the largest b with off[b] <= i (empty meshes are stepped over)
-__device__ __forceinline__ int mesh_of(const long long* __restrict__ off, int B, long long i) {
-  int lo = 0, hi = B - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (off[mid] <= i) lo = mid;
-    else hi = mid - 1;
-  }
-  return lo;
-}
-
-__device__ __forceinline__ unsigned long long mix64(unsigned long long x) {
-  x ^= x >> 30; x *= 0xbf58476d1ce4e5b9ull;
-  x ^= x >> 27; x *= 0x94d049bb133111ebull;
-  return x ^ (x >> 31);
-}
-
-// the slot of `key`, claiming an empty one; -1 when `mask + 1` probes found neither (table full)
-__device__ __forceinline__ long long table_claim(unsigned long long* keys, unsigned long long mask,
-                                                 unsigned long long key) {
-  unsigned long long h = mix64(key) & mask;
-  for (unsigned long long probe = 0; probe <= mask; ++probe) {
-    const unsigned long long prev = atomicCAS(&keys[h], kEmptyKey, key);
-    if (prev == kEmptyKey || prev == key) return (long long)h;
-    h = (h + 1) & mask;
-  }
-  return -1;
-}
-
-#define GRID_STRIDE(i, n) \
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < (n); i += (long long)gridDim.x * blockDim.x)
+enum { ST_CAPACITY = 5 };
 
 struct Lattice {
   double ox, oy, oz, h;
@@ -99,34 +64,6 @@ __device__ __forceinline__ void rel_of(const float* __restrict__ verts, long lon
 
 __device__ __forceinline__ void add_fixed(long long* acc, double x) {
   atomicAdd(reinterpret_cast<unsigned long long*>(acc), (unsigned long long)(long long)rint(x * kFix));
-}
-
-// status 2 for a mesh with an index outside [0, nv_b): the ONLY kernel that looks at an index before it is checked
-__global__ __launch_bounds__(kThreads) void validate_faces_kernel(const int* __restrict__ faces,
-                                                                  const long long* __restrict__ voff,
-                                                                  const long long* __restrict__ foff, int B,
-                                                                  long long nf, int* status) {
-  GRID_STRIDE(f, nf) {
-    const int b = mesh_of(foff, B, f);
-    const long long nvb = voff[b + 1] - voff[b];
-    bool bad = false;
-    for (int k = 0; k < 3; ++k) {
-      const int i = faces[3 * f + k];
-      bad |= i < 0 || (long long)i >= nvb;
-    }
-    if (bad) atomicMax(&status[b], (int)ST_INDEX);
-  }
-}
-
-// status 4 for a mesh with a coordinate that is not finite
-__global__ __launch_bounds__(kThreads) void validate_verts_kernel(const float* __restrict__ verts,
-                                                                  const long long* __restrict__ voff, int B,
-                                                                  long long nv, int* status) {
-  GRID_STRIDE(v, nv) {
-    const float s = (verts[3 * v] - verts[3 * v]) + (verts[3 * v + 1] - verts[3 * v + 1]) +
-                    (verts[3 * v + 2] - verts[3 * v + 2]);          // 0 for finite coordinates, NaN otherwise
-    if (!(s == 0.0f)) atomicMax(&status[mesh_of(voff, B, v)], (int)ST_FINITE);
-  }
 }
 
 // every vertex claims its (mesh, cell) key -- cell < 2^30, the mesh above it -- and lowers the slot's smallest member
@@ -388,66 +325,31 @@ struct SimplifyWs {
 };
 
 SimplifyWs simplify_layout(void* ws, int B, long long nv, long long nf) {
-  char* base = static_cast<char*>(ws);
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    off = (off + 255) & ~size_t(255);
-    char* p = base ? base + off : nullptr;
-    off += bytes;
-    return p;
-  };
+  WsCursor c(ws);
   const size_t b1 = (size_t)B + 1, f = (size_t)(nf > 0 ? nf : 1), v = (size_t)(nv > 0 ? nv : 1);
   SimplifyWs w;
-  w.voff = (long long*)take(b1 * 8); w.foff = (long long*)take(b1 * 8); w.vseg = (long long*)take(b1 * 8);
-  w.lat = (Lattice*)take(b1 * sizeof(Lattice));
-  w.cells = (int*)take(b1 * 4);
-  const size_t z0 = (off + 255) & ~size_t(255);
-  w.status = (int*)take(b1 * 4);
-  w.meshcnt = (unsigned long long*)take(3 * b1 * 8);
-  w.totals = (unsigned long long*)take(2 * 8);
-  w.acc = (long long*)take(kAcc * v * 8);
-  w.zero_bytes = off - z0;
-  w.cbase = (unsigned*)take(b1 * 4);
-  w.vslot = (unsigned*)take(v * 4); w.vflag = (unsigned*)take(v * 4);
-  w.vscan = (unsigned*)take(v * 4); w.vclu = (unsigned*)take(v * 4);
-  w.fslot = (unsigned*)take(f * 4); w.fflag = (unsigned*)take(f * 4); w.fscan = (unsigned*)take(f * 4);
+  w.voff = c.take<long long>(b1); w.foff = c.take<long long>(b1); w.vseg = c.take<long long>(b1);
+  w.lat = c.take<Lattice>(b1);
+  w.cells = c.take<int>(b1);
+  const size_t z0 = c.next();
+  w.status = c.take<int>(b1);
+  w.meshcnt = c.take<unsigned long long>(3 * b1);
+  w.totals = c.take<unsigned long long>(2);
+  w.acc = c.take<long long>(kAcc * v);
+  w.zero_bytes = c.off - z0;
+  w.cbase = c.take<unsigned>(b1);
+  w.vslot = c.take<unsigned>(v); w.vflag = c.take<unsigned>(v);
+  w.vscan = c.take<unsigned>(v); w.vclu = c.take<unsigned>(v);
+  w.fslot = c.take<unsigned>(f); w.fflag = c.take<unsigned>(f); w.fscan = c.take<unsigned>(f);
   unsigned long long Tv = 16, Tf = 16;
   while (Tv < 2ull * v) Tv <<= 1;        // one entry per vertex / per face at most: at most half full
   while (Tf < 2ull * f) Tf <<= 1;
   w.Tv = Tv; w.Tf = Tf;
-  w.vkeys = (unsigned long long*)take(Tv * 8); w.vfirst = (int*)take(Tv * 4);
-  w.fkeys = (unsigned long long*)take(Tf * 8); w.fmin_ = (int*)take(Tf * 4);
-  const size_t longest = f > v ? f : v;
-  w.bsum = (unsigned*)take(((longest + kScanBlockItems - 1) / kScanBlockItems + 1) * 4);
-  w.total = (off + 255) & ~size_t(255);
+  w.vkeys = c.take<unsigned long long>(Tv); w.vfirst = c.take<int>(Tv);
+  w.fkeys = c.take<unsigned long long>(Tf); w.fmin_ = c.take<int>(Tf);
+  w.bsum = c.take<unsigned>(scan_bsum_items(f > v ? f : v));
+  w.total = c.next();
   return w;
-}
-
-inline int blocks_for(long long n) {
-  long long b = (n + kThreads - 1) / kThreads;
-  if (b > 16384) b = 16384;
-  return (int)(b < 1 ? 1 : b);
-}
-
-#define SIMPLIFY_TRY(expr)                \
-  do {                                    \
-    hipError_t _e = (expr);               \
-    if (_e != hipSuccess) return (int)_e; \
-  } while (0)
-#define LAUNCH(kernel, n, ...)                                                                    \
-  do {                                                                                            \
-    hipLaunchKernelGGL(kernel, dim3(blocks_for(n)), dim3(kThreads), 0, st, __VA_ARGS__);          \
-    SIMPLIFY_TRY(hipGetLastError());                                                              \
-  } while (0)
-
-bool offsets_ok(const int64_t* v_off, const int64_t* f_off, int B) {
-  if (!v_off || !f_off || B < 1 || v_off[0] != 0 || f_off[0] != 0) return false;
-  for (int b = 0; b < B; ++b)
-    if (v_off[b + 1] < v_off[b] || f_off[b + 1] < f_off[b]) return false;
-  return true;
-}
-bool batch_ok(int B, int64_t nv, int64_t nf) {
-  return B >= 1 && nv >= 0 && nf >= 0 && nf <= INT32_MAX / 3 && nv <= INT32_MAX;
 }
 
 }  // namespace
@@ -456,7 +358,7 @@ bool batch_ok(int B, int64_t nv, int64_t nf) {
 using namespace disn;
 
 extern "C" size_t disn_mesh_simplify_workspace_bytes(int B, int64_t nv_total, int64_t nf_total) {
-  return batch_ok(B, nv_total, nf_total) ? simplify_layout(nullptr, B, nv_total, nf_total).total : 0;
+  return mesh_limits_ok(B, nv_total, nf_total) ? simplify_layout(nullptr, B, nv_total, nf_total).total : 0;
 }
 
 extern "C" int disn_mesh_simplify_count_batch(const float* verts, const int32_t* faces, const int64_t* v_off_host,
@@ -466,7 +368,7 @@ extern "C" int disn_mesh_simplify_count_batch(const float* verts, const int32_t*
   if (!offsets_ok(v_off_host, f_off_host, B) || !lattice_host || !cells_host || !counts || !ws) return DISN_E_ARG;
   const int64_t nv = v_off_host[B], nf = f_off_host[B];
   if ((nv > 0 && !verts) || (nf > 0 && !faces)) return DISN_E_ARG;
-  if (!batch_ok(B, nv, nf)) return DISN_E_SHAPE;
+  if (!mesh_limits_ok(B, nv, nf)) return DISN_E_SHAPE;
   for (int b = 0; b < B; ++b) {
     const double h = lattice_host[4 * (size_t)b + 3];
     const float inv_h = (float)(1.0 / h);          // the cell's factor: positive and finite, as float32 too
@@ -479,42 +381,40 @@ extern "C" int disn_mesh_simplify_count_batch(const float* verts, const int32_t*
   if (ws_bytes < simplify_layout(nullptr, B, nv, nf).total) return DISN_E_WS;
   hipStream_t st = (hipStream_t)stream;
   const SimplifyWs w = simplify_layout(ws, B, nv, nf);
-  static_assert(sizeof(long long) == sizeof(int64_t), "offsets travel as int64");
   static_assert(sizeof(Lattice) == 4 * sizeof(double), "a lattice travels as four doubles");
-  SIMPLIFY_TRY(hipMemcpyAsync(w.voff, v_off_host, ((size_t)B + 1) * 8, hipMemcpyHostToDevice, st));
-  SIMPLIFY_TRY(hipMemcpyAsync(w.foff, f_off_host, ((size_t)B + 1) * 8, hipMemcpyHostToDevice, st));
-  SIMPLIFY_TRY(hipMemcpyAsync(w.lat, lattice_host, (size_t)B * sizeof(Lattice), hipMemcpyHostToDevice, st));
-  SIMPLIFY_TRY(hipMemcpyAsync(w.cells, cells_host, (size_t)B * 4, hipMemcpyHostToDevice, st));
-  SIMPLIFY_TRY(hipMemsetAsync(w.status, 0, w.zero_bytes, st));
-  if (nf > 0) LAUNCH(validate_faces_kernel, nf, faces, w.voff, w.foff, B, nf, w.status);
+  MESH_TRY(upload_offsets(w.voff, w.foff, v_off_host, f_off_host, B, st));
+  MESH_TRY(hipMemcpyAsync(w.lat, lattice_host, (size_t)B * sizeof(Lattice), hipMemcpyHostToDevice, st));
+  MESH_TRY(hipMemcpyAsync(w.cells, cells_host, (size_t)B * 4, hipMemcpyHostToDevice, st));
+  MESH_TRY(hipMemsetAsync(w.status, 0, w.zero_bytes, st));
+  if (nf > 0) MESH_LAUNCH(validate_faces_kernel, nf, faces, w.voff, w.foff, B, nf, w.status);
   if (nv > 0) {
-    LAUNCH(validate_verts_kernel, nv, verts, w.voff, B, nv, w.status);
-    SIMPLIFY_TRY(hipMemsetAsync(w.vkeys, 0xFF, w.Tv * 8, st));
-    SIMPLIFY_TRY(hipMemsetAsync(w.vfirst, 0x7F, w.Tv * 4, st));
-    LAUNCH(vertex_claim_kernel, nv, verts, w.voff, B, nv, w.lat, w.cells, w.status, w.vkeys, w.Tv - 1, w.vfirst,
+    MESH_LAUNCH(validate_verts_kernel, nv, verts, w.voff, B, nv, w.status);
+    MESH_TRY(hipMemsetAsync(w.vkeys, 0xFF, w.Tv * 8, st));
+    MESH_TRY(hipMemsetAsync(w.vfirst, 0x7F, w.Tv * 4, st));
+    MESH_LAUNCH(vertex_claim_kernel, nv, verts, w.voff, B, nv, w.lat, w.cells, w.status, w.vkeys, w.Tv - 1, w.vfirst,
            w.vslot);
-    LAUNCH(vertex_flag_kernel, nv, w.voff, B, nv, w.status, w.vfirst, w.vslot, w.vflag, w.meshcnt);
-    SIMPLIFY_TRY(exclusive_scan(w.vflag, w.vscan, (size_t)nv, w.bsum, w.totals, st));
+    MESH_LAUNCH(vertex_flag_kernel, nv, w.voff, B, nv, w.status, w.vfirst, w.vslot, w.vflag, w.meshcnt);
+    MESH_TRY(exclusive_scan(w.vflag, w.vscan, (size_t)nv, w.bsum, w.totals, st));
   }
   hipLaunchKernelGGL(cluster_base_kernel, dim3((B + 1 + kThreads - 1) / kThreads), dim3(kThreads), 0, st, w.voff, B,
                      nv, w.vscan, w.totals, w.cbase);
-  SIMPLIFY_TRY(hipGetLastError());
+  MESH_TRY(hipGetLastError());
   if (nv > 0)
-    LAUNCH(vertex_accum_kernel, nv, verts, w.voff, B, nv, w.lat, w.cells, w.status, w.vfirst, w.vslot, w.vscan,
+    MESH_LAUNCH(vertex_accum_kernel, nv, verts, w.voff, B, nv, w.lat, w.cells, w.status, w.vfirst, w.vslot, w.vscan,
            w.vclu, w.acc);
   if (nf > 0) {
     if (dedup) {
-      SIMPLIFY_TRY(hipMemsetAsync(w.fkeys, 0xFF, w.Tf * 8, st));
-      SIMPLIFY_TRY(hipMemsetAsync(w.fmin_, 0x7F, w.Tf * 4, st));
+      MESH_TRY(hipMemsetAsync(w.fkeys, 0xFF, w.Tf * 8, st));
+      MESH_TRY(hipMemsetAsync(w.fmin_, 0x7F, w.Tf * 4, st));
     }
-    LAUNCH(face_kernel, nf, verts, faces, w.voff, w.foff, B, nf, w.lat, w.cells, dedup ? 1 : 0, w.status, w.vclu,
+    MESH_LAUNCH(face_kernel, nf, verts, faces, w.voff, w.foff, B, nf, w.lat, w.cells, dedup ? 1 : 0, w.status, w.vclu,
            w.acc, w.fkeys, w.Tf - 1, w.fmin_, w.fslot, w.meshcnt);
-    LAUNCH(face_flag_kernel, nf, w.foff, B, nf, dedup ? 1 : 0, w.status, w.fmin_, w.fslot, w.fflag, w.meshcnt);
-    SIMPLIFY_TRY(exclusive_scan(w.fflag, w.fscan, (size_t)nf, w.bsum, w.totals + 1, st));
+    MESH_LAUNCH(face_flag_kernel, nf, w.foff, B, nf, dedup ? 1 : 0, w.status, w.fmin_, w.fslot, w.fflag, w.meshcnt);
+    MESH_TRY(exclusive_scan(w.fflag, w.fscan, (size_t)nf, w.bsum, w.totals + 1, st));
   }
   hipLaunchKernelGGL(finish_kernel, dim3(1), dim3(1), 0, st, B, w.status, w.meshcnt, w.vseg,
                      reinterpret_cast<long long*>(counts));
-  SIMPLIFY_TRY(hipGetLastError());
+  MESH_TRY(hipGetLastError());
   return 0;
 }
 
@@ -524,7 +424,7 @@ extern "C" int disn_mesh_simplify_emit_batch(const float* verts, const int32_t* 
                                              void* ws, size_t ws_bytes, void* stream) {
   if (!offsets_ok(v_off_host, f_off_host, B) || !sizes_host || !ws) return DISN_E_ARG;
   const int64_t nv = v_off_host[B], nf = f_off_host[B];
-  if (!batch_ok(B, nv, nf)) return DISN_E_SHAPE;
+  if (!mesh_limits_ok(B, nv, nf)) return DISN_E_SHAPE;
   if (ws_bytes < simplify_layout(nullptr, B, nv, nf).total) return DISN_E_WS;
   hipStream_t st = (hipStream_t)stream;
   const SimplifyWs w = simplify_layout(ws, B, nv, nf);
@@ -540,11 +440,11 @@ extern "C" int disn_mesh_simplify_emit_batch(const float* verts, const int32_t* 
   if (nv == 0) return 0;
   if (!verts || !vmap || (nvo > 0 && (!out_verts || !first)) || (nfo > 0 && (!faces || !out_faces)))
     return DISN_E_ARG;
-  LAUNCH(emit_vmap_kernel, nv, w.voff, B, nv, w.status, w.vclu, w.cbase, vmap);
+  MESH_LAUNCH(emit_vmap_kernel, nv, w.voff, B, nv, w.status, w.vclu, w.cbase, vmap);
   if (nvo > 0)
-    LAUNCH(solve_kernel, nv, verts, w.voff, B, nv, w.lat, w.cells, w.status, w.vflag, w.vclu, w.cbase, w.vseg, w.acc,
+    MESH_LAUNCH(solve_kernel, nv, verts, w.voff, B, nv, w.lat, w.cells, w.status, w.vflag, w.vclu, w.cbase, w.vseg, w.acc,
            nvo, out_verts, first);
   if (nfo > 0)
-    LAUNCH(emit_faces_kernel, nf, faces, w.voff, w.foff, B, nf, w.fflag, w.fscan, w.vclu, w.cbase, nfo, out_faces);
+    MESH_LAUNCH(emit_faces_kernel, nf, faces, w.voff, w.foff, B, nf, w.fflag, w.fscan, w.vclu, w.cbase, nfo, out_faces);
   return 0;
 }

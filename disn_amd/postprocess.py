@@ -499,8 +499,9 @@ def colour_arrays(verts, faces, images, trans_mats, alpha=None, S: int = 2, rel_
     return ((c16 * 255 + 32767) // 65535).astype(np.uint8), cls
 
 
-# ---- the device path (mesh_clean.hip) --------------------------------------------------------------------------
-STATUS_NOTHING_KEPT, STATUS_INDEX, STATUS_TABLE = 1, 2, 3
+# ---- the device path: B meshes back to back (mesh_clean.hip, mesh_simplify.hip, mesh_colour.hip) ---------------
+# a mesh's status word (csrc/mesh_batch.hpp and the stages' own; include/): 1 is the cleanup's, 5 the simplification's
+STATUS_NOTHING_KEPT, STATUS_INDEX, STATUS_TABLE, STATUS_FINITE, STATUS_CAPACITY = 1, 2, 3, 4, 5
 
 
 def _pack(parts, dtype, what: str):
@@ -527,12 +528,38 @@ def _pack(parts, dtype, what: str):
     return whole, off
 
 
-def _clean_ws(B: int, nv: int, nf: int, device):
+def _pack_meshes(meshes, workspace_bytes, what: str = ""):
+    """B x (verts, faces, ...) -> (verts, v_off, faces, f_off, workspace): the meshes packed and the workspace of a
+    stage whose query is ``workspace_bytes(nv, nf)``; ValueError when the query refuses the batch (0)"""
+    import torch
+
     from . import ops
-    need = lib().disn_mesh_clean_workspace_bytes(B, nv, nf)
+    (v, v_off), (f, f_off) = (_pack([m[0] for m in meshes], torch.float32, "verts"),
+                              _pack([m[1] for m in meshes], torch.int32, "faces"))
+    nv, nf = int(v_off[-1]), int(f_off[-1])
+    need = workspace_bytes(nv, nf)
     if need == 0:
-        raise ValueError("unsupported batch: %d meshes, %d vertices, %d triangles" % (B, nv, nf))
-    return ops._ws(need, device)
+        raise ValueError("unsupported batch: %d meshes, %s%d vertices, %d triangles" % (len(meshes), what, nv, nf))
+    return v, v_off, f, f_off, ops._ws(need, v.device)
+
+
+def _raise_status(b: int, status: int, v_off, entry: str):
+    """the statuses the stages share -> their exceptions (a stage adds its own cases behind this)"""
+    if status == STATUS_INDEX:
+        raise ValueError("mesh %d: face index out of range (mesh of %d vertices)" % (b, v_off[b + 1] - v_off[b]))
+    if status == STATUS_FINITE:
+        raise ValueError("mesh %d: a vertex coordinate is not finite" % b)
+    if status == STATUS_TABLE:
+        raise RuntimeError("mesh %d: internal table full (%s)" % (b, entry))
+
+
+def _one_mesh(fn, *args, **kw):
+    """``fn(*args, **kw)``, a group call on one mesh, with the "mesh 0: " taken off its ValueErrors"""
+    try:
+        return fn(*args, **kw)
+    except ValueError as e:
+        msg = str(e)
+        raise ValueError(msg[len("mesh 0: "):] if msg.startswith("mesh 0: ") else msg) from e
 
 
 def _connectivity(connectivity: str) -> int:
@@ -549,13 +576,13 @@ def separate_mesh_device(verts, faces, connectivity: str = "face"):
     from . import ops
     from ._lib import check
     conn = _connectivity(connectivity)
-    (v, v_off), (f, f_off) = _pack([verts], torch.float32, "verts"), _pack([faces], torch.int32, "faces")
+    v, v_off, f, f_off, ws = _pack_meshes([(verts, faces)],
+                                          lambda nv, nf: lib().disn_mesh_clean_workspace_bytes(1, nv, nf))
     nv, nf, dev = int(v_off[1]), int(f_off[1]), f.device
     labels = torch.empty(nf, dtype=torch.int32, device=dev)
     if nf == 0:
         return labels, torch.zeros(0, dtype=torch.int64, device=dev)
     with torch.cuda.device(dev):
-        ws = _clean_ws(1, nv, nf, dev)
         ncomp = torch.zeros(1, dtype=torch.int64, device=dev)
         comp_verts = torch.zeros(nf, dtype=torch.int64, device=dev)
         check("disn_mesh_components_device", lib().disn_mesh_components_device(
@@ -587,12 +614,10 @@ def clean_meshes_device(meshes, dist_thresh: float = 0.5, num_thresh: float = 0.
     meshes = [tuple(m) for m in meshes]
     if not meshes:
         return [], []
-    (v, v_off), (f, f_off) = (_pack([m[0] for m in meshes], torch.float32, "verts"),
-                              _pack([m[1] for m in meshes], torch.int32, "faces"))
-    B, nv, nf, dev = len(meshes), int(v_off[-1]), int(f_off[-1]), v.device
-    h = lib()
+    B, h = len(meshes), lib()
+    v, v_off, f, f_off, ws = _pack_meshes(meshes, lambda nv, nf: h.disn_mesh_clean_workspace_bytes(B, nv, nf))
+    dev = v.device
     with torch.cuda.device(dev):
-        ws = _clean_ws(B, nv, nf, dev)
         counts = torch.zeros((B, 5), dtype=torch.int64, device=dev)
         st = ops._stream()
         check("disn_mesh_clean_count_batch", h.disn_mesh_clean_count_batch(
@@ -600,11 +625,7 @@ def clean_meshes_device(meshes, dist_thresh: float = 0.5, num_thresh: float = 0.
             float(num_thresh), counts.data_ptr(), ws.data_ptr(), ws.numel(), st))
         sizes = np.ascontiguousarray(counts.cpu().numpy())      # the one host sync of the group
         for b in range(B):
-            if sizes[b, 4] == STATUS_INDEX:
-                raise ValueError("mesh %d: face index out of range (mesh of %d vertices)"
-                                 % (b, v_off[b + 1] - v_off[b]))
-            if sizes[b, 4] == STATUS_TABLE:
-                raise RuntimeError("mesh %d: internal table full (disn_mesh_clean_count_batch)" % b)
+            _raise_status(b, sizes[b, 4], v_off, "disn_mesh_clean_count_batch")
             if sizes[b, 4] == STATUS_NOTHING_KEPT and strict:
                 raise ValueError("mesh %d: no part is kept (dist_thresh %g, num_thresh %g): %d parts"
                                  % (b, dist_thresh, num_thresh, sizes[b, 0]))
@@ -637,18 +658,11 @@ def clean_arrays_device(verts, faces, dist_thresh: float = 0.5, num_thresh: floa
     bits of ``clean_arrays``; the same ValueErrors (no triangles, no part kept, index out of range)"""
     if faces.shape[0] == 0:
         raise ValueError("the mesh has no triangles")
-    try:
-        cleaned, kept = clean_meshes_device([(verts, faces)], dist_thresh, num_thresh, connectivity)
-    except ValueError as e:
-        msg = str(e)
-        raise ValueError(msg[len("mesh 0: "):] if msg.startswith("mesh 0: ") else msg) from e
+    cleaned, kept = _one_mesh(clean_meshes_device, [(verts, faces)], dist_thresh, num_thresh, connectivity)
     return cleaned[0][0], cleaned[0][1], kept[0].tolist()
 
 
 # ---- simplification on the device (mesh_simplify.hip) ----------------------------------------------------------
-STATUS_FINITE, STATUS_CAPACITY = 4, 5
-
-
 def simplify_meshes_device(meshes, boxes, cells, dedup: bool = True):
     """``simplify_arrays`` for a group of meshes that lie on the device.  ``meshes``: B x (verts [nv,3] float32, faces
     [nf,3] int32[, further per-vertex arrays]) device tensors (the views ``isosurface.marching_cubes_batch`` and
@@ -674,15 +688,10 @@ def simplify_meshes_device(meshes, boxes, cells, dedup: bool = True):
     for b in range(B):
         lattice[b, :3], lattice[b, 3] = simplify_lattice(boxes[b], cells_in[b])       # (checks the cells too)
     cells_h = np.ascontiguousarray(cells_in, np.int32)
-    (v, v_off), (f, f_off) = (_pack([m[0] for m in meshes], torch.float32, "verts"),
-                              _pack([m[1] for m in meshes], torch.int32, "faces"))
-    nv, nf, dev = int(v_off[-1]), int(f_off[-1]), v.device
     h = lib()
+    v, v_off, f, f_off, ws = _pack_meshes(meshes, lambda nv, nf: h.disn_mesh_simplify_workspace_bytes(B, nv, nf))
+    nv, dev = int(v_off[-1]), v.device
     with torch.cuda.device(dev):
-        need = h.disn_mesh_simplify_workspace_bytes(B, nv, nf)
-        if need == 0:
-            raise ValueError("unsupported batch: %d meshes, %d vertices, %d triangles" % (B, nv, nf))
-        ws = ops._ws(need, dev)
         counts = torch.zeros((B, 4), dtype=torch.int64, device=dev)
         st = ops._stream()
         check("disn_mesh_simplify_count_batch", h.disn_mesh_simplify_count_batch(
@@ -690,13 +699,7 @@ def simplify_meshes_device(meshes, boxes, cells, dedup: bool = True):
             B, 1 if dedup else 0, counts.data_ptr(), ws.data_ptr(), ws.numel(), st))
         sizes = np.ascontiguousarray(counts.cpu().numpy())      # the one host sync of the group
         for b in range(B):
-            if sizes[b, 3] == STATUS_INDEX:
-                raise ValueError("mesh %d: face index out of range (mesh of %d vertices)"
-                                 % (b, v_off[b + 1] - v_off[b]))
-            if sizes[b, 3] == STATUS_FINITE:
-                raise ValueError("mesh %d: a vertex coordinate is not finite" % b)
-            if sizes[b, 3] == STATUS_TABLE:
-                raise RuntimeError("mesh %d: internal table full (disn_mesh_simplify_count_batch)" % b)
+            _raise_status(b, sizes[b, 3], v_off, "disn_mesh_simplify_count_batch")
             if sizes[b, 3] == STATUS_CAPACITY:
                 raise RuntimeError("mesh %d: more than 2^21 clusters in one batch with dedup: simplify fewer meshes "
                                    "per call" % b)
@@ -725,11 +728,7 @@ def simplify_meshes_device(meshes, boxes, cells, dedup: bool = True):
 def simplify_arrays_device(verts, faces, box, cells: int, dedup: bool = True):
     """``simplify_arrays`` for one mesh on the device -> (verts', faces', vmap, first), device tensors with the
     integers and the position bits of ``simplify_arrays``; the same ValueErrors"""
-    try:
-        simplified, maps = simplify_meshes_device([(verts, faces)], [box], cells, dedup)
-    except ValueError as e:
-        msg = str(e)
-        raise ValueError(msg[len("mesh 0: "):] if msg.startswith("mesh 0: ") else msg) from e
+    simplified, maps = _one_mesh(simplify_meshes_device, [(verts, faces)], [box], cells, dedup)
     return simplified[0][0], simplified[0][1], maps[0][0], maps[0][1]
 
 
@@ -737,15 +736,13 @@ def simplify_arrays_device(verts, faces, box, cells: int, dedup: bool = True):
 def _colour_inputs(meshes, trans_mats, views_per_mesh: int, S: int):
     """-> (B, V, verts, v_off, faces, f_off, trans_mat [B,V,4,3] device, workspace)"""
     import torch
-
-    from . import ops
     if S not in COLOUR_SAMPLES:
         raise ValueError("S must be one of %s, got %r" % (COLOUR_SAMPLES, S))
     V, B = int(views_per_mesh), len(meshes)
     if not 1 <= V <= COLOUR_MAX_VIEWS:
         raise ValueError("views_per_mesh must be in 1..%d, got %r" % (COLOUR_MAX_VIEWS, views_per_mesh))
-    (v, v_off), (f, f_off) = (_pack([m[0] for m in meshes], torch.float32, "verts"),
-                              _pack([m[1] for m in meshes], torch.int32, "faces"))
+    v, v_off, f, f_off, ws = _pack_meshes(
+        meshes, lambda nv, nf: lib().disn_mesh_colour_workspace_bytes(B, V, nv, nf, int(S)), "%d views, " % V)
     dev = v.device
     tm = torch.as_tensor(np.ascontiguousarray(trans_mats.detach().cpu().numpy() if hasattr(trans_mats, "detach")
                                               else trans_mats, np.float32))
@@ -753,20 +750,13 @@ def _colour_inputs(meshes, trans_mats, views_per_mesh: int, S: int):
         raise ValueError("trans_mats must hold %d meshes x %d views x [4,3], got %s" % (B, V, tuple(tm.shape)))
     tm_d = torch.empty((B, V, 4, 3), dtype=torch.float32, device=dev)
     tm_d.copy_(tm.reshape(B, V, 4, 3))
-    need = lib().disn_mesh_colour_workspace_bytes(B, V, int(v_off[-1]), int(f_off[-1]), int(S))
-    if need == 0:
-        raise ValueError("unsupported batch: %d meshes, %d views, %d vertices, %d triangles"
-                         % (B, V, v_off[-1], f_off[-1]))
-    return B, V, v, v_off, f, f_off, tm_d, ops._ws(need, dev)
+    return B, V, v, v_off, f, f_off, tm_d, ws
 
 
-def _colour_status(status, v_off, strict: bool) -> np.ndarray:
+def _colour_status(status, v_off, strict: bool, entry: str) -> np.ndarray:
     st = status.cpu().numpy()
     for b in np.nonzero(st)[0] if strict else ():
-        if st[b] == STATUS_INDEX:
-            raise ValueError("mesh %d: face index out of range (mesh of %d vertices)" % (b, v_off[b + 1] - v_off[b]))
-        if st[b] == STATUS_FINITE:
-            raise ValueError("mesh %d: a vertex coordinate is not finite" % b)
+        _raise_status(b, st[b], v_off, entry)
         raise RuntimeError("mesh %d: status %d" % (b, st[b]))
     return st
 
@@ -792,7 +782,7 @@ def zbuffer_meshes_device(meshes, trans_mats, views_per_mesh: int = 1, S: int = 
         check("disn_mesh_zbuffer_batch", lib().disn_mesh_zbuffer_batch(
             v.data_ptr(), f.data_ptr(), v_off.ctypes.data, f_off.ctypes.data, B, tm.data_ptr(), V, int(S),
             zbuf.data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel(), ops._stream()))
-        st = _colour_status(status, v_off, strict)
+        st = _colour_status(status, v_off, strict, "disn_mesh_zbuffer_batch")
     return zbuf if strict else (zbuf, st)
 
 
@@ -836,7 +826,7 @@ def colour_meshes_device(meshes, imgs, trans_mats, views_per_mesh: int = 1, alph
             None if alpha is None else alpha.data_ptr(), tm.data_ptr(), V, S, float(tol), axis, fill_iters,
             1 if bgr else 0, colours.data_ptr(), seen.data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel(),
             ops._stream()))
-        st = _colour_status(status, v_off, strict)
+        st = _colour_status(status, v_off, strict, "disn_mesh_colour_batch")
     cs = [colours[int(v_off[b]):int(v_off[b + 1])] for b in range(B)]
     ss = [seen[int(v_off[b]):int(v_off[b + 1])] for b in range(B)]
     return (cs, ss) if strict else (cs, ss, st)
@@ -846,11 +836,8 @@ def colour_arrays_device(verts, faces, images, trans_mats, alpha=None, **kw):
     """``colour_arrays`` for one mesh on the device: images [V,137,137,3] device float32, trans_mats [V,4,3], alpha None
     or [V,137,137] device uint8 -> (colours uint8 [nv,3], seen uint8 [nv]) device tensors; the same ValueErrors"""
     V = int(np.asarray(trans_mats.shape if hasattr(trans_mats, "shape") else np.shape(trans_mats))[:-2].prod())
-    try:
-        cs, ss = colour_meshes_device([(verts, faces)], images, trans_mats, views_per_mesh=max(V, 1), alpha=alpha, **kw)
-    except ValueError as e:
-        msg = str(e)
-        raise ValueError(msg[len("mesh 0: "):] if msg.startswith("mesh 0: ") else msg) from e
+    cs, ss = _one_mesh(colour_meshes_device, [(verts, faces)], images, trans_mats, views_per_mesh=max(V, 1), alpha=alpha,
+                       **kw)
     return cs[0], ss[0]
 
 

@@ -31,7 +31,7 @@ FLOAT_ATOMICS = {
     "disn_train_step": _GATHER_BWD,               # result key "grads_vgg": everything upstream of the feature map
 }
 
-# The other floating-point atomic of csrc/: disn_amd/csrc/mesh_clean.hip:248, unsafeAtomicAdd of DOUBLES into a component's
+# The other floating-point atomic of csrc/: mesh_clean.hip's pair_kernel, unsafeAtomicAdd of DOUBLES into a component's
 # coordinate sum (disn_mesh_clean_count_batch).  The sum's last bits depend on the order, but it reaches a result only
 # through keep_kernel's test `distance of the centroid < dist_thresh`, a discrete decision: the scenario's meshes (two
 # fans, an icosphere of radius 0.4 about the origin) have their parts' centroids at distances that differ from the 0.5
