@@ -431,89 +431,19 @@ hipError_t gemv_t_launch(const float* w_kn, const float* dy, int B, int K, int N
   return hipSuccess;
 }
 
-// Round 4: both halves of a small-batch fc backward in ONE pass over W (B <= 8):
-//     dW[k][n] = sum_b x[b][k] dy[b][n] + l2 W[k][n]        (outer_kernel's expression)
-//     dx[b][k] = (sum_n W[k][n] dy[b][n]) * (xact[b][k] > 0)   (gemv_t_kernel's expression and summation order)
-// outer_kernel + gemv_t_kernel read W twice and re-load the eight dy rows from L1 / L2 for every output float4 (18 / 9
-// memory instructions per 16 bytes of output: issue-bound, 0.9 / 1.6 TB/s on fc6's 411 MB).  Here dy [B][N] sits in LDS
-// (128 KB at N = 4096), a wave owns a row k: its x values are wave-uniform (scalar loads), each lane streams the row's
-// float4s once (nt), forms the dx partial dots and the dW float4 from the same registers and stores dW (nt): two memory
-// instructions per float4 of W, one read + one write of W's bytes in all.
-template <int NB>
-__global__ __launch_bounds__(512) void fc_bwd_fused_kernel(const float* __restrict__ x, const float* __restrict__ dy,
-                                                           int K, int N, const float* __restrict__ w, float l2,
-                                                           float* __restrict__ dw, const float* __restrict__ xact,
-                                                           float* __restrict__ dx) {
-  extern __shared__ __attribute__((aligned(16))) float dys[];   // [NB][N]
-  for (int i = threadIdx.x * 4; i < NB * N; i += blockDim.x * 4)
-    *reinterpret_cast<float4*>(&dys[i]) = *reinterpret_cast<const float4*>(dy + i);
-  __syncthreads();
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane((int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6));
-  const int nwaves = (gridDim.x * blockDim.x) >> 6;
-  for (int k = wave; k < K; k += nwaves) {
-    float xv[NB], acc[NB];
-#pragma unroll
-    for (int b = 0; b < NB; ++b) {
-      xv[b] = x[(size_t)b * K + k];      // wave-uniform
-      acc[b] = 0.f;
-    }
-    const float* wr = w + (size_t)k * N;
-    float* dwr = dw + (size_t)k * N;
-    for (int n0 = lane * 4; n0 < N; n0 += 1024) {   // four float4s of the row in flight per lane
-      float4 wv[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u)
-        if (n0 + 256 * u < N) wv[u] = nt_load4(wr + n0 + 256 * u);
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int n = n0 + 256 * u;
-        if (n >= N) break;
-        float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-        for (int b = 0; b < NB; ++b) {
-          const float4 d = *reinterpret_cast<const float4*>(&dys[b * N + n]);
-          acc[b] += (wv[u].x * d.x + wv[u].y * d.y) + (wv[u].z * d.z + wv[u].w * d.w);
-          o.x += xv[b] * d.x; o.y += xv[b] * d.y; o.z += xv[b] * d.z; o.w += xv[b] * d.w;
-        }
-        if (l2 != 0.f) { o.x += l2 * wv[u].x; o.y += l2 * wv[u].y; o.z += l2 * wv[u].z; o.w += l2 * wv[u].w; }
-        nt_store4(dwr + n, o);
-      }
-    }
-#pragma unroll
-    for (int b = 0; b < NB; ++b) {
-      float v = acc[b];
-#pragma unroll
-      for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
-      if (lane == 0) {
-        if (xact && !(xact[(size_t)b * K + k] > 0.f)) v = 0.f;
-        dx[(size_t)b * K + k] = v;
-      }
-    }
-  }
-}
-
-// dW and dx of one fc layer; B <= 8 and B * N * 4 <= 128 KB take the fused pass, otherwise outer + gemv_t as before
+// dW and dx of one fc layer: outer_kernel, then gemv_t_kernel (two passes over W).
+// Until this was written there was a one-pass form for B <= 8 (dy in LDS, a wave per row of W forming the dW float4s and
+// the dx partial dots from the same registers: one read of W instead of two).  From three samples on it returned wrong
+// dx elements whenever kernels of another stream ran beside it -- one to three of dz6 / dpool5 per step on the training
+// step's side stream, up to half of dz6 when the overlap was shifted -- while its dW, from the same dy and x, was right,
+// and gemv_t_kernel, launched just before it on the same stream, inputs and overlap, was right in every run.  Never on
+// one stream.  No defect was found in its source or ISA, so it is gone from every path rather than kept where it
+// happened to be alone on the device.
 hipError_t fc_bwd_launch(const float* x, const float* dy, int B, int K, int N, const float* w, float l2, float* dw,
                          const float* xact, float* dx, hipStream_t st) {
-  const size_t lds = (size_t)B * N * sizeof(float);
-  if (B > 8 || lds > 128 * 1024 || N % 4) {
-    hipError_t e = outer_launch(x, dy, B, K, N, dw, w, l2, st);
-    if (e != hipSuccess) return e;
-    return gemv_t_launch(w, dy, B, K, N, xact, dx, st);
-  }
-  int blocks = (K + 7) / 8;
-  if (blocks > 512) blocks = 512;        // two workgroups of 8 waves per CU at N <= 2048, one at N = 4096 (LDS)
-  switch (B) {
-#define DISN_FB_CASE(NB)                                                                                       \
-  case NB:                                                                                                     \
-    hipLaunchKernelGGL((fc_bwd_fused_kernel<NB>), dim3(blocks), dim3(512), lds, st, x, dy, K, N, w, l2, dw, xact, dx); \
-    break;
-    DISN_FB_CASE(1) DISN_FB_CASE(2) DISN_FB_CASE(3) DISN_FB_CASE(4)
-    DISN_FB_CASE(5) DISN_FB_CASE(6) DISN_FB_CASE(7) DISN_FB_CASE(8)
-#undef DISN_FB_CASE
-  }
-  return hipGetLastError();
+  hipError_t e = outer_launch(x, dy, B, K, N, dw, w, l2, st);
+  if (e != hipSuccess) return e;
+  return gemv_t_launch(w, dy, B, K, N, xact, dx, st);
 }
 
 // out[i] = src[i] + l2 * w[i]

@@ -9,16 +9,9 @@ import torch
 import torch.nn.functional as Fnn
 
 from conftest import report_close
+from train_edge_shapes import bf16_round, dev
 
 pytestmark = pytest.mark.gpu
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a, np.float32)).cuda()
-
-
-def bf16_round(a):
-    return torch.from_numpy(np.ascontiguousarray(a, np.float32)).to(torch.bfloat16).to(torch.float64).numpy()
 
 
 @pytest.fixture(scope="module")

@@ -12,27 +12,15 @@ import torch.nn.functional as Fnn
 from conftest import report_close
 from oracle import disn_oracle as O
 from oracle import train_oracle as T
+from train_edge_shapes import dev, host, rel_close, step_feed as _feed
 
 pytestmark = pytest.mark.gpu
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a, np.float32)).cuda()
-
-
-def host(t):
-    return t.detach().cpu().numpy()
 
 
 @pytest.fixture(scope="module")
 def ops():
     from disn_amd import ops as _ops
     return _ops
-
-
-def rel_close(name, got, ref, rtol_of_max):
-    ref = np.asarray(ref, np.float64)
-    report_close(name, got, ref, atol=rtol_of_max * max(float(np.abs(ref).max()), 1e-30))
 
 
 # ------------------------------------------------------------------ dense layer ----------------
@@ -187,14 +175,6 @@ def test_adam_update(ops):
 
 
 # ------------------------------------------------------------------ the whole step --------------
-def _feed(B, N, seed):
-    feed = O.synth_inputs(seed=seed, batch=B, n_points=N)
-    rng = np.random.default_rng(seed + 1)
-    feed["sample_pc_rot"] = (feed["sample_pc"] @ np.array([[0, 0, 1], [0, 1, 0], [-1, 0, 0]], np.float32)).astype(np.float32)
-    feed["sdf"] = (0.05 * rng.standard_normal((B, N, 1))).astype(np.float32)
-    return feed
-
-
 def _dev_feed(feed):
     return {k: dev(feed[k]) for k in ("imgs", "trans_mat", "sample_pc", "sample_pc_rot", "sdf")}
 
