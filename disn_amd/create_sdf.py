@@ -52,9 +52,18 @@ the whole group with one read-back (``isosurface.marching_cubes_batch``) and wri
     level set and the normals are the gradients at the final vertices.  The tree goes to ``<...>[_comb]_s<CELLS>``.
     ``evaluate``'s cd_emd and f_score sample VERTICES, as the reference's do: the scores of a simplified tree are
     not the reference's numbers.  Composes with every flag above.
+  * ``--score GT_DIR [--score_points 2048]`` (not in the reference) scores every group's FINAL meshes -- behind clean,
+    simplify and colour, while they still lie on the device -- on area-weighted surface samples against
+    ``<GT_DIR>/<cat_id>/<obj>/isosurf.obj`` (``metrics.sample_surface_meshes_device`` / ``surface_scores``, DESIGN 4zc;
+    the ground truth is sampled once per object and kept on the device) and appends one JSON line per mesh to
+    ``<out_dir>/scores.jsonl`` (started afresh by a run that scores every listed mesh; with ``--skip_existing`` the
+    lines of the meshes done now are appended to those of the earlier runs).  A ground truth without area is logged
+    and marked ``"gt_status": 6`` in its lines.  A mesh's samples depend on ``--seed`` and its file name alone.  Composes with every
+    flag above; without it nothing changes.
 """
 from __future__ import annotations
 
+import json
 import math
 import os
 import random
@@ -341,6 +350,76 @@ def colour_group(meshes, colour, imgs, trans_mats, views_per_mesh: int = 1, alph
     return out
 
 
+SCORE_POINTS = 2048
+SCORE_CACHE = 8               # ground-truth objects whose samples stay on the device between groups
+
+
+def score_args(score) -> Optional[Tuple[str, int]]:
+    """``score`` = None (off), GT_DIR or (GT_DIR, points) -> None or the checked (gt_dir, points) (ValueError; no
+    device work)"""
+    if score is None:
+        return None
+    gt_dir, n = (score, SCORE_POINTS) if isinstance(score, str) else score
+    if isinstance(n, bool) or int(n) != n or not 1 <= int(n) <= 1 << 20:
+        raise ValueError("--score_points must be an integer in 1..%d, got %r" % (1 << 20, n))
+    if not gt_dir:
+        raise ValueError("--score needs the directory of the ground-truth meshes")
+    return str(gt_dir), int(n)
+
+
+def score_ground_truth(gt_dir: str, cat_id: str, obj: str, n: int, seed: int, device=None, log=None):
+    """-> (points [n,3], normals [n,3], status): the surface samples of <gt_dir>/<cat_id>/<obj>/isosurf.obj as device
+    tensors; status 6 (zeros: the mesh has no area) is reported through ``log``, any other is a ValueError"""
+    from .evaluate import _device_mesh, _sampled
+    pts, nrm, status = _sampled([_device_mesh(os.path.join(gt_dir, cat_id, obj, "isosurf.obj"), device)],
+                                ["%s/%s/isosurf.obj" % (cat_id, obj)], n, seed, log)
+    return pts[0], nrm[0], int(status[0])
+
+
+def score_group(meshes, keys, score, seed: int = 0, cache: Optional[dict] = None, truethreshold: float = 2.5,
+                log=None):
+    """the scoring of one group behind every other stage: ONE ``sample_surface_meshes_device`` call for the meshes that
+    have triangles, ONE ``surface_scores`` call against their objects' ground truth (``cache``: (cat_id, obj) -> its
+    samples, filled here; it keeps every object of the group, however many, and beyond SCORE_CACHE objects drops
+    those the group does not need) -> one dict per mesh, ``keys`` [(cat_id, obj, view)] in mesh order: the scores as
+    floats and lists, "status" (None for a mesh without triangles, which is not scored) and "gt_status" (6: the ground
+    truth has no area, the scores are against n points at the origin; ``log`` gets a line naming it).  The meshes are
+    not touched."""
+    import torch
+
+    from . import metrics
+    gt_dir, n = score
+    cache = {} if cache is None else cache
+    rows = [{"cat_id": c, "obj": o, "view": int(v), "points": n, "status": None} for c, o, v in keys]
+    picked = [b for b, m in enumerate(meshes) if len(m[0]) and len(m[1])]
+    if not picked:
+        return rows
+    dev = getattr(meshes[picked[0]][0], "device", None)
+    need = dict.fromkeys(tuple(keys[b][:2]) for b in picked)
+    if len(set(cache) | set(need)) > SCORE_CACHE:           # make room, but never at the cost of this group's objects
+        for key in [k for k in cache if k not in need]:
+            del cache[key]
+    for c, o in need:
+        if (c, o) not in cache:
+            cache[(c, o)] = score_ground_truth(gt_dir, c, o, n, seed, dev, log)
+    pts, nrm, _, status = metrics.sample_surface_meshes_device(
+        [tuple(meshes[b][:2]) for b in picked], n,
+        [metrics.mesh_seed(seed, os.path.basename(obj_path("", *keys[b]))) for b in picked])
+    gt_pts = torch.stack([cache[tuple(keys[b][:2])][0] for b in picked])
+    gt_nrm = torch.stack([cache[tuple(keys[b][:2])][1] for b in picked])
+    thresholds = metrics.f_score_thresholds(truethreshold)
+    scores = metrics.surface_scores(pts, nrm, gt_pts, gt_nrm, thresholds)
+    status = np.asarray(status.cpu())
+    for k, b in enumerate(picked):
+        rows[b]["status"] = int(status[k])
+        rows[b]["gt_status"] = int(cache[tuple(keys[b][:2])][2])
+        if status[k] == 0:
+            rows[b].update({name: float(scores[name][k]) for name in metrics.SURFACE_SCORES})
+            rows[b].update({name: [float(x) for x in scores[name][k]] for name in ("precision", "recall", "f_score")})
+            rows[b]["thresholds"] = [float(t) for t in thresholds]
+    return rows
+
+
 def reconstruct(engine, imgs, trans_mats, sdf_params, sdf_res: int, iso: float = 0.0, refine: int = 0,
                 normals: bool = False, band=None, clean=None, simplify=None, colour=None, alpha=None):
     """``reconstruct_select`` for callers that clean every mesh or none (see there); -> the meshes"""
@@ -568,7 +647,26 @@ def parser():
     add_clean_flags(p)
     add_simplify_flag(p)
     add_colour_flags(p)
+    add_score_flags(p)
     return p
+
+
+def add_score_flags(p) -> None:
+    p.add_argument("--score", default=None, metavar="GT_DIR",
+                   help="score every final mesh on the device, on area-weighted surface samples, against "
+                        "GT_DIR/<cat_id>/<obj>/isosurf.obj; one JSON line per mesh in <out_dir>/scores.jsonl")
+    p.add_argument("--score_points", type=int, default=None, metavar="N",
+                   help="with --score: surface samples per mesh, 1..1048576 [default: %d]" % SCORE_POINTS)
+
+
+def score_from_flags(a) -> Optional[Tuple[str, int]]:
+    """None without --score, else the checked (gt_dir, points) (ValueError for --score_points without --score or
+    outside its range)"""
+    if a.score is None:
+        if a.score_points is not None:
+            raise ValueError("--score_points needs --score")
+        return None
+    return score_args((a.score, SCORE_POINTS if a.score_points is None else a.score_points))
 
 
 def add_colour_flags(p) -> None:
@@ -666,6 +764,7 @@ def check_flags(a) -> Optional[Tuple[int, str]]:
     clean_cats_from_flags(a)
     simplify_from_flags(a)
     colour_from_flags(a)
+    score_from_flags(a)
     return fuse_from_flags(a)
 
 
@@ -696,7 +795,8 @@ def load_group(group: Sequence, sdf_dir: str, rendered_dir: str, backcolorwhite:
 
 
 def main(argv=None, reconstruct_fn: Optional[Callable] = None) -> dict:
-    """-> {"written", "skipped", "empty", "out_dir"}, with ``--clean`` also "unclean", with ``--simplify`` also "simplified" (the
+    """-> {"written", "skipped", "empty", "out_dir"}, with ``--score`` also "scored" (the meshes with a score line of
+    status 0), with ``--clean`` also "unclean", with ``--simplify`` also "simplified" (the
     meshes with triangles: those that went through the stage), with ``--colour`` also "coloured" (likewise; every mesh
     then ends in ``colours`` uint8 [nv,3], behind the normals when there are any).  ``reconstruct_fn(imgs, trans_mats, sdf_params)``
     replaces the device work (engine + ``reconstruct``) -- for host-side tests of the driver.  With ``--clean`` it is
@@ -714,6 +814,7 @@ def main(argv=None, reconstruct_fn: Optional[Callable] = None) -> dict:
     cleaning = clean_cats_from_flags(a)
     simplify = simplify_from_flags(a)
     colour = colour_from_flags(a)
+    score = score_from_flags(a)
     more = {} if simplify is None else {"simplify": simplify}     # (without the flag every call below is as it was)
     out_dir = result_obj_path(a.log_dir, a.sdf_res, a.iso, a.cam_est, fuse, clean=cleaning is not None, **more,
                               **({} if colour is None else {"colour": True}))
@@ -768,7 +869,11 @@ def main(argv=None, reconstruct_fn: Optional[Callable] = None) -> dict:
             isosurface.write_obj(path, verts, faces, *extras[:-1], colours=extras[-1])
         return path
 
-    written = empty = unclean = 0
+    written = empty = unclean = scored = 0
+    score_cache: dict = {}
+    scores_path = os.path.join(out_dir, "scores.jsonl")
+    if score is not None and not a.skip_existing:           # every mesh is scored again: the file starts afresh
+        open(scores_path, "w").close()
     try:
         log_string(str(a))
         log_string("%s; %d views listed, %d to do in %d groups -> %s  (%s)"
@@ -793,6 +898,12 @@ def main(argv=None, reconstruct_fn: Optional[Callable] = None) -> dict:
                 for f in in_flight:                         # the group before this one: a writer's exception surfaces
                     f.result()
                 in_flight = []
+                if score is not None:                       # the final meshes, still where reconstruct left them
+                    rows = score_group(meshes, group[::per_mesh], score, a.seed, score_cache, log=log_string)
+                    with open(scores_path, "a") as sf:
+                        for row in rows:
+                            sf.write(json.dumps(row) + "\n")
+                    scored += sum(r["status"] == 0 for r in rows)
                 for (cat_id, obj, view), (verts, faces, *vn), as_it_is in zip(group[::per_mesh], meshes, left):
                     path = obj_path(out_dir, cat_id, obj, view)
                     if as_it_is:
@@ -818,6 +929,8 @@ def main(argv=None, reconstruct_fn: Optional[Callable] = None) -> dict:
         res["simplified"] = written - empty
     if colour is not None:
         res["coloured"] = written - empty
+    if score is not None:
+        res["scored"] = scored
     return res
 
 

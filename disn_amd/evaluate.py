@@ -6,6 +6,7 @@ on ``disn_amd.metrics`` instead of the TF1 + CUDA custom ops, and ``test/test_io
     python -m disn_amd.evaluate cd_emd  --cal_dir OBJS --gt_dir GT --test_lst_dir LSTS [--category all]
     python -m disn_amd.evaluate f_score --cal_dir OBJS --gt_dir GT --test_lst_dir LSTS [--truethreshold 2.5]
     python -m disn_amd.evaluate iou     --cal_dir OBJS --gt_dir GT --test_lst_dir LSTS [--dim 110] [--mode reference]
+    python -m disn_amd.evaluate surface --pred_dir OBJS --gt_dir GT --test_lst_dir LSTS [--num_sample_points 2048]
     python -m disn_amd.evaluate sdf_acc --log_dir CKPT --test_lst_dir LSTS --sdf_dir SDF --rendered_dir VIEWS
 
 Layout, as the reference reads it:
@@ -26,6 +27,10 @@ union is empty) raises, where the reference's bare ``try`` prints "error mesh" a
 Kept: the ``os.stat(...)[6] > 200`` size filter on prediction files, the float32 array of per-view values with its
 sum / mean / argmax, the category average over views, and the printed lines.  ``--mode solid`` (not in the
 reference, whose grids are surface shells) fills the voxel sets first.
+
+Surface scores (``surface``; NOT in the reference, whose numbers stay ``cd_emd`` and ``f_score`` on vertex samples):
+accuracy, completeness, Chamfer-L1 and -L2, normal consistency and precision / recall / F-score on area-weighted
+surface samples drawn on the device (``metrics.sample_surface_meshes_device``); layout and view choice as ``cd_emd``.
 
 SDF accuracy (``sdf_acc``, the reference's ``test/test_sdf_acc.py``): the five scalars of ``get_loss`` on sampled
 query points of the test views -- all 24 views of every listed object, ``sdf = sdf_val - 0.003``, one
@@ -224,6 +229,109 @@ def cal_f_score_all_cat(cats: Dict[str, str], pred_dir: str, gt_dir: str, test_l
     return {"categories": per, "thresholds": thresholds, "precision": pre, "recall": rec, "f_score": f}
 
 
+def _device_mesh(path: str, device=None):
+    """a whole .obj (disn_read_obj_mesh) as (verts f32 [nv,3], faces i32 [nf,3]) device tensors"""
+    import torch
+
+    from . import mesh_sdf
+    v, f = mesh_sdf.read_obj_mesh(path)
+    dev = device or torch.device("cuda")
+    return torch.from_numpy(v).to(dev), torch.from_numpy(f).to(dev)
+
+
+def _sampled(meshes, names, n: int, seed: int, log=None):
+    """area-weighted samples of a group of device meshes in ONE call -> (points [B,n,3], normals [B,n,3], status [B]
+    on the host); mesh b is seeded by ``mesh_seed(seed, names[b])``.  ValueError for a bad index or a coordinate that
+    is not finite; a mesh without area (status 6) gives zeros, as ``sample_vertices`` does for a mesh without
+    vertices, and ``log`` (default: a line on stderr) is told its name, so that its numbers are not taken for real ones."""
+    from . import metrics
+    pts, nrm, _, status = metrics.sample_surface_meshes_device(meshes, n, [metrics.mesh_seed(seed, nm) for nm in names])
+    status = np.asarray(status.cpu())
+    log = log or (lambda line: print(line, file=sys.stderr))
+    for b, st in enumerate(status):
+        if st == metrics.STATUS_NO_AREA:
+            log("WARNING: %s has no area to sample (status 6): it is scored as %d points at the origin" % (names[b], n))
+        elif st != 0:
+            raise ValueError("%s: %s" % (names[b], "face index out of range" if st == metrics.STATUS_INDEX
+                                         else "a vertex coordinate is not finite"))
+    return pts, nrm, status
+
+
+def surface_cat(cat_id: str, cat_nm: str, pred_dir: str, gt_dir: str, test_lst_f: str, thresholds,
+                view_num: int = 24, num_sample_points: int = 2048, seed: int = 0,
+                pyrng: Optional[random.Random] = None, out=None) -> dict:
+    """scores on area-weighted SURFACE samples (``metrics.surface_scores``) of every listed object over ``view_num``
+    sampled views; layout, view choice and logging as ``cd_emd_cat``.  The ground truth is sampled once per object,
+    the predictions of its views in one batched call; a mesh's samples depend on ``seed`` and its file name alone.
+    A mesh without area is scored as points at the origin, named in a WARNING line and listed under "no_area".
+    -> {"objects": {obj_id: {name: mean over the views, "views", "per_view", "no_area"}}, name: category mean,
+    "count", "no_area"}"""
+    from . import metrics
+    pyrng = pyrng if pyrng is not None else random.Random(0)
+    out = out or sys.stdout
+    pred_dict = build_file_dict(pred_dir)
+    objs = read_list(test_lst_f)
+    for obj_id in objs:
+        _predictions(pred_dict, obj_id, cat_id, pred_dir)
+    names = metrics.SURFACE_SCORES + ("precision", "recall", "f_score")
+    warn = lambda line: print(line, file=out)
+    res: Dict[str, dict] = {}
+    no_area: List[str] = []
+    sums = {k: 0.0 for k in names}
+    for count, obj_id in enumerate(objs, 1):
+        src_path = os.path.join(gt_dir, obj_id, "isosurf.obj")
+        preds = _predictions(pred_dict, obj_id, cat_id, pred_dir)
+        if len(preds) < view_num:
+            raise ValueError("object %s of category %s has %d predictions, --view_num is %d"
+                             % (obj_id, cat_id, len(preds), view_num))
+        gt_pts, gt_nrm, gt_st = _sampled([_device_mesh(src_path)], ["%s/%s/isosurf.obj" % (cat_id, obj_id)],
+                                         num_sample_points, seed, warn)
+        views = pyrng.sample(preds, view_num)
+        pts, nrm, st = _sampled([_device_mesh(p) for p in views], [os.path.basename(p) for p in views],
+                                num_sample_points, seed, warn)
+        flat = ([src_path] if gt_st[0] else []) + [p for p, s in zip(views, st) if s]
+        no_area += flat
+        per_view = metrics.surface_scores(pts, nrm, gt_pts[0], gt_nrm[0], thresholds)
+        mean = {k: np.asarray(per_view[k], np.float64).mean(0) for k in names}
+        for k in names:
+            sums[k] = sums[k] + mean[k]
+        res[obj_id] = dict(mean, views=views, per_view=per_view, no_area=flat)
+        print("%d  %s %s, f_score:%s" % (count, src_path, ", ".join("%s:%s" % (k, mean[k]) for k in metrics.SURFACE_SCORES),
+                                         mean["f_score"]), file=out)
+    summary = {"cat_nm": cat_nm, "cat_id": cat_id, "objects": res, "count": len(objs), "no_area": no_area}
+    summary.update({k: sums[k] / len(objs) for k in names})
+    if no_area:
+        print("WARNING: cat_id:%s, %d mesh(es) without area entered the averages as points at the origin"
+              % (cat_id, len(no_area)), file=out)
+    print("cat_nm:%s, cat_id:%s, %s, f_score:%s" % (cat_nm, cat_id, ", ".join(
+        "%s:%s" % (k, summary[k]) for k in metrics.SURFACE_SCORES), summary["f_score"]), file=out)
+    return summary
+
+
+def surface_all(cats: Dict[str, str], pred_dir: str, gt_dir: str, test_lst_dir: str, truethreshold: float = 2.5,
+                view_num: int = 24, num_sample_points: int = 2048, seed: int = 0, out=None) -> dict:
+    """``surface_cat`` of every category, then the averages weighted by object count.  NOT in the reference: its
+    numbers are ``cd_emd`` and ``f_score``, on vertex samples."""
+    from . import metrics
+    out = out or sys.stdout
+    thresholds = metrics.f_score_thresholds(truethreshold)
+    pyrng = random.Random(seed)
+    per = {}
+    for cat_nm, cat_id in cats.items():
+        per[cat_id] = surface_cat(cat_id, cat_nm, os.path.join(pred_dir, cat_id), os.path.join(gt_dir, cat_id),
+                                  os.path.join(test_lst_dir, cat_id + "_test.lst"), thresholds, view_num=view_num,
+                                  num_sample_points=num_sample_points, seed=seed, pyrng=pyrng, out=out)
+    print("done!", file=out)
+    counts = [c["count"] for c in per.values()]
+    res = {"categories": per, "thresholds": thresholds}
+    for k in metrics.SURFACE_SCORES + ("precision", "recall", "f_score"):
+        res[k] = metrics.weighted_category_average([c[k] for c in per.values()], counts)
+    print("weighted averages: %s, precision %s, recall %s, f_score %s" % (
+        ", ".join("%s %s" % (k, res[k]) for k in metrics.SURFACE_SCORES), res["precision"], res["recall"], res["f_score"]),
+        file=out)
+    return res
+
+
 def iou_cat(cat_id: str, cat_nm: str, pred_dir: str, gt_dir: str, test_lst_f: str, view_num: int = 24,
             dim: int = 110, mode: str = "reference", pyrng: Optional[random.Random] = None, out=None) -> dict:
     """voxel IoU of every listed object over ``view_num`` sampled views (test_iou.py:174-206)
@@ -336,6 +444,16 @@ def parser() -> argparse.ArgumentParser:
         s.add_argument("--num_sample_points", type=int, default=2048, help="points per mesh [default: 2048]")
         s.add_argument("--truethreshold", type=float, default=2.5, help="F-score side length [default: 2.5]")
         s.add_argument("--seed", type=int, default=0, help="seed of the point and view sampling [default: 0]")
+    s = sub.add_parser("surface", help="Chamfer-L1, normal consistency and F-score on area-weighted surface samples "
+                                       "(not in the reference)")
+    s.add_argument("--pred_dir", required=True, help="directory of the predicted meshes (<cat_id>/*.obj)")
+    s.add_argument("--gt_dir", required=True, help="ground-truth meshes (<cat_id>/<obj_id>/isosurf.obj)")
+    s.add_argument("--test_lst_dir", required=True, help="object lists (<cat_id>_test.lst)")
+    s.add_argument("--category", default="all", help="all, clean or one category name [default: all]")
+    s.add_argument("--view_num", type=int, default=24, help="views per object [default: 24]")
+    s.add_argument("--num_sample_points", type=int, default=2048, help="surface samples per mesh [default: 2048]")
+    s.add_argument("--truethreshold", type=float, default=2.5, help="F-score side length [default: 2.5]")
+    s.add_argument("--seed", type=int, default=0, help="seed of the samples and the view choice [default: 0]")
     s = sub.add_parser("iou", help="voxel IoU per object and category")
     s.add_argument("--cal_dir", required=True, help="directory of the predicted meshes (<cat_id>/*.obj)")
     s.add_argument("--gt_dir", required=True, help="ground-truth meshes (<cat_id>/<obj_id>/isosurf.obj)")
@@ -371,6 +489,9 @@ def main(argv=None) -> dict:
         return sdf_acc(cats, a.log_dir, a.test_lst_dir, a.sdf_dir, a.rendered_dir, batch_size=a.batch_size,
                        num_sample_points=a.num_sample_points, mask_weight=a.mask_weight, view_num=a.view_num,
                        seed=a.seed, random_init=a.random_init, rot=a.rot, backcolorwhite=a.backcolorwhite)
+    if a.command == "surface":
+        return surface_all(cats, a.pred_dir, a.gt_dir, a.test_lst_dir, truethreshold=a.truethreshold,
+                           view_num=a.view_num, num_sample_points=a.num_sample_points, seed=a.seed)
     if a.command == "iou":
         return iou_all(cats, a.cal_dir, a.gt_dir, a.test_lst_dir, dim=a.dim, mode=a.mode, view_num=a.view_num,
                        seed=a.seed)
