@@ -1,9 +1,12 @@
-// extern "C" entry points of include/disn_amd.h: argument checking, workspace carving and
-// the launch sequences.  No allocation, no global mutable state, no host synchronisation.
+// extern "C" entry points of the NETWORK (include/disn_amd.h): the layer entries, the VGG encoder, the point MLPs,
+// disn_encode_query and every disn_query* form, with the workspace layouts and the dispatch they share -- argument
+// checking, workspace carving and the launch sequences.  No allocation, no global mutable state, no host
+// synchronisation.  The entries of every other module (marching cubes, metrics, mesh-to-SDF, rendering, sphere
+// tracing, voxel IoU, batch assembly, the narrow-band selection, the mesh_* and training modules) sit at the end of
+// that module's own .hip file.
 #include "../../include/disn_amd.h"
 
 #include "kernels.hpp"
-#include "mesh_bvh.hpp"
 #include "tuning.hpp"
 
 #include <new>
@@ -425,18 +428,7 @@ QueryWs query_layout(void* ws, int B, int chunk, bool need_feat, bool need_pts, 
 
 inline int chunk_for(long n) { return (int)(n < kChunk ? (n > 0 ? n : 1) : kChunk); }
 
-bool grid_spec(const double* p, int R, GridSpec* g) {
-  if (!p || R < 1) return false;
-  g->res = R + 1;
-  for (int a = 0; a < 3; ++a) {
-    g->start[a] = p[a];
-    g->stop[a] = p[a + 3];
-    g->step[a] = (p[a + 3] - p[a]) / (double)R;  // numpy.linspace: delta / div
-  }
-  return true;
-}
-
-// ... and the range k0..k1-1 of its (R+1)^3 points: false for a bad box or an empty / out-of-grid range
+// grid_spec (kernels.hpp) and the range k0..k1-1 of its (R+1)^3 points: false for a bad box or an empty / out-of-grid range
 bool grid_range(const double* p, int R, int64_t k0, int64_t k1, GridSpec* g) {
   if (!grid_spec(p, R, g)) return false;
   const int64_t total = (int64_t)g->res * g->res * g->res;
@@ -1523,11 +1515,8 @@ int disn_query_grid_fused(const disn_mlp_weights_t* w, const float* pmap, const 
                        sdf_weight, st);
 }
 
-// ---- narrow-band grid evaluation (grid_band.hip) ----
+// ---- narrow-band grid evaluation: the network on a point list (selection and fill: grid_band.hip) ----
 namespace {
-// R <= 1289: (R+1)^3 < 2^31, a flat index fits the int32 list and the 32-bit scan
-bool band_shape_ok(int R, int s) { return (s == 2 || s == 4 || s == 8) && R >= s && R <= 1289 && R % s == 0; }
-
 struct ListedWs {
   float *gbias, *gemv_ws, *gsum, *pts, *vals;
   size_t total;
@@ -1544,28 +1533,6 @@ ListedWs listed_layout(void* ws, int64_t n) {
   return f;
 }
 }  // namespace
-
-size_t disn_grid_band_select_workspace_bytes(int R, int stride) {
-  return band_shape_ok(R, stride) ? band_select_ws_bytes(R, stride) : 0;
-}
-
-int disn_grid_band_select(const float* grid, int R, int stride, float iso, float margin, int dilate,
-                          int32_t* cell_mask, int32_t* idx, int64_t idx_capacity, uint64_t* counts, void* ws,
-                          size_t ws_bytes, void* stream) {
-  if (!grid || !cell_mask || !idx || !counts || !ws || !band_shape_ok(R, stride) || dilate < 0 || idx_capacity < 0 ||
-      !(margin >= 0.0f))
-    return DISN_E_ARG;
-  if (ws_bytes < band_select_ws_bytes(R, stride)) return DISN_E_WS;
-  DISN_TRY(band_select_launch(grid, R, stride, iso, margin, dilate, cell_mask, idx, (size_t)idx_capacity,
-                              reinterpret_cast<unsigned long long*>(counts), ws, (hipStream_t)stream));
-  return 0;
-}
-
-int disn_grid_band_fill(float* grid, int R, int stride, const int32_t* cell_mask, void* stream) {
-  if (!grid || !cell_mask || !band_shape_ok(R, stride)) return DISN_E_ARG;
-  DISN_TRY(band_fill_launch(grid, R, stride, cell_mask, (hipStream_t)stream));
-  return 0;
-}
 
 size_t disn_query_grid_listed_workspace_bytes(int64_t max_points) {
   if (max_points <= 0) return 0;
@@ -1756,286 +1723,6 @@ int disn_query_grid_ctx(disn_ctx_t* ctx, const disn_mlp_weights_t* w, const floa
     DISN_RC(mlp_chunk(w, pts[b], n, q.gbias, feat[b], out + (k - k0), nullptr, nullptr, sdf_weight, q.mlp, st));
     DISN_TRY(hipEventRecord(ctx->ev[3 + b], st));
   }
-  return 0;
-}
-
-size_t disn_mc_workspace_bytes(int R) { return (R < 1 || R > 1290) ? 0 : mc_ws_bytes(R); }
-
-int disn_mc_count(const float* sdf, int R, float iso, uint64_t* counts, void* ws, size_t ws_bytes,
-                  void* stream) {
-  if (!sdf || !counts || !ws || R < 1) return DISN_E_ARG;
-  if (R > 1290) return DISN_E_SHAPE;  // 3*(R+1)^3 edge slots must fit the 32-bit scan
-  if (ws_bytes < mc_ws_bytes(R)) return DISN_E_WS;
-  DISN_TRY(mc_count_launch(sdf, R, iso, reinterpret_cast<unsigned long long*>(counts), ws,
-                           (hipStream_t)stream));
-  return 0;
-}
-
-int disn_mc_emit(const float* sdf, const double* sdf_params_host, int R, float iso, float* verts,
-                 int32_t* faces, void* ws, size_t ws_bytes, void* stream) {
-  GridSpec g;
-  if (!sdf || !verts || !faces || !ws || !grid_spec(sdf_params_host, R, &g)) return DISN_E_ARG;
-  if (R > 1290) return DISN_E_SHAPE;
-  if (ws_bytes < mc_ws_bytes(R)) return DISN_E_WS;
-  DISN_TRY(mc_emit_launch(sdf, g, iso, verts, faces, ws, (hipStream_t)stream));
-  return 0;
-}
-
-// a batch is supported when its 3*B*(R+1)^3 edge slots fit the 32-bit scan
-static bool mc_batch_ok(int B, int R) {
-  if (B < 1 || R < 1 || R > 1290) return false;
-  const unsigned long long n = (unsigned long long)R + 1;
-  return 3ull * (unsigned long long)B * n * n * n < (1ull << 32);
-}
-
-size_t disn_mc_batch_workspace_bytes(int B, int R) { return mc_batch_ok(B, R) ? mc_batch_ws_bytes(B, R) : 0; }
-
-int disn_mc_count_batch(const float* sdf, int B, int R, float iso, uint64_t* counts, void* ws, size_t ws_bytes,
-                        void* stream) {
-  if (!sdf || !counts || !ws || B < 1 || R < 1) return DISN_E_ARG;
-  if (!mc_batch_ok(B, R)) return DISN_E_SHAPE;
-  if (ws_bytes < mc_batch_ws_bytes(B, R)) return DISN_E_WS;
-  DISN_TRY(mc_count_batch_launch(sdf, B, R, iso, reinterpret_cast<unsigned long long*>(counts), ws,
-                                 (hipStream_t)stream));
-  return 0;
-}
-
-int disn_mc_emit_batch(const float* sdf, const double* sdf_params_host, int B, int R, float iso, float* verts,
-                       int32_t* faces, void* ws, size_t ws_bytes, void* stream) {
-  if (!sdf || !verts || !faces || !ws || !sdf_params_host || B < 1 || R < 1) return DISN_E_ARG;
-  if (!mc_batch_ok(B, R)) return DISN_E_SHAPE;
-  if (ws_bytes < mc_batch_ws_bytes(B, R)) return DISN_E_WS;
-  GridSpec g[kMcBatchBoxes];  // the boxes travel as kernel arguments, kMcBatchBoxes grids per vertex launch
-  for (int b0 = 0; b0 < B; b0 += kMcBatchBoxes) {
-    const int nb = B - b0 < kMcBatchBoxes ? B - b0 : kMcBatchBoxes;
-    for (int i = 0; i < nb; ++i) grid_spec(sdf_params_host + 6 * (size_t)(b0 + i), R, &g[i]);
-    DISN_TRY(mc_verts_batch_launch(sdf, g, b0, nb, B, R, iso, verts, ws, (hipStream_t)stream));
-  }
-  DISN_TRY(mc_faces_batch_launch(sdf, B, R, iso, faces, ws, (hipStream_t)stream));
-  return 0;
-}
-
-// ---- evaluation metrics (metrics.hip) ----
-size_t disn_metrics_workspace_bytes(int b, int n, int m) {
-  return (b < 1 || n < 1 || m < 1) ? 0 : metrics_ws_bytes(b, n, m);
-}
-
-static int metrics_shape(int b, int n, int m) {
-  if (b < 1 || n < 1 || m < 1) return DISN_E_ARG;
-  if (b > 65535) return DISN_E_SHAPE;  // one grid row per pair
-  return 0;
-}
-
-int disn_nn_distance(const float* xyz1, const float* xyz2, int b, int n, int m, float* dist1, int32_t* idx1,
-                     float* dist2, int32_t* idx2, void* ws, size_t ws_bytes, void* stream) {
-  if (!xyz1 || !xyz2 || !dist1 || !idx1 || !dist2 || !idx2 || !ws) return DISN_E_ARG;
-  if (int rc = metrics_shape(b, n, m)) return rc;
-  if (ws_bytes < metrics_ws_bytes(b, n, m)) return DISN_E_WS;
-  DISN_TRY(nn_distance_launch(xyz1, xyz2, b, n, m, dist1, idx1, dist2, idx2, ws, (hipStream_t)stream));
-  return 0;
-}
-
-int disn_approx_match(const float* xyz1, const float* xyz2, int b, int n, int m, float* match, void* ws,
-                      size_t ws_bytes, void* stream) {
-  if (!xyz1 || !xyz2 || !match || !ws) return DISN_E_ARG;
-  if (int rc = metrics_shape(b, n, m)) return rc;
-  if (ws_bytes < metrics_ws_bytes(b, n, m)) return DISN_E_WS;
-  DISN_TRY(approx_match_launch(xyz1, xyz2, b, n, m, match, ws, (hipStream_t)stream));
-  return 0;
-}
-
-int disn_match_cost(const float* xyz1, const float* xyz2, const float* match, int b, int n, int m, float* cost,
-                    void* ws, size_t ws_bytes, void* stream) {
-  if (!xyz1 || !xyz2 || !match || !cost || !ws) return DISN_E_ARG;
-  if (int rc = metrics_shape(b, n, m)) return rc;
-  if (ws_bytes < metrics_ws_bytes(b, n, m)) return DISN_E_WS;
-  DISN_TRY(match_cost_launch(xyz1, xyz2, match, b, n, m, cost, ws, (hipStream_t)stream));
-  return 0;
-}
-
-int disn_emd(const float* xyz1, const float* xyz2, int b, int n, int m, float* cost, void* ws, size_t ws_bytes,
-             void* stream) {
-  if (!xyz1 || !xyz2 || !cost || !ws) return DISN_E_ARG;
-  if (int rc = metrics_shape(b, n, m)) return rc;
-  if (ws_bytes < metrics_ws_bytes(b, n, m)) return DISN_E_WS;
-  DISN_TRY(emd_launch(xyz1, xyz2, b, n, m, cost, ws, (hipStream_t)stream));
-  return 0;
-}
-
-// ---- mesh-to-SDF preprocessing (mesh_sdf.hip; host parts in mesh_host.cpp) ----
-static int mesh_grid_shape(int nx, int ny, int nz) {
-  if (nx < 2 || ny < 2 || nz < 2) return DISN_E_ARG;
-  if ((int64_t)nx * ny * nz > INT32_MAX) return DISN_E_SHAPE;  // int32 component labels
-  return 0;
-}
-
-int disn_mesh_udf_points(const void* bvh, int64_t nf, const float* points, int64_t n, int brute, float* dist,
-                         void* stream) {
-  if (!bvh || !points || !dist || nf < 1 || n < 1) return DISN_E_ARG;
-  if (nf > kBvhMaxTris || n > (int64_t)UINT32_MAX * 256) return DISN_E_SHAPE;
-  DISN_TRY(mesh_udf_points_launch(bvh, nf, points, n, brute, dist, (hipStream_t)stream));
-  return 0;
-}
-
-int disn_mesh_udf_grid(const void* bvh, int64_t nf, const float* xs, const float* ys, const float* zs, int nx, int ny,
-                       int nz, int brute, float* dist, void* stream) {
-  if (!bvh || !xs || !ys || !zs || !dist || nf < 1) return DISN_E_ARG;
-  if (int rc = mesh_grid_shape(nx, ny, nz)) return rc;
-  if (nf > kBvhMaxTris) return DISN_E_SHAPE;
-  DISN_TRY(mesh_udf_grid_launch(bvh, nf, xs, ys, zs, nx, ny, nz, brute, dist, (hipStream_t)stream));
-  return 0;
-}
-
-size_t disn_mesh_sign_workspace_bytes(int nx, int ny, int nz) {
-  return mesh_grid_shape(nx, ny, nz) ? 0 : mesh_sign_ws_bytes((int64_t)nx * ny * nz);
-}
-
-int disn_mesh_sign(const void* bvh, int64_t nf, const float* xs, const float* ys, const float* zs, int nx, int ny,
-                   int nz, const float* u, float tau, int steps, float offset, float* sdf, uint8_t* outside, void* ws,
-                   size_t ws_bytes, void* stream) {
-  if (!bvh || !xs || !ys || !zs || !u || !sdf || !ws || nf < 1 || steps < 0) return DISN_E_ARG;
-  if (!(tau > 0.0f) || !(offset == offset)) return DISN_E_ARG;
-  if (int rc = mesh_grid_shape(nx, ny, nz)) return rc;
-  if (nf > kBvhMaxTris) return DISN_E_SHAPE;
-  if (ws_bytes < mesh_sign_ws_bytes((int64_t)nx * ny * nz)) return DISN_E_WS;
-  return mesh_sign_launch(bvh, nf, xs, ys, zs, nx, ny, nz, u, tau, steps, offset, sdf, outside, ws,
-                          (hipStream_t)stream);
-}
-
-// ---- view rendering (render.hip) ----
-int disn_render_views(const void* bvh, int64_t nf, const int32_t* order, const float* albedo, const float* cams,
-                      int V, int H, int W, int S, float ambient, int brute, uint8_t* rgba, float* depth,
-                      int32_t* face, void* stream) {
-  if (!bvh || !cams || !rgba || nf < 1 || V < 1 || H < 1 || W < 1 || S < 1) return DISN_E_ARG;
-  if (!(ambient >= 0.0f && ambient <= 1.0f)) return DISN_E_ARG;
-  if (!order && (albedo || face)) return DISN_E_ARG;
-  if (nf > kBvhMaxTris || S > 4 || H > 1024 || W > 1024 || V > 65535) return DISN_E_SHAPE;
-  DISN_TRY(render_views_launch(bvh, nf, order, albedo, cams, V, H, W, S, ambient, brute, rgba, depth, face,
-                               (hipStream_t)stream));
-  return 0;
-}
-
-// ---- sphere tracing (sdf_trace.hip) ----
-namespace {
-constexpr int64_t kTraceMaxRays = int64_t(1) << 27;
-int64_t trace_rays(int V, int H, int W) {   // 0: not a shape this takes
-  if (V < 1 || H < 1 || W < 1 || H > 8192 || W > 8192) return 0;
-  const int64_t n = (int64_t)V * H * W;
-  return n <= kTraceMaxRays ? n : 0;
-}
-}  // namespace
-
-size_t disn_trace_state_bytes(int64_t n_rays) {
-  return n_rays >= 1 && n_rays <= kTraceMaxRays ? trace_state_bytes((size_t)n_rays) : 0;
-}
-
-int disn_trace_setup(const float* cams, int V, int H, int W, const double* sdf_params_host, float t_min, void* state,
-                     size_t state_bytes, float* pts, void* stream) {
-  const int64_t n = trace_rays(V, H, W);
-  if (!cams || !sdf_params_host || !state || !pts || !n || !(t_min >= 0.0f)) return DISN_E_ARG;
-  if (state_bytes < trace_state_bytes((size_t)n)) return DISN_E_WS;
-  float box[6];
-  for (int a = 0; a < 6; ++a) box[a] = (float)sdf_params_host[a];
-  for (int a = 0; a < 3; ++a)
-    if (!(box[a] <= box[a + 3])) return DISN_E_ARG;
-  DISN_TRY(trace_setup_launch(cams, V, H, W, box, t_min, state, pts, (hipStream_t)stream));
-  return 0;
-}
-
-int disn_trace_advance(const float* cams, int V, int H, int W, const float* values, int64_t n_active, int list_in,
-                       float sdf_weight, float iso, float eps, float step_scale, float min_step, float max_step,
-                       int max_steps, int refine, void* state, size_t state_bytes, float* pts, void* stream) {
-  const int64_t n = trace_rays(V, H, W);
-  if (!cams || !values || !state || !pts || !n || n_active < 1 || n_active > n || (list_in != 0 && list_in != 1))
-    return DISN_E_ARG;
-  if (sdf_weight == 0.0f || !(eps >= 0.0f) || !(step_scale > 0.0f) || !(min_step > 0.0f) || !(max_step >= min_step) ||
-      max_steps < 1 || refine < 1)
-    return DISN_E_ARG;
-  if (state_bytes < trace_state_bytes((size_t)n)) return DISN_E_WS;
-  const TraceMarch p{sdf_weight, iso, eps, step_scale, min_step, max_step, max_steps, refine};
-  DISN_TRY(trace_advance_launch(cams, V, H, W, values, (size_t)n_active, list_in, p, state, pts, (hipStream_t)stream));
-  return 0;
-}
-
-int disn_trace_collect(const float* cams, int V, int H, int W, void* state, size_t state_bytes, float* pts,
-                       void* stream) {
-  const int64_t n = trace_rays(V, H, W);
-  if (!cams || !state || !pts || !n) return DISN_E_ARG;
-  if (state_bytes < trace_state_bytes((size_t)n)) return DISN_E_WS;
-  DISN_TRY(trace_collect_launch(cams, V, H, W, state, pts, (hipStream_t)stream));
-  return 0;
-}
-
-int disn_trace_shade(const float* cams, int V, int H, int W, const void* state, size_t state_bytes, const float* pred,
-                     const float* grad, int64_t n_hits, float sdf_weight, float iso, float ambient, float* depth,
-                     float* normal, float* residual, uint8_t* status, uint8_t* rgba, void* stream) {
-  const int64_t n = trace_rays(V, H, W);
-  if (!cams || !state || !n || n_hits < 0 || n_hits > n || (n_hits > 0 && (!pred || !grad)) || sdf_weight == 0.0f ||
-      !(ambient >= 0.0f && ambient <= 1.0f))
-    return DISN_E_ARG;
-  if (state_bytes < trace_state_bytes((size_t)n)) return DISN_E_WS;
-  DISN_TRY(trace_shade_launch(cams, V, H, W, state, pred, grad, (size_t)n_hits, sdf_weight, iso, ambient, depth, normal,
-                              residual, status, rgba, (hipStream_t)stream));
-  return 0;
-}
-
-// ---- voxel IoU (voxel.hip) ----
-static int voxel_axis(int n) { return n < 1 ? DISN_E_ARG : (n > 1024 ? DISN_E_SHAPE : 0); }
-
-size_t disn_voxel_grid_words(int n) { return voxel_axis(n) ? 0 : voxel_grid_words(n); }
-
-size_t disn_voxel_surface_workspace_bytes(int64_t nf) { return nf < 0 ? 0 : voxel_surface_ws_bytes(nf); }
-
-int disn_voxel_surface(const float* verts, int64_t nv, const int32_t* faces, int64_t nf, int dim, int kmin, int nkeys,
-                       uint32_t* bits, int32_t* flags, void* ws, size_t ws_bytes, void* stream) {
-  if (!bits || !flags || !ws || nv < 0 || nf < 0 || dim < 1) return DISN_E_ARG;
-  if (nf > 0 && (!verts || !faces)) return DISN_E_ARG;
-  if (int rc = voxel_axis(nkeys)) return rc;
-  if (dim > 1024 || kmin < -4096 || kmin > 4096 || nf > INT32_MAX) return DISN_E_SHAPE;
-  if (ws_bytes < voxel_surface_ws_bytes(nf)) return DISN_E_WS;
-  DISN_TRY(voxel_surface_launch(verts, nv, faces, nf, dim, kmin, nkeys, bits, flags, ws, (hipStream_t)stream));
-  return 0;
-}
-
-size_t disn_voxel_fill_workspace_bytes(int n) { return voxel_axis(n) ? 0 : voxel_fill_ws_bytes(n); }
-
-int disn_voxel_fill(const uint32_t* surface, int n, uint32_t* solid, void* ws, size_t ws_bytes, void* stream) {
-  if (!surface || !solid || !ws) return DISN_E_ARG;
-  if (int rc = voxel_axis(n)) return rc;
-  if (ws_bytes < voxel_fill_ws_bytes(n)) return DISN_E_WS;
-  return voxel_fill_launch(surface, n, solid, ws, (hipStream_t)stream);
-}
-
-int disn_voxel_index_grid(const uint32_t* keys, int nkeys, const int32_t* lut, int dim, uint32_t* index_bits,
-                          void* stream) {
-  if (!keys || !lut || !index_bits) return DISN_E_ARG;
-  if (int rc = voxel_axis(nkeys)) return rc;
-  if (int rc = voxel_axis(dim)) return rc;
-  DISN_TRY(voxel_index_grid_launch(keys, nkeys, lut, dim, index_bits, (hipStream_t)stream));
-  return 0;
-}
-
-int disn_voxel_iou(const uint32_t* gt, const uint32_t* preds, int nviews, int64_t words, int64_t* inter,
-                   int64_t* uni, void* stream) {
-  if (!gt || !preds || !inter || !uni || nviews < 1 || words < 1) return DISN_E_ARG;
-  if (nviews > 65535 || words > ((int64_t)1 << 25)) return DISN_E_SHAPE;
-  DISN_TRY(voxel_iou_launch(gt, preds, nviews, words, inter, uni, (hipStream_t)stream));
-  return 0;
-}
-
-int disn_assemble_batch(const float* samples, const int64_t* sample_off, int64_t n_obj, const uint8_t* img,
-                        const float* trans_mat_all, const float* rot_all, int64_t n_view, const int32_t* obj_idx,
-                        const int32_t* view_idx, const int32_t* choice, int B, int S, int rot, int backcolorwhite,
-                        float* imgs, float* sample_pc, float* sample_pc_rot, float* sdf, float* trans_mat,
-                        int32_t* flags, void* stream) {
-  if (!samples || !sample_off || !img || !trans_mat_all || !obj_idx || !view_idx || !choice || !imgs || !sample_pc ||
-      !sample_pc_rot || !sdf || !trans_mat || !flags || (rot && !rot_all) || n_obj < 1 || n_view < 1 || B < 1 || S < 1)
-    return DISN_E_ARG;
-  if (((uintptr_t)samples & 15) || ((uintptr_t)img & 3)) return DISN_E_ARG;   // float4 rows, uchar4 pixels
-  if (B > 65535) return DISN_E_SHAPE;
-  DISN_TRY(assemble_batch_launch(samples, sample_off, n_obj, img, trans_mat_all, rot_all, n_view, obj_idx, view_idx,
-                                 choice, B, S, rot != 0, backcolorwhite != 0, imgs, sample_pc, sample_pc_rot, sdf,
-                                 trans_mat, flags, (hipStream_t)stream));
   return 0;
 }
 

@@ -100,11 +100,12 @@ __global__ void __launch_bounds__(256) assemble_batch_kernel(const AssembleArgs 
 
 }  // namespace
 
-hipError_t assemble_batch_launch(const float* samples, const int64_t* sample_off, int64_t n_obj,
-                                 const unsigned char* img, const float* trans_mat_all, const float* rot_all,
-                                 int64_t n_view, const int* obj_idx, const int* view_idx, const int* choice, int B,
-                                 int S, int rot, int white, float* imgs, float* sample_pc, float* sample_pc_rot,
-                                 float* sdf, float* trans_mat, int* flags, hipStream_t st) {
+static hipError_t assemble_batch_launch(const float* samples, const int64_t* sample_off, int64_t n_obj,
+                                        const unsigned char* img, const float* trans_mat_all, const float* rot_all,
+                                        int64_t n_view, const int* obj_idx, const int* view_idx, const int* choice,
+                                        int B, int S, int rot, int white, float* imgs, float* sample_pc,
+                                        float* sample_pc_rot, float* sdf, float* trans_mat, int* flags,
+                                        hipStream_t st) {
   AssembleArgs a;
   a.samples = reinterpret_cast<const float4*>(samples);
   a.sample_off = sample_off;
@@ -132,3 +133,32 @@ hipError_t assemble_batch_launch(const float* samples, const int64_t* sample_off
 }
 
 }  // namespace disn
+
+// ---- the C entries of include/disn_amd.h: argument and workspace checks, then the launchers above ----
+using namespace disn;
+
+#define DISN_TRY(expr)                    \
+  do {                                    \
+    hipError_t _e = (expr);               \
+    if (_e != hipSuccess) return (int)_e; \
+  } while (0)
+
+extern "C" {
+
+int disn_assemble_batch(const float* samples, const int64_t* sample_off, int64_t n_obj, const uint8_t* img,
+                        const float* trans_mat_all, const float* rot_all, int64_t n_view, const int32_t* obj_idx,
+                        const int32_t* view_idx, const int32_t* choice, int B, int S, int rot, int backcolorwhite,
+                        float* imgs, float* sample_pc, float* sample_pc_rot, float* sdf, float* trans_mat,
+                        int32_t* flags, void* stream) {
+  if (!samples || !sample_off || !img || !trans_mat_all || !obj_idx || !view_idx || !choice || !imgs || !sample_pc ||
+      !sample_pc_rot || !sdf || !trans_mat || !flags || (rot && !rot_all) || n_obj < 1 || n_view < 1 || B < 1 || S < 1)
+    return DISN_E_ARG;
+  if (((uintptr_t)samples & 15) || ((uintptr_t)img & 3)) return DISN_E_ARG;   // float4 rows, uchar4 pixels
+  if (B > 65535) return DISN_E_SHAPE;
+  DISN_TRY(assemble_batch_launch(samples, sample_off, n_obj, img, trans_mat_all, rot_all, n_view, obj_idx, view_idx,
+                                 choice, B, S, rot != 0, backcolorwhite != 0, imgs, sample_pc, sample_pc_rot, sdf,
+                                 trans_mat, flags, (hipStream_t)stream));
+  return 0;
+}
+
+}  // extern "C"

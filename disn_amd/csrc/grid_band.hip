@@ -12,7 +12,7 @@
 //
 // THIS FILE IS COMPILED WITH -ffp-contract=off: tests/grid_band_reference.py restates the arithmetic in float32 and the
 // results are compared bit for bit.  Streaming kernels, no LDS beyond the scan's; a grid has (R+1)^3 < 2^31 points
-// (R <= 1289, api.hip), so every flat index fits 32 bits and an int32 list.
+// (R <= 1289, band_shape_ok), so every flat index fits 32 bits and an int32 list.
 #include "kernels.hpp"
 
 namespace disn {
@@ -216,10 +216,13 @@ BandWs band_layout(void* ws, int R, int s) {
 
 }  // namespace
 
-size_t band_select_ws_bytes(int R, int s) { return band_layout(nullptr, R, s).total; }
+static size_t band_select_ws_bytes(int R, int s) { return band_layout(nullptr, R, s).total; }
 
-hipError_t band_select_launch(const float* grid, int R, int s, float iso, float margin, int dilate, int* cell_mask,
-                              int* idx, size_t idx_capacity, unsigned long long* counts, void* ws, hipStream_t st) {
+// band_shape_ok(R, s) is the caller's to check.  cell_mask [(R/s)^3] 0 / 1; idx: the band points' flat indices in
+// ascending order (entries beyond idx_capacity are dropped); counts (device) = {band points, active cells}
+static hipError_t band_select_launch(const float* grid, int R, int s, float iso, float margin, int dilate,
+                                     int* cell_mask, int* idx, size_t idx_capacity, unsigned long long* counts,
+                                     void* ws, hipStream_t st) {
   const BandWs w = band_layout(ws, R, s);
   const unsigned n = (unsigned)R + 1, C = (unsigned)(R / s);
   const size_t np = (size_t)n * n * n, nc = (size_t)C * C * C;
@@ -262,7 +265,7 @@ hipError_t band_scatter_launch(const float* vals, const int* idx, int R, int s, 
   return hipGetLastError();
 }
 
-hipError_t band_fill_launch(float* grid, int R, int s, const int* cell_mask, hipStream_t st) {
+static hipError_t band_fill_launch(float* grid, int R, int s, const int* cell_mask, hipStream_t st) {
   const unsigned n = (unsigned)R + 1;
   hipLaunchKernelGGL(band_fill_kernel, dim3(band_blocks((size_t)n * n * n)), dim3(256), 0, st, grid, n, (unsigned)s,
                      (unsigned)(R / s), reinterpret_cast<const unsigned*>(cell_mask));
@@ -270,3 +273,38 @@ hipError_t band_fill_launch(float* grid, int R, int s, const int* cell_mask, hip
 }
 
 }  // namespace disn
+
+// ---- the C entries of include/disn_amd.h: argument and workspace checks, then the launchers above ----
+using namespace disn;
+
+#define DISN_TRY(expr)                    \
+  do {                                    \
+    hipError_t _e = (expr);               \
+    if (_e != hipSuccess) return (int)_e; \
+  } while (0)
+
+extern "C" {
+
+size_t disn_grid_band_select_workspace_bytes(int R, int stride) {
+  return band_shape_ok(R, stride) ? band_select_ws_bytes(R, stride) : 0;
+}
+
+int disn_grid_band_select(const float* grid, int R, int stride, float iso, float margin, int dilate,
+                          int32_t* cell_mask, int32_t* idx, int64_t idx_capacity, uint64_t* counts, void* ws,
+                          size_t ws_bytes, void* stream) {
+  if (!grid || !cell_mask || !idx || !counts || !ws || !band_shape_ok(R, stride) || dilate < 0 || idx_capacity < 0 ||
+      !(margin >= 0.0f))
+    return DISN_E_ARG;
+  if (ws_bytes < band_select_ws_bytes(R, stride)) return DISN_E_WS;
+  DISN_TRY(band_select_launch(grid, R, stride, iso, margin, dilate, cell_mask, idx, (size_t)idx_capacity,
+                              reinterpret_cast<unsigned long long*>(counts), ws, (hipStream_t)stream));
+  return 0;
+}
+
+int disn_grid_band_fill(float* grid, int R, int stride, const int32_t* cell_mask, void* stream) {
+  if (!grid || !cell_mask || !band_shape_ok(R, stride)) return DISN_E_ARG;
+  DISN_TRY(band_fill_launch(grid, R, stride, cell_mask, (hipStream_t)stream));
+  return 0;
+}
+
+}  // extern "C"

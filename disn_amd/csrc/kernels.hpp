@@ -166,6 +166,17 @@ struct GridSpec {
   double start[3], step[3], stop[3];
   int res;  // R+1
 };
+// the (R+1)^3 grid of sdf_params_host = {x0, y0, z0, x1, y1, z1}
+inline bool grid_spec(const double* p, int R, GridSpec* g) {
+  if (!p || R < 1) return false;
+  g->res = R + 1;
+  for (int a = 0; a < 3; ++a) {
+    g->start[a] = p[a];
+    g->stop[a] = p[a + 3];
+    g->step[a] = (p[a + 3] - p[a]) / (double)R;  // numpy.linspace: delta / div
+  }
+  return true;
+}
 hipError_t grid_points_launch(const GridSpec& g, int64_t k0, int64_t k1, float* pts,
                               hipStream_t st);
 hipError_t scale_div_launch(const float* in, float divisor, int64_t n, float* out, hipStream_t st);
@@ -263,22 +274,8 @@ hipError_t maxpool_bwd_launch(const float* x, const float* dy, int B, int H, int
 hipError_t im2col_c3_launch(const float* img, int B, int H, int W, float* col, hipStream_t st);
 
 // ---- marching_cubes.hip (compiled with -ffp-contract=off) ------------------------
-size_t mc_ws_bytes(int R);
-// counts[0] = vertices, counts[1] = triangles (device memory); fills ws for mc_emit_launch
-hipError_t mc_count_launch(const float* vol, int R, float iso, unsigned long long* counts, void* ws,
-                           hipStream_t st);
-hipError_t mc_emit_launch(const float* vol, const GridSpec& g, float iso, float* verts, int* faces,
-                          void* ws, hipStream_t st);
-// B grids [B,(R+1)^3] in one set of passes (B*3*(R+1)^3 < 2^32): counts [B,2] per grid; verts / faces of all grids
-// back to back in grid order, face indices local to their grid
-size_t mc_batch_ws_bytes(int B, int R);
-hipError_t mc_count_batch_launch(const float* vol, int B, int R, float iso, unsigned long long* counts, void* ws,
-                                 hipStream_t st);
-constexpr int kMcBatchBoxes = 32;  // grids per vertex launch (their boxes are kernel arguments)
-// vertices of grids b0 .. b0+nb-1 (g[0..nb), nb <= kMcBatchBoxes) / triangles of all B grids
-hipError_t mc_verts_batch_launch(const float* vol, const GridSpec* g, int b0, int nb, int B, int R, float iso,
-                                 float* verts, void* ws, hipStream_t st);
-hipError_t mc_faces_batch_launch(const float* vol, int B, int R, float iso, int* faces, void* ws, hipStream_t st);
+// disn_mc_count / disn_mc_emit and their *_batch forms are defined there whole (checks, workspace layout, launches)
+constexpr int kMcBatchBoxes = 32;  // grids per vertex launch of a batch (their boxes are kernel arguments)
 
 // exclusive scan of n < 2^32 uint32 (three passes); bsum: one uint32 per kScanBlockItems items and one more; *total
 // (device memory) = the grand total
@@ -309,83 +306,33 @@ struct WsCursor {
 // sort run on exclusive_scan above
 
 // ---- grid_band.hip (compiled with -ffp-contract=off): narrow-band grid evaluation around a dense tensor ----
-// R % s == 0, s in {2, 4, 8}, R <= 1289 are the caller's to check (api.hip).  cell_mask [(R/s)^3] 0 / 1; idx: the band
-// points' flat indices in ascending order (entries beyond idx_capacity are dropped); counts (device) = {band points,
-// active cells}
-size_t band_select_ws_bytes(int R, int s);
-hipError_t band_select_launch(const float* grid, int R, int s, float iso, float margin, int dilate, int* cell_mask,
-                              int* idx, size_t idx_capacity, unsigned long long* counts, void* ws, hipStream_t st);
+// disn_grid_band_select and disn_grid_band_fill are defined there whole (checks, workspace layout, launches); the
+// listed query (api.hip) runs the network between the two launchers below
+// R <= 1289: (R+1)^3 < 2^31, a flat index fits the int32 list and the 32-bit scan
+inline bool band_shape_ok(int R, int s) { return (s == 2 || s == 4 || s == 8) && R >= s && R <= 1289 && R % s == 0; }
 // entries first .. first + count - 1 of a point list: idx, or (idx == nullptr) the lattice of stride s in flat order
 hipError_t band_coords_launch(const GridSpec& g, const int* idx, int s, size_t first, size_t count, float* pts,
                               hipStream_t st);
 hipError_t band_scatter_launch(const float* vals, const int* idx, int R, int s, size_t first, size_t count, float* grid,
                                hipStream_t st);
-hipError_t band_fill_launch(float* grid, int R, int s, const int* cell_mask, hipStream_t st);
 
 // ---- metrics.hip (compiled with -ffp-contract=off): evaluation metrics, one workspace for every entry ----
-size_t metrics_ws_bytes(int b, int n, int m);
-hipError_t nn_distance_launch(const float* xyz1, const float* xyz2, int b, int n, int m, float* dist1, int* idx1,
-                              float* dist2, int* idx2, void* ws, hipStream_t st);
-hipError_t approx_match_launch(const float* xyz1, const float* xyz2, int b, int n, int m, float* match, void* ws,
-                               hipStream_t st);
-hipError_t emd_launch(const float* xyz1, const float* xyz2, int b, int n, int m, float* cost, void* ws,
-                      hipStream_t st);
-hipError_t match_cost_launch(const float* xyz1, const float* xyz2, const float* match, int b, int n, int m,
-                             float* cost, void* ws, hipStream_t st);
+// disn_nn_distance, disn_approx_match, disn_match_cost, disn_emd are defined there whole (checks, workspace, launches)
 
 // ---- mesh_sdf.hip (compiled with -ffp-contract=off): mesh-to-SDF preprocessing; BVH image: mesh_bvh.hpp ----
-size_t mesh_sign_ws_bytes(int64_t N);
-hipError_t mesh_udf_points_launch(const void* bvh, int64_t nf, const float* pts, int64_t n, int brute, float* dist,
-                                  hipStream_t st);
-hipError_t mesh_udf_grid_launch(const void* bvh, int64_t nf, const float* xs, const float* ys, const float* zs,
-                                int nx, int ny, int nz, int brute, float* dist, hipStream_t st);
-// 0, a hipError_t, or DISN_E_CONVERGE; synchronises `st` once per labelling round
-int mesh_sign_launch(const void* bvh, int64_t nf, const float* xs, const float* ys, const float* zs, int nx, int ny,
-                     int nz, const float* u, float tau, int steps, float offset, float* sdf, unsigned char* outside,
-                     void* ws, hipStream_t st);
+// disn_mesh_udf_points, disn_mesh_udf_grid, disn_mesh_sign are defined there whole (checks, workspace, launches)
 
 // ---- render.hip (compiled with -ffp-contract=off): V pinhole views of one mesh over the same BVH image ----
-hipError_t render_views_launch(const void* bvh, int64_t nf, const int32_t* order, const float* albedo,
-                               const float* cams, int V, int H, int W, int S, float ambient, int brute,
-                               uint8_t* rgba, float* depth, int32_t* face, hipStream_t st);
+// disn_render_views is defined there whole (checks, launch)
 
 // ---- sdf_trace.hip (compiled with -ffp-contract=off): sphere tracing of an implicit field, V views of H x W rays ----
-// the state machine, the lists and the counts live in the caller's state (trace_state_bytes); `pts` takes one point per
-// listed ray (room for every ray at setup and collect, for n_active at advance); list `in` (0 / 1) is read, the other
-// one written; the sizes are the caller's to check (api.hip)
-struct TraceMarch {
-  float sdf_weight, iso, eps, step_scale, min_step, max_step;
-  int max_steps, refine;
-};
-size_t trace_state_bytes(size_t n_rays);
-hipError_t trace_setup_launch(const float* cams, int V, int H, int W, const float box[6], float t_min, void* state,
-                              float* pts, hipStream_t st);
-hipError_t trace_advance_launch(const float* cams, int V, int H, int W, const float* values, size_t n_active, int in,
-                                const TraceMarch& p, void* state, float* pts, hipStream_t st);
-hipError_t trace_collect_launch(const float* cams, int V, int H, int W, void* state, float* pts, hipStream_t st);
-hipError_t trace_shade_launch(const float* cams, int V, int H, int W, const void* state, const float* pred,
-                              const float* grad, size_t n_hits, float sdf_weight, float iso, float ambient, float* depth,
-                              float* normal, float* residual, uint8_t* status, uint8_t* rgba, hipStream_t st);
+// disn_trace_setup, _advance, _collect, _shade are defined there whole (checks, state size, launches)
 
 // ---- voxel.hip (compiled with -ffp-contract=off): voxel IoU; n^3 bit grids of n*n rows of ceil(n/32) words ----
-size_t voxel_grid_words(int n);
-size_t voxel_surface_ws_bytes(int64_t nf);
-size_t voxel_fill_ws_bytes(int n);
-hipError_t voxel_surface_launch(const float* verts, int64_t nv, const int* faces, int64_t nf, int dim, int kmin,
-                                int nkeys, unsigned* bits, int* flags, void* ws, hipStream_t st);
-// 0, a hipError_t, or DISN_E_CONVERGE; synchronises `st` once per batch of sweeps
-int voxel_fill_launch(const unsigned* surf, int n, unsigned* solid, void* ws, hipStream_t st);
-hipError_t voxel_index_grid_launch(const unsigned* keys, int nkeys, const int* lut, int dim, unsigned* out,
-                                   hipStream_t st);
-hipError_t voxel_iou_launch(const unsigned* gt, const unsigned* preds, int nviews, int64_t words, int64_t* inter,
-                            int64_t* uni, hipStream_t st);
+// disn_voxel_surface, _fill, _index_grid, _iou and their size queries are defined there whole (checks, launches)
 
 // ---- batch_assemble.hip (compiled with -ffp-contract=off): a training batch out of the device-resident set ----
-hipError_t assemble_batch_launch(const float* samples, const int64_t* sample_off, int64_t n_obj,
-                                 const unsigned char* img, const float* trans_mat_all, const float* rot_all,
-                                 int64_t n_view, const int* obj_idx, const int* view_idx, const int* choice, int B,
-                                 int S, int rot, int white, float* imgs, float* sample_pc, float* sample_pc_rot,
-                                 float* sdf, float* trans_mat, int* flags, hipStream_t st);
+// disn_assemble_batch is defined there whole (checks, launch)
 
 // ---- mlp_fused.hip: both point MLPs as one persistent kernel per stream, activations in registers ----
 size_t mlp_fused_image_bytes();

@@ -319,7 +319,7 @@ static McWs mc_layout(void* ws, int R) {
   return w;
 }
 
-size_t mc_ws_bytes(int R) { return mc_layout(nullptr, R).total; }
+static size_t mc_ws_bytes(int R) { return mc_layout(nullptr, R).total; }
 
 struct McBatchWs {
   unsigned *eflag, *eidx, *ccount, *coff, *bsum;
@@ -341,7 +341,7 @@ static McBatchWs mc_batch_layout(void* ws, int B, int R) {
   return w;
 }
 
-size_t mc_batch_ws_bytes(int B, int R) { return mc_batch_layout(nullptr, B, R).total; }
+static size_t mc_batch_ws_bytes(int B, int R) { return mc_batch_layout(nullptr, B, R).total; }
 
 static inline int blocks_for(size_t total) {
   size_t b = (total + 255) / 256;
@@ -349,8 +349,9 @@ static inline int blocks_for(size_t total) {
   return (int)(b < 1 ? 1 : b);
 }
 
-hipError_t mc_count_launch(const float* vol, int R, float iso, unsigned long long* counts, void* ws,
-                           hipStream_t st) {
+// counts[0] = vertices, counts[1] = triangles (device memory); fills ws for mc_emit_launch
+static hipError_t mc_count_launch(const float* vol, int R, float iso, unsigned long long* counts, void* ws,
+                                  hipStream_t st) {
   const McWs w = mc_layout(ws, R);
   const int n = R + 1;
   const size_t np = (size_t)n * n * n, nc = (size_t)R * R * R;
@@ -362,8 +363,8 @@ hipError_t mc_count_launch(const float* vol, int R, float iso, unsigned long lon
   return exclusive_scan(w.ccount, w.coff, nc, w.bsum, counts + 1, st);
 }
 
-hipError_t mc_emit_launch(const float* vol, const GridSpec& g, float iso, float* verts, int* faces,
-                          void* ws, hipStream_t st) {
+static hipError_t mc_emit_launch(const float* vol, const GridSpec& g, float iso, float* verts, int* faces,
+                                 void* ws, hipStream_t st) {
   const int R = g.res - 1;
   const McWs w = mc_layout(ws, R);
   const size_t np = (size_t)g.res * g.res * g.res, nc = (size_t)R * R * R;
@@ -374,9 +375,10 @@ hipError_t mc_emit_launch(const float* vol, const GridSpec& g, float iso, float*
   return hipGetLastError();
 }
 
-// B*3*(R+1)^3 < 2^32 is the caller's to check (api.hip)
-hipError_t mc_count_batch_launch(const float* vol, int B, int R, float iso, unsigned long long* counts, void* ws,
-                                 hipStream_t st) {
+// B grids [B,(R+1)^3] in one set of passes: counts [B,2] per grid; verts / faces of all grids back to back in grid
+// order, face indices local to their grid.  B*3*(R+1)^3 < 2^32 is the caller's to check (mc_batch_ok below)
+static hipError_t mc_count_batch_launch(const float* vol, int B, int R, float iso, unsigned long long* counts,
+                                        void* ws, hipStream_t st) {
   const McBatchWs w = mc_batch_layout(ws, B, R);
   const int n = R + 1;
   const size_t np = (size_t)n * n * n, nc = (size_t)R * R * R;
@@ -391,8 +393,9 @@ hipError_t mc_count_batch_launch(const float* vol, int B, int R, float iso, unsi
   return hipGetLastError();
 }
 
-hipError_t mc_verts_batch_launch(const float* vol, const GridSpec* g, int b0, int nb, int B, int R, float iso,
-                                 float* verts, void* ws, hipStream_t st) {
+// vertices of grids b0 .. b0+nb-1 (g[0..nb), nb <= kMcBatchBoxes) / triangles of all B grids
+static hipError_t mc_verts_batch_launch(const float* vol, const GridSpec* g, int b0, int nb, int B, int R, float iso,
+                                        float* verts, void* ws, hipStream_t st) {
   const McBatchWs w = mc_batch_layout(ws, B, R);
   const int n = R + 1;
   const size_t np = (size_t)n * n * n;
@@ -408,7 +411,8 @@ hipError_t mc_verts_batch_launch(const float* vol, const GridSpec* g, int b0, in
   return hipGetLastError();
 }
 
-hipError_t mc_faces_batch_launch(const float* vol, int B, int R, float iso, int* faces, void* ws, hipStream_t st) {
+static hipError_t mc_faces_batch_launch(const float* vol, int B, int R, float iso, int* faces, void* ws,
+                                        hipStream_t st) {
   const McBatchWs w = mc_batch_layout(ws, B, R);
   const int n = R + 1;
   const size_t np = (size_t)n * n * n, nc = (size_t)R * R * R;
@@ -418,3 +422,72 @@ hipError_t mc_faces_batch_launch(const float* vol, int B, int R, float iso, int*
 }
 
 }  // namespace disn
+
+// ---- the C entries of include/disn_amd.h: argument and workspace checks, then the launchers above ----
+using namespace disn;
+
+#define DISN_TRY(expr)                    \
+  do {                                    \
+    hipError_t _e = (expr);               \
+    if (_e != hipSuccess) return (int)_e; \
+  } while (0)
+
+extern "C" {
+
+size_t disn_mc_workspace_bytes(int R) { return (R < 1 || R > 1290) ? 0 : mc_ws_bytes(R); }
+
+int disn_mc_count(const float* sdf, int R, float iso, uint64_t* counts, void* ws, size_t ws_bytes,
+                  void* stream) {
+  if (!sdf || !counts || !ws || R < 1) return DISN_E_ARG;
+  if (R > 1290) return DISN_E_SHAPE;  // 3*(R+1)^3 edge slots must fit the 32-bit scan
+  if (ws_bytes < mc_ws_bytes(R)) return DISN_E_WS;
+  DISN_TRY(mc_count_launch(sdf, R, iso, reinterpret_cast<unsigned long long*>(counts), ws,
+                           (hipStream_t)stream));
+  return 0;
+}
+
+int disn_mc_emit(const float* sdf, const double* sdf_params_host, int R, float iso, float* verts,
+                 int32_t* faces, void* ws, size_t ws_bytes, void* stream) {
+  GridSpec g;
+  if (!sdf || !verts || !faces || !ws || !grid_spec(sdf_params_host, R, &g)) return DISN_E_ARG;
+  if (R > 1290) return DISN_E_SHAPE;
+  if (ws_bytes < mc_ws_bytes(R)) return DISN_E_WS;
+  DISN_TRY(mc_emit_launch(sdf, g, iso, verts, faces, ws, (hipStream_t)stream));
+  return 0;
+}
+
+// a batch is supported when its 3*B*(R+1)^3 edge slots fit the 32-bit scan
+static bool mc_batch_ok(int B, int R) {
+  if (B < 1 || R < 1 || R > 1290) return false;
+  const unsigned long long n = (unsigned long long)R + 1;
+  return 3ull * (unsigned long long)B * n * n * n < (1ull << 32);
+}
+
+size_t disn_mc_batch_workspace_bytes(int B, int R) { return mc_batch_ok(B, R) ? mc_batch_ws_bytes(B, R) : 0; }
+
+int disn_mc_count_batch(const float* sdf, int B, int R, float iso, uint64_t* counts, void* ws, size_t ws_bytes,
+                        void* stream) {
+  if (!sdf || !counts || !ws || B < 1 || R < 1) return DISN_E_ARG;
+  if (!mc_batch_ok(B, R)) return DISN_E_SHAPE;
+  if (ws_bytes < mc_batch_ws_bytes(B, R)) return DISN_E_WS;
+  DISN_TRY(mc_count_batch_launch(sdf, B, R, iso, reinterpret_cast<unsigned long long*>(counts), ws,
+                                 (hipStream_t)stream));
+  return 0;
+}
+
+int disn_mc_emit_batch(const float* sdf, const double* sdf_params_host, int B, int R, float iso, float* verts,
+                       int32_t* faces, void* ws, size_t ws_bytes, void* stream) {
+  if (!sdf || !verts || !faces || !ws || !sdf_params_host || B < 1 || R < 1) return DISN_E_ARG;
+  if (!mc_batch_ok(B, R)) return DISN_E_SHAPE;
+  if (ws_bytes < mc_batch_ws_bytes(B, R)) return DISN_E_WS;
+  GridSpec g[kMcBatchBoxes];  // the boxes travel as kernel arguments, kMcBatchBoxes grids per vertex launch
+  for (int b0 = 0; b0 < B; b0 += kMcBatchBoxes) {
+    const int nb = B - b0 < kMcBatchBoxes ? B - b0 : kMcBatchBoxes;
+    for (int i = 0; i < nb; ++i) grid_spec(sdf_params_host + 6 * (size_t)(b0 + i), R, &g[i]);
+    DISN_TRY(mc_verts_batch_launch(sdf, g, b0, nb, B, R, iso, verts, ws, (hipStream_t)stream));
+  }
+  DISN_TRY(mc_faces_batch_launch(sdf, B, R, iso, faces, ws, (hipStream_t)stream));
+  return 0;
+}
+
+}  // extern "C"

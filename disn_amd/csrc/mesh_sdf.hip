@@ -391,24 +391,25 @@ SignWs carve(void* ws, int64_t N) {
 
 }  // namespace
 
-size_t mesh_sign_ws_bytes(int64_t N) { return al256(4 * (size_t)N) + 4 * al256(N) + 256; }
+static size_t mesh_sign_ws_bytes(int64_t N) { return al256(4 * (size_t)N) + 4 * al256(N) + 256; }
 
-hipError_t mesh_udf_points_launch(const void* bvh, int64_t nf, const float* pts, int64_t n, int brute, float* dist,
-                                  hipStream_t st) {
+static hipError_t mesh_udf_points_launch(const void* bvh, int64_t nf, const float* pts, int64_t n, int brute,
+                                         float* dist, hipStream_t st) {
   udf_points_kernel<<<blocks256(n), 256, 0, st>>>(bvh_view(bvh, nf), pts, n, brute, dist);
   return hipGetLastError();
 }
 
-hipError_t mesh_udf_grid_launch(const void* bvh, int64_t nf, const float* xs, const float* ys, const float* zs,
-                                int nx, int ny, int nz, int brute, float* dist, hipStream_t st) {
+static hipError_t mesh_udf_grid_launch(const void* bvh, int64_t nf, const float* xs, const float* ys, const float* zs,
+                                       int nx, int ny, int nz, int brute, float* dist, hipStream_t st) {
   const int64_t bricks = (int64_t)((nx + 3) >> 2) * ((ny + 3) >> 2) * ((nz + 3) >> 2);
   udf_grid_kernel<<<(unsigned)bricks, 64, 0, st>>>(bvh_view(bvh, nf), xs, ys, zs, nx, ny, nz, brute, dist);
   return hipGetLastError();
 }
 
-int mesh_sign_launch(const void* bvh, int64_t nf, const float* xs, const float* ys, const float* zs, int nx, int ny,
-                     int nz, const float* u, float tau, int steps, float offset, float* sdf, unsigned char* outside,
-                     void* ws, hipStream_t st) {
+// 0, a hipError_t, or DISN_E_CONVERGE; synchronises `st` once per labelling round
+static int mesh_sign_launch(const void* bvh, int64_t nf, const float* xs, const float* ys, const float* zs, int nx,
+                            int ny, int nz, const float* u, float tau, int steps, float offset, float* sdf,
+                            unsigned char* outside, void* ws, hipStream_t st) {
   const Bvh h = bvh_view(bvh, nf);
   const Grid g{{xs, ys, zs}, {nx, ny, nz}};
   const int64_t N = (int64_t)nx * ny * nz;
@@ -444,3 +445,55 @@ int mesh_sign_launch(const void* bvh, int64_t nf, const float* xs, const float* 
 }
 
 }  // namespace disn
+
+// ---- the C entries of include/disn_amd.h: argument and workspace checks, then the launchers above ----
+using namespace disn;
+
+#define DISN_TRY(expr)                    \
+  do {                                    \
+    hipError_t _e = (expr);               \
+    if (_e != hipSuccess) return (int)_e; \
+  } while (0)
+
+extern "C" {
+
+static int mesh_grid_shape(int nx, int ny, int nz) {
+  if (nx < 2 || ny < 2 || nz < 2) return DISN_E_ARG;
+  if ((int64_t)nx * ny * nz > INT32_MAX) return DISN_E_SHAPE;  // int32 component labels
+  return 0;
+}
+
+int disn_mesh_udf_points(const void* bvh, int64_t nf, const float* points, int64_t n, int brute, float* dist,
+                         void* stream) {
+  if (!bvh || !points || !dist || nf < 1 || n < 1) return DISN_E_ARG;
+  if (nf > kBvhMaxTris || n > (int64_t)UINT32_MAX * 256) return DISN_E_SHAPE;
+  DISN_TRY(mesh_udf_points_launch(bvh, nf, points, n, brute, dist, (hipStream_t)stream));
+  return 0;
+}
+
+int disn_mesh_udf_grid(const void* bvh, int64_t nf, const float* xs, const float* ys, const float* zs, int nx, int ny,
+                       int nz, int brute, float* dist, void* stream) {
+  if (!bvh || !xs || !ys || !zs || !dist || nf < 1) return DISN_E_ARG;
+  if (int rc = mesh_grid_shape(nx, ny, nz)) return rc;
+  if (nf > kBvhMaxTris) return DISN_E_SHAPE;
+  DISN_TRY(mesh_udf_grid_launch(bvh, nf, xs, ys, zs, nx, ny, nz, brute, dist, (hipStream_t)stream));
+  return 0;
+}
+
+size_t disn_mesh_sign_workspace_bytes(int nx, int ny, int nz) {
+  return mesh_grid_shape(nx, ny, nz) ? 0 : mesh_sign_ws_bytes((int64_t)nx * ny * nz);
+}
+
+int disn_mesh_sign(const void* bvh, int64_t nf, const float* xs, const float* ys, const float* zs, int nx, int ny,
+                   int nz, const float* u, float tau, int steps, float offset, float* sdf, uint8_t* outside, void* ws,
+                   size_t ws_bytes, void* stream) {
+  if (!bvh || !xs || !ys || !zs || !u || !sdf || !ws || nf < 1 || steps < 0) return DISN_E_ARG;
+  if (!(tau > 0.0f) || !(offset == offset)) return DISN_E_ARG;
+  if (int rc = mesh_grid_shape(nx, ny, nz)) return rc;
+  if (nf > kBvhMaxTris) return DISN_E_SHAPE;
+  if (ws_bytes < mesh_sign_ws_bytes((int64_t)nx * ny * nz)) return DISN_E_WS;
+  return mesh_sign_launch(bvh, nf, xs, ys, zs, nx, ny, nz, u, tau, steps, offset, sdf, outside, ws,
+                          (hipStream_t)stream);
+}
+
+}  // extern "C"

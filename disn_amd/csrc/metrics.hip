@@ -313,7 +313,7 @@ hipError_t emd_levels(const float* xyz1, const float* xyz2, int b, int n, int m,
 
 }  // namespace
 
-size_t metrics_ws_bytes(int b, int n, int m) {
+static size_t metrics_ws_bytes(int b, int n, int m) {
   const size_t nn = align256((size_t)b * ((size_t)n + m) * 8);
   const size_t emd = emd_layout(nullptr, b, n, m).total;
   const size_t mc = align256((size_t)b * cdiv(m, kCostRows) * 8);
@@ -321,8 +321,8 @@ size_t metrics_ws_bytes(int b, int n, int m) {
   return t > mc ? t : mc;
 }
 
-hipError_t nn_distance_launch(const float* xyz1, const float* xyz2, int b, int n, int m, float* dist1, int* idx1,
-                              float* dist2, int* idx2, void* ws, hipStream_t st) {
+static hipError_t nn_distance_launch(const float* xyz1, const float* xyz2, int b, int n, int m, float* dist1,
+                                     int* idx1, float* dist2, int* idx2, void* ws, hipStream_t st) {
   unsigned long long* keys = static_cast<unsigned long long*>(ws);
   const size_t total1 = (size_t)b * n, total = total1 + (size_t)b * m;
   hipError_t e = hipMemsetAsync(keys, 0xff, total * 8, st);
@@ -335,13 +335,13 @@ hipError_t nn_distance_launch(const float* xyz1, const float* xyz2, int b, int n
   return hipGetLastError();
 }
 
-hipError_t approx_match_launch(const float* xyz1, const float* xyz2, int b, int n, int m, float* match, void* ws,
-                               hipStream_t st) {
+static hipError_t approx_match_launch(const float* xyz1, const float* xyz2, int b, int n, int m, float* match,
+                                      void* ws, hipStream_t st) {
   return emd_levels<true, false>(xyz1, xyz2, b, n, m, emd_layout(ws, b, n, m), match, st);
 }
 
-hipError_t emd_launch(const float* xyz1, const float* xyz2, int b, int n, int m, float* cost, void* ws,
-                      hipStream_t st) {
+static hipError_t emd_launch(const float* xyz1, const float* xyz2, int b, int n, int m, float* cost, void* ws,
+                             hipStream_t st) {
   const EmdWs w = emd_layout(ws, b, n, m);
   hipError_t e = emd_levels<false, true>(xyz1, xyz2, b, n, m, w, nullptr, st);
   if (e != hipSuccess) return e;
@@ -349,8 +349,8 @@ hipError_t emd_launch(const float* xyz1, const float* xyz2, int b, int n, int m,
   return hipGetLastError();
 }
 
-hipError_t match_cost_launch(const float* xyz1, const float* xyz2, const float* match, int b, int n, int m,
-                             float* cost, void* ws, hipStream_t st) {
+static hipError_t match_cost_launch(const float* xyz1, const float* xyz2, const float* match, int b, int n, int m,
+                                    float* cost, void* ws, hipStream_t st) {
   double* part = static_cast<double*>(ws);
   const int tiles = cdiv(m, kCostRows);
   match_cost_kernel<<<dim3(tiles, b), 256, 0, st>>>(xyz1, xyz2, match, n, m, part);
@@ -359,3 +359,62 @@ hipError_t match_cost_launch(const float* xyz1, const float* xyz2, const float* 
 }
 
 }  // namespace disn
+
+// ---- the C entries of include/disn_amd.h: argument and workspace checks, then the launchers above ----
+using namespace disn;
+
+#define DISN_TRY(expr)                    \
+  do {                                    \
+    hipError_t _e = (expr);               \
+    if (_e != hipSuccess) return (int)_e; \
+  } while (0)
+
+extern "C" {
+
+size_t disn_metrics_workspace_bytes(int b, int n, int m) {
+  return (b < 1 || n < 1 || m < 1) ? 0 : metrics_ws_bytes(b, n, m);
+}
+
+static int metrics_shape(int b, int n, int m) {
+  if (b < 1 || n < 1 || m < 1) return DISN_E_ARG;
+  if (b > 65535) return DISN_E_SHAPE;  // one grid row per pair
+  return 0;
+}
+
+int disn_nn_distance(const float* xyz1, const float* xyz2, int b, int n, int m, float* dist1, int32_t* idx1,
+                     float* dist2, int32_t* idx2, void* ws, size_t ws_bytes, void* stream) {
+  if (!xyz1 || !xyz2 || !dist1 || !idx1 || !dist2 || !idx2 || !ws) return DISN_E_ARG;
+  if (int rc = metrics_shape(b, n, m)) return rc;
+  if (ws_bytes < metrics_ws_bytes(b, n, m)) return DISN_E_WS;
+  DISN_TRY(nn_distance_launch(xyz1, xyz2, b, n, m, dist1, idx1, dist2, idx2, ws, (hipStream_t)stream));
+  return 0;
+}
+
+int disn_approx_match(const float* xyz1, const float* xyz2, int b, int n, int m, float* match, void* ws,
+                      size_t ws_bytes, void* stream) {
+  if (!xyz1 || !xyz2 || !match || !ws) return DISN_E_ARG;
+  if (int rc = metrics_shape(b, n, m)) return rc;
+  if (ws_bytes < metrics_ws_bytes(b, n, m)) return DISN_E_WS;
+  DISN_TRY(approx_match_launch(xyz1, xyz2, b, n, m, match, ws, (hipStream_t)stream));
+  return 0;
+}
+
+int disn_match_cost(const float* xyz1, const float* xyz2, const float* match, int b, int n, int m, float* cost,
+                    void* ws, size_t ws_bytes, void* stream) {
+  if (!xyz1 || !xyz2 || !match || !cost || !ws) return DISN_E_ARG;
+  if (int rc = metrics_shape(b, n, m)) return rc;
+  if (ws_bytes < metrics_ws_bytes(b, n, m)) return DISN_E_WS;
+  DISN_TRY(match_cost_launch(xyz1, xyz2, match, b, n, m, cost, ws, (hipStream_t)stream));
+  return 0;
+}
+
+int disn_emd(const float* xyz1, const float* xyz2, int b, int n, int m, float* cost, void* ws, size_t ws_bytes,
+             void* stream) {
+  if (!xyz1 || !xyz2 || !cost || !ws) return DISN_E_ARG;
+  if (int rc = metrics_shape(b, n, m)) return rc;
+  if (ws_bytes < metrics_ws_bytes(b, n, m)) return DISN_E_WS;
+  DISN_TRY(emd_launch(xyz1, xyz2, b, n, m, cost, ws, (hipStream_t)stream));
+  return 0;
+}
+
+}  // extern "C"

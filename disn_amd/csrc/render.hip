@@ -189,9 +189,9 @@ __global__ __launch_bounds__(64) void render_views_kernel(Scene s, const float* 
 
 }  // namespace
 
-hipError_t render_views_launch(const void* bvh, int64_t nf, const int32_t* order, const float* albedo,
-                               const float* cams, int V, int H, int W, int S, float ambient, int brute,
-                               uint8_t* rgba, float* depth, int32_t* face, hipStream_t st) {
+static hipError_t render_views_launch(const void* bvh, int64_t nf, const int32_t* order, const float* albedo,
+                                      const float* cams, int V, int H, int W, int S, float ambient, int brute,
+                                      uint8_t* rgba, float* depth, int32_t* face, hipStream_t st) {
   const char* b = static_cast<const char*>(bvh);
   Scene s;
   s.nodes = reinterpret_cast<const float4*>(b + sizeof(BvhHeader));
@@ -205,3 +205,28 @@ hipError_t render_views_launch(const void* bvh, int64_t nf, const int32_t* order
 }
 
 }  // namespace disn
+
+// ---- the C entries of include/disn_amd.h: argument and workspace checks, then the launchers above ----
+using namespace disn;
+
+#define DISN_TRY(expr)                    \
+  do {                                    \
+    hipError_t _e = (expr);               \
+    if (_e != hipSuccess) return (int)_e; \
+  } while (0)
+
+extern "C" {
+
+int disn_render_views(const void* bvh, int64_t nf, const int32_t* order, const float* albedo, const float* cams,
+                      int V, int H, int W, int S, float ambient, int brute, uint8_t* rgba, float* depth,
+                      int32_t* face, void* stream) {
+  if (!bvh || !cams || !rgba || nf < 1 || V < 1 || H < 1 || W < 1 || S < 1) return DISN_E_ARG;
+  if (!(ambient >= 0.0f && ambient <= 1.0f)) return DISN_E_ARG;
+  if (!order && (albedo || face)) return DISN_E_ARG;
+  if (nf > kBvhMaxTris || S > 4 || H > 1024 || W > 1024 || V > 65535) return DISN_E_SHAPE;
+  DISN_TRY(render_views_launch(bvh, nf, order, albedo, cams, V, H, W, S, ambient, brute, rgba, depth, face,
+                               (hipStream_t)stream));
+  return 0;
+}
+
+}  // extern "C"

@@ -318,10 +318,18 @@ hipError_t clear_count(const State& s, int l, hipStream_t st) {
 
 }  // namespace
 
-size_t trace_state_bytes(size_t n_rays) { return ((size_t)(DISN_TRACE_FIELDS + 3) * pad64(n_rays) + 64) * 4; }
+// The state machine, the lists and the counts live in the caller's state (trace_state_bytes); `pts` takes one point per
+// listed ray (room for every ray at setup and collect, for n_active at advance); list `in` (0 / 1) is read, the other
+// one written; the sizes are the caller's to check (the entries below)
+struct TraceMarch {
+  float sdf_weight, iso, eps, step_scale, min_step, max_step;
+  int max_steps, refine;
+};
 
-hipError_t trace_setup_launch(const float* cams, int V, int H, int W, const float box[6], float t_min, void* state,
-                              float* pts, hipStream_t st) {
+static size_t trace_state_bytes(size_t n_rays) { return ((size_t)(DISN_TRACE_FIELDS + 3) * pad64(n_rays) + 64) * 4; }
+
+static hipError_t trace_setup_launch(const float* cams, int V, int H, int W, const float box[6], float t_min,
+                                     void* state, float* pts, hipStream_t st) {
   const Rays g = rays_of(cams, V, H, W);
   const State s = state_of(state, g.n);
   Box b;
@@ -332,8 +340,8 @@ hipError_t trace_setup_launch(const float* cams, int V, int H, int W, const floa
   return hipGetLastError();
 }
 
-hipError_t trace_advance_launch(const float* cams, int V, int H, int W, const float* values, size_t n_active, int in,
-                                const TraceMarch& p, void* state, float* pts, hipStream_t st) {
+static hipError_t trace_advance_launch(const float* cams, int V, int H, int W, const float* values, size_t n_active,
+                                       int in, const TraceMarch& p, void* state, float* pts, hipStream_t st) {
   const Rays g = rays_of(cams, V, H, W);
   const State s = state_of(state, g.n);
   hipError_t e = clear_count(s, 1 - in, st);
@@ -344,7 +352,8 @@ hipError_t trace_advance_launch(const float* cams, int V, int H, int W, const fl
   return hipGetLastError();
 }
 
-hipError_t trace_collect_launch(const float* cams, int V, int H, int W, void* state, float* pts, hipStream_t st) {
+static hipError_t trace_collect_launch(const float* cams, int V, int H, int W, void* state, float* pts,
+                                       hipStream_t st) {
   const Rays g = rays_of(cams, V, H, W);
   const State s = state_of(state, g.n);
   hipError_t e = clear_count(s, 2, st);
@@ -353,9 +362,10 @@ hipError_t trace_collect_launch(const float* cams, int V, int H, int W, void* st
   return hipGetLastError();
 }
 
-hipError_t trace_shade_launch(const float* cams, int V, int H, int W, const void* state, const float* pred,
-                              const float* grad, size_t n_hits, float sdf_weight, float iso, float ambient, float* depth,
-                              float* normal, float* residual, uint8_t* status, uint8_t* rgba, hipStream_t st) {
+static hipError_t trace_shade_launch(const float* cams, int V, int H, int W, const void* state, const float* pred,
+                                     const float* grad, size_t n_hits, float sdf_weight, float iso, float ambient,
+                                     float* depth, float* normal, float* residual, uint8_t* status, uint8_t* rgba,
+                                     hipStream_t st) {
   const Rays g = rays_of(cams, V, H, W);
   const State s = state_of(const_cast<void*>(state), g.n);
   hipLaunchKernelGGL(trace_shade_kernel, dim3(blocks_of(g.n)), dim3(256), 0, st, g, s, pred, grad, n_hits, sdf_weight,
@@ -364,3 +374,79 @@ hipError_t trace_shade_launch(const float* cams, int V, int H, int W, const void
 }
 
 }  // namespace disn
+
+// ---- the C entries of include/disn_amd.h: argument and workspace checks, then the launchers above ----
+using namespace disn;
+
+#define DISN_TRY(expr)                    \
+  do {                                    \
+    hipError_t _e = (expr);               \
+    if (_e != hipSuccess) return (int)_e; \
+  } while (0)
+
+extern "C" {
+
+namespace {
+constexpr int64_t kTraceMaxRays = int64_t(1) << 27;
+int64_t trace_rays(int V, int H, int W) {   // 0: not a shape this takes
+  if (V < 1 || H < 1 || W < 1 || H > 8192 || W > 8192) return 0;
+  const int64_t n = (int64_t)V * H * W;
+  return n <= kTraceMaxRays ? n : 0;
+}
+}  // namespace
+
+size_t disn_trace_state_bytes(int64_t n_rays) {
+  return n_rays >= 1 && n_rays <= kTraceMaxRays ? trace_state_bytes((size_t)n_rays) : 0;
+}
+
+int disn_trace_setup(const float* cams, int V, int H, int W, const double* sdf_params_host, float t_min, void* state,
+                     size_t state_bytes, float* pts, void* stream) {
+  const int64_t n = trace_rays(V, H, W);
+  if (!cams || !sdf_params_host || !state || !pts || !n || !(t_min >= 0.0f)) return DISN_E_ARG;
+  if (state_bytes < trace_state_bytes((size_t)n)) return DISN_E_WS;
+  float box[6];
+  for (int a = 0; a < 6; ++a) box[a] = (float)sdf_params_host[a];
+  for (int a = 0; a < 3; ++a)
+    if (!(box[a] <= box[a + 3])) return DISN_E_ARG;
+  DISN_TRY(trace_setup_launch(cams, V, H, W, box, t_min, state, pts, (hipStream_t)stream));
+  return 0;
+}
+
+int disn_trace_advance(const float* cams, int V, int H, int W, const float* values, int64_t n_active, int list_in,
+                       float sdf_weight, float iso, float eps, float step_scale, float min_step, float max_step,
+                       int max_steps, int refine, void* state, size_t state_bytes, float* pts, void* stream) {
+  const int64_t n = trace_rays(V, H, W);
+  if (!cams || !values || !state || !pts || !n || n_active < 1 || n_active > n || (list_in != 0 && list_in != 1))
+    return DISN_E_ARG;
+  if (sdf_weight == 0.0f || !(eps >= 0.0f) || !(step_scale > 0.0f) || !(min_step > 0.0f) || !(max_step >= min_step) ||
+      max_steps < 1 || refine < 1)
+    return DISN_E_ARG;
+  if (state_bytes < trace_state_bytes((size_t)n)) return DISN_E_WS;
+  const TraceMarch p{sdf_weight, iso, eps, step_scale, min_step, max_step, max_steps, refine};
+  DISN_TRY(trace_advance_launch(cams, V, H, W, values, (size_t)n_active, list_in, p, state, pts, (hipStream_t)stream));
+  return 0;
+}
+
+int disn_trace_collect(const float* cams, int V, int H, int W, void* state, size_t state_bytes, float* pts,
+                       void* stream) {
+  const int64_t n = trace_rays(V, H, W);
+  if (!cams || !state || !pts || !n) return DISN_E_ARG;
+  if (state_bytes < trace_state_bytes((size_t)n)) return DISN_E_WS;
+  DISN_TRY(trace_collect_launch(cams, V, H, W, state, pts, (hipStream_t)stream));
+  return 0;
+}
+
+int disn_trace_shade(const float* cams, int V, int H, int W, const void* state, size_t state_bytes, const float* pred,
+                     const float* grad, int64_t n_hits, float sdf_weight, float iso, float ambient, float* depth,
+                     float* normal, float* residual, uint8_t* status, uint8_t* rgba, void* stream) {
+  const int64_t n = trace_rays(V, H, W);
+  if (!cams || !state || !n || n_hits < 0 || n_hits > n || (n_hits > 0 && (!pred || !grad)) || sdf_weight == 0.0f ||
+      !(ambient >= 0.0f && ambient <= 1.0f))
+    return DISN_E_ARG;
+  if (state_bytes < trace_state_bytes((size_t)n)) return DISN_E_WS;
+  DISN_TRY(trace_shade_launch(cams, V, H, W, state, pred, grad, (size_t)n_hits, sdf_weight, iso, ambient, depth, normal,
+                              residual, status, rgba, (hipStream_t)stream));
+  return 0;
+}
+
+}  // extern "C"

@@ -343,14 +343,14 @@ inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 }  // namespace
 
-size_t voxel_grid_words(int n) { return (size_t)n * n * ((n + 31) / 32); }
+static size_t voxel_grid_words(int n) { return (size_t)n * n * ((n + 31) / 32); }
 
-size_t voxel_surface_ws_bytes(int64_t nf) { return 256 + al256(sizeof(int2) * (size_t)(nf > 0 ? nf : 0)); }
+static size_t voxel_surface_ws_bytes(int64_t nf) { return 256 + al256(sizeof(int2) * (size_t)(nf > 0 ? nf : 0)); }
 
-size_t voxel_fill_ws_bytes(int n) { return 256 + al256(4 * voxel_grid_words(n)); }
+static size_t voxel_fill_ws_bytes(int n) { return 256 + al256(4 * voxel_grid_words(n)); }
 
-hipError_t voxel_surface_launch(const float* verts, int64_t nv, const int* faces, int64_t nf, int dim, int kmin,
-                                int nkeys, unsigned* bits, int* flags, void* ws, hipStream_t st) {
+static hipError_t voxel_surface_launch(const float* verts, int64_t nv, const int* faces, int64_t nf, int dim, int kmin,
+                                       int nkeys, unsigned* bits, int* flags, void* ws, hipStream_t st) {
   hipError_t e;
   if ((e = hipMemsetAsync(bits, 0, 4 * voxel_grid_words(nkeys), st)) != hipSuccess) return e;
   if (nf == 0) return hipSuccess;
@@ -365,7 +365,8 @@ hipError_t voxel_surface_launch(const float* verts, int64_t nv, const int* faces
   return hipGetLastError();
 }
 
-int voxel_fill_launch(const unsigned* surf, int n, unsigned* solid, void* ws, hipStream_t st) {
+// 0, a hipError_t, or DISN_E_CONVERGE; synchronises `st` once per batch of sweeps
+static int voxel_fill_launch(const unsigned* surf, int n, unsigned* solid, void* ws, hipStream_t st) {
   const int wpr = (n + 31) / 32;
   const unsigned nb = blocks256((int64_t)voxel_grid_words(n));
   int* changed = static_cast<int*>(ws);
@@ -387,8 +388,8 @@ int voxel_fill_launch(const unsigned* surf, int n, unsigned* solid, void* ws, hi
   return (int)hipGetLastError();
 }
 
-hipError_t voxel_index_grid_launch(const unsigned* keys, int nkeys, const int* lut, int dim, unsigned* out,
-                                   hipStream_t st) {
+static hipError_t voxel_index_grid_launch(const unsigned* keys, int nkeys, const int* lut, int dim, unsigned* out,
+                                          hipStream_t st) {
   hipError_t e;
   if ((e = hipMemsetAsync(out, 0, 4 * voxel_grid_words(dim), st)) != hipSuccess) return e;
   index_scatter_kernel<<<blocks256((int64_t)voxel_grid_words(nkeys)), 256, 0, st>>>(
@@ -396,8 +397,8 @@ hipError_t voxel_index_grid_launch(const unsigned* keys, int nkeys, const int* l
   return hipGetLastError();
 }
 
-hipError_t voxel_iou_launch(const unsigned* gt, const unsigned* preds, int nviews, int64_t words, int64_t* inter,
-                            int64_t* uni, hipStream_t st) {
+static hipError_t voxel_iou_launch(const unsigned* gt, const unsigned* preds, int nviews, int64_t words,
+                                   int64_t* inter, int64_t* uni, hipStream_t st) {
   hipError_t e;
   if ((e = hipMemsetAsync(inter, 0, sizeof(int64_t) * nviews, st)) != hipSuccess) return e;
   if ((e = hipMemsetAsync(uni, 0, sizeof(int64_t) * nviews, st)) != hipSuccess) return e;
@@ -410,3 +411,59 @@ hipError_t voxel_iou_launch(const unsigned* gt, const unsigned* preds, int nview
 }
 
 }  // namespace disn
+
+// ---- the C entries of include/disn_amd.h: argument and workspace checks, then the launchers above ----
+using namespace disn;
+
+#define DISN_TRY(expr)                    \
+  do {                                    \
+    hipError_t _e = (expr);               \
+    if (_e != hipSuccess) return (int)_e; \
+  } while (0)
+
+extern "C" {
+
+static int voxel_axis(int n) { return n < 1 ? DISN_E_ARG : (n > 1024 ? DISN_E_SHAPE : 0); }
+
+size_t disn_voxel_grid_words(int n) { return voxel_axis(n) ? 0 : voxel_grid_words(n); }
+
+size_t disn_voxel_surface_workspace_bytes(int64_t nf) { return nf < 0 ? 0 : voxel_surface_ws_bytes(nf); }
+
+int disn_voxel_surface(const float* verts, int64_t nv, const int32_t* faces, int64_t nf, int dim, int kmin, int nkeys,
+                       uint32_t* bits, int32_t* flags, void* ws, size_t ws_bytes, void* stream) {
+  if (!bits || !flags || !ws || nv < 0 || nf < 0 || dim < 1) return DISN_E_ARG;
+  if (nf > 0 && (!verts || !faces)) return DISN_E_ARG;
+  if (int rc = voxel_axis(nkeys)) return rc;
+  if (dim > 1024 || kmin < -4096 || kmin > 4096 || nf > INT32_MAX) return DISN_E_SHAPE;
+  if (ws_bytes < voxel_surface_ws_bytes(nf)) return DISN_E_WS;
+  DISN_TRY(voxel_surface_launch(verts, nv, faces, nf, dim, kmin, nkeys, bits, flags, ws, (hipStream_t)stream));
+  return 0;
+}
+
+size_t disn_voxel_fill_workspace_bytes(int n) { return voxel_axis(n) ? 0 : voxel_fill_ws_bytes(n); }
+
+int disn_voxel_fill(const uint32_t* surface, int n, uint32_t* solid, void* ws, size_t ws_bytes, void* stream) {
+  if (!surface || !solid || !ws) return DISN_E_ARG;
+  if (int rc = voxel_axis(n)) return rc;
+  if (ws_bytes < voxel_fill_ws_bytes(n)) return DISN_E_WS;
+  return voxel_fill_launch(surface, n, solid, ws, (hipStream_t)stream);
+}
+
+int disn_voxel_index_grid(const uint32_t* keys, int nkeys, const int32_t* lut, int dim, uint32_t* index_bits,
+                          void* stream) {
+  if (!keys || !lut || !index_bits) return DISN_E_ARG;
+  if (int rc = voxel_axis(nkeys)) return rc;
+  if (int rc = voxel_axis(dim)) return rc;
+  DISN_TRY(voxel_index_grid_launch(keys, nkeys, lut, dim, index_bits, (hipStream_t)stream));
+  return 0;
+}
+
+int disn_voxel_iou(const uint32_t* gt, const uint32_t* preds, int nviews, int64_t words, int64_t* inter,
+                   int64_t* uni, void* stream) {
+  if (!gt || !preds || !inter || !uni || nviews < 1 || words < 1) return DISN_E_ARG;
+  if (nviews > 65535 || words > ((int64_t)1 << 25)) return DISN_E_SHAPE;
+  DISN_TRY(voxel_iou_launch(gt, preds, nviews, words, inter, uni, (hipStream_t)stream));
+  return 0;
+}
+
+}  // extern "C"
