@@ -1,5 +1,6 @@
 """ctypes binding of libdisn_amd.so (include/disn_amd.h and, for the mesh simplification and the vertex colours,
-include/disn_amd_simplify.h and include/disn_amd_colour.h; for the surface samples, include/disn_amd_sample.h).
+include/disn_amd_simplify.h and include/disn_amd_colour.h; for the surface samples, include/disn_amd_sample.h; for
+the Taubin smoothing, include/disn_amd_smooth.h).
 
 The HIP library is the product: there is NO CPU fallback.  ``lib()`` raises
 ``DisnLibraryError`` when the shared object is missing or does not export the
@@ -271,6 +272,13 @@ SIGNATURES_SAMPLE = {
     "disn_mesh_sample_batch": (I, [P, P, P, P, I, P, I, P, P, P, P, P, Z, P]),
 }
 
+# name -> (restype, argtypes); every symbol declared in include/disn_amd_smooth.h (the fifth header, added the same way)
+D = C.c_double
+SIGNATURES_SMOOTH = {
+    "disn_mesh_smooth_workspace_bytes": (Z, [I, L, L]),
+    "disn_mesh_smooth_batch": (I, [P, P, P, P, I, I, D, D, I, P, P, P, P, Z, P]),
+}
+
 _LIB: Optional[C.CDLL] = None
 
 
@@ -287,8 +295,8 @@ def lib() -> C.CDLL:
         h = C.CDLL(LIB_PATH)
     except OSError as e:  # pragma: no cover - depends on the box
         raise DisnLibraryError("cannot load %s: %s" % (LIB_PATH, e)) from e
-    for name, (res, args) in [kv for t in (SIGNATURES, SIGNATURES_SIMPLIFY, SIGNATURES_COLOUR, SIGNATURES_SAMPLE)
-                              for kv in t.items()]:
+    for name, (res, args) in [kv for t in (SIGNATURES, SIGNATURES_SIMPLIFY, SIGNATURES_COLOUR, SIGNATURES_SAMPLE,
+                                                     SIGNATURES_SMOOTH) for kv in t.items()]:
         try:
             fn = getattr(h, name)
         except AttributeError as e:

@@ -60,6 +60,13 @@ the whole group with one read-back (``isosurface.marching_cubes_batch``) and wri
     lines of the meshes done now are appended to those of the earlier runs).  A ground truth without area is logged
     and marked ``"gt_status": 6`` in its lines.  A mesh's samples depend on ``--seed`` and its file name alone.  Composes with every
     flag above; without it nothing changes.
+  * ``--smooth ITERS [--smooth_cap CELLS] [--smooth_free_boundary]`` (1..64 iterations; not in the reference) fairs every
+    mesh by Taubin's lambda|mu smoothing (``postprocess.smooth_meshes_device``) while the group still lies
+    on the device: behind ``--clean`` and ``--simplify`` and BEFORE ``--refine`` and ``--normals``, so the smoothed
+    vertices are what the Newton steps pull back onto the level set and what is coloured and scored.  No coordinate
+    moves further than CELLS grid cells of its view's box (longest side / sdf_res each; default 0.5) from where it was;
+    boundary vertices stay where they are unless ``--smooth_free_boundary`` is given.  Faces never change.  The tree
+    goes to ``<...>[_comb]_t<ITERS>[_s<CELLS>]``.  Composes with every flag above; without it nothing changes.
 """
 from __future__ import annotations
 
@@ -293,6 +300,64 @@ def simplify_group(meshes, simplify, boxes):
     return meshes
 
 
+SMOOTH_CAP_CELLS = 0.5        # --smooth_cap: the largest move of a coordinate, in grid cells of the view's box
+
+
+def smooth_args(smooth) -> Optional[dict]:
+    """``smooth`` = None (off), the number of iterations, or a dict with ``iters`` and some of ``lam``, ``mu``, ``cap``
+    (grid cells of the view's box a coordinate may move; None: no cap) and ``pin_boundary`` -> None or the checked,
+    complete dict (ValueError; no device work): what ``reconstruct`` / ``reconstruct_fused`` hand to ``smooth_group``"""
+    if smooth is None:
+        return None
+    from .postprocess import smooth_params
+    given = dict(smooth) if isinstance(smooth, dict) else {"iters": smooth}
+    unknown = sorted(set(given) - {"iters", "lam", "mu", "cap", "pin_boundary"})
+    if unknown:
+        raise ValueError("--smooth takes iters, lam, mu, cap and pin_boundary, not %s" % ", ".join(unknown))
+    if "iters" not in given:
+        raise ValueError("--smooth needs the number of iterations")
+    c = dict({"lam": 0.5, "mu": -0.53, "cap": SMOOTH_CAP_CELLS, "pin_boundary": True}, **given)
+    try:
+        c["iters"], c["lam"], c["mu"], _ = smooth_params(c["iters"], c["lam"], c["mu"])
+    except ValueError as e:
+        raise ValueError("--smooth: %s" % e) from e
+    if c["cap"] is not None:
+        try:
+            cap = float(c["cap"])
+        except (TypeError, ValueError):
+            cap = float("nan")
+        if isinstance(c["cap"], bool) or not (math.isfinite(cap) and cap >= 0.0):
+            raise ValueError("--smooth_cap must be a finite number of cells >= 0, got %r" % (c["cap"],))
+        c["cap"] = cap
+    c["pin_boundary"] = bool(c["pin_boundary"])
+    return c
+
+
+def smooth_cap(smooth, boxes, sdf_res: int):
+    """the cap of every mesh in the units of its vertices: ``cap`` grid cells of its box, longest side / sdf_res each
+    -> float64 [B], or None without a cap"""
+    if smooth["cap"] is None:
+        return None
+    boxes = np.asarray(boxes, np.float64).reshape(-1, 6)
+    return smooth["cap"] * ((boxes[:, 3:] - boxes[:, :3]).max(1) / np.float64(sdf_res))
+
+
+def smooth_group(meshes, smooth, boxes, sdf_res: int):
+    """the smoothing of one group behind its meshing, cleanup and simplification: the meshes that have triangles go
+    through ONE ``smooth_meshes_device`` call, each with the cap of its own box (``boxes`` [B,6]) -> the meshes"""
+    from .postprocess import smooth_meshes_device
+    meshes = list(meshes)
+    picked = [b for b, m in enumerate(meshes) if len(m[1])]
+    if smooth is None or not picked:
+        return meshes
+    cap = smooth_cap(smooth, np.asarray(boxes, np.float64).reshape(len(meshes), 6), sdf_res)
+    smoothed, _ = smooth_meshes_device([meshes[b] for b in picked], smooth["iters"], smooth["lam"], smooth["mu"],
+                                       smooth["pin_boundary"], None if cap is None else cap[picked])
+    for b, m in zip(picked, smoothed):
+        meshes[b] = m
+    return meshes
+
+
 MIRROR_AXES = {"x": 0, "y": 1, "z": 2, "0": 0, "1": 1, "2": 2, 0: 0, 1: 1, 2: 2}
 COLOUR_DEFAULTS = {"S": 2, "rel_tol": 1e-3, "mirror_axis": None, "fill_iters": 32, "bgr": True}
 
@@ -421,16 +486,18 @@ def score_group(meshes, keys, score, seed: int = 0, cache: Optional[dict] = None
 
 
 def reconstruct(engine, imgs, trans_mats, sdf_params, sdf_res: int, iso: float = 0.0, refine: int = 0,
-                normals: bool = False, band=None, clean=None, simplify=None, colour=None, alpha=None):
+                normals: bool = False, band=None, clean=None, simplify=None, colour=None, alpha=None, smooth=None):
     """``reconstruct_select`` for callers that clean every mesh or none (see there); -> the meshes"""
     more = {} if colour is None or colour is False else {"colour": colour, "alpha": alpha}
+    if smooth is not None:
+        more["smooth"] = smooth
     return reconstruct_select(engine, imgs, trans_mats, sdf_params, sdf_res, iso, refine, normals, band, clean,
                               simplify=simplify, **more)[0]
 
 
 def reconstruct_select(engine, imgs, trans_mats, sdf_params, sdf_res: int, iso: float = 0.0, refine: int = 0,
                        normals: bool = False, band=None, clean=None, select=None, strict: bool = True,
-                       simplify=None, colour=None, alpha=None):
+                       simplify=None, colour=None, alpha=None, smooth=None):
     """images -> meshes for one group of views: one ``engine.encode`` call, the per-image grids of
     ``create_sdf`` in one [B,(res+1)^3] tensor, ONE batched meshing (one host sync for the group).
     -> B x (verts [nv,3] float32, faces [nf,3] int32) device views; the bits are those of ``create_sdf``
@@ -450,6 +517,10 @@ def reconstruct_select(engine, imgs, trans_mats, sdf_params, sdf_res: int, iso: 
     sync for the group, the simplified sizes); the bits are those of ``postprocess.simplify_arrays`` on the (cleaned)
     mesh.  The refinement then pulls the moved vertices back onto the network's level set, and the normals are the
     gradients at the final vertices.
+    ``smooth`` = ITERS or a dict (``smooth_args``): behind the simplification and BEFORE the refinement every mesh with
+    triangles is faired by Taubin smoothing (``smooth_group``: one more host sync for the group, the status words), no
+    coordinate further than ``cap`` grid cells of its view's box from where it was; the bits are those of
+    ``postprocess.smooth_arrays`` on the (cleaned, simplified) mesh.  Faces never change.
     ``colour`` = True or a dict (``colour_args``): behind every other stage each mesh is coloured from its own view
     (``colour_group``; ``alpha`` None or [B,137,137] uint8 masks the background) and gains ``colours`` uint8 [nv,3] as
     its last element: (verts, faces[, normals], colours).  Vertices, faces and normals are bit for bit those of the
@@ -460,6 +531,7 @@ def reconstruct_select(engine, imgs, trans_mats, sdf_params, sdf_res: int, iso: 
     clean = clean_args(clean)
     simplify = simplify_args(simplify)
     colour = colour_args(colour)
+    smooth = smooth_args(smooth)
     if band is None:
         enc, grids = _encode_grids(engine, imgs, trans_mats, sdf_params, sdf_res)
     else:
@@ -467,6 +539,8 @@ def reconstruct_select(engine, imgs, trans_mats, sdf_params, sdf_res: int, iso: 
     sp = np.asarray(sdf_params, dtype=np.float64).reshape(grids.shape[0], 6)
     meshes, unclean = clean_group(isosurface.marching_cubes_batch(grids, sp, sdf_res, iso), clean, select, strict)
     meshes = simplify_group(meshes, simplify, sp)
+    if smooth is not None:
+        meshes = smooth_group(meshes, smooth, sp, sdf_res)
     if refine <= 0 and not normals:
         return (meshes if colour is None else colour_group(meshes, colour, imgs, trans_mats, 1, alpha)), unclean
     out = []
@@ -492,22 +566,25 @@ def fuse_args(fuse, pool: str = "max") -> Optional[Tuple[int, str]]:
 
 
 def reconstruct_fused(engine, imgs, trans_mats, sdf_params, sdf_res: int, iso: float = 0.0, fuse: int = 2,
-                      pool: str = "max", clean=None, simplify=None, colour=None, alpha=None):
+                      pool: str = "max", clean=None, simplify=None, colour=None, alpha=None, smooth=None):
     """``reconstruct_fused_select`` for callers that clean every mesh or none (see there); -> the meshes"""
     more = {} if colour is None or colour is False else {"colour": colour, "alpha": alpha}
+    if smooth is not None:
+        more["smooth"] = smooth
     return reconstruct_fused_select(engine, imgs, trans_mats, sdf_params, sdf_res, iso, fuse, pool, clean,
                                     simplify=simplify, **more)[0]
 
 
 def reconstruct_fused_select(engine, imgs, trans_mats, sdf_params, sdf_res: int, iso: float = 0.0, fuse: int = 2,
                              pool: str = "max", clean=None, select=None, strict: bool = True, simplify=None,
-                             colour=None, alpha=None):
+                             colour=None, alpha=None, smooth=None):
     """multi-view ``reconstruct``: the B images are B / ``fuse`` runs of ``fuse`` consecutive views of one object each
     (cameras trans_mats [B,4,3] in the object's frame, the run's grid box = its first view's sdf_params).  One
     ``engine.encode`` call, one ``engine.query_grid_views`` grid per run (features pooled over the run's views,
     ``pool`` = "max" or "mean"), ONE batched meshing -> B / fuse x (verts, faces); a run's bits are those of
     ``query_grid_views`` followed by ``isosurface.marching_cubes`` on that run alone.  ``clean``, ``select`` (one
-    entry per RUN), ``strict`` and ``simplify`` (on the lattice of the run's box) as in ``reconstruct_select``;
+    entry per RUN), ``strict``, ``simplify`` (on the lattice of the run's box) and ``smooth`` (the cap in cells of the
+    run's box) as in ``reconstruct_select``;
     ``colour``: every run's mesh is coloured from ALL ``fuse`` views of the run (``alpha`` None or [B,137,137]).
     -> (meshes, unclean [B / fuse] bool)"""
     import torch
@@ -520,6 +597,7 @@ def reconstruct_fused_select(engine, imgs, trans_mats, sdf_params, sdf_res: int,
     clean = clean_args(clean)
     simplify = simplify_args(simplify)
     colour = colour_args(colour)
+    smooth = smooth_args(smooth)
     imgs = np.asarray(imgs, np.float32) if not isinstance(imgs, torch.Tensor) else imgs
     B = imgs.shape[0]
     if B % V:
@@ -533,6 +611,8 @@ def reconstruct_fused_select(engine, imgs, trans_mats, sdf_params, sdf_res: int,
         engine.query_grid_views(enc, (r * V, V), tm[r * V:(r + 1) * V], sp[r], sdf_res, pool, out=grids[r])
     meshes, unclean = clean_group(isosurface.marching_cubes_batch(grids, sp, sdf_res, iso), clean, select, strict)
     meshes = simplify_group(meshes, simplify, sp)
+    if smooth is not None:
+        meshes = smooth_group(meshes, smooth, sp, sdf_res)
     return (meshes if colour is None else colour_group(meshes, colour, imgs, tm, V, alpha)), unclean
 
 
@@ -582,13 +662,15 @@ def groups(entries: Sequence, batch_size: int) -> List[List]:
 
 
 def result_obj_path(log_dir: str, sdf_res: int, iso: float, cam_est: bool = False, fuse=None,
-                    clean: bool = False, simplify=None, colour: bool = False) -> str:
+                    clean: bool = False, simplify=None, colour: bool = False, smooth=None) -> str:
     """test/create_sdf.py:88-93: <log_dir>/test_objs/[camest_]<res+1>_<str(iso)>; ``fuse`` = (V, pool): the fused
     meshes' own directory [camest_]fuse<V><pool>_<res+1>_<str(iso)>; ``clean``: the tree with the cleaned categories,
     <...>_comb (the name INTEGRATION 3e gives the combined tree); ``simplify`` = CELLS: the simplified meshes' tree,
-    <...>[_comb]_s<CELLS>; ``colour``: the coloured meshes' tree, <...>[_comb][_s<CELLS>]_col"""
+    <...>[_comb]_s<CELLS>; ``colour``: the coloured meshes' tree, <...>[_comb][_s<CELLS>]_col; ``smooth`` = ITERS: the
+    smoothed meshes' tree, _t<ITERS> between _comb and _s<CELLS>: <...>[_comb]_t<ITERS>[_s<CELLS>][_col]"""
     prefix = ("camest_" if cam_est else "") + ("fuse%d%s_" % tuple(fuse) if fuse else "")
     return os.path.join(log_dir, "test_objs", prefix + str(sdf_res + 1) + "_" + str(iso) + ("_comb" if clean else "")
+                        + ("_t%d" % smooth if smooth is not None else "")
                         + ("_s%d" % simplify if simplify is not None else "") + ("_col" if colour else ""))
 
 
@@ -646,9 +728,33 @@ def parser():
                         "reference's five), all, or names separated by commas; results go to <...>_comb")
     add_clean_flags(p)
     add_simplify_flag(p)
+    add_smooth_flags(p)
     add_colour_flags(p)
     add_score_flags(p)
     return p
+
+
+def add_smooth_flags(p) -> None:
+    p.add_argument("--smooth", type=int, default=None, metavar="ITERS",
+                   help="fair every mesh on the device by ITERS (1..64) iterations of Taubin's lambda|mu smoothing, "
+                        "behind --simplify and before --refine; results go to <...>_t<ITERS>")
+    p.add_argument("--smooth_cap", type=float, default=None, metavar="CELLS",
+                   help="with --smooth: no coordinate moves further than CELLS grid cells of the view's box "
+                        "[default: %g]" % SMOOTH_CAP_CELLS)
+    p.add_argument("--smooth_free_boundary", action="store_true",
+                   help="with --smooth: boundary vertices move too [default: they stay where they are]")
+
+
+def smooth_from_flags(a) -> Optional[dict]:
+    """None without --smooth, else the checked dict of ``smooth_args`` (ValueError for --smooth_cap or
+    --smooth_free_boundary without --smooth, iterations outside 1..64, a cap that is negative or not finite)"""
+    if a.smooth is None:
+        for flag in ("smooth_cap", "smooth_free_boundary"):
+            if getattr(a, flag) not in (None, False):
+                raise ValueError("--%s needs --smooth" % flag)
+        return None
+    return smooth_args({"iters": a.smooth, "cap": SMOOTH_CAP_CELLS if a.smooth_cap is None else a.smooth_cap,
+                        "pin_boundary": not a.smooth_free_boundary})
 
 
 def add_score_flags(p) -> None:
@@ -763,6 +869,7 @@ def check_flags(a) -> Optional[Tuple[int, str]]:
     band_from_flags(a)
     clean_cats_from_flags(a)
     simplify_from_flags(a)
+    smooth_from_flags(a)
     colour_from_flags(a)
     score_from_flags(a)
     return fuse_from_flags(a)
@@ -797,7 +904,8 @@ def load_group(group: Sequence, sdf_dir: str, rendered_dir: str, backcolorwhite:
 def main(argv=None, reconstruct_fn: Optional[Callable] = None) -> dict:
     """-> {"written", "skipped", "empty", "out_dir"}, with ``--score`` also "scored" (the meshes with a score line of
     status 0), with ``--clean`` also "unclean", with ``--simplify`` also "simplified" (the
-    meshes with triangles: those that went through the stage), with ``--colour`` also "coloured" (likewise; every mesh
+    meshes with triangles: those that went through the stage), with ``--smooth`` also "smoothed" (likewise), with
+    ``--colour`` also "coloured" (likewise; every mesh
     then ends in ``colours`` uint8 [nv,3], behind the normals when there are any).  ``reconstruct_fn(imgs, trans_mats, sdf_params)``
     replaces the device work (engine + ``reconstruct``) -- for host-side tests of the driver.  With ``--clean`` it is
     called as ``reconstruct_fn(imgs, trans_mats, sdf_params, select)`` -- ``select``: one bool per mesh, True for the
@@ -815,9 +923,13 @@ def main(argv=None, reconstruct_fn: Optional[Callable] = None) -> dict:
     simplify = simplify_from_flags(a)
     colour = colour_from_flags(a)
     score = score_from_flags(a)
+    smooth = smooth_from_flags(a)
     more = {} if simplify is None else {"simplify": simplify}     # (without the flag every call below is as it was)
     out_dir = result_obj_path(a.log_dir, a.sdf_res, a.iso, a.cam_est, fuse, clean=cleaning is not None, **more,
-                              **({} if colour is None else {"colour": True}))
+                              **({} if colour is None else {"colour": True}),
+                              **({} if smooth is None else {"smooth": smooth["iters"]}))
+    if smooth is not None:
+        more["smooth"] = smooth
     if colour is not None:
         more["colour"] = colour
     entries = sample_list(categories(a.category), a.test_lst_dir, a.view_num, a.seed, a.num_shards, a.shard_id)
@@ -927,6 +1039,8 @@ def main(argv=None, reconstruct_fn: Optional[Callable] = None) -> dict:
         res["unclean"] = unclean
     if simplify is not None:
         res["simplified"] = written - empty
+    if smooth is not None:
+        res["smoothed"] = written - empty
     if colour is not None:
         res["coloured"] = written - empty
     if score is not None:

@@ -5,6 +5,7 @@
                             [--band STRIDE --band_margin 0.5 --band_dilate 1]
                             [--clean --clean_dist_thresh 0.5 --clean_num_thresh 0.3 --clean_connectivity face]
                             [--simplify CELLS]
+                            [--smooth ITERS --smooth_cap 0.5 --smooth_free_boundary]
                             [--preview OUT.png [--preview_size 137]]
 
 The image is read as demo/demo.py:261-279 reads it (``cv2.imread(IMREAD_UNCHANGED)[:, :, :3] / 255``: the
@@ -22,6 +23,10 @@ an alpha channel, the 2-D IoU of the predicted silhouette with it: low with a go
 ``--simplify CELLS`` simplifies the mesh on the device before it is written (``postprocess.simplify_meshes_device``,
 DESIGN §4za): one quadric-placed vertex per cell of a lattice of CELLS cells per side of the box, behind ``--clean`` and
 before ``--refine`` / ``--normals``.
+
+``--smooth ITERS`` fairs the mesh on the device by Taubin's lambda|mu smoothing (``postprocess.smooth_meshes_device``,
+DESIGN §4zd) behind ``--simplify`` and before ``--refine`` / ``--normals``: the faces stay, no coordinate moves further
+than ``--smooth_cap`` grid cells (default 0.5), boundary vertices stay unless ``--smooth_free_boundary`` is given.
 """
 from __future__ import annotations
 
@@ -96,12 +101,13 @@ def parser() -> argparse.ArgumentParser:
     p.add_argument("--preview", default=None, metavar="OUT.png",
                    help="also write the sphere-traced view of the predicted surface from the camera in use")
     p.add_argument("--preview_size", type=int, default=137, metavar="N", help="the preview is N x N [default: 137]")
-    from .create_sdf import add_band_flags, add_clean_flags, add_colour_flags, add_simplify_flag
+    from .create_sdf import add_band_flags, add_clean_flags, add_colour_flags, add_simplify_flag, add_smooth_flags
     add_band_flags(p)
     p.add_argument("--clean", action="store_true",
                    help="drop the mesh's small and far parts on the device (postprocess.clean_meshes_device)")
     add_clean_flags(p)
     add_simplify_flag(p)
+    add_smooth_flags(p)
     add_colour_flags(p)
     return p
 
@@ -140,11 +146,12 @@ def main(argv=None) -> dict:
     a = parser().parse_args(argv)
     from . import isosurface
     from .create_sdf import (band_from_flags, clean_from_flags, colour_from_flags, reconstruct, restore_weights,
-                             simplify_from_flags)
+                             simplify_from_flags, smooth_from_flags)
     band = band_from_flags(a)                                          # a bad stride / resolution: before anything else
     clean = clean_from_flags(a, a.clean)
     simplify = simplify_from_flags(a)
     colour = colour_from_flags(a)
+    smooth = smooth_from_flags(a)
     img = read_image(a.img)
     if img.shape[1:3] != (137, 137):
         raise ValueError("%s is %dx%d; the network reads 137x137 renderings" % (a.img, img.shape[2], img.shape[1]))
@@ -166,6 +173,8 @@ def main(argv=None) -> dict:
         extra["clean"] = clean
     if simplify is not None:
         extra["simplify"] = simplify
+    if smooth is not None:
+        extra["smooth"] = smooth
     if colour is not None:
         alpha = read_alpha(a.img)                                      # the background of the rendering colours nothing
         extra.update(colour=colour, alpha=None if alpha is None else alpha[None])

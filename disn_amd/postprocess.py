@@ -25,6 +25,10 @@ Not in the reference either: vertex colours from the input views (``--colour`` o
 4zb).  ``zbuffer_arrays`` / ``colour_arrays`` are the rule, on the host; ``zbuffer_meshes_device``,
 ``colour_meshes_device`` and ``colour_arrays_device`` (mesh_colour.hip) give its depth bits and its colour bytes for
 meshes that lie on the device.
+
+Not in the reference either: fairing by Taubin's lambda|mu smoothing (``--smooth ITERS`` of ``create_sdf`` and ``demo``,
+DESIGN 4zd).  ``smooth_arrays`` is the rule, on the host; ``smooth_meshes_device`` / ``smooth_arrays_device``
+(mesh_smooth.hip) give its position bits for meshes that lie on the device.
 """
 from __future__ import annotations
 
@@ -234,6 +238,139 @@ def simplify_arrays(verts, faces, box, cells: int, dedup: bool = True, placement
         keep = np.zeros(nf, bool)
         keep[ids[lowest]] = True
     return out_v, g[keep].astype(np.int32).reshape(-1, 3), vmap.astype(np.int32), first.astype(np.int32)
+
+
+# ---- Taubin smoothing: the rule (the device restates it, mesh_smooth.hip) -------------------------------
+SMOOTH_MAX_ITERS = 64
+SMOOTH_RANGE = 1024.0          # a coordinate beyond it, at input or after a step: status 7
+SMOOTH_MAX_DEGREE = 1 << 20    # with the range: every sum of neighbours stays below 2^20 2^10 2^32 = 2^62
+STATUS_SMOOTH_RANGE = 7
+
+
+def smooth_params(iters=10, lam=0.5, mu=-0.53, max_move=None):
+    """-> (iters, lam, mu, max_move) checked: ``iters`` an integer in 1..64, 0 < ``lam`` <= 1, -1.5 <= ``mu`` < 0,
+    ``max_move`` None or finite and >= 0 (a scalar or an array); ValueError otherwise"""
+    if isinstance(iters, bool) or not isinstance(iters, (int, np.integer)) or not 1 <= int(iters) <= SMOOTH_MAX_ITERS:
+        raise ValueError("smooth: iters must be an integer in 1..%d, got %r" % (SMOOTH_MAX_ITERS, iters))
+    try:
+        lam, mu = float(lam), float(mu)
+    except (TypeError, ValueError):
+        raise ValueError("smooth: lam and mu must be numbers, got %r and %r" % (lam, mu)) from None
+    if not 0.0 < lam <= 1.0:
+        raise ValueError("smooth: lam must lie in (0, 1], got %r" % lam)
+    if not -1.5 <= mu < 0.0:
+        raise ValueError("smooth: mu must lie in [-1.5, 0), got %r" % mu)
+    if max_move is not None:
+        try:
+            r = np.asarray(max_move, np.float64)
+        except (TypeError, ValueError):
+            raise ValueError("smooth: max_move must be None or finite and >= 0, got %r" % (max_move,)) from None
+        if not (np.isfinite(r).all() and (r >= 0.0).all()):
+            raise ValueError("smooth: max_move must be None or finite and >= 0, got %r" % (max_move,))
+        max_move = float(r) if r.ndim == 0 else r
+    return int(iters), lam, mu, max_move
+
+
+def smooth_graph(faces, nv: int):
+    """the edges of the rule -> (indptr int64 [nv+1], nbr int64 [2 E], boundary bool [nv]): row i of the CSR holds the
+    distinct neighbours of i, ascending; an undirected edge counts once however many faces hold it, a corner pair
+    (i, i) not at all; a vertex is on the boundary when one of its edges is held by exactly one corner pair"""
+    f = np.asarray(faces, np.int64).reshape(-1, 3)
+    a, b = f[:, (0, 1, 2)].reshape(-1), f[:, (1, 2, 0)].reshape(-1)
+    proper = a != b
+    lo, hi = np.minimum(a, b)[proper], np.maximum(a, b)[proper]
+    key, held = np.unique(lo * np.int64(max(nv, 1)) + hi, return_counts=True)
+    lo, hi = key // max(nv, 1), key % max(nv, 1)
+    boundary = np.zeros(nv, bool)
+    boundary[lo[held == 1]] = True
+    boundary[hi[held == 1]] = True
+    src, dst = np.concatenate([lo, hi]), np.concatenate([hi, lo])
+    order = np.lexsort((dst, src))
+    indptr = np.zeros(nv + 1, np.int64)
+    indptr[1:] = np.cumsum(np.bincount(src, minlength=nv))
+    return indptr, dst[order], boundary
+
+
+def smooth_status(verts, faces) -> int:
+    """the status of a mesh BEFORE its first step: the largest of 2 (a face index outside the mesh), 4 (a coordinate that
+    is not finite), 7 (a finite coordinate beyond +-1024; more than 2^20 distinct neighbours at a vertex of a mesh that
+    is otherwise in order); 0 when none applies"""
+    v, f = _host(verts, faces)
+    status = 0
+    if f.size and (f.min() < 0 or f.max() >= v.shape[0]):
+        status = STATUS_INDEX
+    finite = np.isfinite(v)
+    if not finite.all():
+        status = max(status, STATUS_FINITE)
+    if (np.abs(v[finite]) > np.float32(SMOOTH_RANGE)).any():
+        status = STATUS_SMOOTH_RANGE
+    if status == 0 and f.size and np.diff(smooth_graph(f, v.shape[0])[0]).max() > SMOOTH_MAX_DEGREE:
+        status = STATUS_SMOOTH_RANGE
+    return status
+
+
+def smooth_arrays_status(verts, faces, iters=10, lam=0.5, mu=-0.53, pin_boundary=True, max_move=None
+                         ) -> Tuple[np.ndarray, int]:
+    """``smooth_arrays`` with the status word instead of the exceptions -> (verts', status): a mesh with a status keeps
+    its input vertices, as on the device"""
+    iters, lam, mu, max_move = smooth_params(iters, lam, mu, max_move)
+    if max_move is not None and np.ndim(max_move):
+        raise ValueError("smooth: one mesh takes one max_move")
+    v0, f = _host(verts, faces)
+    nv = v0.shape[0]
+    status = smooth_status(v0, f)
+    if status or nv == 0:
+        return v0.copy(), status
+    indptr, nbr, boundary = smooth_graph(f, nv)
+    deg = np.diff(indptr)
+    movable = deg > 0
+    if pin_boundary:
+        movable &= ~boundary
+    rows = np.nonzero(movable)[0]
+    n = deg[rows].astype(np.float64)[:, None]
+    x0 = v0.astype(np.float64)
+    cur = v0.copy()
+    for t in range(2 * iters):
+        s = lam if t % 2 == 0 else mu
+        q = np.rint(cur.astype(np.float64) * _FIX).astype(np.int64)
+        run = np.zeros((nbr.size + 1, 3), np.int64)
+        np.cumsum(q[nbr], axis=0, out=run[1:])                  # int64: exact, whatever the order
+        S = run[indptr[rows + 1]] - run[indptr[rows]]
+        m = (S.astype(np.float64) * (1.0 / _FIX)) / n
+        x = cur[rows].astype(np.float64)
+        y = x + s * (m - x)
+        if max_move is not None:
+            y = np.minimum(np.maximum(y, x0[rows] - max_move), x0[rows] + max_move)
+        new = y.astype(np.float32)
+        if (np.abs(new) > np.float32(SMOOTH_RANGE)).any():
+            return v0.copy(), STATUS_SMOOTH_RANGE
+        cur = cur.copy()
+        cur[rows] = new
+    return cur, 0
+
+
+def smooth_arrays(verts, faces, iters=10, lam=0.5, mu=-0.53, pin_boundary=True, max_move=None) -> np.ndarray:
+    """Taubin lambda|mu smoothing on the host: THE SPECIFICATION of ``smooth_meshes_device`` (same position bits).
+    -> verts' float32 [nv,3]; the faces never change.
+
+    Edges: every face gives its three corner pairs, a pair of equal indices is ignored (degenerate faces are legal), an
+    undirected edge {i, j} counts once however many faces hold it; N(i) the distinct neighbours of i, deg(i) = |N(i)|.
+    An edge held by exactly ONE corner pair of the whole mesh is a boundary edge, its two ends boundary vertices.  A
+    vertex moves when deg(i) > 0 and it is no pinned boundary vertex (``pin_boundary``); any other vertex keeps its
+    input bits.  2 ``iters`` Jacobi steps, step t with the factor s = ``lam`` (t even) or ``mu`` (t odd), every vertex
+    from the positions of the step before:  q(x) = int64(rint(float64(x) 2^32));  S_i = sum of q(v_j) over N(i), an
+    int64 sum, so its order does not matter;  m_i = (float64(S_i) 2^-32) / float64(deg(i));  v'_i = float32(float64(v_i)
+    + s (m_i - float64(v_i))) in float64 exactly as written.  ``max_move`` = r: after every step each coordinate is
+    clamped in float64 to [float64(v0_i) - r, float64(v0_i) + r], v0 the input position, before the cast -- a box, not
+    a ball.  ValueError (the device: the status word) for a face index outside the mesh (2), a coordinate that is not
+    finite (4), and for a coordinate beyond +-1024 at input or after any step or a vertex of more than 2^20 neighbours
+    (7: ``smooth_arrays_status``); ValueError for parameters outside ``smooth_params``' ranges."""
+    out, status = smooth_arrays_status(verts, faces, iters, lam, mu, pin_boundary, max_move)
+    if status == STATUS_SMOOTH_RANGE:
+        raise ValueError("a coordinate leaves +-%g (at input or after a step), or a vertex has more than 2^20 neighbours"
+                         % SMOOTH_RANGE)
+    _one_mesh(_raise_status, 0, status, [0, out.shape[0]], "smooth_arrays")
+    return out
 
 
 # ---- vertex colours from the input views: the rule (DESIGN 4zb; the device restates it, mesh_colour.hip) ----------
@@ -500,7 +637,8 @@ def colour_arrays(verts, faces, images, trans_mats, alpha=None, S: int = 2, rel_
 
 
 # ---- the device path: B meshes back to back (mesh_clean.hip, mesh_simplify.hip, mesh_colour.hip) ---------------
-# a mesh's status word (csrc/mesh_batch.hpp and the stages' own; include/): 1 is the cleanup's, 5 the simplification's
+# a mesh's status word (csrc/mesh_batch.hpp and the stages' own; include/): 1 is the cleanup's, 5 the simplification's,
+# 7 the smoothing's (STATUS_SMOOTH_RANGE above; 6 is the sampler's, metrics.STATUS_NO_AREA)
 STATUS_NOTHING_KEPT, STATUS_INDEX, STATUS_TABLE, STATUS_FINITE, STATUS_CAPACITY = 1, 2, 3, 4, 5
 
 
@@ -730,6 +868,55 @@ def simplify_arrays_device(verts, faces, box, cells: int, dedup: bool = True):
     integers and the position bits of ``simplify_arrays``; the same ValueErrors"""
     simplified, maps = _one_mesh(simplify_meshes_device, [(verts, faces)], [box], cells, dedup)
     return simplified[0][0], simplified[0][1], maps[0][0], maps[0][1]
+
+
+# ---- Taubin smoothing on the device (mesh_smooth.hip) ------------------------------------------------------------
+def smooth_meshes_device(meshes, iters=10, lam=0.5, mu=-0.53, pin_boundary=True, max_move=None, strict: bool = True):
+    """``smooth_arrays`` for a group of meshes that lie on the device.  ``meshes``: B x (verts [nv,3] float32, faces
+    [nf,3] int32[, further arrays]) device tensors (the views the earlier stages return are used in place);
+    ``max_move`` None, one number or B numbers (each mesh's own cap).  ONE call, no read-back but the B status words.
+    -> (smoothed, status): B x (verts', faces[, arrays]) -- verts' views of one output with the bits of
+    ``smooth_arrays``, the faces and every further array as they were given -- and the status words, int32 [B] on the
+    host.  An empty mesh stays empty.  A mesh with a status (2 a face index out of range, 4 a coordinate that is not
+    finite, 7 a coordinate beyond +-1024 at input or after a step) raises ValueError naming the mesh -- with
+    ``strict=False`` it keeps its input vertices and the call returns."""
+    import torch
+
+    from . import ops
+    from ._lib import check
+    iters, lam, mu, max_move = smooth_params(iters, lam, mu, max_move)
+    meshes = [tuple(m) for m in meshes]
+    if not meshes:
+        return [], np.zeros(0, np.int32)
+    B, h = len(meshes), lib()
+    cap = None
+    if max_move is not None:
+        if np.ndim(max_move) and np.shape(max_move) != (B,):
+            raise ValueError("smooth: %d values of max_move for %d meshes" % (np.size(max_move), B))
+        cap = np.ascontiguousarray(np.broadcast_to(np.asarray(max_move, np.float64), (B,)))
+    v, v_off, f, f_off, ws = _pack_meshes(meshes, lambda nv, nf: h.disn_mesh_smooth_workspace_bytes(B, nv, nf))
+    nv, dev = int(v_off[-1]), v.device
+    with torch.cuda.device(dev):
+        out = torch.empty((nv, 3), dtype=torch.float32, device=dev)
+        status = torch.empty(B, dtype=torch.int32, device=dev)
+        check("disn_mesh_smooth_batch", h.disn_mesh_smooth_batch(
+            v.data_ptr(), f.data_ptr(), v_off.ctypes.data, f_off.ctypes.data, B, iters, lam, mu, 1 if pin_boundary else 0,
+            None if cap is None else cap.ctypes.data, out.data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel(),
+            ops._stream()))
+        st = status.cpu().numpy()                               # the one host sync of the group
+    for b in np.nonzero(st)[0] if strict else ():
+        _raise_status(b, st[b], v_off, "disn_mesh_smooth_batch")
+        if st[b] == STATUS_SMOOTH_RANGE:
+            raise ValueError("mesh %d: a coordinate leaves +-%g (at input or after a step), or a vertex has more than "
+                             "2^20 neighbours" % (b, SMOOTH_RANGE))
+        raise RuntimeError("mesh %d: disn_mesh_smooth_batch gave status %d" % (b, st[b]))
+    return [(out[int(v_off[b]):int(v_off[b + 1])],) + m[1:] for b, m in enumerate(meshes)], st
+
+
+def smooth_arrays_device(verts, faces, **kw):
+    """``smooth_arrays`` for one mesh on the device -> verts' (a device tensor with the bits of ``smooth_arrays``); the
+    same ValueErrors"""
+    return _one_mesh(smooth_meshes_device, [(verts, faces)], **kw)[0][0][0]
 
 
 # ---- vertex colours on the device (mesh_colour.hip) -------------------------------------------------------------
