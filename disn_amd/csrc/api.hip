@@ -110,6 +110,13 @@ VggWs vgg_layout(void* ws, int B, int num_classes) {
   return w;
 }
 
+// the shapes disn_conv3x3 / disn_conv3x3_planned admit: 0, or the status that refuses the others
+int conv3x3_shape(int B, int H, int W, int Cin, int Cout) {
+  if (B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0) return DISN_E_ARG;
+  if (!(Cin == 3 || Cin % 32 == 0) || Cout % 64 != 0 || H >= 32768 || W >= 32768) return DISN_E_SHAPE;
+  return conv3x3_fits(B, H, W, Cin, Cout) ? 0 : DISN_E_SHAPE;
+}
+
 int conv3x3_impl(const float* in, int B, int H, int W, int Cin, const float* w_packed,
                  const float* bias, int Cout, int relu, float* out, float* ws, size_t ws_bytes,
                  hipStream_t st, const void* x3 = nullptr, float* pool_out = nullptr,
@@ -426,6 +433,13 @@ QueryWs query_layout(void* ws, int B, int chunk, bool need_feat, bool need_pts, 
   return q;
 }
 
+// pts [B][N][3]: the element count of a point set in int (kernels.hpp)
+inline bool points_fit(int B, int64_t N) { return fits_int(B, N, 3); }
+// x [B][K], W [K][N], out [B][N]
+inline bool fc_fits(int B, int K, int N) { return fits_int(B, K) && fits_int(K, N) && fits_int(B, N); }
+// the convolutions of a batch are GEMMs of B * 224 * 224 rows, counted in int (gemm_plan, GemmParams.M)
+inline bool vgg_batch_fits(int B) { return fits_int(B, 224 * 224); }
+
 inline int chunk_for(long n) { return (int)(n < kChunk ? (n > 0 ? n : 1) : kChunk); }
 
 // grid_spec (kernels.hpp) and the range k0..k1-1 of its (R+1)^3 points: false for a bad box or an empty / out-of-grid range
@@ -442,20 +456,20 @@ extern "C" {
 int disn_abi_version(void) { return DISN_ABI_VERSION; }
 
 size_t disn_pack_kn_x3_bytes(int K, int N) {
-  if (K <= 0 || N <= 0 || N % 32) return 0;
+  if (K <= 0 || N <= 0 || N % 32 || !fits_int(3, (long long)K + 31, N)) return 0;
   return (size_t)3 * ((K + 31) & ~31) * N * 2;
 }
 
 int disn_pack_kn_x3(const float* w_kn, int K, int N, void* packed, void* stream) {
   if (!w_kn || !packed || K <= 0 || N <= 0) return DISN_E_ARG;
-  if (N % 32) return DISN_E_SHAPE;
+  if (N % 32 || !fits_int(3, (long long)K + 31, N)) return DISN_E_SHAPE;
   DISN_TRY(pack_bf16_launch(w_kn, 0, K, N, packed, (hipStream_t)stream, 3));
   return 0;
 }
 
 int disn_pack_kn(const float* w_kn, int K, int N, int Kpad, float* packed, void* stream) {
   if (!w_kn || !packed || K <= 0 || N <= 0) return DISN_E_ARG;
-  if (N % 32 || Kpad % 32 || Kpad < K) return DISN_E_SHAPE;
+  if (N % 32 || Kpad % 32 || Kpad < K || !fits_int(Kpad, N)) return DISN_E_SHAPE;
   DISN_TRY(pack_kn_launch(w_kn, K, N, Kpad, packed, (hipStream_t)stream));
   return 0;
 }
@@ -464,26 +478,30 @@ int disn_resize_bilinear(const float* in, int B, int Hin, int Win, int C, float*
                          int Wout, int out_cstride, int out_coff, void* stream) {
   if (!in || !out || B <= 0 || Hin <= 0 || Win <= 0 || C <= 0 || Hout <= 0 || Wout <= 0)
     return DISN_E_ARG;
-  if (out_coff < 0 || out_coff + C > out_cstride) return DISN_E_SHAPE;
+  if (out_coff < 0 || (long long)out_coff + C > out_cstride) return DISN_E_SHAPE;
+  if (!fits_int(B, Hin, Win, C) || !fits_int(B, Hout, Wout, out_cstride)) return DISN_E_SHAPE;
   DISN_TRY(resize_bilinear_launch(in, B, Hin, Win, C, out, Hout, Wout, out_cstride, out_coff,
                                   (hipStream_t)stream));
   return 0;
 }
 
 size_t disn_conv3x3_workspace_bytes(int B, int H, int W, int Cin, int Cout) {
-  if (B <= 0 || H <= 0 || W <= 0 || Cout <= 0) return 0;
+  if (conv3x3_shape(B, H, W, Cin, Cout)) return 0;
   return gemm_plan(B * H * W, Cout, conv_k(Cin)).ws_bytes;
 }
 
 int disn_conv3x3(const float* in, int B, int H, int W, int Cin, const float* w_packed,
                  const float* bias, int Cout, int relu, float* out, void* ws, size_t ws_bytes,
                  void* stream) {
+  if (!in || !w_packed || !bias || !out) return DISN_E_ARG;
+  if (int rc = conv3x3_shape(B, H, W, Cin, Cout)) return rc;
+  if (gemm_plan(B * H * W, Cout, conv_k(Cin)).ws_bytes > (ws ? ws_bytes : 0)) return DISN_E_WS;
   return conv3x3_impl(in, B, H, W, Cin, w_packed, bias, Cout, relu, out, (float*)ws, ws_bytes,
                       (hipStream_t)stream);
 }
 
 size_t disn_conv3x3_planned_workspace_bytes(int B, int H, int W, int Cin, int Cout, int bm, int bn, int wgs) {
-  if (B <= 0 || H <= 0 || W <= 0 || Cout <= 0) return 0;
+  if (conv3x3_shape(B, H, W, Cin, Cout)) return 0;
   const int force[3] = {bm, bn, wgs};
   return gemm_plan(B * H * W, Cout, conv_k(Cin), ~size_t(0), force).ws_bytes;
 }
@@ -491,8 +509,8 @@ size_t disn_conv3x3_planned_workspace_bytes(int B, int H, int W, int Cin, int Co
 int disn_conv3x3_planned(const float* in, int B, int H, int W, int Cin, const float* w_packed,
                          const float* bias, int Cout, int relu, float* out, void* ws, size_t ws_bytes,
                          int bm, int bn, int wgs, void* stream) {
-  if (!in || !w_packed || !bias || !out || B <= 0 || H <= 0 || W <= 0) return DISN_E_ARG;
-  if (!(Cin == 3 || Cin % 32 == 0) || Cout % 64 != 0 || H >= 32768 || W >= 32768) return DISN_E_SHAPE;
+  if (!in || !w_packed || !bias || !out) return DISN_E_ARG;
+  if (int rc = conv3x3_shape(B, H, W, Cin, Cout)) return rc;
   if (!((bm == 64 || bm == 128) && (bn == 64 || bn == 128) && Cout % bn == 0 && (wgs >= 1 || wgs == -1)))
     return DISN_E_SHAPE;
   GemmParams p{};
@@ -509,21 +527,21 @@ int disn_conv3x3_planned(const float* in, int B, int H, int W, int Cin, const fl
 }
 
 int disn_maxpool2x2(const float* in, int B, int H, int W, int C, float* out, void* stream) {
-  if (!in || !out || B <= 0 || H < 2 || W < 2) return DISN_E_ARG;
-  if (C % 4) return DISN_E_SHAPE;
+  if (!in || !out || B <= 0 || H < 2 || W < 2 || C <= 0) return DISN_E_ARG;
+  if (C % 4 || !fits_int(B, H, W, C)) return DISN_E_SHAPE;
   DISN_TRY(maxpool2x2_launch(in, B, H, W, C, out, (hipStream_t)stream));
   return 0;
 }
 
 size_t disn_fc_workspace_bytes(int B, int K, int N) {
-  if (B <= 0 || K <= 0 || N <= 0 || N % 256) return 0;
+  if (B <= 0 || K <= 0 || N <= 0 || N % 256 || !fc_fits(B, K, N)) return 0;
   return gemv_ws_bytes(B, K, N);
 }
 
 int disn_fc(const float* x, int B, int K, const float* w_kn, const float* bias, int N, int relu,
             float* out, void* ws, size_t ws_bytes, void* stream) {
   if (!x || !w_kn || !bias || !out || !ws || B <= 0 || K <= 0) return DISN_E_ARG;
-  if (N <= 0 || N % 256) return DISN_E_SHAPE;
+  if (N <= 0 || N % 256 || !fc_fits(B, K, N)) return DISN_E_SHAPE;
   if (ws_bytes < gemv_ws_bytes(B, K, N)) return DISN_E_WS;
   DISN_TRY(gemv_launch(x, B, K, w_kn, bias, N, relu, out, (float*)ws, (hipStream_t)stream));
   return 0;
@@ -532,7 +550,7 @@ int disn_fc(const float* x, int B, int K, const float* w_kn, const float* bias, 
 int disn_fc_t(const float* x, int B, int K, const float* wt_nk, const float* bias, int N, int relu, float* out,
               void* stream) {
   if (!x || !wt_nk || !bias || !out || B <= 0 || K <= 0 || N <= 0) return DISN_E_ARG;
-  if (K % 4) return DISN_E_SHAPE;
+  if (K % 4 || !fc_fits(B, K, N)) return DISN_E_SHAPE;
   DISN_TRY(gemv_rows_launch(x, B, K, wt_nk, bias, N, relu, out, (hipStream_t)stream));
   return 0;
 }
@@ -540,7 +558,7 @@ int disn_fc_t(const float* x, int B, int K, const float* wt_nk, const float* bia
 int disn_scale_channels(const float* in, int64_t rows, int C, const float* scale, int invert, float* out,
                         void* stream) {
   if (!in || !scale || !out || rows < 0 || C <= 0) return DISN_E_ARG;
-  if (C % 4) return DISN_E_SHAPE;
+  if (C % 4 || !fits_int(rows, C)) return DISN_E_SHAPE;
   if (rows == 0) return 0;
   DISN_TRY(scale_channels_launch(in, rows, C, scale, invert, out, (hipStream_t)stream));
   return 0;
@@ -549,12 +567,13 @@ int disn_scale_channels(const float* in, int64_t rows, int C, const float* scale
 int disn_get_loss(const float* pred, const float* gt, int64_t M, float sdf_weight, float mask_weight, float* out5,
                   void* stream) {
   if (!pred || !gt || !out5 || M <= 0 || sdf_weight == 0.0f) return DISN_E_ARG;
+  if (!fits_int(M, 2)) return DISN_E_SHAPE;
   DISN_TRY(loss_reduce_launch(pred, gt, (long)M, sdf_weight, mask_weight, out5, (hipStream_t)stream));
   return 0;
 }
 
 size_t disn_dense_workspace_bytes(int M, int K, int N) {
-  if (M <= 0 || K <= 0 || N <= 0 || K % 32 || N % 64) return 0;
+  if (M <= 0 || K <= 0 || N <= 0 || K % 32 || N % 64 || !dense_fits(M, K, 0, K, 0, N)) return 0;
   return gemm_plan(M, N, K).ws_bytes;
 }
 
@@ -564,20 +583,21 @@ int disn_dense(const float* a1, int lda1, int k1, const float* a2, int lda2, int
   if (!a1 || !w_packed || !bias || !out || M <= 0 || k1 <= 0 || k2 < 0 || (k2 > 0 && !a2))
     return DISN_E_ARG;
   if (k1 % 32 || k2 % 32 || N <= 0 || N % 64 || lda1 < k1 || (k2 > 0 && lda2 < k2) || lda1 % 4 ||
-      (k2 > 0 && lda2 % 4))
+      (k2 > 0 && lda2 % 4) || !dense_fits(M, lda1, k2 > 0 ? lda2 : 0, k1, k2, N))
     return DISN_E_SHAPE;
   GemmParams p{};
   p.a1 = a1; p.lda1 = lda1; p.k1 = k1; p.a2 = a2; p.lda2 = lda2;
   p.M = M; p.N = N; p.K = k1 + k2;
   p.bp = w_packed; p.bias = bias; p.rows_per_bias = 0;
   p.out = out; p.ldc = N; p.relu = relu;
-  const GemmPlan pl = gemm_plan(M, N, p.K, ws ? ws_bytes : 0);
+  const GemmPlan pl = gemm_plan(M, N, p.K);           // the plan of a workspace of disn_dense_workspace_bytes: what the
+  if (pl.ws_bytes > (ws ? ws_bytes : 0)) return DISN_E_WS;   // query promised, hence what a capped second plan would give
   DISN_TRY(gemm_launch(p, GEMM_DENSE, pl, (float*)ws, (hipStream_t)stream));
   return 0;
 }
 
 size_t disn_vgg16_workspace_bytes(int B) {
-  if (B <= 0) return 0;
+  if (B <= 0 || !vgg_batch_fits(B)) return 0;
   return vgg_layout(nullptr, B, DISN_EMBED_DIM).total;
 }
 
@@ -961,6 +981,7 @@ int query_impl(const disn_mlp_weights_t* w, bool folded, const float* map, const
   if (!mlp_weights_ok(w) || (folded && !w->l_w4_point) || !map || !embedding || !trans_mat || !pts || !pts_rot ||
       !sdf || !ws || B <= 0 || N <= 0)
     return DISN_E_ARG;
+  if (!points_fit(B, N)) return DISN_E_SHAPE;
   const int chunk = chunk_for(N);
   const QueryWs q = query_layout(ws, B, chunk, true, false);
   if (q.total > ws_bytes) return DISN_E_WS;
@@ -1076,7 +1097,7 @@ int disn_vgg16_forward(const disn_vgg_weights_t* w, const float* img, int B, flo
                        float* const taps[5], float* embedding, void* ws, size_t ws_bytes,
                        void* stream) {
   if (!vgg_weights_ok(w) || !img || !taps_ok(taps) || !embedding || !ws || B <= 0) return DISN_E_ARG;
-  if (w->num_classes <= 0 || w->num_classes % 256) return DISN_E_SHAPE;
+  if (w->num_classes <= 0 || w->num_classes % 256 || !vgg_batch_fits(B)) return DISN_E_SHAPE;
   hipStream_t st = (hipStream_t)stream;
   const VggWs s = vgg_layout(ws, B, w->num_classes);
   if (s.total > ws_bytes) return DISN_E_WS;
@@ -1088,6 +1109,7 @@ int disn_vgg16_forward(const disn_vgg_weights_t* w, const float* img, int B, flo
 int disn_vgg16_conv_stack(const disn_vgg_weights_t* w, const float* img, int B, float* resized224,
                           float* const taps[5], float* pool5, void* ws, size_t ws_bytes, void* stream) {
   if (!vgg_weights_ok(w) || !img || !taps_ok(taps) || !ws || B <= 0) return DISN_E_ARG;
+  if (!vgg_batch_fits(B)) return DISN_E_SHAPE;
   hipStream_t st = (hipStream_t)stream;
   const VggWs s = vgg_layout(ws, B, w->num_classes > 0 ? w->num_classes : DISN_EMBED_DIM);
   if (s.total > ws_bytes) return DISN_E_WS;
@@ -1104,7 +1126,7 @@ int disn_encode(disn_ctx_t* ctx, const disn_vgg_weights_t* w, const float* img, 
                 size_t ws_bytes, void* stream) {
   if (!vgg_weights_ok(w) || !img || !taps_ok(taps) || !embedding || !featmap || !ws || B <= 0)
     return DISN_E_ARG;
-  if (w->num_classes <= 0 || w->num_classes % 256) return DISN_E_SHAPE;
+  if (w->num_classes <= 0 || w->num_classes % 256 || !vgg_batch_fits(B)) return DISN_E_SHAPE;
   hipStream_t st = (hipStream_t)stream;
   const VggWs s = vgg_layout(ws, B, w->num_classes);
   if (s.total > ws_bytes) return DISN_E_WS;
@@ -1115,7 +1137,7 @@ int disn_encode(disn_ctx_t* ctx, const disn_vgg_weights_t* w, const float* img, 
 }
 
 size_t disn_encode_query_workspace_bytes(int B, int N) {
-  if (B <= 0 || N <= 0 || (long)B * N > kChunk) return 0;
+  if (B <= 0 || N <= 0 || (long)B * N > kChunk || !vgg_batch_fits(B)) return 0;
   return encq_layout(nullptr, B, N, DISN_EMBED_DIM).total;
 }
 
@@ -1127,7 +1149,7 @@ int disn_encode_query(disn_ctx_t* ctx, const disn_vgg_weights_t* vw, const disn_
   if (!ctx || !vgg_weights_ok(vw) || !mlp_weights_ok(mw) || !img || !trans_mat || !pts || !pts_rot ||
       !taps_ok(taps) || !embedding || !sdf || !ws || B <= 0 || N <= 0)
     return DISN_E_ARG;
-  if ((long)B * N > kChunk || vw->num_classes != DISN_EMBED_DIM) return DISN_E_SHAPE;
+  if ((long)B * N > kChunk || !vgg_batch_fits(B) || vw->num_classes != DISN_EMBED_DIM) return DISN_E_SHAPE;
   hipStream_t st = (hipStream_t)stream;
   const EncQueryWs e = encq_layout(ws, B, N, vw->num_classes);
   if (e.total > ws_bytes) return DISN_E_WS;
@@ -1148,6 +1170,7 @@ int disn_encode_query(disn_ctx_t* ctx, const disn_vgg_weights_t* vw, const disn_
 
 int disn_build_featmap(const float* const taps[5], int B, float* featmap, void* stream) {
   if (!taps_ok(taps) || !featmap || B <= 0) return DISN_E_ARG;
+  if (!vgg_batch_fits(B)) return DISN_E_SHAPE;
   for (int i = 0; i < 5; ++i)
     DISN_TRY(resize_bilinear_launch(taps[i], B, kTap[i].hw, kTap[i].hw, kTap[i].ch, featmap, DISN_IMG_H,
                                     DISN_IMG_W, DISN_FEAT_DIM, kTap[i].off, (hipStream_t)stream));
@@ -1156,12 +1179,14 @@ int disn_build_featmap(const float* const taps[5], int B, float* featmap, void* 
 
 int disn_project(const float* pts, const float* trans_mat, int B, int N, float* xy, void* stream) {
   if (!pts || !trans_mat || !xy || B <= 0 || N <= 0) return DISN_E_ARG;
+  if (!points_fit(B, N)) return DISN_E_SHAPE;
   DISN_TRY(project_launch(pts, trans_mat, B, N, xy, (hipStream_t)stream));
   return 0;
 }
 
 int disn_gather(const float* featmap, const float* xy, int B, int N, float* feat, void* stream) {
   if (!featmap || !xy || !feat || B <= 0 || N <= 0) return DISN_E_ARG;
+  if (!points_fit(B, N)) return DISN_E_SHAPE;
   DISN_TRY(gather_launch(featmap, xy, B, N, feat, (hipStream_t)stream));
   return 0;
 }
@@ -1169,6 +1194,7 @@ int disn_gather(const float* featmap, const float* xy, int B, int N, float* feat
 int disn_gather_taps(const float* const taps[5], const float* trans_mat, const float* pts, int B, int N,
                      float* feat, void* stream) {
   if (!taps_ok(taps) || !trans_mat || !pts || !feat || B <= 0 || N <= 0) return DISN_E_ARG;
+  if (!points_fit(B, N)) return DISN_E_SHAPE;
   DISN_TRY(project_gather_taps_launch(taps, trans_mat, pts, B, N, 0, 5, feat, (hipStream_t)stream));
   return 0;
 }
@@ -1176,6 +1202,7 @@ int disn_gather_taps(const float* const taps[5], const float* trans_mat, const f
 int disn_gather_taps_split(const float* const taps[5], const float* trans_mat, const float* pts, int B, int N,
                            const float* feat_amax, void* feat_split, void* stream) {
   if (!taps_ok(taps) || !trans_mat || !pts || !feat_amax || !feat_split || B <= 0 || N <= 0) return DISN_E_ARG;
+  if (!points_fit(B, N)) return DISN_E_SHAPE;
   DISN_TRY(project_gather_taps_launch(taps, trans_mat, pts, B, N, 0, 5, static_cast<float*>(feat_split),
                                       (hipStream_t)stream, kFeatPad, nullptr, 0, 0, feat_amax));
   return 0;
@@ -1184,12 +1211,13 @@ int disn_gather_taps_split(const float* const taps[5], const float* trans_mat, c
 int disn_gather_fold(const float* pmap_b, const float* trans_mat_b, const float* pts, int N, const float* pre,
                      const float* bias, float* h, void* stream) {
   if (!pmap_b || !trans_mat_b || !pts || !pre || !bias || !h || N <= 0) return DISN_E_ARG;
+  if (!points_fit(1, N)) return DISN_E_SHAPE;
   DISN_TRY(gather_fold_launch(pmap_b, trans_mat_b, pts, N, pre, bias, h, (hipStream_t)stream));
   return 0;
 }
 
 size_t disn_sdf_mlp_workspace_bytes(int B, int N) {
-  if (B <= 0 || N <= 0) return 0;
+  if (B <= 0 || N <= 0 || !points_fit(B, N)) return 0;
   return query_layout(nullptr, B, chunk_for(N), false, false).total;
 }
 
@@ -1198,6 +1226,7 @@ int disn_sdf_mlp(const disn_mlp_weights_t* w, const float* pts_rot, const float*
                  void* ws, size_t ws_bytes, void* stream) {
   if (!mlp_weights_ok(w) || !pts_rot || !embedding || !feat || !sdf || !ws || B <= 0 || N <= 0)
     return DISN_E_ARG;
+  if (!points_fit(B, N)) return DISN_E_SHAPE;
   hipStream_t st = (hipStream_t)stream;
   const int chunk = chunk_for(N);
   const QueryWs q = query_layout(ws, B, chunk, false, false);
@@ -1207,7 +1236,7 @@ int disn_sdf_mlp(const disn_mlp_weights_t* w, const float* pts_rot, const float*
 }
 
 size_t disn_query_workspace_bytes(int B, int N) {
-  if (B <= 0 || N <= 0) return 0;
+  if (B <= 0 || N <= 0 || !points_fit(B, N)) return 0;
   return query_layout(nullptr, B, chunk_for(N), true, false).total;
 }
 
@@ -1321,7 +1350,7 @@ int grad_chunk(const disn_mlp_weights_t* w, const float* pmap_b, const float* tr
 }  // namespace
 
 size_t disn_query_grad_workspace_bytes(int B, int64_t N) {
-  if (B <= 0 || N <= 0) return 0;
+  if (B <= 0 || N <= 0 || !points_fit(B, N)) return 0;
   return grad_layout(nullptr, B, (int)(N < kGradChunk ? N : kGradChunk)).total;
 }
 
@@ -1331,6 +1360,7 @@ int disn_query_grad(const disn_mlp_weights_t* w, const float* pmap, const float*
   if (!mlp_weights_ok(w) || !w->l_w4_point || !pmap || !embedding || !trans_mat || !pts || !grad || !ws || B <= 0 ||
       N <= 0)
     return DISN_E_ARG;
+  if (!points_fit(B, N)) return DISN_E_SHAPE;
   hipStream_t st = (hipStream_t)stream;
   const int chunk = (int)(N < kGradChunk ? N : kGradChunk);
   const GradWs s = grad_layout(ws, B, chunk);
@@ -1399,7 +1429,7 @@ TapsFusedWs taps_fused_layout(void* ws, int B, int N) {
 }  // namespace
 
 size_t disn_query_taps_fused_workspace_bytes(int B, int N) {
-  if (B <= 0 || N <= 0 || (long)B * pad128(N) > kChunk) return 0;
+  if (B <= 0 || N <= 0 || N > kChunk || (long)B * pad128(N) > kChunk) return 0;
   return taps_fused_layout(nullptr, B, pad128(N)).total;
 }
 
@@ -1409,7 +1439,7 @@ int disn_query_taps_fused(const disn_mlp_weights_t* w, const float* const taps[5
   if (!mlp_weights_ok(w) || !w->g_fused || !w->l_feat || !taps_ok(taps) || !embedding || !trans_mat || !pts ||
       !pts_rot || !sdf || !ws || B <= 0 || N <= 0)
     return DISN_E_ARG;
-  if ((long)B * pad128(N) > kChunk) return DISN_E_SHAPE;
+  if (N > kChunk || (long)B * pad128(N) > kChunk) return DISN_E_SHAPE;
   hipStream_t st = (hipStream_t)stream;
   const TapsFusedWs f = taps_fused_layout(ws, B, pad128(N));
   if (f.total > ws_bytes) return DISN_E_WS;
@@ -1433,7 +1463,7 @@ int disn_query_taps_fused(const disn_mlp_weights_t* w, const float* const taps[5
 
 int disn_amax(const float* x, int64_t n, float* out, void* stream) {
   if (!x || !out || n <= 0) return DISN_E_ARG;
-  if (n % 4) return DISN_E_SHAPE;
+  if (n % 4 || !fits_int(n)) return DISN_E_SHAPE;
   DISN_TRY(amax_launch(x, (size_t)n, out, (hipStream_t)stream));
   return 0;
 }
@@ -1470,7 +1500,7 @@ int fused_streams(const disn_mlp_weights_t* w, const float* gbias_b, const float
 }  // namespace
 
 size_t disn_query_fused_workspace_bytes(int B, int64_t N) {
-  if (B <= 0 || N <= 0) return 0;
+  if (B <= 0 || N <= 0 || !points_fit(B, N)) return 0;
   return fused_layout(nullptr, B, N).total;
 }
 
@@ -1480,6 +1510,7 @@ int disn_query_fused(const disn_mlp_weights_t* w, const float* pmap, const float
   if (!fused_ok(w) || !pmap || !pmap_amax || !embedding || !trans_mat || !pts || !pts_rot || !sdf || !ws ||
       B <= 0 || N <= 0)
     return DISN_E_ARG;
+  if (!points_fit(B, N)) return DISN_E_SHAPE;
   hipStream_t st = (hipStream_t)stream;
   const FusedWs f = fused_layout(ws, B, N);
   if (f.total > ws_bytes) return DISN_E_WS;
@@ -1494,7 +1525,7 @@ int disn_query_fused(const disn_mlp_weights_t* w, const float* pmap, const float
 }
 
 size_t disn_query_grid_fused_workspace_bytes(int64_t max_points) {
-  if (max_points <= 0) return 0;
+  if (max_points <= 0 || !points_fit(1, max_points)) return 0;
   return fused_layout(nullptr, 1, max_points).total;
 }
 
@@ -1535,7 +1566,7 @@ ListedWs listed_layout(void* ws, int64_t n) {
 }  // namespace
 
 size_t disn_query_grid_listed_workspace_bytes(int64_t max_points) {
-  if (max_points <= 0) return 0;
+  if (max_points <= 0 || !points_fit(1, max_points)) return 0;
   return listed_layout(nullptr, max_points).total;
 }
 
@@ -1595,6 +1626,7 @@ int disn_gather_taps_pool(const float* const taps[5], int V, const float* trans_
                           const float* pts, int N, float* feat, void* stream) {
   if (!taps_ok(taps) || !trans_mat || !pts || !feat || N <= 0) return DISN_E_ARG;
   DISN_RC(pool_status(V, pool));
+  if (!points_fit(1, N)) return DISN_E_SHAPE;
   DISN_TRY(gather_taps_pool_launch(taps, V, trans_mat, weights, pool == DISN_POOL_MEAN, pts, N, feat,
                                    (hipStream_t)stream));
   return 0;
@@ -1608,7 +1640,7 @@ int disn_pool_embedding(const float* emb, int V, const float* weights, int pool,
 }
 
 size_t disn_query_views_workspace_bytes(int N) {
-  if (N <= 0) return 0;
+  if (N <= 0 || !points_fit(1, N)) return 0;
   return query_layout(nullptr, 1, chunk_for(N), true, false).total;
 }
 
@@ -1618,6 +1650,7 @@ int disn_query_views(const disn_mlp_weights_t* w, const float* const taps[5], in
   if (!mlp_weights_ok(w) || !taps_ok(taps) || !embedding_pooled || !trans_mat || !pts || !sdf || !ws || N <= 0)
     return DISN_E_ARG;
   DISN_RC(pool_status(V, pool));
+  if (!points_fit(1, N)) return DISN_E_SHAPE;
   hipStream_t st = (hipStream_t)stream;
   const int chunk = chunk_for(N);
   const QueryWs q = query_layout(ws, 1, chunk, true, false);

@@ -154,7 +154,8 @@ int disn_assemble_batch(const float* samples, const int64_t* sample_off, int64_t
       !sample_pc_rot || !sdf || !trans_mat || !flags || (rot && !rot_all) || n_obj < 1 || n_view < 1 || B < 1 || S < 1)
     return DISN_E_ARG;
   if (((uintptr_t)samples & 15) || ((uintptr_t)img & 3)) return DISN_E_ARG;   // float4 rows, uchar4 pixels
-  if (B > 65535) return DISN_E_SHAPE;
+  if (B > 65535 || !disn::fits_int(B, S, 3)) return DISN_E_SHAPE;
+  if (!disn::fits_int(n_obj, 2) || !disn::fits_int(n_view, 2)) return DISN_E_SHAPE;   // obj_idx / view_idx are int32
   DISN_TRY(assemble_batch_launch(samples, sample_off, n_obj, img, trans_mat_all, rot_all, n_view, obj_idx, view_idx,
                                  choice, B, S, rot != 0, backcolorwhite != 0, imgs, sample_pc, sample_pc_rot, sdf,
                                  trans_mat, flags, (hipStream_t)stream));

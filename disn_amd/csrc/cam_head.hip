@@ -122,6 +122,7 @@ extern "C" int disn_cam_head(const disn_cam_weights_t* w, const float* embedding
                              int B, float* rotation, float* translation, float* RT, float* trans_mat,
                              void* stream) {
   if (!w || !embedding || !rotation || !translation || !RT || !trans_mat || B <= 0) return DISN_E_ARG;
+  if (!disn::fits_int(B, DISN_EMBED_DIM)) return DISN_E_SHAPE;
   const float* const* p = reinterpret_cast<const float* const*>(w);
   for (size_t i = 0; i < sizeof(disn_cam_weights_t) / sizeof(const float*); ++i)
     if (!p[i]) return DISN_E_ARG;

@@ -391,7 +391,7 @@ CamLossWs cam_loss_layout(void* base, int B, int N) {
 }  // namespace
 
 extern "C" size_t disn_cam_loss_backward_workspace_bytes(int B, int N) {
-  if (B <= 0 || N <= 0) return 0;
+  if (B <= 0 || N <= 0 || !disn::fits_int(B, N, 3) || !disn::fits_int(B, DISN_EMBED_DIM)) return 0;
   return cam_loss_layout(nullptr, B, N).total;
 }
 
@@ -402,6 +402,7 @@ extern "C" int disn_cam_loss_backward(const disn_cam_weights_t* w, const float* 
   if (!w || !embedding || !pts || !RT || !trans_mat || !pred_trans_mat || !losses || !dists || !dRT || !demb ||
       !head_grads || !ws || B <= 0 || N <= 0 || loss_mode < 0 || loss_mode > 3)
     return DISN_E_ARG;
+  if (!disn::fits_int(B, N, 3) || !disn::fits_int(B, DISN_EMBED_DIM)) return DISN_E_SHAPE;
   const float* const* wp = reinterpret_cast<const float* const*>(w);
   for (int i = 0; i < 18; ++i)
     if (!wp[i]) return DISN_E_ARG;

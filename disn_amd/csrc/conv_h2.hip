@@ -942,20 +942,20 @@ hipError_t conv_h2_launch(const float* in, int B, int H, int W, int Cin, const v
 extern "C" {
 
 size_t disn_pack_conv_h2_bytes(int Cin, int Cout) {
-  if (Cin <= 0 || Cout <= 0 || Cin % 64 || Cout % 64) return 0;
+  if (Cin <= 0 || Cout <= 0 || Cin % 64 || Cout % 64 || !disn::fits_int(9, Cin, Cout)) return 0;
   return disn::conv_h2_image_bytes(Cin, Cout);
 }
 
 int disn_pack_conv_h2(const float* w_hwio, int Cin, int Cout, void* image, void* stream) {
   if (!w_hwio || !image || Cin <= 0 || Cout <= 0) return DISN_E_ARG;
-  if (Cin % 64 || Cout % 64) return DISN_E_SHAPE;
+  if (Cin % 64 || Cout % 64 || !disn::fits_int(9, Cin, Cout)) return DISN_E_SHAPE;
   const hipError_t e = disn::conv_h2_pack_launch(w_hwio, Cin, Cout, image, (hipStream_t)stream);
   return e == hipSuccess ? 0 : (int)e;
 }
 
 int disn_conv_h2_gain_span(const void* image, int Cin, int Cout, float* span_log2, void* stream) {
   if (!image || !span_log2 || Cin <= 0 || Cout <= 0 || Cout > 4096) return DISN_E_ARG;
-  if (Cin % 64 || Cout % 64) return DISN_E_SHAPE;
+  if (Cin % 64 || Cout % 64 || !disn::fits_int(9, Cin, Cout)) return DISN_E_SHAPE;
   // the image's tail: inv_sw[Cout], then the column maxima cmax[Cout] the pack measured (what the scales came from)
   float inv[4096];
   hipError_t e = hipMemcpyAsync(inv, static_cast<const unsigned char*>(image) + (size_t)Cin * 9 * Cout * 4 + (size_t)Cout * 4,
@@ -976,6 +976,8 @@ int disn_conv_h2_gain_span(const void* image, int Cin, int Cout, float* span_log
 size_t disn_conv3x3_h2_workspace_bytes(int B) { return B > 0 ? (size_t)B * 512 : 0; }
 
 int disn_conv3x3_h2_plan(int B, int H, int W, int Cin, int Cout, int tiling, int* grid, int* block) {
+  if (B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0) return DISN_E_ARG;
+  if (!disn::conv3x3_fits(B, H, W, Cin, Cout)) return DISN_E_SHAPE;
   const disn::ConvPlan p = disn::conv_h2_plan(B, H, W, Cin, Cout, tiling);
   if (p.form < 0) return DISN_E_SHAPE;
   if (grid) *grid = p.grid;
@@ -987,6 +989,8 @@ int disn_conv3x3_h2(const float* in, int B, int H, int W, int Cin, const void* i
                     int relu, float* out, float* pool_out, float* out_amax, int tiling, void* ws, size_t ws_bytes,
                     void* stream) {
   if (!in || !image || !bias || !out || !ws || B <= 0 || H <= 0 || W <= 0) return DISN_E_ARG;
+  if (Cin <= 0 || Cout <= 0) return DISN_E_ARG;
+  if (!disn::conv3x3_fits(B, H, W, Cin, Cout)) return DISN_E_SHAPE;
   if (disn::conv_h2_plan(B, H, W, Cin, Cout, tiling).form < 0 || (pool_out && ((H | W) & 1))) return DISN_E_SHAPE;
   if (ws_bytes < (size_t)B * 512) return DISN_E_WS;
   hipStream_t st = (hipStream_t)stream;
@@ -1009,6 +1013,7 @@ size_t disn_conv1_1_workspace_bytes(void) { return 256; }
 int disn_conv1_1(const float* in, int B, int H, int W, const float* w_hwio, const float* bias, int relu, float* out,
                  float* out_amax, void* ws, size_t ws_bytes, void* stream) {
   if (!in || !w_hwio || !bias || !out || !ws || B <= 0 || H <= 0 || W <= 0) return DISN_E_ARG;
+  if (!disn::fits_int(B, H, W, 64)) return DISN_E_SHAPE;
   if (ws_bytes < 256) return DISN_E_WS;
   hipStream_t st = (hipStream_t)stream;
   float* slots = static_cast<float*>(ws);

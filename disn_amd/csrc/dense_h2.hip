@@ -264,24 +264,25 @@ hipError_t dense_h2_launch(const DenseH2Prob* probs, int nprob, hipStream_t st) 
 extern "C" {
 
 size_t disn_pack_dense_h2_bytes(int K, int N) {
-  if (K <= 0 || N <= 0 || K % 64 || N % 64) return 0;
+  if (K <= 0 || N <= 0 || K % 64 || N % 64 || !disn::fits_int(K, N)) return 0;
   return disn::h2_image_bytes(K, N, 1);
 }
 
 int disn_pack_dense_h2(const float* w_kn, int K, int N, void* image, void* stream) {
   if (!w_kn || !image || K <= 0 || N <= 0) return DISN_E_ARG;
-  if (K % 64 || N % 64) return DISN_E_SHAPE;
+  if (K % 64 || N % 64 || !disn::fits_int(K, N)) return DISN_E_SHAPE;
   const hipError_t e = disn::conv_h2_pack_launch(w_kn, K, N, image, (hipStream_t)stream, 1);
   return e == hipSuccess ? 0 : (int)e;
 }
 
-size_t disn_dense_h2_workspace_bytes(int images) { return (size_t)(images > 0 ? images : 1) * 1024; }
+size_t disn_dense_h2_workspace_bytes(int images) { return images > 0 ? (size_t)images * 1024 : 0; }
 
 int disn_dense_h2(const float* a1, int lda1, int k1, const float* a2, int lda2, int k2, const float* in_bias, int M,
                   int rows_per_image, const void* image, int image_k, int k_begin, const float* add_in, const float* bias,
                   int N, int relu, float* out, float* out_amax, void* ws, size_t ws_bytes, void* stream) {
   if (!a1 || !image || !bias || !out || !ws || M <= 0 || k1 <= 0 || k2 < 0 || (k2 > 0 && !a2) || rows_per_image < 0)
     return DISN_E_ARG;
+  if (N <= 0 || !disn::dense_fits(M, lda1, k2 > 0 ? lda2 : 0, k1, k2, N)) return DISN_E_SHAPE;
   const int K = k1 + k2;
   if (!disn::dense_h2_supported(M, K, N, k1) || lda1 != k1 || (k2 > 0 && lda2 != k2)) return DISN_E_SHAPE;
   if (image_k < 0 || k_begin < 0 || k_begin % 16 || (image_k > 0 && k_begin + K > image_k) || (image_k == 0 && k_begin)) return DISN_E_SHAPE;

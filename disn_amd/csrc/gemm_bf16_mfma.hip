@@ -542,7 +542,7 @@ extern "C" {
 static size_t bf_packed_bytes(int K, int N) { return (((size_t)3 * K * N * 2) + 255) & ~size_t(255); }
 
 size_t disn_dense_bf16_workspace_bytes(int M, int K, int N) {
-  if (M <= 0 || K <= 0 || N <= 0 || K % 32 || N % 64) return 0;
+  if (M <= 0 || K <= 0 || N <= 0 || K % 32 || N % 64 || !disn::dense_fits(M, K, 0, K, 0, N)) return 0;
   return bf_packed_bytes(K, N) + disn::gemm_bf16_ws_bytes(M, N, K);
 }
 
@@ -551,7 +551,7 @@ int disn_dense_bf16(const float* a1, int lda1, int k1, const float* a2, int lda2
                     size_t ws_bytes, void* stream) {
   if (!a1 || !w_kn || !bias || !out || !ws || M <= 0 || k1 <= 0 || k2 < 0 || (k2 > 0 && !a2)) return DISN_E_ARG;
   if (k1 % 32 || k2 % 32 || N <= 0 || N % 64 || lda1 < k1 || (k2 > 0 && lda2 < k2) || lda1 % 4 ||
-      (k2 > 0 && lda2 % 4))
+      (k2 > 0 && lda2 % 4) || !disn::dense_fits(M, lda1, k2 > 0 ? lda2 : 0, k1, k2, N))
     return DISN_E_SHAPE;
   const int K = k1 + k2;
   if (ws_bytes < disn_dense_bf16_workspace_bytes(M, K, N)) return DISN_E_WS;
@@ -571,6 +571,7 @@ int disn_dense_bf16(const float* a1, int lda1, int k1, const float* a2, int lda2
 // the product form of the three-term path: weights already in disn_pack_kn_x3 order
 size_t disn_conv3x3_x3_workspace_bytes(int B, int H, int W, int Cin, int Cout) {
   if (B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || Cin % 32 || Cout % 64) return 0;
+  if (H >= 32768 || W >= 32768 || !disn::conv3x3_fits(B, H, W, Cin, Cout)) return 0;
   const size_t b = disn::gemm_bf16_ws_bytes(B * H * W, Cout, 9 * Cin);
   return b > 256 ? b : 256;
 }
@@ -579,6 +580,8 @@ int disn_conv3x3_x3(const float* in, int B, int H, int W, int Cin, const void* w
                     int Cout, int relu, float* out, void* ws, size_t ws_bytes, void* stream) {
   if (!in || !w_x3 || !bias || !out || B <= 0 || H <= 0 || W <= 0) return DISN_E_ARG;
   if (Cin <= 0 || Cin % 32 || Cout <= 0 || Cout % 64) return DISN_E_SHAPE;
+  if (H >= 32768 || W >= 32768 || !disn::conv3x3_fits(B, H, W, Cin, Cout)) return DISN_E_SHAPE;
+  if (disn_conv3x3_x3_workspace_bytes(B, H, W, Cin, Cout) > (ws ? ws_bytes : 0)) return DISN_E_WS;
   disn::GemmParams p{};
   p.a1 = in; p.H = H; p.W = W; p.Cin = Cin;
   p.M = B * H * W; p.N = Cout; p.K = 9 * Cin;
@@ -590,6 +593,7 @@ int disn_conv3x3_x3(const float* in, int B, int H, int W, int Cin, const void* w
 
 size_t disn_conv3x3_bf16_workspace_bytes(int B, int H, int W, int Cin, int Cout) {
   if (B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || Cin % 32 || Cout % 64) return 0;
+  if (H >= 32768 || W >= 32768 || !disn::conv3x3_fits(B, H, W, Cin, Cout)) return 0;
   return bf_packed_bytes(9 * Cin, Cout) + disn::gemm_bf16_ws_bytes(B * H * W, Cout, 9 * Cin);
 }
 
@@ -598,6 +602,7 @@ int disn_conv3x3_bf16(const float* in, int B, int H, int W, int Cin, const float
                       size_t ws_bytes, void* stream) {
   if (!in || !w_hwio || !bias || !out || !ws || B <= 0 || H <= 0 || W <= 0) return DISN_E_ARG;
   if (Cin <= 0 || Cin % 32 || Cout <= 0 || Cout % 64) return DISN_E_SHAPE;
+  if (H >= 32768 || W >= 32768 || !disn::conv3x3_fits(B, H, W, Cin, Cout)) return DISN_E_SHAPE;
   if (ws_bytes < disn_conv3x3_bf16_workspace_bytes(B, H, W, Cin, Cout)) return DISN_E_WS;
   hipStream_t st = (hipStream_t)stream;
   hipError_t e = disn::pack_bf16_launch(w_hwio, 0, 9 * Cin, Cout, ws, st, nsplit);

@@ -18,6 +18,33 @@ struct disn_ctx {
 
 namespace disn {
 
+// Sizes beyond an entry's index arithmetic are DISN_E_SHAPE, and 0 from its size query (include/disn_amd.h, Conventions).
+// One rule for every entry, a chosen simplification: rows, elements, K extents and workgroups are counted in int
+// somewhere on the way to most launches (GemmParams, gemm_plan, the grid sizes), so an entry admits a shape only when the
+// element count of EACH operand it names -- one call of fits_int per operand, the product of the factors given -- is at
+// most kMaxCount: an int with room left for a launcher to round the count up to a tile or a block (2^16) in int.  Some
+// kernels index in size_t throughout and could take more; they are held to the same rule.  Formed without overflow.
+constexpr long long kMaxCount = 2147483647LL - 65535;
+inline bool fits_int(long long a, long long b = 1, long long c = 1, long long d = 1) {
+  const long long f[4] = {a, b, c, d};
+  long long p = 1;
+  for (long long x : f) {
+    if (x < 0) return false;
+    if (x > 0 && p > kMaxCount / x) return false;
+    p *= x;
+  }
+  return true;
+}
+inline int max_of(int a, int b) { return a > b ? a : b; }
+// a [M][lda1] | [M][lda2], W [k1 + k2][N], out [M][N] of the dense entries; k1 + k2 is added in 64 bits
+inline bool dense_fits(int M, int lda1, int lda2, int k1, int k2, int N) {
+  return fits_int((long long)k1 + k2, N) && fits_int(M, max_of(max_of(lda1, lda2), N)) && fits_int(M, (long long)k1 + k2);
+}
+// x [B][H][W][Cin], W [3][3][Cin][Cout], out [B][H][W][Cout] of the convolution entries
+inline bool conv3x3_fits(int B, int H, int W, int Cin, int Cout) {
+  return fits_int(B, H, W, max_of(Cin, Cout)) && fits_int(9, Cin, Cout);
+}
+
 // Non-temporal 16-byte access for data that is streamed exactly once (fc weights, optimizer state):
 // measured 4.4 -> 5.7 TB/s on the 411 MB fc6 weight read, and it leaves L2 / MALL to the activations.
 #ifdef __HIPCC__
@@ -168,7 +195,7 @@ struct GridSpec {
 };
 // the (R+1)^3 grid of sdf_params_host = {x0, y0, z0, x1, y1, z1}
 inline bool grid_spec(const double* p, int R, GridSpec* g) {
-  if (!p || R < 1) return false;
+  if (!p || R < 1 || R > (1 << 20)) return false;  // (R+1)^3 points are counted in int64
   g->res = R + 1;
   for (int a = 0; a < 3; ++a) {
     g->start[a] = p[a];

@@ -181,7 +181,7 @@ extern "C" size_t disn_mesh_bvh_bytes(int64_t nf) {
 extern "C" int disn_mesh_bvh_build_order(const float* verts, int64_t nv, const int32_t* faces, int64_t nf,
                                          void* out, size_t out_bytes, int32_t* order) {
   if (!verts || !faces || !out || nv < 1 || nf < 1) return DISN_E_ARG;
-  if (nf > disn::kBvhMaxTris) return DISN_E_SHAPE;
+  if (nf > disn::kBvhMaxTris || nv > INT32_MAX) return DISN_E_SHAPE;   // the faces index the vertices in int32
   if (out_bytes < disn::bvh_bytes(nf)) return DISN_E_WS;
   for (int64_t i = 0; i < 3 * nf; ++i)
     if (faces[i] < 0 || faces[i] >= nv) return DISN_E_ARG;

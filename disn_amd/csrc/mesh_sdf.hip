@@ -459,7 +459,7 @@ extern "C" {
 
 static int mesh_grid_shape(int nx, int ny, int nz) {
   if (nx < 2 || ny < 2 || nz < 2) return DISN_E_ARG;
-  if ((int64_t)nx * ny * nz > INT32_MAX) return DISN_E_SHAPE;  // int32 component labels
+  if (!disn::fits_int(nx, ny, nz)) return DISN_E_SHAPE;  // int32 component labels
   return 0;
 }
 

@@ -33,7 +33,7 @@ constexpr int kEmdMaxWaves = 16;
 constexpr int kCostRows = 16;                   // match rows per match_cost workgroup
 
 inline size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
-inline int cdiv(int a, int b) { return (a + b - 1) / b; }
+inline int cdiv(int a, int b) { return (int)(((long long)a + b - 1) / b); }
 
 struct NnPlan {
   int qblocks, chunk, splits;
@@ -371,14 +371,16 @@ using namespace disn;
 
 extern "C" {
 
-size_t disn_metrics_workspace_bytes(int b, int n, int m) {
-  return (b < 1 || n < 1 || m < 1) ? 0 : metrics_ws_bytes(b, n, m);
-}
-
 static int metrics_shape(int b, int n, int m) {
   if (b < 1 || n < 1 || m < 1) return DISN_E_ARG;
   if (b > 65535) return DISN_E_SHAPE;  // one grid row per pair
+  if (!fits_int(b, n, 3) || !fits_int(b, m, 3)) return DISN_E_SHAPE;  // xyz1 [b,n,3], xyz2 [b,m,3]
   return 0;
+}
+
+size_t disn_metrics_workspace_bytes(int b, int n, int m) {
+  // b > 65535 is the entries' DISN_E_SHAPE, not the query's
+  return (b < 1 || n < 1 || m < 1 || !fits_int(b, n, 3) || !fits_int(b, m, 3)) ? 0 : metrics_ws_bytes(b, n, m);
 }
 
 int disn_nn_distance(const float* xyz1, const float* xyz2, int b, int n, int m, float* dist1, int32_t* idx1,

@@ -254,7 +254,7 @@ EncTrainWs enc_train_layout(Bump& b, int B, size_t extra_fc_ws_bytes) {
     e.pooled[i] = L.pool ? b.take((size_t)B * (L.hw / 2) * (L.hw / 2) * L.cout) : nullptr;
   }
   e.amax = b.take((size_t)27 * B * 64);
-  e.amax_bwd = e.amax + (size_t)14 * B * 64;  // zeroed with the others by the resize launch
+  e.amax_bwd = e.amax ? e.amax + (size_t)14 * B * 64 : nullptr;  // zeroed with the others by the resize launch
   e.resized = b.take((size_t)B * 224 * 224 * 3);
   e.h6 = b.take((size_t)B * 4096); e.h7 = b.take((size_t)B * 4096);
   e.emb = b.take((size_t)B * DISN_EMBED_DIM); e.demb = b.take((size_t)B * DISN_EMBED_DIM);
@@ -557,7 +557,7 @@ int disn_param_layout(disn_param_layout_t* out) {
 
 // ---- building blocks (unit-test / composition surface) -------------------------------
 size_t disn_dense_backward_workspace_bytes(int M, int K, int N) {
-  if (M <= 0 || K <= 0 || N <= 0 || K % 64 || N % 64) return 0;
+  if (M <= 0 || K <= 0 || N <= 0 || K % 64 || N % 64 || !disn::dense_fits(M, K, 0, K, 0, N)) return 0;
   Bump b(nullptr);
   const size_t g = max_sz(max_sz(gemm_plan(M, K, N).ws_bytes, gemm_bf16_ws_bytes(M, K, N)), 256);
   return bwd_layout(b, (size_t)K * N, M, g, colsum_ws_bytes(M, N)).total;
@@ -567,7 +567,7 @@ int disn_dense_backward(const float* a, int lda, int K, const float* w_kn, const
                         int M, int N, float wd, int compute_bf16, float* da, float* dw, float* db,
                         void* ws, size_t ws_bytes, void* stream) {
   if (!a || !w_kn || !dy || !dw || !db || !ws || M <= 0 || K <= 0 || N <= 0) return DISN_E_ARG;
-  if (K % 64 || N % 64 || lda < K || lda % 4) return DISN_E_SHAPE;
+  if (K % 64 || N % 64 || lda < K || lda % 4 || !disn::dense_fits(M, lda, 0, K, 0, N)) return DISN_E_SHAPE;
   if (ws_bytes < disn_dense_backward_workspace_bytes(M, K, N)) return DISN_E_WS;
   hipStream_t st = (hipStream_t)stream;
   Bump b(ws);
@@ -581,7 +581,8 @@ int disn_dense_backward(const float* a, int lda, int K, const float* w_kn, const
 }
 
 size_t disn_conv3x3_backward_workspace_bytes(int B, int H, int W, int Cin, int Cout) {
-  if (B <= 0 || H <= 0 || W <= 0 || Cout <= 0 || Cout % 64 || !(Cin == 3 || Cin % 64 == 0)) return 0;
+  if (B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || Cout % 64 || !(Cin == 3 || Cin % 64 == 0)) return 0;
+  if (!disn::conv3x3_fits(B, H, W, Cin, Cout)) return 0;
   Bump b(nullptr);
   const int M = B * H * W;
   const size_t g = Cin == 3 ? 256
@@ -598,8 +599,9 @@ size_t disn_conv3x3_backward_workspace_bytes(int B, int H, int W, int Cin, int C
 int disn_conv3x3_backward(const float* x, int B, int H, int W, int Cin, const float* w_hwio,
                           const float* y, float* dy, int Cout, float wd, int compute_bf16, float* dx,
                           float* dw, float* db, void* ws, size_t ws_bytes, void* stream) {
-  if (!x || !w_hwio || !dy || !dw || !db || !ws || B <= 0 || H <= 0 || W <= 0) return DISN_E_ARG;
+  if (!x || !w_hwio || !dy || !dw || !db || !ws || B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0) return DISN_E_ARG;
   if (Cout % 64 || !(Cin == 3 || Cin % 64 == 0) || (Cin == 3 && dx)) return DISN_E_SHAPE;
+  if (!disn::conv3x3_fits(B, H, W, Cin, Cout)) return DISN_E_SHAPE;
   if (ws_bytes < disn_conv3x3_backward_workspace_bytes(B, H, W, Cin, Cout)) return DISN_E_WS;
   hipStream_t st = (hipStream_t)stream;
   Bump b(ws);
@@ -628,14 +630,15 @@ int disn_conv3x3_backward(const float* x, int B, int H, int W, int Cin, const fl
 
 int disn_maxpool2x2_backward(const float* x, const float* dy, int B, int H, int W, int C, float* dx,
                              void* stream) {
-  if (!x || !dy || !dx || B <= 0 || H < 2 || W < 2) return DISN_E_ARG;
-  if (C % 4 || H % 2 || W % 2) return DISN_E_SHAPE;
+  if (!x || !dy || !dx || B <= 0 || H < 2 || W < 2 || C <= 0) return DISN_E_ARG;
+  if (C % 4 || H % 2 || W % 2 || !disn::fits_int(B, H, W, C)) return DISN_E_SHAPE;
   DISN_TRY(maxpool_bwd_launch(x, dy, B, H, W, C, dx, (hipStream_t)stream));
   return 0;
 }
 
 size_t disn_resize_bilinear_backward_workspace_bytes(int B, int Hin, int Win, int C, int Hout, int Wout) {
   if (B <= 0 || Hin <= 0 || Win <= 0 || C <= 0 || Hout <= 0 || Wout <= 0) return 0;
+  if (!disn::fits_int(B, Hin, Win, C) || !disn::fits_int(B, Hout, Wout, C)) return 0;
   return resize_bwd_ws_bytes(B, Hin, Win, C, Hout, Wout);
 }
 
@@ -644,8 +647,9 @@ int disn_resize_bilinear_backward(const float* dout, int B, int Hin, int Win, in
                                   size_t ws_bytes, void* stream) {
   if (!dout || !din || B <= 0 || Hin <= 0 || Win <= 0 || C <= 0 || Hout <= 0 || Wout <= 0)
     return DISN_E_ARG;
-  if (C % 4 || out_cstride % 4 || out_coff % 4 || out_coff < 0 || out_coff + C > out_cstride)
+  if (C % 4 || out_cstride % 4 || out_coff % 4 || out_coff < 0 || (long long)out_coff + C > out_cstride)
     return DISN_E_SHAPE;
+  if (!disn::fits_int(B, Hin, Win, C) || !disn::fits_int(B, Hout, Wout, out_cstride)) return DISN_E_SHAPE;
   const size_t need = resize_bwd_ws_bytes(B, Hin, Win, C, Hout, Wout);
   if (need > 0 && (!ws || ws_bytes < need)) return DISN_E_WS;
   DISN_TRY(resize_bwd_launch(dout, B, Hin, Win, C, Hout, Wout, out_cstride, out_coff, din, accumulate,
@@ -656,6 +660,7 @@ int disn_resize_bilinear_backward(const float* dout, int B, int Hin, int Win, in
 int disn_gather_backward(const float* dfeat, const float* xy, int B, int N, float* dfeatmap,
                          void* stream) {
   if (!dfeat || !xy || !dfeatmap || B <= 0 || N <= 0) return DISN_E_ARG;
+  if (!disn::fits_int(B, N, 3) || !disn::fits_int(B, DISN_IMG_H * DISN_IMG_W)) return DISN_E_SHAPE;
   hipStream_t st = (hipStream_t)stream;
   DISN_TRY(hipMemsetAsync(dfeatmap, 0, (size_t)B * 137 * 137 * DISN_FEAT_DIM * sizeof(float), st));
   DISN_TRY(gather_bwd_launch(dfeat, xy, B, N, dfeatmap, st));
@@ -665,7 +670,7 @@ int disn_gather_backward(const float* dfeat, const float* xy, int B, int N, floa
 int disn_adam_update(float* params, const float* grads, float* m, float* v, int64_t n, float lr_t,
                      float beta1, float beta2, float eps, float grad_scale, void* stream) {
   if (!params || !grads || !m || !v || n <= 0) return DISN_E_ARG;
-  if (n % 4) return DISN_E_SHAPE;
+  if (n % 4 || !disn::fits_int(n)) return DISN_E_SHAPE;
   DISN_TRY(adam_launch(params, grads, m, v, (size_t)n, lr_t, beta1, beta2, eps, grad_scale,
                        (hipStream_t)stream));
   return 0;
@@ -858,7 +863,7 @@ int disn_cam_param_layout(disn_cam_param_layout_t* out) {
 }
 
 size_t disn_cam_train_workspace_bytes(int B, int N) {
-  if (B <= 0 || N <= 0 || B > 256) return 0;
+  if (B <= 0 || N <= 0 || B > 256 || !disn::fits_int(B, N, 3)) return 0;
   return cam_train_layout(nullptr, B, N).total;
 }
 
@@ -869,7 +874,7 @@ int disn_cam_train_step(disn_ctx_t* ctx, const float* params, float* grads, cons
   if (!params || !grads || !img || !pts || !RT || !trans_mat || !pred_trans_mat || !losses || !dists || !ws ||
       B <= 0 || N <= 0 || loss_mode < 0 || loss_mode > 3)
     return DISN_E_ARG;
-  if (B > 256) return DISN_E_SHAPE;
+  if (B > 256 || !disn::fits_int(B, N, 3)) return DISN_E_SHAPE;
   const CamTrainWs t = cam_train_layout(ws, B, N);
   if (ws_bytes < t.total) return DISN_E_WS;
   hipStream_t st = (hipStream_t)stream;

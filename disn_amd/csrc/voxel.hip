@@ -427,14 +427,16 @@ static int voxel_axis(int n) { return n < 1 ? DISN_E_ARG : (n > 1024 ? DISN_E_SH
 
 size_t disn_voxel_grid_words(int n) { return voxel_axis(n) ? 0 : voxel_grid_words(n); }
 
-size_t disn_voxel_surface_workspace_bytes(int64_t nf) { return nf < 0 ? 0 : voxel_surface_ws_bytes(nf); }
+size_t disn_voxel_surface_workspace_bytes(int64_t nf) {
+  return (nf < 0 || nf > INT32_MAX) ? 0 : voxel_surface_ws_bytes(nf);
+}
 
 int disn_voxel_surface(const float* verts, int64_t nv, const int32_t* faces, int64_t nf, int dim, int kmin, int nkeys,
                        uint32_t* bits, int32_t* flags, void* ws, size_t ws_bytes, void* stream) {
   if (!bits || !flags || !ws || nv < 0 || nf < 0 || dim < 1) return DISN_E_ARG;
   if (nf > 0 && (!verts || !faces)) return DISN_E_ARG;
   if (int rc = voxel_axis(nkeys)) return rc;
-  if (dim > 1024 || kmin < -4096 || kmin > 4096 || nf > INT32_MAX) return DISN_E_SHAPE;
+  if (dim > 1024 || kmin < -4096 || kmin > 4096 || nf > INT32_MAX || nv > INT32_MAX) return DISN_E_SHAPE;   // int32 faces
   if (ws_bytes < voxel_surface_ws_bytes(nf)) return DISN_E_WS;
   DISN_TRY(voxel_surface_launch(verts, nv, faces, nf, dim, kmin, nkeys, bits, flags, ws, (hipStream_t)stream));
   return 0;

@@ -15,7 +15,13 @@
  *   - `stream` is a hipStream_t passed as void* (NULL = default stream);
  *   - return value: 0 ok; <0 invalid argument (DISN_E_*); >0 a hipError_t.
  *     Nothing throws or aborts.  Entry points are re-entrant per stream and keep
- *     no global mutable state.
+ *     no global mutable state;
+ *   - a size beyond an entry's index arithmetic is DISN_E_SHAPE, and the entry's size
+ *     query returns 0 for it.  One rule for every entry, a chosen simplification: the
+ *     element count of every operand (activations, weights, point sets, also where a
+ *     size is an int64_t) is at most 2^31 - 2^16, an int with room for a launcher to
+ *     round it up to a tile.  Some kernels index in 64 bits and could take more; the
+ *     ABI does not promise it.
  */
 #ifndef DISN_AMD_H
 #define DISN_AMD_H
@@ -179,7 +185,9 @@ size_t disn_vgg16_workspace_bytes(int B);
 /* img: [B,137,137,3] BGR in [0,1] (demo/demo.py:263-264).  Outputs:
  * resized224 [B,224,224,3] ('resized_ref_img'); taps[0..4] = conv1_2
  * [B,224,224,64], conv2_2 [B,112,112,128], conv3_3 [B,56,56,256], conv4_3
- * [B,28,28,512], conv5_3 [B,14,14,512]; embedding [B,num_classes]. */
+ * [B,28,28,512], conv5_3 [B,14,14,512]; embedding [B,num_classes].
+ * resized224 may be NULL: the resized images then stay inside ws (here and in
+ * disn_vgg16_conv_stack, disn_encode, disn_encode_query). */
 int disn_vgg16_forward(const disn_vgg_weights_t* w, const float* img, int B, float* resized224,
                        float* const taps[5], float* embedding, void* ws, size_t ws_bytes,
                        void* stream);
@@ -237,7 +245,8 @@ int disn_fc_t(const float* x, int B, int K, const float* wt_nk, const float* bia
  * a partial product formed earlier: out = act([a1 | a2] . W[k_begin..] + bias + add_in), may alias out.  (How
  * disn_encode_query cuts the 1984-deep local fold2/conv1 into the part whose inputs exist before conv5 and the rest.)
  * image_k = 0: the image has exactly K rows.
- * ws: disn_dense_h2_workspace_bytes(images). */
+ * ws: disn_dense_h2_workspace_bytes(images), images = M / rows_per_image, or 1 when rows_per_image is 0 (the query
+ * returns 0 for images < 1, like every size query for a non-positive size). */
 size_t disn_pack_dense_h2_bytes(int K, int N);
 int disn_pack_dense_h2(const float* w_kn, int K, int N, void* image, void* stream);
 size_t disn_dense_h2_workspace_bytes(int images);
@@ -993,7 +1002,8 @@ int disn_mesh_sign(const void* bvh, int64_t nf, const float* xs, const float* ys
  * reference reads; a ray caster over the BVH above, not Blender).          *
  *   disn_mesh_bvh_build_order  (host) disn_mesh_bvh_build (the same image, *
  *       byte for byte) that also writes order_host [nf] int32: the file-   *
- *       order face stored in triangle slot s of the image.                 *
+ *       order face stored in triangle slot s of the image (order_host NULL: *
+ *       disn_mesh_bvh_build).                                              *
  *   disn_render_views  V views of one mesh in one launch.                  *
  *       cams [V,12] f32 per view: org[3], d0[3], dx[3], dy[3]; the ray of  *
  *       image point (x, y) is org + t * ((d0 + x*dx) + y*dy), scaled so    *

@@ -74,9 +74,20 @@ def head_grad_views(flat):
 @pytest.mark.parametrize("case", ["random", "near_degenerate", "below_eps"])
 @pytest.mark.parametrize("mode", MODES)
 def test_head_losses_and_gradients(case, mode):
+    check_head(case, mode)
+
+
+@pytest.mark.parametrize("mode", MODES)
+def test_head_at_one_image_and_one_point(mode):
+    """B = 1, N = 1: the smallest call disn_cam_loss_backward and disn_cam_head admit, same reference, same bounds"""
+    check_head("random", mode, B=1, N=1)
+
+
+def check_head(case, mode, B=4, N=2048):
     w = head_weights(5, case)
-    emb, pts, RT, tm = head_inputs(7)
-    _, got = run_head(w, emb, pts, RT, tm, mode)
+    emb, pts, RT, tm = head_inputs(7, B=B, N=N)
+    h, got = run_head(w, emb, pts, RT, tm, mode)
+    assert np.array_equal(got["pred_trans_mat"], host(h.run(dev(emb))[3]))       # disn_cam_head on the same embedding
     ref, g, ptm = R.head_loss_and_grads(emb, w, pts, RT, tm, mode)
     for i, n in enumerate(("rotpc_loss", "rot2d_loss", "rotmatrix_loss", "rot2d_dist", "rot3d_dist")):
         assert abs(got["losses"][i] - ref[n]) <= 1e-5 * abs(ref[n]) + 1e-12, (n, got["losses"][i], ref[n])
@@ -133,6 +144,26 @@ def step_case():
     feed = R.synth_feed(21, B, N)
     refs = {m: R.loss_and_grads(feed, weights, m) for m in ("3D", "ALL")}
     return dict(weights=weights, feed=feed, refs=refs, B=B, N=N)
+
+
+@pytest.fixture(scope="module")
+def smallest_step_case():
+    """B = 1, N = 1: the smallest step disn_cam_train_step admits"""
+    weights = cam_weights(11)
+    feed = R.synth_feed(23, 1, 1)
+    return dict(weights=weights, feed=feed, refs={"3D": R.loss_and_grads(feed, weights, "3D")}, B=1, N=1)
+
+
+def test_step_losses_at_one_image_and_one_point(smallest_step_case):
+    s = smallest_step_case
+    ref = s["refs"]["3D"][0]
+    _, tm, losses, dists = run_step(s, "3D", "f32")
+    from disn_amd.train_cam import LOSS_NAMES
+    for i, n in enumerate(LOSS_NAMES):
+        want = mode_total(ref, "3D") if n == "overall_loss" else ref[n]
+        assert abs(losses[i] - want) <= 1e-5 * abs(want) + 1e-9, (n, losses[i], want)     # test_step_losses' bounds
+    report_close("rot3d_dist_all", dists[1], ref["rot3d_dist_all"], atol=0, rtol=1e-5)
+    report_close("pred_trans_mat", tm, s["refs"]["3D"][2], atol=1e-5 * np.abs(tm).max())
 
 
 def run_step(s, mode, precision):

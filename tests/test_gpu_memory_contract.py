@@ -1441,7 +1441,21 @@ EXEMPT.update({name: "workspace size query: host arithmetic" for name in (
     "disn_mesh_sign_workspace_bytes", "disn_voxel_surface_workspace_bytes", "disn_voxel_fill_workspace_bytes",
     "disn_metrics_workspace_bytes", "disn_query_grid_workspace_bytes", "disn_fold_local_workspace_bytes",
     "disn_query_views_workspace_bytes", "disn_query_grid_views_workspace_bytes", "disn_query_grad_workspace_bytes",
-    "disn_mesh_clean_workspace_bytes")})
+    "disn_mesh_clean_workspace_bytes", "disn_mesh_simplify_workspace_bytes", "disn_mesh_colour_workspace_bytes",
+    "disn_mesh_sample_workspace_bytes", "disn_mesh_smooth_workspace_bytes")})
+EXEMPT["disn_write_obj_colours"] = "host file writer: reads host arrays, no device work"
+
+# The launching entries of the mesh modules' own headers (include/disn_amd_{simplify,colour,sample,smooth}.h) run under
+# guards in their own files, not in a scenario here: entry -> file::test.  tests/test_guarded_alloc_host.py checks that
+# the test exists, that the file's NEW tuple lists the entry and that the test asserts set(NEW) <= set(called).
+MESH_MODULE_COVERAGE = {
+    "disn_mesh_simplify_count_batch": "test_gpu_mesh_simplify.py::test_memory_contract_of_the_simplify_entries",
+    "disn_mesh_simplify_emit_batch": "test_gpu_mesh_simplify.py::test_memory_contract_of_the_simplify_entries",
+    "disn_mesh_zbuffer_batch": "test_gpu_mesh_colour.py::test_memory_contract_of_the_colour_entries",
+    "disn_mesh_colour_batch": "test_gpu_mesh_colour.py::test_memory_contract_of_the_colour_entries",
+    "disn_mesh_sample_batch": "test_gpu_mesh_sample.py::test_memory_contract_of_both_entries",
+    "disn_mesh_smooth_batch": "test_gpu_mesh_smooth.py::test_memory_contract_of_the_smooth_entries",
+}
 
 
 # =====================================================================================================================

@@ -172,6 +172,10 @@ def test_null_normals_and_face_idx_are_accepted():
         assert idx is None or np.array_equal(idx, batch[2][:3])
 
 
+# the entries of include/disn_amd_sample.h (tests/test_guarded_alloc_host.py reads this tuple)
+NEW = ("disn_mesh_sample_workspace_bytes", "disn_mesh_sample_batch")
+
+
 def test_memory_contract_of_both_entries():
     """nothing is written outside points, normals, face_idx, status and ws[:workspace_bytes] (every one of them lies
     between guard bands, the workspace exactly as large as disn_mesh_sample_workspace_bytes says), and the result does
@@ -201,7 +205,7 @@ def test_memory_contract_of_both_entries():
             g.check()
             for x, y in zip(packed, batch):
                 assert np.array_equal(_bits(x.cpu().numpy()), _bits(y[some]))
-            assert {"disn_mesh_sample_workspace_bytes", "disn_mesh_sample_batch"} <= set(called)
+            assert set(NEW) <= set(called)
             assert len(g.records) >= 5                                     # four outputs and the workspace, at least
             results[variant] = [t.cpu().numpy() for t in out] + [pts, status]
             assert rc == 0

@@ -90,7 +90,7 @@ def test_approx_match_against_float64(b, n, m):
     _check_match(match, x1, x2)
 
 
-@pytest.mark.parametrize("b,n,m", [(4, 2048, 2048), (2, 2048, 1000), (2, 300, 2048), (1, 7, 5)])
+@pytest.mark.parametrize("b,n,m", [(4, 2048, 2048), (2, 2048, 1000), (2, 300, 2048), (1, 7, 5), (1, 1, 1)])
 def test_fused_emd_equals_match_cost_of_approx_match(b, n, m):
     from disn_amd import metrics
     x1, x2 = _clouds(11 + n + m, b, n, m)

@@ -67,6 +67,19 @@ def test_kernel_equals_the_host_restatement(tree, rot, white):
         assert (np.abs(feed["sample_pc_rot"] - exact) <= 0.5 * bound).all()
 
 
+def test_kernel_at_one_sample_of_one_point(tree):
+    """B = 1, S = 1: the smallest batch disn_assemble_batch admits, against the same host restatement"""
+    _, _, rset = tree
+    plan = R.PlanStream(rset, 1, 1, 1, seed=9).work(0)
+    want = rset.host_batch(plan, rot=False, backcolorwhite=False)
+    feed = {k: _host(v) for k, v in rset.assemble(plan, rot=False, backcolorwhite=False).items()}
+    rset.raise_on_flags()
+    assert feed["sample_pc"].shape == (1, 1, 3) and feed["sdf"].shape == (1, 1, 1)
+    assert np.array_equal(feed["imgs"], want["img"]) and np.array_equal(feed["sample_pc"], want["sdf_pt"])
+    assert np.array_equal(feed["sdf"], want["sdf_val"] - np.float32(0.003))
+    assert np.array_equal(feed["trans_mat"], want["trans_mat"]) and np.array_equal(feed["sample_pc_rot"], want["sdf_pt"])
+
+
 def test_kernel_reads_nothing_outside_the_set(tree):
     """the library's own range check (ResidentSet.assemble refuses such a plan on the host before any launch): an
     index outside its range gives zeros and raises the flag, the other samples are untouched"""

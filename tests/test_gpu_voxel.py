@@ -66,9 +66,12 @@ def _cases():
     yield "mc_sphere", (v.cpu().numpy(), f.cpu().numpy()), 110
     yield "degenerate", _degenerate(), 110
     yield "empty", (np.zeros((4, 3), np.float32), np.zeros((0, 3), np.int32)), 110
+    yield "one_triangle", (np.array([[0.1, 0.2, 0.3], [0.4, 0.2, 0.3], [0.1, 0.5, 0.35]], np.float32),
+                           np.array([[0, 1, 2]], np.int32)), 110        # nv = 3, nf = 1: the smallest soup with a face
 
 
-@pytest.mark.parametrize("case", ["soup", "soup_dim64", "cube_27.2", "cube_20.2", "mc_sphere", "degenerate", "empty"])
+@pytest.mark.parametrize("case", ["soup", "soup_dim64", "cube_27.2", "cube_20.2", "mc_sphere", "degenerate", "empty",
+                                  "one_triangle"])
 def test_bits_equal_the_restatement(case):
     from disn_amd import voxel
     (v, f), dim = next((m, d) for n, m, d in _cases() if n == case)

@@ -1,6 +1,9 @@
 """The guard-band helper (tests/guarded_alloc.py) on CPU tensors, and the header coverage of the memory-contract table
-(tests/test_gpu_memory_contract.py): every entry of include/disn_amd.h is either run under guards by a scenario or
-exempt because it writes no device memory and launches nothing."""
+(tests/test_gpu_memory_contract.py): every entry of every header under include/ is either run under guards -- by a
+scenario, or for the mesh modules' own headers by the test their file names -- or exempt because it writes no device
+memory and launches nothing."""
+import ast
+import glob
 import os
 import re
 
@@ -180,23 +183,54 @@ def test_recording_notes_the_entries_called_and_restores_the_handle():
 EXEMPT_ALLOWED = re.compile(
     r"^disn_(abi_version|\w+_bytes|\w+_words|\w+_plan|\w*_?layout|param_layout"
     r"|stream_create|stream_destroy|ctx_create|ctx_destroy|ctx_pipeline"
-    r"|write_obj|write_obj_normals|read_obj_verts|read_obj_mesh|mesh_bvh_build|mesh_bvh_build_order)$")
+    r"|write_obj|write_obj_normals|write_obj_colours|read_obj_verts|read_obj_mesh|mesh_bvh_build|mesh_bvh_build_order)$")
+
+
+DECLARED = 162            # the functions the five headers declare today: a floor, so that a parse that misses some fails
 
 
 def header_entries():
-    text = open(os.path.join(ROOT, "include", "disn_amd.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    text = re.sub(r"//[^\n]*", "", text)
-    return re.findall(r"\b(disn_\w+)\s*\(", text)
+    """the functions of every include/*.h"""
+    out = []
+    for path in sorted(glob.glob(os.path.join(ROOT, "include", "*.h"))):
+        text = open(path).read()
+        text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+        text = re.sub(r"//[^\n]*", "", text)
+        out += re.findall(r"\b(disn_\w+)\s*\(", text)
+    return out
+
+
+def covered_in_its_own_file(entry, where):
+    """`where` = file::test names a test of tests/ that asserts set(NEW) <= set(called), and that file's NEW lists `entry`"""
+    fname, test = where.split("::")
+    src = open(os.path.join(ROOT, "tests", fname)).read()
+    tree = ast.parse(src)
+    new = [n for n in tree.body if isinstance(n, ast.Assign) and [t.id for t in n.targets if isinstance(t, ast.Name)] == ["NEW"]]
+    assert len(new) == 1, "%s: one module-level NEW tuple" % fname
+    assert entry in ast.literal_eval(new[0].value), "%s: NEW does not list %s" % (fname, entry)
+    fn = [n for n in tree.body if isinstance(n, ast.FunctionDef) and n.name == test]
+    assert len(fn) == 1, "%s has no test %s" % (fname, test)
+    body = ast.get_source_segment(src, fn[0])
+    assert "set(NEW) <= set(called)" in body and "guarded(" in body and ".recording()" in body, where
+    gpu = "pytestmark = pytest.mark.gpu" in src or any("gpu" in ast.get_source_segment(src, d) for d in fn[0].decorator_list)
+    assert gpu, "%s is not a gpu test" % where
 
 
 def test_every_header_entry_is_covered_exactly_once():
     import test_gpu_memory_contract as T
     from disn_amd import _lib
     declared = header_entries()
-    assert len(declared) == len(set(declared)) >= 149 and set(declared) == set(_lib.SIGNATURES)
+    tables = (_lib.SIGNATURES, _lib.SIGNATURES_SIMPLIFY, _lib.SIGNATURES_COLOUR, _lib.SIGNATURES_SAMPLE,
+              _lib.SIGNATURES_SMOOTH)
+    bound = [name for t in tables for name in t]
+    assert len(bound) == len(set(bound))
+    assert len(declared) == len(set(declared)) >= DECLARED and set(declared) == set(bound)
+    assert len(glob.glob(os.path.join(ROOT, "include", "*.h"))) == len(tables)       # a sixth header brings its table
     claimed = [e for entries in T.ENTRY_COVERAGE.values() for e in entries]
-    listed = claimed + list(T.EXEMPT)
+    listed = claimed + list(T.EXEMPT) + list(T.MESH_MODULE_COVERAGE)
+    for entry, where in T.MESH_MODULE_COVERAGE.items():
+        assert entry not in _lib.SIGNATURES, "%s belongs to include/disn_amd.h: it needs a scenario" % entry
+        covered_in_its_own_file(entry, where)
     twice = sorted({e for e in listed if listed.count(e) > 1})
     assert not twice, "listed more than once: %s" % twice
     assert not sorted(set(listed) - set(declared)), "not in the header: %s" % sorted(set(listed) - set(declared))
