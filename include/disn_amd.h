@@ -276,7 +276,23 @@ int disn_dense(const float* a1, int lda1, int k1, const float* a2, int lda2, int
 int disn_build_featmap(const float* const taps[5], int B, float* featmap, void* stream);
 
 /* Row D: get_img_points -- models/model_normalization.py:241-251.
- * pts [B,N,3], trans_mat [B,4,3] -> xy [B,N,2], clamped to [0,136]. */
+ * pts [B,N,3], trans_mat [B,4,3] -> xy [B,N,2], clamped to [0,136].
+ *
+ * THE CORNER RULE, stated once.  Every kernel that projects a point and
+ * resamples a map at it (the gathers from the map, from the taps and from the
+ * folded map, the pooled multi-view gather, the fused point-MLP kernels, the
+ * gradient seed, the gather's backward) carries its own copy of it:
+ *   p = ((x T0 + y T1) + z T2) + T3, xy = p[0..1] / p[2], each clamped to
+ *   [0,136], a NaN quotient kept NaN;
+ *   the cell is fx = floor(x), its other corner cx = fx + 1 (never ceil: on a
+ *   cell line the weight of cx is zero, not that of fx), pixels outside the
+ *   image read as zero -- so at x = 136 the corner 137 is a zero-weight pixel
+ *   outside, not a repeat of 136;
+ *   out = ((w_ff m_ff + w_cc m_cc) + w_fc m_fc) + w_cf m_cf in that order;
+ *   a coordinate that fails x > -1 && x < 137 (NaN does) gives zeros.
+ * What holds the copies together is tests/test_gpu_resample_lattice.py: every
+ * copy on exact pixel coordinates (cell lines, both clamps, the corners, every
+ * tap-row relation of the resize table, NaN) against the oracle. */
 int disn_project(const float* pts, const float* trans_mat, int B, int N, float* xy, void* stream);
 
 /* Row F: 5 x tf.contrib.resampler.resampler + concat --

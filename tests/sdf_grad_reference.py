@@ -158,7 +158,9 @@ def reference(weights: Dict[str, np.ndarray], imgs: np.ndarray, pts: np.ndarray,
 
 
 def included(ref) -> np.ndarray:
-    """the points a gradient comparison may use: away from every ReLU kink, not clamped, not near a cell line"""
+    """the points a gradient comparison may use: away from every ReLU kink, not clamped, not near a cell line
+    (ON a line and on a clamp the convention is tested by test_gpu_resample_lattice.py::test_query_grad, whose camera
+    makes float32 and float64 agree on the cell)"""
     return (ref["margin"] >= MARGIN) & ~ref["clamped"] & ~ref["near_line"]
 
 
