@@ -7,7 +7,10 @@
 // (Real-Time Collision Detection §5.1.5) with every division guarded (a zero denominator gives 0), a
 // degenerate-interior fall-back to the three edges, and for slivers (sin^2 of the angle at a <= 2^-20,
 // cross = (ay*bz - az*by, az*bx - ax*bz, ax*by - ay*bx)) the minimum with the three edge distances, so that
-// sliver, collinear and repeated-vertex triangles give finite, accurate values.  dot(a, b) = (ax*bx + ay*by) + az*bz,
+// sliver, collinear and repeated-vertex triangles give finite, accurate values.  In the face region a point with
+// n . (p - a) == 0 (n = cross, fp32) lies in the face: d2 = 0 exactly, so a point on a vertex or in the face has
+// u == 0 whatever vb / s and vc / s round to (an edge point: when its parameter is exact); p is then inside the leaf's
+// inflated box, so the walk below keeps the leaf (tests/test_gpu_geometry_lattice.py).  dot(a, b) = (ax*bx + ay*by) + az*bz,
 // d2 = (dx*dx + dy*dy) + dz*dz, one correctly rounded sqrtf of the minimum (HIP's default fp32 sqrt lowering: correctly rounded, not v_sqrt_f32 alone).
 // The BVH walk is stackless (depth-first node order + escape links, mesh_bvh.hpp): one greedy descent to the
 // nearer child seeds the bound, then the full walk prunes a box when box_d2 > best * (1 + 2^-18).  Boxes are
@@ -63,7 +66,7 @@ __device__ __forceinline__ V3 cross(V3 a, V3 b) {
   return V3{a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x};
 }
 
-__device__ float ericson_d2(V3 p, V3 a, V3 b, V3 c, V3 ab, V3 ac) {
+__device__ float ericson_d2(V3 p, V3 a, V3 b, V3 c, V3 ab, V3 ac, V3 n) {
   const V3 ap = sub(p, a);
   const float d1 = dot(ab, ap), d2 = dot(ac, ap);
   if (d1 <= 0.0f && d2 <= 0.0f) return dist2(p, a);
@@ -91,6 +94,7 @@ __device__ float ericson_d2(V3 p, V3 a, V3 b, V3 c, V3 ab, V3 ac) {
   }
   const float s = (va + vb) + vc;
   if (va >= 0.0f && vb >= 0.0f && vc >= 0.0f && s > 0.0f) {
+    if (dot(n, ap) == 0.0f) return 0.0f;   // in the face's plane, foot in the face: ON the triangle (vb / s may round)
     const float v = vb / s, w = vc / s;
     return dist2(p, axpy(axpy(a, v, ab), w, ac));
   }
@@ -103,7 +107,7 @@ __device__ float tri_d2(V3 p, const float* __restrict__ t) {
   const V3 a = ld3(t), b = ld3(t + 3), c = ld3(t + 6);
   const V3 ab = sub(b, a), ac = sub(c, a);
   const V3 n = cross(ab, ac);
-  const float d = ericson_d2(p, a, b, c, ab, ac);
+  const float d = ericson_d2(p, a, b, c, ab, ac, n);
   if (dot(n, n) > 0x1p-20f * (dot(ab, ab) * dot(ac, ac))) return d;
   return fminf(d, fminf(fminf(seg_d2(p, a, b), seg_d2(p, b, c)), seg_d2(p, c, a)));
 }

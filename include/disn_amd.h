@@ -988,7 +988,9 @@ int64_t disn_read_obj_verts(const char* path, float* verts_host, int64_t cap);
  *       nf triangles into a HOST buffer (private format); copy the buffer  *
  *       to the device as it is and pass it with the same nf below.         *
  *   disn_mesh_udf_points  dist[n] = min over triangles of |p - T| for the  *
- *       points [n,3] (fp32, bit-identical to the brute = 1 loop).          *
+ *       points [n,3] (fp32, bit-identical to the brute = 1 loop).  A point *
+ *       on a vertex, or over the face with fp32 n.(p - a) == 0, has        *
+ *       dist == 0 exactly; on an edge, when its fp32 parameter is exact.   *
  *   disn_mesh_udf_grid  the same at the nodes (xs[ix], ys[iy], zs[iz]),    *
  *       dist[(iz*ny + iy)*nx + ix] (the .dist order, x fastest).           *
  *   disn_mesh_sign  sdf = (outside ? u : -u) - offset on that grid, u from *

@@ -2,7 +2,7 @@
 the rules in csrc/mesh_sdf.hip and DESIGN §4p:
 
 tri_d2 / udf   float32, the kernel's operation order: Ericson's region-based closest point with guarded divisions
-               and the three-edge fall-back, the minimum with the edges for slivers, dot = (ax*bx + ay*by) + az*bz, d2 = (dx*dx + dy*dy) + dz*dz, one
+               (in the face region n . (p - a) == 0 gives 0: a point on the face has u == 0) and the three-edge fall-back, the minimum with the edges for slivers, dot = (ax*bx + ay*by) + az*bz, d2 = (dx*dx + dy*dy) + dz*dz, one
                sqrt of the minimum.  Bit-identical to the kernel.
 crossing_bits  float64 edge/triangle crossing from the float32 inputs, same operation order as the kernel.
 flood          the sign rule on given u and crossing arrays: far flood of {u >= tau} from the box boundary
@@ -56,6 +56,9 @@ def tri_d2(p, tris):
         va = d3 * d6 - d5 * d4
         e1, e2 = d4 - d3, d5 - d6
         s = (va + vb) + vc
+        n = np.stack([ab[..., 1] * ac[..., 2] - ab[..., 2] * ac[..., 1], ab[..., 2] * ac[..., 0] - ab[..., 0] * ac[..., 2],
+                      ab[..., 0] * ac[..., 1] - ab[..., 1] * ac[..., 0]], -1)
+        in_plane = np.broadcast_to(_dot(n, ap) == 0, s.shape)
         cases = [
             ((d1 <= 0) & (d2 <= 0), lambda: _d2(p, a)),
             ((d3 >= 0) & (d4 <= d3), lambda: _d2(p, b)),
@@ -64,7 +67,7 @@ def tri_d2(p, tris):
             ((vb <= 0) & (d2 >= 0) & (d6 <= 0), lambda: _d2(p, a + _safe_div(d2, d2 - d6)[..., None] * ac)),
             ((va <= 0) & (e1 >= 0) & (e2 >= 0), lambda: _d2(p, b + _safe_div(e1, e1 + e2)[..., None] * (c - b))),
             ((va >= 0) & (vb >= 0) & (vc >= 0) & (s > 0),
-             lambda: _d2(p, (a + (vb / s)[..., None] * ab) + (vc / s)[..., None] * ac)),
+             lambda: np.where(in_plane, f32(0), _d2(p, (a + (vb / s)[..., None] * ab) + (vc / s)[..., None] * ac))),
         ]
         edges = np.minimum(np.minimum(_seg_d2(p, a, b), _seg_d2(p, b, c)), _seg_d2(p, c, a))
         out = edges
@@ -74,8 +77,6 @@ def tri_d2(p, tris):
             if take.any():
                 out = np.where(take, val(), out)
             done |= cond
-        n = np.stack([ab[..., 1] * ac[..., 2] - ab[..., 2] * ac[..., 1], ab[..., 2] * ac[..., 0] - ab[..., 0] * ac[..., 2],
-                      ab[..., 0] * ac[..., 1] - ab[..., 1] * ac[..., 0]], -1)
         sliver = ~(_dot(n, n) > f32(2.0 ** -20) * (_dot(ab, ab) * _dot(ac, ac)))
         out = np.where(sliver, np.minimum(out, edges), out)
     return out.astype(f32)
