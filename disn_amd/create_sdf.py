@@ -485,19 +485,65 @@ def score_group(meshes, keys, score, seed: int = 0, cache: Optional[dict] = None
     return rows
 
 
+def dc_args(mesher: str = "mc", dc=None) -> Optional[dict]:
+    """``mesher`` = "mc" (marching cubes, the default) or "dc" (dual contouring, ``isosurface.dual_contour_batch``);
+    ``dc`` = None, a regulariser REG, or a dict with any of ``normals`` ("network": the network's unit gradients at the
+    Hermite points, the default; "grid": the grid's finite differences) and ``reg`` (0 < reg <= 1, default 2^-10 --
+    the constant of the simplification, NOT measured on a trained network's normals).  -> None for "mc", else the
+    checked dict (ValueError; no device work): what ``reconstruct*`` and ``--mesher`` take"""
+    if mesher not in ("mc", "dc"):
+        raise ValueError("--mesher must be mc or dc, got %r" % (mesher,))
+    if mesher == "mc":
+        if dc is not None:
+            raise ValueError("--dc_normals / --dc_reg need --mesher dc")
+        return None
+    from .isosurface import DC_REG
+    d = {"normals": "network", "reg": DC_REG}
+    if isinstance(dc, dict):
+        if set(dc) - set(d):
+            raise ValueError("dc: unknown keys %s" % sorted(set(dc) - set(d)))
+        d.update({k: v for k, v in dc.items() if v is not None})
+    elif dc is not None:
+        d["reg"] = dc
+    if d["normals"] not in ("network", "grid"):
+        raise ValueError("--dc_normals must be network or grid, got %r" % (d["normals"],))
+    d["reg"] = float(d["reg"])
+    if not (0.0 < d["reg"] <= 1.0):
+        raise ValueError("--dc_reg must be in (0, 1], got %r" % (d["reg"],))
+    return d
+
+
+def mesh_group(grids, sp, sdf_res: int, iso: float, dc=None, engine=None, enc=None, trans_mats=None):
+    """the group's grids [B,(res+1)^3] -> B x (verts, faces): ``isosurface.marching_cubes_batch`` (``dc`` None), or
+    ``isosurface.dual_contour_batch`` with the checked ``dc`` of ``dc_args``: the normals of view b are the network's
+    unit gradients at its Hermite points from the view's cached folded map (``SdfEngine.refine_vertices(iters=0)``),
+    or -- ``normals`` = "grid", or no ``enc`` (the fused route has no gradient entry) -- the grid normals"""
+    from . import isosurface
+    if dc is None:
+        return isosurface.marching_cubes_batch(grids, sp, sdf_res, iso)
+    fn = None
+    if dc["normals"] == "network" and enc is not None:
+        def fn(b, points):
+            return engine.refine_vertices(enc, b, trans_mats, points, iso=iso, iters=0)[1]
+    return isosurface.dual_contour_batch(grids, sp, sdf_res, iso, fn, dc["reg"])
+
+
 def reconstruct(engine, imgs, trans_mats, sdf_params, sdf_res: int, iso: float = 0.0, refine: int = 0,
-                normals: bool = False, band=None, clean=None, simplify=None, colour=None, alpha=None, smooth=None):
+                normals: bool = False, band=None, clean=None, simplify=None, colour=None, alpha=None, smooth=None,
+                mesher: str = "mc", dc=None):
     """``reconstruct_select`` for callers that clean every mesh or none (see there); -> the meshes"""
     more = {} if colour is None or colour is False else {"colour": colour, "alpha": alpha}
     if smooth is not None:
         more["smooth"] = smooth
+    if mesher != "mc" or dc is not None:
+        more.update(mesher=mesher, dc=dc)
     return reconstruct_select(engine, imgs, trans_mats, sdf_params, sdf_res, iso, refine, normals, band, clean,
                               simplify=simplify, **more)[0]
 
 
 def reconstruct_select(engine, imgs, trans_mats, sdf_params, sdf_res: int, iso: float = 0.0, refine: int = 0,
                        normals: bool = False, band=None, clean=None, select=None, strict: bool = True,
-                       simplify=None, colour=None, alpha=None, smooth=None):
+                       simplify=None, colour=None, alpha=None, smooth=None, mesher: str = "mc", dc=None):
     """images -> meshes for one group of views: one ``engine.encode`` call, the per-image grids of
     ``create_sdf`` in one [B,(res+1)^3] tensor, ONE batched meshing (one host sync for the group).
     -> B x (verts [nv,3] float32, faces [nf,3] int32) device views; the bits are those of ``create_sdf``
@@ -525,6 +571,10 @@ def reconstruct_select(engine, imgs, trans_mats, sdf_params, sdf_res: int, iso: 
     (``colour_group``; ``alpha`` None or [B,137,137] uint8 masks the background) and gains ``colours`` uint8 [nv,3] as
     its last element: (verts, faces[, normals], colours).  Vertices, faces and normals are bit for bit those of the
     call without it; the bytes are those of ``postprocess.colour_arrays`` on the final mesh.
+    ``mesher`` = "dc" (``dc``: see ``dc_args``): the grids, dense or banded, go through dual contouring instead of
+    marching cubes (``mesh_group``: one vertex per crossed cell placed by a quadric from the network's gradients at
+    the cut edges, so creases survive; the mesh can be non-manifold where a cell holds several sheets); every later
+    stage sees a (verts, faces) pair as before.  The bits are those of ``isosurface.dual_contour_batch`` on the grids.
     -> (meshes, unclean [B] bool)"""
     from . import isosurface
     band = band_args(band, sdf_res)
@@ -532,12 +582,13 @@ def reconstruct_select(engine, imgs, trans_mats, sdf_params, sdf_res: int, iso: 
     simplify = simplify_args(simplify)
     colour = colour_args(colour)
     smooth = smooth_args(smooth)
+    dc = dc_args(mesher, dc)
     if band is None:
         enc, grids = _encode_grids(engine, imgs, trans_mats, sdf_params, sdf_res)
     else:
         enc, grids, _ = _encode_grids_band(engine, imgs, trans_mats, sdf_params, sdf_res, iso, band)
     sp = np.asarray(sdf_params, dtype=np.float64).reshape(grids.shape[0], 6)
-    meshes, unclean = clean_group(isosurface.marching_cubes_batch(grids, sp, sdf_res, iso), clean, select, strict)
+    meshes, unclean = clean_group(mesh_group(grids, sp, sdf_res, iso, dc, engine, enc, trans_mats), clean, select, strict)
     meshes = simplify_group(meshes, simplify, sp)
     if smooth is not None:
         meshes = smooth_group(meshes, smooth, sp, sdf_res)
@@ -566,18 +617,21 @@ def fuse_args(fuse, pool: str = "max") -> Optional[Tuple[int, str]]:
 
 
 def reconstruct_fused(engine, imgs, trans_mats, sdf_params, sdf_res: int, iso: float = 0.0, fuse: int = 2,
-                      pool: str = "max", clean=None, simplify=None, colour=None, alpha=None, smooth=None):
+                      pool: str = "max", clean=None, simplify=None, colour=None, alpha=None, smooth=None,
+                      mesher: str = "mc", dc=None):
     """``reconstruct_fused_select`` for callers that clean every mesh or none (see there); -> the meshes"""
     more = {} if colour is None or colour is False else {"colour": colour, "alpha": alpha}
     if smooth is not None:
         more["smooth"] = smooth
+    if mesher != "mc" or dc is not None:
+        more.update(mesher=mesher, dc=dc)
     return reconstruct_fused_select(engine, imgs, trans_mats, sdf_params, sdf_res, iso, fuse, pool, clean,
                                     simplify=simplify, **more)[0]
 
 
 def reconstruct_fused_select(engine, imgs, trans_mats, sdf_params, sdf_res: int, iso: float = 0.0, fuse: int = 2,
                              pool: str = "max", clean=None, select=None, strict: bool = True, simplify=None,
-                             colour=None, alpha=None, smooth=None):
+                             colour=None, alpha=None, smooth=None, mesher: str = "mc", dc=None):
     """multi-view ``reconstruct``: the B images are B / ``fuse`` runs of ``fuse`` consecutive views of one object each
     (cameras trans_mats [B,4,3] in the object's frame, the run's grid box = its first view's sdf_params).  One
     ``engine.encode`` call, one ``engine.query_grid_views`` grid per run (features pooled over the run's views,
@@ -586,6 +640,7 @@ def reconstruct_fused_select(engine, imgs, trans_mats, sdf_params, sdf_res: int,
     entry per RUN), ``strict``, ``simplify`` (on the lattice of the run's box) and ``smooth`` (the cap in cells of the
     run's box) as in ``reconstruct_select``;
     ``colour``: every run's mesh is coloured from ALL ``fuse`` views of the run (``alpha`` None or [B,137,137]).
+    ``mesher`` = "dc": dual contouring with the GRID normals whatever ``dc`` asks for (this route has no gradient entry).
     -> (meshes, unclean [B / fuse] bool)"""
     import torch
 
@@ -598,6 +653,7 @@ def reconstruct_fused_select(engine, imgs, trans_mats, sdf_params, sdf_res: int,
     simplify = simplify_args(simplify)
     colour = colour_args(colour)
     smooth = smooth_args(smooth)
+    dc = dc_args(mesher, dc)
     imgs = np.asarray(imgs, np.float32) if not isinstance(imgs, torch.Tensor) else imgs
     B = imgs.shape[0]
     if B % V:
@@ -609,7 +665,7 @@ def reconstruct_fused_select(engine, imgs, trans_mats, sdf_params, sdf_res: int,
     grids = torch.empty((B // V, (sdf_res + 1) ** 3), dtype=torch.float32, device=engine.device)
     for r in range(B // V):
         engine.query_grid_views(enc, (r * V, V), tm[r * V:(r + 1) * V], sp[r], sdf_res, pool, out=grids[r])
-    meshes, unclean = clean_group(isosurface.marching_cubes_batch(grids, sp, sdf_res, iso), clean, select, strict)
+    meshes, unclean = clean_group(mesh_group(grids, sp, sdf_res, iso, dc), clean, select, strict)
     meshes = simplify_group(meshes, simplify, sp)
     if smooth is not None:
         meshes = smooth_group(meshes, smooth, sp, sdf_res)
@@ -662,14 +718,16 @@ def groups(entries: Sequence, batch_size: int) -> List[List]:
 
 
 def result_obj_path(log_dir: str, sdf_res: int, iso: float, cam_est: bool = False, fuse=None,
-                    clean: bool = False, simplify=None, colour: bool = False, smooth=None) -> str:
+                    clean: bool = False, simplify=None, colour: bool = False, smooth=None, mesher: str = "mc") -> str:
     """test/create_sdf.py:88-93: <log_dir>/test_objs/[camest_]<res+1>_<str(iso)>; ``fuse`` = (V, pool): the fused
     meshes' own directory [camest_]fuse<V><pool>_<res+1>_<str(iso)>; ``clean``: the tree with the cleaned categories,
     <...>_comb (the name INTEGRATION 3e gives the combined tree); ``simplify`` = CELLS: the simplified meshes' tree,
     <...>[_comb]_s<CELLS>; ``colour``: the coloured meshes' tree, <...>[_comb][_s<CELLS>]_col; ``smooth`` = ITERS: the
-    smoothed meshes' tree, _t<ITERS> between _comb and _s<CELLS>: <...>[_comb]_t<ITERS>[_s<CELLS>][_col]"""
+    smoothed meshes' tree, _t<ITERS> between _comb and _s<CELLS>: <...>[_comb]_t<ITERS>[_s<CELLS>][_col];
+    ``mesher`` = "dc": the dual-contoured meshes' tree, _dc directly behind <res+1>_<str(iso)>"""
     prefix = ("camest_" if cam_est else "") + ("fuse%d%s_" % tuple(fuse) if fuse else "")
-    return os.path.join(log_dir, "test_objs", prefix + str(sdf_res + 1) + "_" + str(iso) + ("_comb" if clean else "")
+    return os.path.join(log_dir, "test_objs", prefix + str(sdf_res + 1) + "_" + str(iso)
+                        + ("_dc" if mesher == "dc" else "") + ("_comb" if clean else "")
                         + ("_t%d" % smooth if smooth is not None else "")
                         + ("_s%d" % simplify if simplify is not None else "") + ("_col" if colour else ""))
 
@@ -731,7 +789,28 @@ def parser():
     add_smooth_flags(p)
     add_colour_flags(p)
     add_score_flags(p)
+    add_dc_flags(p)
     return p
+
+
+def add_dc_flags(p) -> None:
+    p.add_argument("--mesher", default="mc", choices=("mc", "dc"),
+                   help="mc: marching cubes; dc: dual contouring from Hermite data (one vertex per crossed cell, placed "
+                        "by a quadric: keeps creases; can be non-manifold where a cell holds several sheets); results "
+                        "go to <...>_dc [default: mc]")
+    p.add_argument("--dc_normals", default=None, choices=("network", "grid"),
+                   help="with --mesher dc: the network's gradients at the cut edges, or the grid's finite differences "
+                        "(always grid with --fuse_views) [default: network]")
+    p.add_argument("--dc_reg", type=float, default=None, metavar="REG",
+                   help="with --mesher dc: the pull towards the mean of a cell's crossings, 0 < REG <= 1 [default: "
+                        "2^-10, the simplification's constant; not measured on a trained network]")
+
+
+def dc_from_flags(a) -> Optional[dict]:
+    """None without --mesher dc (ValueError for --dc_normals / --dc_reg without it), else the checked dict of
+    ``dc_args``"""
+    dc = {"normals": a.dc_normals, "reg": a.dc_reg}
+    return dc_args(a.mesher, None if a.dc_normals is None and a.dc_reg is None else dc)
 
 
 def add_smooth_flags(p) -> None:
@@ -872,6 +951,7 @@ def check_flags(a) -> Optional[Tuple[int, str]]:
     smooth_from_flags(a)
     colour_from_flags(a)
     score_from_flags(a)
+    dc_from_flags(a)
     return fuse_from_flags(a)
 
 
@@ -924,10 +1004,14 @@ def main(argv=None, reconstruct_fn: Optional[Callable] = None) -> dict:
     colour = colour_from_flags(a)
     score = score_from_flags(a)
     smooth = smooth_from_flags(a)
+    dc = dc_from_flags(a)
     more = {} if simplify is None else {"simplify": simplify}     # (without the flag every call below is as it was)
     out_dir = result_obj_path(a.log_dir, a.sdf_res, a.iso, a.cam_est, fuse, clean=cleaning is not None, **more,
                               **({} if colour is None else {"colour": True}),
-                              **({} if smooth is None else {"smooth": smooth["iters"]}))
+                              **({} if smooth is None else {"smooth": smooth["iters"]}),
+                              **({} if dc is None else {"mesher": "dc"}))
+    if dc is not None:
+        more.update(mesher="dc", dc=dc)
     if smooth is not None:
         more["smooth"] = smooth
     if colour is not None:

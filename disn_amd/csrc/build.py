@@ -51,6 +51,7 @@ SOURCES = {
     "mesh_colour.hip": ["-ffp-contract=off"],     # the raster and the samples round as colour_arrays states them
     "mesh_sample.hip": ["-ffp-contract=off"],     # the weights and the points round as sample_surface_arrays states them
     "mesh_smooth.hip": ["-ffp-contract=off"],     # the steps' float64 arithmetic rounds as smooth_arrays states it
+    "dual_contour.hip": ["-ffp-contract=off"],    # the points, the quadric and the solve round as dual_contour_arrays states them
     "batch_assemble.hip": ["-ffp-contract=off"],  # sample_pc_rot in the order its bound is derived for
     "api.hip": [],
     "host_util.cpp": ["-msse4.2"],
@@ -60,7 +61,8 @@ COMMON = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno
 HEADERS = ["kernels.hpp", "tuning.hpp", "h2_common.hpp", "mc_tables.h", "mesh_bvh.hpp", "mesh_batch.hpp",
            os.path.join(ROOT, "include", "disn_amd.h"),
            os.path.join(ROOT, "include", "disn_amd_simplify.h"), os.path.join(ROOT, "include", "disn_amd_colour.h"),
-           os.path.join(ROOT, "include", "disn_amd_sample.h"), os.path.join(ROOT, "include", "disn_amd_smooth.h")]
+           os.path.join(ROOT, "include", "disn_amd_sample.h"), os.path.join(ROOT, "include", "disn_amd_smooth.h"),
+           os.path.join(ROOT, "include", "dc", "disn_amd_dc.h")]
 
 
 def _digest(paths, extra=""):

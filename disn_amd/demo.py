@@ -109,6 +109,8 @@ def parser() -> argparse.ArgumentParser:
     add_simplify_flag(p)
     add_smooth_flags(p)
     add_colour_flags(p)
+    from .create_sdf import add_dc_flags
+    add_dc_flags(p)
     return p
 
 
@@ -152,6 +154,8 @@ def main(argv=None) -> dict:
     simplify = simplify_from_flags(a)
     colour = colour_from_flags(a)
     smooth = smooth_from_flags(a)
+    from .create_sdf import dc_from_flags
+    dc = dc_from_flags(a)
     img = read_image(a.img)
     if img.shape[1:3] != (137, 137):
         raise ValueError("%s is %dx%d; the network reads 137x137 renderings" % (a.img, img.shape[2], img.shape[1]))
@@ -175,6 +179,8 @@ def main(argv=None) -> dict:
         extra["simplify"] = simplify
     if smooth is not None:
         extra["smooth"] = smooth
+    if dc is not None:
+        extra.update(mesher="dc", dc=dc)
     if colour is not None:
         alpha = read_alpha(a.img)                                      # the background of the rendering colours nothing
         extra.update(colour=colour, alpha=None if alpha is None else alpha[None])

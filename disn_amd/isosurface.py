@@ -200,3 +200,309 @@ def create_obj(pred_sdf_val, sdf_params, dir, cat_id, obj_nm, view_id, i, res: O
     verts, faces = marching_cubes(pred_sdf_val, np.asarray(sdf_params, np.float64), res, float(i))
     write_obj(cube_obj_file, verts, faces)
     return cube_obj_file
+
+
+# ---- dual contouring from Hermite data (include/dc/disn_amd_dc.h) ----------------------------------------------
+# cube edge -> (dx, dy, dz) of its lower grid point and its axis: tools/gen_mc_tables.edge_geometry(), the order in
+# which a cell visits its cut edges (csrc/mc_tables.h kMcEdge is the same table)
+DC_CUBE_EDGES = ((0, 0, 0, 0), (1, 0, 0, 1), (0, 1, 0, 0), (0, 0, 0, 1), (0, 0, 1, 0), (1, 0, 1, 1), (0, 1, 1, 0),
+                 (0, 0, 1, 1), (0, 0, 0, 2), (1, 0, 0, 2), (1, 1, 0, 2), (0, 1, 0, 2))
+DC_REG = 2.0 ** -10          # the regulariser ``postprocess.simplify_arrays`` uses; NOT measured on a trained network's normals
+_DC_QUAD = ((-1, -1), (0, -1), (0, 0), (-1, 0))      # (u, v) offsets of the cells q0 .. q3 around an edge
+
+
+def _dc_axes(sdf_params, R: int):
+    """the float32 axis values ``disn_mc_emit`` uses for the box (numpy.linspace in float64, cast)"""
+    p = np.asarray(sdf_params, np.float64).reshape(6)
+    return [np.linspace(p[a], p[a + 3], num=R + 1).astype(np.float32) for a in range(3)]
+
+
+class _DcEdges:
+    """the cut grid edges of one grid in rank order (flat order 3*p + axis), with what every rule below needs"""
+
+    def __init__(self, vol, sdf_params, iso):
+        vol = np.ascontiguousarray(vol, np.float32).reshape(-1)
+        n = int(round(vol.size ** (1.0 / 3.0)))
+        if n < 2 or n * n * n != vol.size:
+            raise ValueError("vol must hold (R+1)^3 values with R >= 1, got %d" % vol.size)
+        self.vol, self.n, self.R = vol, n, n - 1
+        self.iso = np.float32(iso)
+        self.ax = _dc_axes(sdf_params, n - 1)
+        cube = vol.reshape(n, n, n)
+        self.inside = cube < self.iso
+        flags = np.zeros((n, n, n, 3), bool)
+        flags[:, :, :-1, 0] = self.inside[:, :, :-1] != self.inside[:, :, 1:]
+        flags[:, :-1, :, 1] = self.inside[:, :-1, :] != self.inside[:, 1:, :]
+        flags[:-1, :, :, 2] = self.inside[:-1, :, :] != self.inside[1:, :, :]
+        self.flat = flags.reshape(-1)
+        self.eidx = np.cumsum(self.flat, dtype=np.int64) - self.flat          # exclusive scan: an edge's rank
+        act = np.nonzero(self.flat)[0]
+        self.p, self.axis = act // 3, act % 3
+        self.idx = np.stack([self.p % n, (self.p // n) % n, self.p // (n * n)], 1)       # ix, iy, iz
+        self.step = np.array([1, n, n * n])[self.axis]
+        self.v0, self.v1 = vol[self.p], vol[self.p + self.step]
+        with np.errstate(all="ignore"):
+            self.t = ((self.iso - self.v0) / (self.v1 - self.v0)).astype(np.float32)
+        ia = self.idx[np.arange(len(act)), self.axis] if len(act) else np.zeros(0, np.int64)
+        self.c0 = np.zeros(len(act), np.float32)
+        self.c1 = np.zeros(len(act), np.float32)
+        for a in range(3):
+            m = self.axis == a
+            self.c0[m], self.c1[m] = self.ax[a][ia[m]], self.ax[a][ia[m] + 1]
+
+    def points(self) -> np.ndarray:
+        pts = np.stack([self.ax[k][self.idx[:, k]] for k in range(3)], 1).astype(np.float32)
+        with np.errstate(all="ignore"):
+            cut = (self.c0 + (self.t * (self.c1 - self.c0).astype(np.float32)).astype(np.float32)).astype(np.float32)
+        for a in range(3):
+            m = self.axis == a
+            pts[m, a] = cut[m]
+        return pts.reshape(-1, 3)
+
+
+def hermite_points_arrays(vol, sdf_params, iso: float = 0.0) -> np.ndarray:
+    """The Hermite points of a grid on the host: one per cut grid edge, ranked in the flat order 3*p + axis
+    (p = (iz*n + iy)*n + ix, inside = vol < float32(iso)), c0 + t*(c1 - c0) on the cut axis with
+    t = (iso - v0)/(v1 - v0) in float32 -- bit for bit and in order the vertices ``marching_cubes`` gives for the same
+    grid.  ``vol``: (R+1)^3 float32 values in ``.dist`` order -> float32 [ne,3]."""
+    return _DcEdges(vol, sdf_params, iso).points()
+
+
+def grid_normals_arrays(vol, sdf_params, iso: float = 0.0) -> np.ndarray:
+    """The field's finite-difference gradient at the Hermite points, for callers without a network: THE SPECIFICATION
+    of ``disn_dc_grid_normals_batch``.  At the point of an edge of axis a between grid points p0, p1, in float64 from
+    the float32 values: g_a = (v1 - v0)/(c1 - c0); for another axis k, g_k = (1 - t) D_k(p0) + t D_k(p1) with the
+    float32 t of the point and D_k(p) = (vol[p + e_k] - vol[p - e_k]) / (ax_k[i+1] - ax_k[i-1]), the indices clamped
+    to the grid.  Cast to float32, NOT normalised -> float32 [ne,3] in the points' order."""
+    E = _DcEdges(vol, sdf_params, iso)
+    n, R = E.n, E.R
+    vol = E.vol.astype(np.float64)
+    t = E.t.astype(np.float64)
+    g = np.zeros((len(E.p), 3), np.float64)
+    with np.errstate(all="ignore"):
+        for k in range(3):
+            stepk = (1, n, n * n)[k]
+            axk = E.ax[k].astype(np.float64)
+            on = E.axis == k
+            g[on, k] = (E.v1[on].astype(np.float64) - E.v0[on].astype(np.float64)) \
+                / (E.c1[on].astype(np.float64) - E.c0[on].astype(np.float64))
+            off = ~on
+            i = E.idx[off, k]
+            ip, im = np.minimum(i + 1, R), np.maximum(i - 1, 0)
+            den = axk[ip] - axk[im]
+            d = []
+            for pt in (E.p[off], E.p[off] + E.step[off]):
+                d.append((vol[pt + (ip - i) * stepk] - vol[pt - (i - im) * stepk]) / den)
+            g[off, k] = (1.0 - t[off]) * d[0] + t[off] * d[1]
+        return g.astype(np.float32)
+
+
+def dual_contour_arrays(vol, sdf_params, iso, normals, reg: float = DC_REG) -> Tuple[np.ndarray, np.ndarray]:
+    """Dual contouring of one grid from Hermite data, on the host: THE SPECIFICATION of ``dual_contour`` /
+    ``dual_contour_batch`` (same position bits, same integers).  ``vol``: (R+1)^3 float32 in ``.dist`` order,
+    ``normals`` float32 [ne,3]: the field's gradient at ``hermite_points_arrays(vol, sdf_params, iso)``, any length
+    -> (verts float32 [nv,3], faces int32 [nf,3]).
+
+    Cells: a cell of the R^3 cells is active when any of its 12 edges is cut; its vertex id is its rank among the
+    active cells in flat (iz,iy,ix) order.
+    Quadric of a cell, float64, relative to its low corner: d_i = double(point_i) - double(corner); the cut edges in
+    the order of ``DC_CUBE_EDGES``; a row with normal g: s = (gx gx + gy gy) + gz gz; s finite and positive:
+    A += g g^T / s, b -= g (g.d) / s (no square root); otherwise nothing is added to A and b.  Every cut edge counts
+    in the mean m of the d_i.
+    Position: lam = reg tr(A)/3 + 2^-40; x solves (A + lam I) x = lam m - b by the adjugate in the operation order of
+    ``postprocess._simplify_solve``; det <= 0 or x not finite: x = m; x is clipped to the cell
+    [0, double(ax[i+1]) - double(ax[i])] per axis; v = float32(double(corner) + x).  ``reg`` in (0, 1]; the default
+    2^-10 is the constant ``simplify_arrays`` uses -- whether it is the best value on a trained network's normals has
+    NOT been measured.
+    Faces: the cut edges in rank order; an edge of axis a has a quad when its two other indices are in 1..R-1; (u, v)
+    the two axes after a in cyclic order; the cells at (u, v) offsets (-1,-1), (0,-1), (0,0), (-1,0) are q0..q3; split
+    along q0-q2 unless |q1-q3|^2 < |q0-q2|^2 (float64 of the float32 positions, (dx^2+dy^2)+dz^2; equality keeps
+    q0-q2).  Low end of the edge inside: (q0,q1,q2),(q0,q2,q3) or (q0,q1,q3),(q1,q2,q3); otherwise each triangle has
+    its last two indices swapped: the geometric normal points along +grad (``refine_mesh``).  Edges on the grid's
+    boundary leave the surface open there, as marching cubes does.
+    KNOWN LIMITS: in a cell that the surface crosses in more than one sheet one vertex serves both sheets, so the mesh
+    can be non-manifold there; triangles may be degenerate in position, never in index."""
+    reg = float(reg)
+    if not (0.0 < reg <= 1.0):
+        raise ValueError("reg must be in (0, 1], got %r" % (reg,))
+    E = _DcEdges(vol, sdf_params, iso)
+    n, R = E.n, E.R
+    pts = E.points().astype(np.float64)
+    nrm = np.ascontiguousarray(normals, np.float32).reshape(-1, 3).astype(np.float64)
+    if nrm.shape != pts.shape:
+        raise ValueError("normals must be [ne,3] with ne = %d, got %s" % (pts.shape[0], nrm.shape))
+    ins = E.inside
+    cnt8 = np.zeros((R, R, R), np.int32)
+    for dz in (0, 1):
+        for dy in (0, 1):
+            for dx in (0, 1):
+                cnt8 += ins[dz:dz + R, dy:dy + R, dx:dx + R]
+    active = ((cnt8 != 0) & (cnt8 != 8)).reshape(-1)
+    cid = np.cumsum(active, dtype=np.int64) - active
+    cells = np.nonzero(active)[0]
+    cx, cy, cz = cells % R, (cells // R) % R, cells // (R * R)
+    ci = np.stack([cx, cy, cz], 1)
+    corner = np.stack([E.ax[k][ci[:, k]].astype(np.float64) for k in range(3)], 1).reshape(-1, 3)
+    hi = np.stack([E.ax[k][ci[:, k] + 1].astype(np.float64) for k in range(3)], 1).reshape(-1, 3) - corner
+    nc = len(cells)
+    A = {k: np.zeros(nc) for k in ("xx", "xy", "xz", "yy", "yz", "zz")}
+    b = [np.zeros(nc) for _ in range(3)]
+    sm = [np.zeros(nc) for _ in range(3)]
+    cnt = np.zeros(nc)
+    with np.errstate(all="ignore"):
+        for dx, dy, dz, a in DC_CUBE_EDGES:
+            slot = 3 * (((cz + dz) * n + (cy + dy)) * n + (cx + dx)) + a
+            cut = E.flat[slot]
+            r = np.where(cut, E.eidx[slot], 0)
+            if not len(pts):
+                break
+            d = [pts[r, k] - corner[:, k] for k in range(3)]
+            for k in range(3):
+                sm[k] = np.where(cut, sm[k] + d[k], sm[k])
+            cnt = np.where(cut, cnt + 1.0, cnt)
+            gx, gy, gz = nrm[r, 0], nrm[r, 1], nrm[r, 2]
+            s = (gx * gx + gy * gy) + gz * gz
+            ok = cut & np.isfinite(s) & (s > 0.0)
+            gd = (gx * d[0] + gy * d[1]) + gz * d[2]
+            for key, u, v in (("xx", gx, gx), ("xy", gx, gy), ("xz", gx, gz), ("yy", gy, gy), ("yz", gy, gz), ("zz", gz, gz)):
+                A[key] = np.where(ok, A[key] + (u * v) / s, A[key])
+            for k, u in enumerate((gx, gy, gz)):
+                b[k] = np.where(ok, b[k] - (u * gd) / s, b[k])
+        mx, my, mz = sm[0] / cnt, sm[1] / cnt, sm[2] / cnt
+        axx, axy, axz, ayy, ayz, azz = (A[k] for k in ("xx", "xy", "xz", "yy", "yz", "zz"))
+        lam = (((axx + ayy) + azz) * reg) / 3.0 + 9.094947017729282e-13                  # reg tr / 3 + 2^-40
+        m00, m11, m22 = axx + lam, ayy + lam, azz + lam
+        m01, m02, m12 = axy, axz, ayz
+        r0, r1, r2 = lam * mx - b[0], lam * my - b[1], lam * mz - b[2]
+        c00 = m11 * m22 - m12 * m12
+        c01 = m02 * m12 - m01 * m22
+        c02 = m01 * m12 - m02 * m11
+        c11 = m00 * m22 - m02 * m02
+        c12 = m01 * m02 - m00 * m12
+        c22 = m00 * m11 - m01 * m01
+        det = (m00 * c00 + m01 * c01) + m02 * c02
+        x0 = ((c00 * r0 + c01 * r1) + c02 * r2) / det
+        x1 = ((c01 * r0 + c11 * r1) + c12 * r2) / det
+        x2 = ((c02 * r0 + c12 * r1) + c22 * r2) / det
+        ok = (det > 0.0) & np.isfinite(x0) & np.isfinite(x1) & np.isfinite(x2)
+        x = np.where(ok[:, None], np.stack([x0, x1, x2], 1), np.stack([mx, my, mz], 1)).reshape(-1, 3)
+        x = np.where(x < 0.0, 0.0, np.where(x > hi, hi, x))
+        verts = (corner + x).astype(np.float32)
+    # ---- faces: the cut edges with a quad, in rank order
+    u, v = (E.axis + 1) % 3, (E.axis + 2) % 3
+    rows = np.arange(len(E.p))
+    iu, iv = E.idx[rows, u] if len(rows) else rows, E.idx[rows, v] if len(rows) else rows
+    has = (iu >= 1) & (iu <= R - 1) & (iv >= 1) & (iv <= R - 1)
+    sel = np.nonzero(has)[0]
+    if not len(sel):
+        return verts.reshape(-1, 3), np.zeros((0, 3), np.int32)
+    q = []
+    for du, dv in _DC_QUAD:
+        c = E.idx[sel].copy()
+        c[np.arange(len(sel)), u[sel]] += du
+        c[np.arange(len(sel)), v[sel]] += dv
+        q.append(cid[(c[:, 2] * R + c[:, 1]) * R + c[:, 0]])
+    P = [verts[k].astype(np.float64) for k in q]
+    d02, d13 = P[0] - P[2], P[1] - P[3]
+    d02 = (d02[:, 0] * d02[:, 0] + d02[:, 1] * d02[:, 1]) + d02[:, 2] * d02[:, 2]
+    d13 = (d13[:, 0] * d13[:, 0] + d13[:, 1] * d13[:, 1]) + d13[:, 2] * d13[:, 2]
+    other = d13 < d02
+    t1 = np.where(other[:, None], np.stack([q[0], q[1], q[3]], 1), np.stack([q[0], q[1], q[2]], 1))
+    t2 = np.where(other[:, None], np.stack([q[1], q[2], q[3]], 1), np.stack([q[0], q[2], q[3]], 1))
+    tri = np.stack([t1, t2], 1).reshape(-1, 3)
+    flip = np.repeat(~ins.reshape(-1)[E.p[sel]], 2)
+    tri[flip] = tri[flip][:, [0, 2, 1]]
+    return verts.reshape(-1, 3), tri.astype(np.int32)
+
+
+def dual_contour_batch(sdf: torch.Tensor, sdf_params, res: int, iso: float = 0.0, normals_fn=None,
+                       reg: float = DC_REG, ws: Optional[torch.Tensor] = None, max_edge_slots: int = MC_EDGE_SLOTS,
+                       hermite: bool = False) -> List[Tuple[torch.Tensor, ...]]:
+    """sdf: float32 device tensor [B,(res+1)^3], sdf_params [B,6] -> B x (verts [nv,3] float32, faces [nf,3] int32),
+    views of two device tensors; every pair is bit for bit ``dual_contour_arrays`` of that grid with its normals.
+    One count call, ONE device-to-host copy of the [B,3] sizes {ne, nv, nf}, one points call and one emit call for the
+    whole batch (a batch whose 3*B*(res+1)^3 edge slots reach ``max_edge_slots`` is meshed in several such rounds).
+    ``normals_fn(b, points_b)`` -> float32 [ne_b,3] on the device: the field's gradient at grid b's Hermite points
+    (any length; a NaN, infinite or zero row only counts in its cells' means); None: the grid's own finite
+    differences (``grid_normals_arrays``, one more call).  ``reg``: see ``dual_contour_arrays`` (the default is
+    unmeasured on a trained network).  ``hermite``: every item is (verts, faces, points, normals).
+    The mesh can be non-manifold where a cell holds more than one sheet of the surface; triangles may be degenerate in
+    position, never in index; the winding is ``marching_cubes``' (geometric normal along +grad)."""
+    n = res + 1
+    if sdf.dim() != 2 or sdf.shape[1] != n * n * n:
+        raise ValueError("sdf must be [B, (res+1)^3 = %d], got %s" % (n * n * n, tuple(sdf.shape)))
+    reg = float(reg)
+    if not (0.0 < reg <= 1.0):
+        raise ValueError("reg must be in (0, 1], got %r" % (reg,))
+    sdf = ops._chk(sdf, "sdf")
+    B = sdf.shape[0]
+    sp = np.ascontiguousarray(np.asarray(sdf_params, np.float64).reshape(-1, 6))
+    if sp.shape[0] != B:
+        raise ValueError("sdf_params must be [B,6] with B = %d, got %s" % (B, sp.shape))
+    per = (min(int(max_edge_slots), MC_EDGE_SLOTS) - 1) // (3 * n * n * n)      # grids per round
+    if B and (per < 1 or lib().disn_dc_workspace_bytes(1, res) == 0):
+        raise ValueError("unsupported resolution %d" % res)
+    dev = sdf.device
+    h = lib()
+    out: List[Tuple[torch.Tensor, ...]] = []
+    with torch.cuda.device(dev):
+        st = ops._stream()
+        for b0 in range(0, B, max(per, 1)):
+            nb = min(per, B - b0)
+            need = h.disn_dc_workspace_bytes(nb, res)
+            if ws is None or ws.numel() < need:
+                ws = torch.empty(need, dtype=torch.uint8, device=dev)
+            part, boxes = sdf[b0:b0 + nb], sp[b0:b0 + nb]
+            counts = torch.zeros((nb, 3), dtype=torch.int64, device=dev)
+            check("disn_dc_count_batch", h.disn_dc_count_batch(part.data_ptr(), nb, res, float(iso), counts.data_ptr(),
+                                                               ws.data_ptr(), ws.numel(), st))
+            sizes = counts.cpu().numpy()                   # the one host sync of the round: sizes are data dependent
+            ne, nv, nf = (int(sizes[:, k].sum()) for k in range(3))
+            points = torch.empty((ne, 3), dtype=torch.float32, device=dev)
+            verts = torch.empty((nv, 3), dtype=torch.float32, device=dev)
+            faces = torch.empty((nf, 3), dtype=torch.int32, device=dev)
+            e_off = np.concatenate([[0], np.cumsum(sizes[:, 0])]).astype(np.int64)
+            normals = points
+            if ne:
+                check("disn_dc_points_batch", h.disn_dc_points_batch(part.data_ptr(), boxes.ctypes.data, nb, res,
+                                                                     float(iso), points.data_ptr(), ws.data_ptr(),
+                                                                     ws.numel(), st))
+                if normals_fn is None:
+                    normals = torch.empty((ne, 3), dtype=torch.float32, device=dev)
+                    check("disn_dc_grid_normals_batch", h.disn_dc_grid_normals_batch(
+                        part.data_ptr(), boxes.ctypes.data, nb, res, float(iso), normals.data_ptr(), ws.data_ptr(),
+                        ws.numel(), st))
+                else:
+                    rows = []
+                    for k in range(nb):
+                        pk = points[e_off[k]:e_off[k + 1]]
+                        nk = normals_fn(b0 + k, pk) if len(pk) else pk
+                        if nk.shape != pk.shape or nk.dtype != torch.float32 or nk.device != pk.device:
+                            raise ValueError("normals_fn must return float32 %s on %s for grid %d, got %s %s" % (
+                                tuple(pk.shape), dev, b0 + k, nk.dtype, tuple(nk.shape)))
+                        rows.append(nk)
+                    normals = rows[0].contiguous() if nb == 1 else torch.cat(rows)
+                # a batch without a quad still has its vertices: the entry takes no NULL, so faces gets one spare row
+                fbuf = faces if nf else torch.empty((1, 3), dtype=torch.int32, device=dev)
+                check("disn_dc_emit_batch", h.disn_dc_emit_batch(part.data_ptr(), boxes.ctypes.data, nb, res, float(iso),
+                                                                 points.data_ptr(), normals.data_ptr(), reg,
+                                                                 verts.data_ptr(), fbuf.data_ptr(), ws.data_ptr(),
+                                                                 ws.numel(), st))
+            v0 = f0 = 0
+            for k in range(nb):
+                item = (verts[v0:v0 + int(sizes[k, 1])], faces[f0:f0 + int(sizes[k, 2])])
+                if hermite:
+                    item += (points[e_off[k]:e_off[k + 1]], normals[e_off[k]:e_off[k + 1]])
+                out.append(item)
+                v0 += int(sizes[k, 1])
+                f0 += int(sizes[k, 2])
+    return out
+
+
+def dual_contour(sdf: torch.Tensor, sdf_params, res: int, iso: float = 0.0, normals_fn=None, reg: float = DC_REG,
+                 ws: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``dual_contour_batch`` for one grid of (res+1)^3 values; ``normals_fn(points)`` -> [ne,3] on the device, or
+    None for the grid normals.  -> (verts [nv,3] float32, faces [nf,3] int32), on the device."""
+    fn = None if normals_fn is None else (lambda b, pts: normals_fn(pts))
+    return dual_contour_batch(sdf.reshape(1, -1), np.asarray(sdf_params, np.float64).reshape(1, 6), res, iso, fn, reg,
+                              ws)[0][:2]
