@@ -1,6 +1,7 @@
 """ctypes binding of libdisn_amd.so (include/disn_amd.h and, for the mesh simplification and the vertex colours,
 include/disn_amd_simplify.h and include/disn_amd_colour.h; for the surface samples, include/disn_amd_sample.h; for
-the Taubin smoothing, include/disn_amd_smooth.h; for dual contouring, include/dc/disn_amd_dc.h).
+the Taubin smoothing, include/disn_amd_smooth.h; for dual contouring, include/dc/disn_amd_dc.h and
+include/dc/disn_amd_dc_sheets.h).
 
 The HIP library is the product: there is NO CPU fallback.  ``lib()`` raises
 ``DisnLibraryError`` when the shared object is missing or does not export the
@@ -289,6 +290,16 @@ SIGNATURES_DC = {
     "disn_dc_emit_batch": (I, [P, P, I, I, F, P, P, D, P, P, P, Z, P]),
 }
 
+# name -> (restype, argtypes); every symbol declared in include/dc/disn_amd_dc_sheets.h (the seventh header, beside the
+# sixth: per-sheet dual contouring, the argument lists of disn_dc_*)
+SIGNATURES_DCS = {
+    "disn_dcs_workspace_bytes": (Z, [I, I]),
+    "disn_dcs_count_batch": (I, [P, I, I, F, P, P, Z, P]),
+    "disn_dcs_points_batch": (I, [P, P, I, I, F, P, P, Z, P]),
+    "disn_dcs_grid_normals_batch": (I, [P, P, I, I, F, P, P, Z, P]),
+    "disn_dcs_emit_batch": (I, [P, P, I, I, F, P, P, D, P, P, P, Z, P]),
+}
+
 _LIB: Optional[C.CDLL] = None
 
 
@@ -306,7 +317,7 @@ def lib() -> C.CDLL:
     except OSError as e:  # pragma: no cover - depends on the box
         raise DisnLibraryError("cannot load %s: %s" % (LIB_PATH, e)) from e
     for name, (res, args) in [kv for t in (SIGNATURES, SIGNATURES_SIMPLIFY, SIGNATURES_COLOUR, SIGNATURES_SAMPLE,
-                                                     SIGNATURES_SMOOTH, SIGNATURES_DC) for kv in t.items()]:
+                                                     SIGNATURES_SMOOTH, SIGNATURES_DC, SIGNATURES_DCS) for kv in t.items()]:
         try:
             fn = getattr(h, name)
         except AttributeError as e:

@@ -486,23 +486,26 @@ def score_group(meshes, keys, score, seed: int = 0, cache: Optional[dict] = None
 
 
 def dc_args(mesher: str = "mc", dc=None) -> Optional[dict]:
-    """``mesher`` = "mc" (marching cubes, the default) or "dc" (dual contouring, ``isosurface.dual_contour_batch``);
+    """``mesher`` = "mc" (marching cubes, the default), "dc" (dual contouring, ``isosurface.dual_contour_batch``) or
+    "dcs" (the same with one vertex per SHEET of a cell, ``sheets=True``: the checked dict then carries "sheets": True);
     ``dc`` = None, a regulariser REG, or a dict with any of ``normals`` ("network": the network's unit gradients at the
     Hermite points, the default; "grid": the grid's finite differences) and ``reg`` (0 < reg <= 1, default 2^-10 --
     the constant of the simplification, NOT measured on a trained network's normals).  -> None for "mc", else the
     checked dict (ValueError; no device work): what ``reconstruct*`` and ``--mesher`` take"""
-    if mesher not in ("mc", "dc"):
-        raise ValueError("--mesher must be mc or dc, got %r" % (mesher,))
+    if mesher not in ("mc", "dc", "dcs"):
+        raise ValueError("--mesher must be mc, dc or dcs, got %r" % (mesher,))
     if mesher == "mc":
         if dc is not None:
-            raise ValueError("--dc_normals / --dc_reg need --mesher dc")
+            raise ValueError("--dc_normals / --dc_reg need --mesher dc or dcs")
         return None
     from .isosurface import DC_REG
     d = {"normals": "network", "reg": DC_REG}
     if isinstance(dc, dict):
-        if set(dc) - set(d):
-            raise ValueError("dc: unknown keys %s" % sorted(set(dc) - set(d)))
-        d.update({k: v for k, v in dc.items() if v is not None})
+        if set(dc) - set(d) - {"sheets"}:
+            raise ValueError("dc: unknown keys %s" % sorted(set(dc) - set(d) - {"sheets"}))
+        if "sheets" in dc and bool(dc["sheets"]) != (mesher == "dcs"):       # a checked dict handed on: it must agree
+            raise ValueError("dc: sheets = %r does not go with --mesher %s" % (dc["sheets"], mesher))
+        d.update({k: v for k, v in dc.items() if v is not None and k != "sheets"})
     elif dc is not None:
         d["reg"] = dc
     if d["normals"] not in ("network", "grid"):
@@ -510,6 +513,8 @@ def dc_args(mesher: str = "mc", dc=None) -> Optional[dict]:
     d["reg"] = float(d["reg"])
     if not (0.0 < d["reg"] <= 1.0):
         raise ValueError("--dc_reg must be in (0, 1], got %r" % (d["reg"],))
+    if mesher == "dcs":
+        d["sheets"] = True
     return d
 
 
@@ -517,7 +522,8 @@ def mesh_group(grids, sp, sdf_res: int, iso: float, dc=None, engine=None, enc=No
     """the group's grids [B,(res+1)^3] -> B x (verts, faces): ``isosurface.marching_cubes_batch`` (``dc`` None), or
     ``isosurface.dual_contour_batch`` with the checked ``dc`` of ``dc_args``: the normals of view b are the network's
     unit gradients at its Hermite points from the view's cached folded map (``SdfEngine.refine_vertices(iters=0)``),
-    or -- ``normals`` = "grid", or no ``enc`` (the fused route has no gradient entry) -- the grid normals"""
+    or -- ``normals`` = "grid", or no ``enc`` (the fused route has no gradient entry) -- the grid normals; with
+    "sheets" in ``dc`` (``mesher`` = "dcs") one vertex per sheet of a cell"""
     from . import isosurface
     if dc is None:
         return isosurface.marching_cubes_batch(grids, sp, sdf_res, iso)
@@ -525,7 +531,7 @@ def mesh_group(grids, sp, sdf_res: int, iso: float, dc=None, engine=None, enc=No
     if dc["normals"] == "network" and enc is not None:
         def fn(b, points):
             return engine.refine_vertices(enc, b, trans_mats, points, iso=iso, iters=0)[1]
-    return isosurface.dual_contour_batch(grids, sp, sdf_res, iso, fn, dc["reg"])
+    return isosurface.dual_contour_batch(grids, sp, sdf_res, iso, fn, dc["reg"], sheets=bool(dc.get("sheets")))
 
 
 def reconstruct(engine, imgs, trans_mats, sdf_params, sdf_res: int, iso: float = 0.0, refine: int = 0,
@@ -724,10 +730,10 @@ def result_obj_path(log_dir: str, sdf_res: int, iso: float, cam_est: bool = Fals
     <...>_comb (the name INTEGRATION 3e gives the combined tree); ``simplify`` = CELLS: the simplified meshes' tree,
     <...>[_comb]_s<CELLS>; ``colour``: the coloured meshes' tree, <...>[_comb][_s<CELLS>]_col; ``smooth`` = ITERS: the
     smoothed meshes' tree, _t<ITERS> between _comb and _s<CELLS>: <...>[_comb]_t<ITERS>[_s<CELLS>][_col];
-    ``mesher`` = "dc": the dual-contoured meshes' tree, _dc directly behind <res+1>_<str(iso)>"""
+    ``mesher`` = "dc" / "dcs": the dual-contoured meshes' tree, _dc / _dcs directly behind <res+1>_<str(iso)>"""
     prefix = ("camest_" if cam_est else "") + ("fuse%d%s_" % tuple(fuse) if fuse else "")
     return os.path.join(log_dir, "test_objs", prefix + str(sdf_res + 1) + "_" + str(iso)
-                        + ("_dc" if mesher == "dc" else "") + ("_comb" if clean else "")
+                        + ("_" + mesher if mesher in ("dc", "dcs") else "") + ("_comb" if clean else "")
                         + ("_t%d" % smooth if smooth is not None else "")
                         + ("_s%d" % simplify if simplify is not None else "") + ("_col" if colour else ""))
 
@@ -794,20 +800,21 @@ def parser():
 
 
 def add_dc_flags(p) -> None:
-    p.add_argument("--mesher", default="mc", choices=("mc", "dc"),
+    p.add_argument("--mesher", default="mc", choices=("mc", "dc", "dcs"),
                    help="mc: marching cubes; dc: dual contouring from Hermite data (one vertex per crossed cell, placed "
-                        "by a quadric: keeps creases; can be non-manifold where a cell holds several sheets); results "
-                        "go to <...>_dc [default: mc]")
+                        "by a quadric: keeps creases; can be non-manifold where a cell holds several sheets); dcs: the "
+                        "same with one vertex per sheet of a cell (thin parts stay apart); results go to <...>_dc / "
+                        "<...>_dcs [default: mc]")
     p.add_argument("--dc_normals", default=None, choices=("network", "grid"),
-                   help="with --mesher dc: the network's gradients at the cut edges, or the grid's finite differences "
+                   help="with --mesher dc or dcs: the network's gradients at the cut edges, or the grid's finite differences "
                         "(always grid with --fuse_views) [default: network]")
     p.add_argument("--dc_reg", type=float, default=None, metavar="REG",
-                   help="with --mesher dc: the pull towards the mean of a cell's crossings, 0 < REG <= 1 [default: "
+                   help="with --mesher dc or dcs: the pull towards the mean of a cell's crossings, 0 < REG <= 1 [default: "
                         "2^-10, the simplification's constant; not measured on a trained network]")
 
 
 def dc_from_flags(a) -> Optional[dict]:
-    """None without --mesher dc (ValueError for --dc_normals / --dc_reg without it), else the checked dict of
+    """None without --mesher dc or dcs (ValueError for --dc_normals / --dc_reg without it), else the checked dict of
     ``dc_args``"""
     dc = {"normals": a.dc_normals, "reg": a.dc_reg}
     return dc_args(a.mesher, None if a.dc_normals is None and a.dc_reg is None else dc)
@@ -1009,9 +1016,9 @@ def main(argv=None, reconstruct_fn: Optional[Callable] = None) -> dict:
     out_dir = result_obj_path(a.log_dir, a.sdf_res, a.iso, a.cam_est, fuse, clean=cleaning is not None, **more,
                               **({} if colour is None else {"colour": True}),
                               **({} if smooth is None else {"smooth": smooth["iters"]}),
-                              **({} if dc is None else {"mesher": "dc"}))
+                              **({} if dc is None else {"mesher": a.mesher}))
     if dc is not None:
-        more.update(mesher="dc", dc=dc)
+        more.update(mesher=a.mesher, dc=dc)
     if smooth is not None:
         more["smooth"] = smooth
     if colour is not None:

@@ -180,7 +180,7 @@ def main(argv=None) -> dict:
     if smooth is not None:
         extra["smooth"] = smooth
     if dc is not None:
-        extra.update(mesher="dc", dc=dc)
+        extra.update(mesher=a.mesher, dc=dc)
     if colour is not None:
         alpha = read_alpha(a.img)                                      # the background of the rendering colours nothing
         extra.update(colour=colour, alpha=None if alpha is None else alpha[None])

@@ -321,25 +321,46 @@ def dual_contour_arrays(vol, sdf_params, iso, normals, reg: float = DC_REG) -> T
     its last two indices swapped: the geometric normal points along +grad (``refine_mesh``).  Edges on the grid's
     boundary leave the surface open there, as marching cubes does.
     KNOWN LIMITS: in a cell that the surface crosses in more than one sheet one vertex serves both sheets, so the mesh
-    can be non-manifold there; triangles may be degenerate in position, never in index."""
+    can be non-manifold there (``dual_contour_sheets_arrays`` gives every sheet its own vertex); triangles may be
+    degenerate in position, never in index."""
     reg = float(reg)
     if not (0.0 < reg <= 1.0):
         raise ValueError("reg must be in (0, 1], got %r" % (reg,))
+    E, pts, nrm = _dc_hermite(vol, sdf_params, iso, normals)
+    active = _dc_cases(E)[1].reshape(-1)
+    cid = np.cumsum(active, dtype=np.int64) - active
+    cells = np.nonzero(active)[0]
+    verts = _dc_vertices(E, pts, nrm, cells, None, reg)
+    return verts.reshape(-1, 3), _dc_faces(E, verts, lambda k, cell, axis: cid[cell])
+
+
+def _dc_hermite(vol, sdf_params, iso, normals):
+    """the edges of a grid, their points and the given normals in float64 (ValueError for normals of another shape)"""
     E = _DcEdges(vol, sdf_params, iso)
-    n, R = E.n, E.R
     pts = E.points().astype(np.float64)
     nrm = np.ascontiguousarray(normals, np.float32).reshape(-1, 3).astype(np.float64)
     if nrm.shape != pts.shape:
         raise ValueError("normals must be [ne,3] with ne = %d, got %s" % (pts.shape[0], nrm.shape))
-    ins = E.inside
+    return E, pts, nrm
+
+
+def _dc_cases(E):
+    """per cell [R,R,R]: its marching-cubes case (bit i = corner i of ``gen_mc_tables`` inside) and whether it is
+    active (its eight corners not all on one side)"""
+    R, ins = E.R, E.inside
+    case = np.zeros((R, R, R), np.int32)
     cnt8 = np.zeros((R, R, R), np.int32)
-    for dz in (0, 1):
-        for dy in (0, 1):
-            for dx in (0, 1):
-                cnt8 += ins[dz:dz + R, dy:dy + R, dx:dx + R]
-    active = ((cnt8 != 0) & (cnt8 != 8)).reshape(-1)
-    cid = np.cumsum(active, dtype=np.int64) - active
-    cells = np.nonzero(active)[0]
+    for i, (dx, dy, dz) in enumerate(_DC_CORNERS):
+        c = ins[dz:dz + R, dy:dy + R, dx:dx + R]
+        case |= c.astype(np.int32) << i
+        cnt8 += c
+    return case, (cnt8 != 0) & (cnt8 != 8)
+
+
+def _dc_vertices(E, pts, nrm, cells, member, reg):
+    """one vertex per entry of ``cells`` (flat cell ids, a cell may repeat): the quadric of the cell's cut edges, or --
+    ``member`` bool [len(cells),12] -- of those of its cube edges that ``member`` names (all of them cut)"""
+    n, R = E.n, E.R
     cx, cy, cz = cells % R, (cells // R) % R, cells // (R * R)
     ci = np.stack([cx, cy, cz], 1)
     corner = np.stack([E.ax[k][ci[:, k]].astype(np.float64) for k in range(3)], 1).reshape(-1, 3)
@@ -350,9 +371,9 @@ def dual_contour_arrays(vol, sdf_params, iso, normals, reg: float = DC_REG) -> T
     sm = [np.zeros(nc) for _ in range(3)]
     cnt = np.zeros(nc)
     with np.errstate(all="ignore"):
-        for dx, dy, dz, a in DC_CUBE_EDGES:
+        for e, (dx, dy, dz, a) in enumerate(DC_CUBE_EDGES):
             slot = 3 * (((cz + dz) * n + (cy + dy)) * n + (cx + dx)) + a
-            cut = E.flat[slot]
+            cut = E.flat[slot] if member is None else member[:, e]
             r = np.where(cut, E.eidx[slot], 0)
             if not len(pts):
                 break
@@ -387,21 +408,26 @@ def dual_contour_arrays(vol, sdf_params, iso, normals, reg: float = DC_REG) -> T
         ok = (det > 0.0) & np.isfinite(x0) & np.isfinite(x1) & np.isfinite(x2)
         x = np.where(ok[:, None], np.stack([x0, x1, x2], 1), np.stack([mx, my, mz], 1)).reshape(-1, 3)
         x = np.where(x < 0.0, 0.0, np.where(x > hi, hi, x))
-        verts = (corner + x).astype(np.float32)
-    # ---- faces: the cut edges with a quad, in rank order
+        return (corner + x).astype(np.float32)
+
+
+def _dc_faces(E, verts, vertex_of):
+    """the triangles of the cut edges with a quad, in rank order; ``vertex_of(k, cell, axis)`` -> the vertex ids that
+    the flat cells ``cell`` (q_k of edges of axes ``axis``) contribute"""
+    R, ins = E.R, E.inside
     u, v = (E.axis + 1) % 3, (E.axis + 2) % 3
     rows = np.arange(len(E.p))
     iu, iv = E.idx[rows, u] if len(rows) else rows, E.idx[rows, v] if len(rows) else rows
     has = (iu >= 1) & (iu <= R - 1) & (iv >= 1) & (iv <= R - 1)
     sel = np.nonzero(has)[0]
     if not len(sel):
-        return verts.reshape(-1, 3), np.zeros((0, 3), np.int32)
+        return np.zeros((0, 3), np.int32)
     q = []
-    for du, dv in _DC_QUAD:
+    for k, (du, dv) in enumerate(_DC_QUAD):
         c = E.idx[sel].copy()
         c[np.arange(len(sel)), u[sel]] += du
         c[np.arange(len(sel)), v[sel]] += dv
-        q.append(cid[(c[:, 2] * R + c[:, 1]) * R + c[:, 0]])
+        q.append(vertex_of(k, (c[:, 2] * R + c[:, 1]) * R + c[:, 0], E.axis[sel]))
     P = [verts[k].astype(np.float64) for k in q]
     d02, d13 = P[0] - P[2], P[1] - P[3]
     d02 = (d02[:, 0] * d02[:, 0] + d02[:, 1] * d02[:, 1]) + d02[:, 2] * d02[:, 2]
@@ -412,12 +438,69 @@ def dual_contour_arrays(vol, sdf_params, iso, normals, reg: float = DC_REG) -> T
     tri = np.stack([t1, t2], 1).reshape(-1, 3)
     flip = np.repeat(~ins.reshape(-1)[E.p[sel]], 2)
     tri[flip] = tri[flip][:, [0, 2, 1]]
-    return verts.reshape(-1, 3), tri.astype(np.int32)
+    return tri.astype(np.int32)
+
+
+# the cell's corners in the order of the case bits (tools/gen_mc_tables.CORNERS)
+_DC_CORNERS = ((0, 0, 0), (1, 0, 0), (1, 1, 0), (0, 1, 0), (0, 0, 1), (1, 0, 1), (1, 1, 1), (0, 1, 1))
+
+
+def _dcs_quad_edges():
+    """[axis][k]: the cube-edge id under which cell q_k sees a grid edge of that axis -- the cube edge of the same axis
+    whose low corner lies at (-du, -dv) on the (u, v) axes, (du, dv) = q_k's offset"""
+    out = []
+    for a in range(3):
+        u, v = (a + 1) % 3, (a + 2) % 3
+        out.append(tuple([e for e, g in enumerate(DC_CUBE_EDGES) if g[3] == a and (g[u], g[v]) == (-du, -dv)][0]
+                         for du, dv in _DC_QUAD))
+    return tuple(out)
+
+
+DCS_QUAD_EDGES = _dcs_quad_edges()
+
+
+def dual_contour_sheets_arrays(vol, sdf_params, iso, normals, reg: float = DC_REG) -> Tuple[np.ndarray, np.ndarray]:
+    """Dual contouring with one vertex per SHEET of a cell, on the host: THE SPECIFICATION of
+    ``dual_contour_batch(sheets=True)`` (same position bits, same integers).  Arguments, Hermite points, their order
+    and ``normals`` are those of ``dual_contour_arrays`` -> (verts float32 [nv,3], faces int32 [nf,3]).
+
+    Case of a cell: bit i set when corner i is inside (vol < float32(iso)), in the corner order of
+    ``tools/gen_mc_tables``.  The cut edges of a case lie on closed loops, one per sheet of the surface in the cell
+    (``mc_loops.MC_NLOOP`` / ``MC_LOOP``, derived by ``tools/gen_mc_loops.py``: 0..4 loops of 3..7 edges, numbered by
+    their smallest cube-edge id).
+    Vertex ids: the cells in flat (iz,iy,ix) order, the loops of a cell in loop-id order:
+    id = (exclusive scan of MC_NLOOP[case] over the cells)[cell] + loop; nv = the sum of the loop counts.
+    Quadric of a (cell, loop): ``dual_contour_arrays``' quadric restricted to the loop's edges -- visited in cube-edge-id
+    order, the same float64 arithmetic, the same s = g.g rule for NaN, infinite and zero rows, the mean m over the
+    loop's edges only, the same lam, adjugate solve, fallback to m and clip to the cell.  A loop in a one-loop cell has
+    ``dual_contour_arrays``' vertex bit for bit; a grid whose active cells all have one loop gives its mesh bit for bit.
+    Faces: the quads, their order, the shorter-diagonal split, the tie rule and the winding flip are
+    ``dual_contour_arrays``' (ne and nf too); the index of cell q_k is base[cell] + MC_LOOP[case(cell)][e], e the cube
+    edge under which that cell sees the grid edge (``DCS_QUAD_EDGES[axis][k]``).
+    KNOWN LIMIT that remains: when two cells share an ambiguous face (four cut edges) and in BOTH cells both of that
+    face's segments lie on one loop, the two dual edges across the face join the same two vertices; that edge then
+    carries four faces (three where a quad is missing at the grid's boundary).  Curing it means re-pairing such faces
+    per grid; not built.  Triangles may be degenerate in position, never in index."""
+    from .mc_loops import MC_LOOP, MC_NLOOP
+    reg = float(reg)
+    if not (0.0 < reg <= 1.0):
+        raise ValueError("reg must be in (0, 1], got %r" % (reg,))
+    E, pts, nrm = _dc_hermite(vol, sdf_params, iso, normals)
+    case = _dc_cases(E)[0].reshape(-1)
+    nloop = np.asarray(MC_NLOOP, np.int64)[case]
+    loops = np.asarray(MC_LOOP, np.int64)
+    base = np.cumsum(nloop) - nloop
+    cells = np.repeat(np.arange(len(case)), nloop)
+    which = np.arange(len(cells)) - base[cells]
+    member = loops[case[cells]] == which[:, None]
+    verts = _dc_vertices(E, pts, nrm, cells, member, reg)
+    quad = np.asarray(DCS_QUAD_EDGES, np.int64)
+    return verts.reshape(-1, 3), _dc_faces(E, verts, lambda k, cell, axis: base[cell] + loops[case[cell], quad[axis, k]])
 
 
 def dual_contour_batch(sdf: torch.Tensor, sdf_params, res: int, iso: float = 0.0, normals_fn=None,
                        reg: float = DC_REG, ws: Optional[torch.Tensor] = None, max_edge_slots: int = MC_EDGE_SLOTS,
-                       hermite: bool = False) -> List[Tuple[torch.Tensor, ...]]:
+                       hermite: bool = False, sheets: bool = False) -> List[Tuple[torch.Tensor, ...]]:
     """sdf: float32 device tensor [B,(res+1)^3], sdf_params [B,6] -> B x (verts [nv,3] float32, faces [nf,3] int32),
     views of two device tensors; every pair is bit for bit ``dual_contour_arrays`` of that grid with its normals.
     One count call, ONE device-to-host copy of the [B,3] sizes {ne, nv, nf}, one points call and one emit call for the
@@ -426,8 +509,12 @@ def dual_contour_batch(sdf: torch.Tensor, sdf_params, res: int, iso: float = 0.0
     (any length; a NaN, infinite or zero row only counts in its cells' means); None: the grid's own finite
     differences (``grid_normals_arrays``, one more call).  ``reg``: see ``dual_contour_arrays`` (the default is
     unmeasured on a trained network).  ``hermite``: every item is (verts, faces, points, normals).
-    The mesh can be non-manifold where a cell holds more than one sheet of the surface; triangles may be degenerate in
-    position, never in index; the winding is ``marching_cubes``' (geometric normal along +grad)."""
+    The mesh can be non-manifold where a cell holds more than one sheet of the surface (``sheets`` splits such cells);
+    triangles may be degenerate in position, never in index; the winding is ``marching_cubes``' (geometric normal along
+    +grad).
+    ``sheets``: one vertex per sheet of a cell instead (include/dc/disn_amd_dc_sheets.h): every pair is bit for bit
+    ``dual_contour_sheets_arrays`` of that grid, nv the grid's loops; the same points, normals, ne and nf.  A round then
+    also keeps 4*B*res^3 below 2^32.  Its remaining limit is stated there."""
     n = res + 1
     if sdf.dim() != 2 or sdf.shape[1] != n * n * n:
         raise ValueError("sdf must be [B, (res+1)^3 = %d], got %s" % (n * n * n, tuple(sdf.shape)))
@@ -440,22 +527,27 @@ def dual_contour_batch(sdf: torch.Tensor, sdf_params, res: int, iso: float = 0.0
     if sp.shape[0] != B:
         raise ValueError("sdf_params must be [B,6] with B = %d, got %s" % (B, sp.shape))
     per = (min(int(max_edge_slots), MC_EDGE_SLOTS) - 1) // (3 * n * n * n)      # grids per round
-    if B and (per < 1 or lib().disn_dc_workspace_bytes(1, res) == 0):
+    h = lib()
+    fam = "disn_dcs_" if sheets else "disn_dc_"
+    ws_bytes, count_batch, points_batch, grid_normals_batch, emit_batch = (
+        getattr(h, fam + k) for k in ("workspace_bytes", "count_batch", "points_batch", "grid_normals_batch", "emit_batch"))
+    if sheets:
+        per = min(per, (MC_EDGE_SLOTS - 1) // max(4 * res ** 3, 1))             # the loop ranks: 4*B*res^3 < 2^32
+    if B and (per < 1 or ws_bytes(1, res) == 0):
         raise ValueError("unsupported resolution %d" % res)
     dev = sdf.device
-    h = lib()
     out: List[Tuple[torch.Tensor, ...]] = []
     with torch.cuda.device(dev):
         st = ops._stream()
         for b0 in range(0, B, max(per, 1)):
             nb = min(per, B - b0)
-            need = h.disn_dc_workspace_bytes(nb, res)
+            need = ws_bytes(nb, res)
             if ws is None or ws.numel() < need:
                 ws = torch.empty(need, dtype=torch.uint8, device=dev)
             part, boxes = sdf[b0:b0 + nb], sp[b0:b0 + nb]
             counts = torch.zeros((nb, 3), dtype=torch.int64, device=dev)
-            check("disn_dc_count_batch", h.disn_dc_count_batch(part.data_ptr(), nb, res, float(iso), counts.data_ptr(),
-                                                               ws.data_ptr(), ws.numel(), st))
+            check(fam + "count_batch", count_batch(part.data_ptr(), nb, res, float(iso), counts.data_ptr(), ws.data_ptr(),
+                                                   ws.numel(), st))
             sizes = counts.cpu().numpy()                   # the one host sync of the round: sizes are data dependent
             ne, nv, nf = (int(sizes[:, k].sum()) for k in range(3))
             points = torch.empty((ne, 3), dtype=torch.float32, device=dev)
@@ -464,12 +556,11 @@ def dual_contour_batch(sdf: torch.Tensor, sdf_params, res: int, iso: float = 0.0
             e_off = np.concatenate([[0], np.cumsum(sizes[:, 0])]).astype(np.int64)
             normals = points
             if ne:
-                check("disn_dc_points_batch", h.disn_dc_points_batch(part.data_ptr(), boxes.ctypes.data, nb, res,
-                                                                     float(iso), points.data_ptr(), ws.data_ptr(),
-                                                                     ws.numel(), st))
+                check(fam + "points_batch", points_batch(part.data_ptr(), boxes.ctypes.data, nb, res, float(iso),
+                                                         points.data_ptr(), ws.data_ptr(), ws.numel(), st))
                 if normals_fn is None:
                     normals = torch.empty((ne, 3), dtype=torch.float32, device=dev)
-                    check("disn_dc_grid_normals_batch", h.disn_dc_grid_normals_batch(
+                    check(fam + "grid_normals_batch", grid_normals_batch(
                         part.data_ptr(), boxes.ctypes.data, nb, res, float(iso), normals.data_ptr(), ws.data_ptr(),
                         ws.numel(), st))
                 else:
@@ -484,10 +575,9 @@ def dual_contour_batch(sdf: torch.Tensor, sdf_params, res: int, iso: float = 0.0
                     normals = rows[0].contiguous() if nb == 1 else torch.cat(rows)
                 # a batch without a quad still has its vertices: the entry takes no NULL, so faces gets one spare row
                 fbuf = faces if nf else torch.empty((1, 3), dtype=torch.int32, device=dev)
-                check("disn_dc_emit_batch", h.disn_dc_emit_batch(part.data_ptr(), boxes.ctypes.data, nb, res, float(iso),
-                                                                 points.data_ptr(), normals.data_ptr(), reg,
-                                                                 verts.data_ptr(), fbuf.data_ptr(), ws.data_ptr(),
-                                                                 ws.numel(), st))
+                check(fam + "emit_batch", emit_batch(part.data_ptr(), boxes.ctypes.data, nb, res, float(iso),
+                                                     points.data_ptr(), normals.data_ptr(), reg, verts.data_ptr(),
+                                                     fbuf.data_ptr(), ws.data_ptr(), ws.numel(), st))
             v0 = f0 = 0
             for k in range(nb):
                 item = (verts[v0:v0 + int(sizes[k, 1])], faces[f0:f0 + int(sizes[k, 2])])
@@ -500,9 +590,10 @@ def dual_contour_batch(sdf: torch.Tensor, sdf_params, res: int, iso: float = 0.0
 
 
 def dual_contour(sdf: torch.Tensor, sdf_params, res: int, iso: float = 0.0, normals_fn=None, reg: float = DC_REG,
-                 ws: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+                 ws: Optional[torch.Tensor] = None, sheets: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
     """``dual_contour_batch`` for one grid of (res+1)^3 values; ``normals_fn(points)`` -> [ne,3] on the device, or
-    None for the grid normals.  -> (verts [nv,3] float32, faces [nf,3] int32), on the device."""
+    None for the grid normals; ``sheets``: one vertex per sheet of a cell.  -> (verts [nv,3] float32, faces [nf,3]
+    int32), on the device."""
     fn = None if normals_fn is None else (lambda b, pts: normals_fn(pts))
     return dual_contour_batch(sdf.reshape(1, -1), np.asarray(sdf_params, np.float64).reshape(1, 6), res, iso, fn, reg,
-                              ws)[0][:2]
+                              ws, sheets=sheets)[0][:2]

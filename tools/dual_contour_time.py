@@ -1,13 +1,18 @@
-"""What dual contouring costs beside marching cubes (DESIGN, "Dual contouring"): one sphere field per resolution, both
-meshers in one process, the network-normal pass timed on its own.
+"""What dual contouring costs beside marching cubes (DESIGN, "Dual contouring" and "Per-sheet dual contouring"): one
+sphere field per resolution, the three meshers in one process, the network-normal pass timed on its own.
 
-    python tools/dual_contour_time.py [--reps 20] [--out profiles/dual_contour_time.json]
+    python tools/dual_contour_time.py [--reps 20] [--out profiles/dual_contour_sheets_time.json]
+
+(profiles/dual_contour_time.json is the record of this tool before it timed the per-sheet mesher.)
 
 Per resolution (--sdf_res 64 and 256, one grid, a sphere of radius 0.6 in [-1,1]^3, iso 0), alternating who goes first:
   marching_cubes    ``isosurface.marching_cubes_batch``: count, read-back of the sizes, emit
   dual_contour      ``isosurface.dual_contour_batch`` with normals that are already on the device (the analytic ones,
                     computed before the clock starts): count, read-back of the sizes, points, emit
   dual_contour_grid the same with the grid normals (one more kernel)
+  dual_contour_sheets, dual_contour_sheets_grid
+                    the two above with ``sheets=True``: one vertex per sheet of a cell (on a sphere every cell has one
+                    sheet, so the meshes are the same and the difference is the cost of the rule alone)
   network_normals   the network's unit gradients at the Hermite points (``SdfEngine.refine_vertices(iters=0)``, random
                     weights, in chunks of 32768 points): what ``--dc_normals network`` adds per view
 with a device synchronise on both sides of every stage; every figure is the median over ``--reps`` repetitions with the
@@ -62,6 +67,9 @@ def shape(eng, enc, R, reps):
         "marching_cubes": lambda: isosurface.marching_cubes_batch(grid, box, R, 0.0),
         "dual_contour": lambda: isosurface.dual_contour_batch(grid, box, R, 0.0, lambda b, p: analytic),
         "dual_contour_grid": lambda: isosurface.dual_contour_batch(grid, box, R, 0.0, None),
+        "dual_contour_sheets": lambda: isosurface.dual_contour_batch(grid, box, R, 0.0, lambda b, p: analytic,
+                                                                     sheets=True),
+        "dual_contour_sheets_grid": lambda: isosurface.dual_contour_batch(grid, box, R, 0.0, None, sheets=True),
         "network_normals": lambda: network(points),
     }
     T = {k: [] for k in stages}
@@ -76,10 +84,11 @@ def shape(eng, enc, R, reps):
                 sizes[k] = {"vertices": int(len(out[0][0])), "triangles": int(len(out[0][1]))}
     s = {k: stats(v) for k, v in T.items()}
     res = {"sdf_res": R, "grids": 1, "reps": reps, "hermite_points": int(len(points)), "sizes": sizes, "stages": s,
-           "dual_contour_over_marching_cubes": s["dual_contour"]["median_ms"] / s["marching_cubes"]["median_ms"]}
+           "dual_contour_over_marching_cubes": s["dual_contour"]["median_ms"] / s["marching_cubes"]["median_ms"],
+           "dual_contour_sheets_over_dual_contour": s["dual_contour_sheets"]["median_ms"] / s["dual_contour"]["median_ms"]}
     print("sdf_res %d, %d Hermite points, %d repetitions (median, min .. max; ms)" % (R, len(points), reps))
     for k in stages:
-        print("  %-20s %10.3f  (%.3f .. %.3f)   %s" % (k, s[k]["median_ms"], s[k]["min_ms"], s[k]["max_ms"],
+        print("  %-26s %10.3f  (%.3f .. %.3f)   %s" % (k, s[k]["median_ms"], s[k]["min_ms"], s[k]["max_ms"],
                                                         sizes.get(k, "")))
     return res
 
@@ -87,7 +96,7 @@ def shape(eng, enc, R, reps):
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
-    ap.add_argument("--out", default=os.path.join("profiles", "dual_contour_time.json"))
+    ap.add_argument("--out", default=os.path.join("profiles", "dual_contour_sheets_time.json"))
     a = ap.parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit("dual_contour_time.py measures on a HIP device; none is visible")
