@@ -292,13 +292,7 @@ SIGNATURES_DC = {
 
 # name -> (restype, argtypes); every symbol declared in include/dc/disn_amd_dc_sheets.h (the seventh header, beside the
 # sixth: per-sheet dual contouring, the argument lists of disn_dc_*)
-SIGNATURES_DCS = {
-    "disn_dcs_workspace_bytes": (Z, [I, I]),
-    "disn_dcs_count_batch": (I, [P, I, I, F, P, P, Z, P]),
-    "disn_dcs_points_batch": (I, [P, P, I, I, F, P, P, Z, P]),
-    "disn_dcs_grid_normals_batch": (I, [P, P, I, I, F, P, P, Z, P]),
-    "disn_dcs_emit_batch": (I, [P, P, I, I, F, P, P, D, P, P, P, Z, P]),
-}
+SIGNATURES_DCS = {name.replace("disn_dc_", "disn_dcs_"): sig for name, sig in SIGNATURES_DC.items()}
 
 _LIB: Optional[C.CDLL] = None
 

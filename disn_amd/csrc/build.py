@@ -52,7 +52,6 @@ SOURCES = {
     "mesh_sample.hip": ["-ffp-contract=off"],     # the weights and the points round as sample_surface_arrays states them
     "mesh_smooth.hip": ["-ffp-contract=off"],     # the steps' float64 arithmetic rounds as smooth_arrays states it
     "dual_contour.hip": ["-ffp-contract=off"],    # the points, the quadric and the solve round as dual_contour_arrays states them
-    "dual_contour_sheets.hip": ["-ffp-contract=off"],   # the same bodies, per loop of a cell: dual_contour_sheets_arrays
     "batch_assemble.hip": ["-ffp-contract=off"],  # sample_pc_rot in the order its bound is derived for
     "api.hip": [],
     "host_util.cpp": ["-msse4.2"],
@@ -60,7 +59,7 @@ SOURCES = {
 }
 COMMON = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 HEADERS = ["kernels.hpp", "tuning.hpp", "h2_common.hpp", "mc_tables.h", "mesh_bvh.hpp", "mesh_batch.hpp",
-           "dual_contour_common.hpp", "mc_loops.h",
+           "grid_mesh.hpp", "mc_loops.h",
            os.path.join(ROOT, "include", "disn_amd.h"),
            os.path.join(ROOT, "include", "disn_amd_simplify.h"), os.path.join(ROOT, "include", "disn_amd_colour.h"),
            os.path.join(ROOT, "include", "disn_amd_sample.h"), os.path.join(ROOT, "include", "disn_amd_smooth.h"),

@@ -11,11 +11,10 @@
 //   faces      = cells in flat order (iz,iy,ix) over R^3, triangles in table order
 // All kernels are HBM-bound streaming passes over the (R+1)^3 grid; the scans are three-pass
 // (block scan, scan of block sums, add).  The per-element bodies are shared by the single-grid kernels and
-// the batched ones (B grids, one scan, one read-back of the sizes: a group of views of the test set).
-#include "kernels.hpp"
-
-#define DISN_MC_QUAL __constant__ const
-#include "mc_tables.h"
+// the batched ones (B grids, one scan, one read-back of the sizes: a group of views of the test set); those that dual
+// contouring needs as well (axis value, case, flags, cut edge and its point, the batched vertex kernel) are
+// grid_mesh.hpp's.  This file keeps the scan, the triangle table walk, the workspaces and its entries.
+#include "grid_mesh.hpp"
 
 namespace disn {
 
@@ -111,31 +110,13 @@ hipError_t exclusive_scan(const unsigned* in, unsigned* out, size_t n, unsigned*
 // pass 1: cut-edge flags (3 per grid point) and triangle counts (1 per cell)
 // ---------------------------------------------------------------------------
 // one grid point p of an n^3 grid: its three edge flags and (where it is the low corner of a cell) the cell's count;
-// vol, eflag and ccount are the grid's OWN blocks, so no neighbour (+1, +n, +n^2) leaves the grid
+// vol, eflag and ccount are the grid's OWN blocks
 __device__ __forceinline__ void mc_flags_point(const float* __restrict__ vol, int n, float iso, size_t p,
                                                unsigned* __restrict__ eflag, unsigned* __restrict__ ccount) {
   const int R = n - 1;
   const int ix = (int)(p % n), iy = (int)((p / n) % n), iz = (int)(p / ((size_t)n * n));
-  const bool in0 = vol[p] < iso;
-  const bool hx = ix < R, hy = iy < R, hz = iz < R;
-  const bool inx = hx ? vol[p + 1] < iso : in0;
-  const bool iny = hy ? vol[p + n] < iso : in0;
-  const bool inz = hz ? vol[p + (size_t)n * n] < iso : in0;
-  eflag[3 * p + 0] = (hx && inx != in0) ? 1u : 0u;
-  eflag[3 * p + 1] = (hy && iny != in0) ? 1u : 0u;
-  eflag[3 * p + 2] = (hz && inz != in0) ? 1u : 0u;
-  if (hx && hy && hz) {
-    const size_t nn = (size_t)n * n;
-    unsigned mask = in0 ? 1u : 0u;
-    mask |= inx ? 2u : 0u;
-    mask |= (vol[p + 1 + n] < iso) ? 4u : 0u;
-    mask |= iny ? 8u : 0u;
-    mask |= inz ? 16u : 0u;
-    mask |= (vol[p + nn + 1] < iso) ? 32u : 0u;
-    mask |= (vol[p + nn + 1 + n] < iso) ? 64u : 0u;
-    mask |= (vol[p + nn + n] < iso) ? 128u : 0u;
-    ccount[((size_t)iz * R + iy) * R + ix] = kMcNtri[mask];
-  }
+  const int c = grid_flags_point(vol, n, iso, p, ix, iy, iz, eflag);
+  if (c >= 0) ccount[((size_t)iz * R + iy) * R + ix] = kMcNtri[c];
 }
 
 __global__ __launch_bounds__(256) void mc_flags_kernel(const float* __restrict__ vol, int n,
@@ -147,32 +128,7 @@ __global__ __launch_bounds__(256) void mc_flags_kernel(const float* __restrict__
     mc_flags_point(vol, n, iso, p, eflag, ccount);
 }
 
-__device__ __forceinline__ float grid_coord(const GridSpec& g, int a, int i) {
-  double v = (double)i * g.step[a];
-  v = v + g.start[a];
-  if (i == g.res - 1 && g.res > 1) v = g.stop[a];
-  return (float)v;
-}
-
-// pass 2: one vertex per cut edge.  e: edge slot of this grid (3*p + axis), o: where its vertex goes
-__device__ __forceinline__ void mc_edge_vertex(const float* __restrict__ vol, const GridSpec& g, float iso,
-                                               size_t e, float* __restrict__ o) {
-  const int n = g.res;
-  const size_t p = e / 3;
-  const int a = (int)(e - 3 * p);
-  const int idx[3] = {(int)(p % n), (int)((p / n) % n), (int)(p / ((size_t)n * n))};
-  const size_t step = a == 0 ? 1 : (a == 1 ? (size_t)n : (size_t)n * n);
-  const float v0 = vol[p], v1 = vol[p + step];
-  const float t = (iso - v0) / (v1 - v0);
-  float pos[3];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) pos[k] = grid_coord(g, k, idx[k]);
-  const float c0 = pos[a], c1 = grid_coord(g, a, idx[a] + 1);
-  const float d = t * (c1 - c0);
-  pos[a] = c0 + d;
-  o[0] = pos[0]; o[1] = pos[1]; o[2] = pos[2];
-}
-
+// pass 2: one vertex per cut edge, at its rank
 __global__ __launch_bounds__(256) void mc_verts_kernel(const float* __restrict__ vol, GridSpec g,
                                                        float iso, const unsigned* __restrict__ eflag,
                                                        const unsigned* __restrict__ eidx,
@@ -182,7 +138,7 @@ __global__ __launch_bounds__(256) void mc_verts_kernel(const float* __restrict__
   for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total;
        e += (size_t)gridDim.x * blockDim.x) {
     if (!eflag[e]) continue;
-    mc_edge_vertex(vol, g, iso, e, verts + (size_t)eidx[e] * 3);
+    grid_edge_point(g, grid_edge(vol, g, iso, e), verts + (size_t)eidx[e] * 3);
   }
 }
 
@@ -193,24 +149,14 @@ __device__ __forceinline__ void mc_cell_faces(const float* __restrict__ vol, int
                                               const unsigned* __restrict__ eidx, unsigned vbase,
                                               int* __restrict__ faces) {
   const int R = n - 1;
-  const size_t nn = (size_t)n * n;
   const int ix = (int)(c % R), iy = (int)((c / R) % R), iz = (int)(c / ((size_t)R * R));
-  const size_t p = ((size_t)iz * n + iy) * n + ix;
-  unsigned mask = (vol[p] < iso) ? 1u : 0u;
-  mask |= (vol[p + 1] < iso) ? 2u : 0u;
-  mask |= (vol[p + 1 + n] < iso) ? 4u : 0u;
-  mask |= (vol[p + n] < iso) ? 8u : 0u;
-  mask |= (vol[p + nn] < iso) ? 16u : 0u;
-  mask |= (vol[p + nn + 1] < iso) ? 32u : 0u;
-  mask |= (vol[p + nn + 1 + n] < iso) ? 64u : 0u;
-  mask |= (vol[p + nn + n] < iso) ? 128u : 0u;
+  const int mask = grid_cell_case(vol, n, iso, ((size_t)iz * n + iy) * n + ix);
   const int nt = kMcNtri[mask];
   if (!nt) return;
   int* o = faces + (size_t)coff[c] * 3;
   for (int k = 0; k < 3 * nt; ++k) {
     const int e = kMcTri[mask][k];
-    const size_t gp = ((size_t)(iz + kMcEdge[e][2]) * n + (iy + kMcEdge[e][1])) * n + (ix + kMcEdge[e][0]);
-    o[k] = (int)(eidx[3 * gp + kMcEdge[e][3]] - vbase);
+    o[k] = (int)(eidx[grid_cube_edge_slot(n, ix, iy, iz, e)] - vbase);
   }
 }
 
@@ -230,11 +176,9 @@ __global__ __launch_bounds__(256) void mc_faces_kernel(const float* __restrict__
 // concatenated arrays, ONE scan runs over each, and a grid's first scan value is its vertex / triangle base.  Every
 // grid is addressed through its own block of vol (the element bodies above see one grid and nothing else), so the
 // order and the arithmetic per grid are those of the single-grid kernels.  All flat counts are below 2^32 (the API
-// refuses larger batches), so the split of a flat index into (grid, element) is 32-bit.
+// refuses larger batches), so the split of a flat index into (grid, element) is 32-bit.  The vertices of a batch are
+// written by grid_mesh.hpp's grid_points_batch_kernel.
 // ---------------------------------------------------------------------------
-struct McBox { double start[3], step[3], stop[3]; };
-struct McBoxes { McBox b[kMcBatchBoxes]; };   // 32 * 72 B of kernel arguments
-
 __global__ __launch_bounds__(256) void mc_flags_batch_kernel(const float* __restrict__ vol, int n, unsigned np,
                                                              unsigned total, float iso,
                                                              unsigned* __restrict__ eflag,
@@ -258,29 +202,6 @@ __global__ void mc_batch_counts_kernel(const unsigned* __restrict__ eidx, const 
   const unsigned long long f1 = b + 1 < B ? coff[(size_t)(b + 1) * nc] : totals[1];
   counts[2 * b + 0] = v1 - v0;
   counts[2 * b + 1] = f1 - f0;
-}
-
-// grids b0 .. b0+nb-1 (boxes.b[0..nb)); the vertex goes to its GLOBAL rank
-__global__ __launch_bounds__(256) void mc_verts_batch_kernel(const float* __restrict__ vol, McBoxes boxes, int n,
-                                                             unsigned ne, unsigned b0, unsigned nb, float iso,
-                                                             const unsigned* __restrict__ eflag,
-                                                             const unsigned* __restrict__ eidx,
-                                                             float* __restrict__ verts) {
-  const size_t first = (size_t)b0 * ne, total = (size_t)nb * ne;
-  const unsigned np = ne / 3;
-  for (size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x; q < total; q += (size_t)gridDim.x * blockDim.x) {
-    if (!eflag[first + q]) continue;
-    const unsigned lb = (unsigned)q / ne, e = (unsigned)q - lb * ne;
-    GridSpec g;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      g.start[a] = boxes.b[lb].start[a];
-      g.step[a] = boxes.b[lb].step[a];
-      g.stop[a] = boxes.b[lb].stop[a];
-    }
-    g.res = n;
-    mc_edge_vertex(vol + (size_t)(b0 + lb) * np, g, iso, e, verts + (size_t)eidx[first + q] * 3);
-  }
 }
 
 // the triangle goes to its GLOBAL rank; its vertex ids are LOCAL to the grid (the grid's vertex base taken off)
@@ -343,12 +264,6 @@ static McBatchWs mc_batch_layout(void* ws, int B, int R) {
 
 static size_t mc_batch_ws_bytes(int B, int R) { return mc_batch_layout(nullptr, B, R).total; }
 
-static inline int blocks_for(size_t total) {
-  size_t b = (total + 255) / 256;
-  if (b > 16384) b = 16384;
-  return (int)(b < 1 ? 1 : b);
-}
-
 // counts[0] = vertices, counts[1] = triangles (device memory); fills ws for mc_emit_launch
 static hipError_t mc_count_launch(const float* vol, int R, float iso, unsigned long long* counts, void* ws,
                                   hipStream_t st) {
@@ -376,7 +291,7 @@ static hipError_t mc_emit_launch(const float* vol, const GridSpec& g, float iso,
 }
 
 // B grids [B,(R+1)^3] in one set of passes: counts [B,2] per grid; verts / faces of all grids back to back in grid
-// order, face indices local to their grid.  B*3*(R+1)^3 < 2^32 is the caller's to check (mc_batch_ok below)
+// order, face indices local to their grid.  B*3*(R+1)^3 < 2^32 is the caller's to check (grid_batch_ok)
 static hipError_t mc_count_batch_launch(const float* vol, int B, int R, float iso, unsigned long long* counts,
                                         void* ws, hipStream_t st) {
   const McBatchWs w = mc_batch_layout(ws, B, R);
@@ -393,22 +308,21 @@ static hipError_t mc_count_batch_launch(const float* vol, int B, int R, float is
   return hipGetLastError();
 }
 
-// vertices of grids b0 .. b0+nb-1 (g[0..nb), nb <= kMcBatchBoxes) / triangles of all B grids
-static hipError_t mc_verts_batch_launch(const float* vol, const GridSpec* g, int b0, int nb, int B, int R, float iso,
+// vertices of all B grids, their boxes kMcBatchBoxes per launch / triangles of all B grids
+static hipError_t mc_verts_batch_launch(const float* vol, const double* sdf_params_host, int B, int R, float iso,
                                         float* verts, void* ws, hipStream_t st) {
   const McBatchWs w = mc_batch_layout(ws, B, R);
   const int n = R + 1;
   const size_t np = (size_t)n * n * n;
-  McBoxes boxes = {};
-  for (int i = 0; i < nb; ++i)
-    for (int a = 0; a < 3; ++a) {
-      boxes.b[i].start[a] = g[i].start[a];
-      boxes.b[i].step[a] = g[i].step[a];
-      boxes.b[i].stop[a] = g[i].stop[a];
-    }
-  hipLaunchKernelGGL(mc_verts_batch_kernel, dim3(blocks_for(3 * np * nb)), dim3(256), 0, st, vol, boxes, n,
-                     (unsigned)(3 * np), (unsigned)b0, (unsigned)nb, iso, w.eflag, w.eidx, verts);
-  return hipGetLastError();
+  for (int b0 = 0; b0 < B; b0 += kMcBatchBoxes) {
+    const int nb = B - b0 < kMcBatchBoxes ? B - b0 : kMcBatchBoxes;
+    hipLaunchKernelGGL(grid_points_batch_kernel, dim3(blocks_for(3 * np * nb)), dim3(256), 0, st, vol,
+                       grid_boxes(sdf_params_host, b0, nb, R), n, (unsigned)(3 * np), (unsigned)b0, (unsigned)nb, iso,
+                       w.eflag, w.eidx, verts);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
 }
 
 static hipError_t mc_faces_batch_launch(const float* vol, int B, int R, float iso, int* faces, void* ws,
@@ -425,12 +339,6 @@ static hipError_t mc_faces_batch_launch(const float* vol, int B, int R, float is
 
 // ---- the C entries of include/disn_amd.h: argument and workspace checks, then the launchers above ----
 using namespace disn;
-
-#define DISN_TRY(expr)                    \
-  do {                                    \
-    hipError_t _e = (expr);               \
-    if (_e != hipSuccess) return (int)_e; \
-  } while (0)
 
 extern "C" {
 
@@ -456,19 +364,12 @@ int disn_mc_emit(const float* sdf, const double* sdf_params_host, int R, float i
   return 0;
 }
 
-// a batch is supported when its 3*B*(R+1)^3 edge slots fit the 32-bit scan
-static bool mc_batch_ok(int B, int R) {
-  if (B < 1 || R < 1 || R > 1290) return false;
-  const unsigned long long n = (unsigned long long)R + 1;
-  return 3ull * (unsigned long long)B * n * n * n < (1ull << 32);
-}
-
-size_t disn_mc_batch_workspace_bytes(int B, int R) { return mc_batch_ok(B, R) ? mc_batch_ws_bytes(B, R) : 0; }
+size_t disn_mc_batch_workspace_bytes(int B, int R) { return grid_batch_ok(B, R) ? mc_batch_ws_bytes(B, R) : 0; }
 
 int disn_mc_count_batch(const float* sdf, int B, int R, float iso, uint64_t* counts, void* ws, size_t ws_bytes,
                         void* stream) {
   if (!sdf || !counts || !ws || B < 1 || R < 1) return DISN_E_ARG;
-  if (!mc_batch_ok(B, R)) return DISN_E_SHAPE;
+  if (!grid_batch_ok(B, R)) return DISN_E_SHAPE;
   if (ws_bytes < mc_batch_ws_bytes(B, R)) return DISN_E_WS;
   DISN_TRY(mc_count_batch_launch(sdf, B, R, iso, reinterpret_cast<unsigned long long*>(counts), ws,
                                  (hipStream_t)stream));
@@ -478,14 +379,9 @@ int disn_mc_count_batch(const float* sdf, int B, int R, float iso, uint64_t* cou
 int disn_mc_emit_batch(const float* sdf, const double* sdf_params_host, int B, int R, float iso, float* verts,
                        int32_t* faces, void* ws, size_t ws_bytes, void* stream) {
   if (!sdf || !verts || !faces || !ws || !sdf_params_host || B < 1 || R < 1) return DISN_E_ARG;
-  if (!mc_batch_ok(B, R)) return DISN_E_SHAPE;
+  if (!grid_batch_ok(B, R)) return DISN_E_SHAPE;
   if (ws_bytes < mc_batch_ws_bytes(B, R)) return DISN_E_WS;
-  GridSpec g[kMcBatchBoxes];  // the boxes travel as kernel arguments, kMcBatchBoxes grids per vertex launch
-  for (int b0 = 0; b0 < B; b0 += kMcBatchBoxes) {
-    const int nb = B - b0 < kMcBatchBoxes ? B - b0 : kMcBatchBoxes;
-    for (int i = 0; i < nb; ++i) grid_spec(sdf_params_host + 6 * (size_t)(b0 + i), R, &g[i]);
-    DISN_TRY(mc_verts_batch_launch(sdf, g, b0, nb, B, R, iso, verts, ws, (hipStream_t)stream));
-  }
+  DISN_TRY(mc_verts_batch_launch(sdf, sdf_params_host, B, R, iso, verts, ws, (hipStream_t)stream));
   DISN_TRY(mc_faces_batch_launch(sdf, B, R, iso, faces, ws, (hipStream_t)stream));
   return 0;
 }

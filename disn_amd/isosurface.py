@@ -55,13 +55,8 @@ def marching_cubes(sdf: torch.Tensor, sdf_params, res: int, iso: float = 0.0,
 MC_EDGE_SLOTS = 1 << 32      # a batch's 3*B*(res+1)^3 edge slots must stay below this (the 32-bit scan)
 
 
-def marching_cubes_batch(sdf: torch.Tensor, sdf_params, res: int, iso: float = 0.0,
-                         ws: Optional[torch.Tensor] = None, max_edge_slots: int = MC_EDGE_SLOTS
-                         ) -> List[Tuple[torch.Tensor, torch.Tensor]]:
-    """sdf: float32 device tensor [B,(res+1)^3], sdf_params [B,6] -> B x (verts [nv,3], faces [nf,3]), views of
-    two device tensors; every pair is bit for bit what ``marching_cubes`` gives for that grid alone.  One count
-    call, ONE device-to-host copy of the [B,2] sizes and one emit call for the whole batch; a batch whose
-    3*B*(res+1)^3 edge slots reach ``max_edge_slots`` is meshed in several such rounds."""
+def _batch_args(sdf: torch.Tensor, sdf_params, res: int, max_edge_slots: int):
+    """the arguments of a batched mesher -> (sdf checked, sdf_params as float64 [B,6], grids per round)"""
     n = res + 1
     if sdf.dim() != 2 or sdf.shape[1] != n * n * n:
         raise ValueError("sdf must be [B, (res+1)^3 = %d], got %s" % (n * n * n, tuple(sdf.shape)))
@@ -70,36 +65,63 @@ def marching_cubes_batch(sdf: torch.Tensor, sdf_params, res: int, iso: float = 0
     sp = np.ascontiguousarray(np.asarray(sdf_params, np.float64).reshape(-1, 6))
     if sp.shape[0] != B:
         raise ValueError("sdf_params must be [B,6] with B = %d, got %s" % (B, sp.shape))
-    per = (min(int(max_edge_slots), MC_EDGE_SLOTS) - 1) // (3 * n * n * n)      # grids per round
-    if B and (per < 1 or lib().disn_mc_batch_workspace_bytes(1, res) == 0):
+    return sdf, sp, (min(int(max_edge_slots), MC_EDGE_SLOTS) - 1) // (3 * n * n * n)
+
+
+def _batch_rounds(sdf: torch.Tensor, sp: np.ndarray, res: int, per: int, ws: Optional[torch.Tensor], ws_bytes,
+                  width: int, count, emit) -> List[Tuple[torch.Tensor, ...]]:
+    """The rounds of a batched mesher, ``per`` grids each: the workspace grown to ``ws_bytes(nb, res)``,
+    ``count(part, nb, counts, ws, st)`` fills the [nb, width] sizes, ONE device-to-host copy brings them over,
+    ``emit(b0, part, boxes, nb, sizes, ws, st)`` -> the round's arrays as (tensor, its column of ``sizes``), all grids
+    back to back.  -> per grid the tuple of its views of those arrays."""
+    B = sdf.shape[0]
+    if B and (per < 1 or ws_bytes(1, res) == 0):
         raise ValueError("unsupported resolution %d" % res)
     dev = sdf.device
-    out: List[Tuple[torch.Tensor, torch.Tensor]] = []
+    out: List[Tuple[torch.Tensor, ...]] = []
     with torch.cuda.device(dev):
         st = ops._stream()
         for b0 in range(0, B, max(per, 1)):
             nb = min(per, B - b0)
-            need = lib().disn_mc_batch_workspace_bytes(nb, res)
+            need = ws_bytes(nb, res)
             if ws is None or ws.numel() < need:
                 ws = torch.empty(need, dtype=torch.uint8, device=dev)
-            part = sdf[b0:b0 + nb]
-            counts = torch.zeros((nb, 2), dtype=torch.int64, device=dev)
-            check("disn_mc_count_batch", lib().disn_mc_count_batch(part.data_ptr(), nb, res, float(iso),
-                                                                   counts.data_ptr(), ws.data_ptr(), ws.numel(), st))
+            part, boxes = sdf[b0:b0 + nb], sp[b0:b0 + nb]
+            counts = torch.zeros((nb, width), dtype=torch.int64, device=dev)
+            count(part, nb, counts, ws, st)
             sizes = counts.cpu().numpy()                   # the one host sync of the round: sizes are data dependent
-            nv, nf = int(sizes[:, 0].sum()), int(sizes[:, 1].sum())
-            verts = torch.empty((nv, 3), dtype=torch.float32, device=dev)
-            faces = torch.empty((nf, 3), dtype=torch.int32, device=dev)
-            if nv and nf:
-                check("disn_mc_emit_batch", lib().disn_mc_emit_batch(part.data_ptr(), sp[b0:b0 + nb].ctypes.data, nb,
-                                                                     res, float(iso), verts.data_ptr(),
-                                                                     faces.data_ptr(), ws.data_ptr(), ws.numel(), st))
-            v0 = f0 = 0
+            arrays = emit(b0, part, boxes, nb, sizes, ws, st)
+            offs = [np.concatenate([[0], np.cumsum(sizes[:, col])]).tolist() for _, col in arrays]
             for k in range(nb):
-                out.append((verts[v0:v0 + int(sizes[k, 0])], faces[f0:f0 + int(sizes[k, 1])]))
-                v0 += int(sizes[k, 0])
-                f0 += int(sizes[k, 1])
+                out.append(tuple(a[o[k]:o[k + 1]] for (a, _), o in zip(arrays, offs)))
     return out
+
+
+def marching_cubes_batch(sdf: torch.Tensor, sdf_params, res: int, iso: float = 0.0,
+                         ws: Optional[torch.Tensor] = None, max_edge_slots: int = MC_EDGE_SLOTS
+                         ) -> List[Tuple[torch.Tensor, torch.Tensor]]:
+    """sdf: float32 device tensor [B,(res+1)^3], sdf_params [B,6] -> B x (verts [nv,3], faces [nf,3]), views of
+    two device tensors; every pair is bit for bit what ``marching_cubes`` gives for that grid alone.  One count
+    call, ONE device-to-host copy of the [B,2] sizes and one emit call for the whole batch; a batch whose
+    3*B*(res+1)^3 edge slots reach ``max_edge_slots`` is meshed in several such rounds."""
+    sdf, sp, per = _batch_args(sdf, sdf_params, res, max_edge_slots)
+    dev = sdf.device
+
+    def count(part, nb, counts, ws, st):
+        check("disn_mc_count_batch", lib().disn_mc_count_batch(part.data_ptr(), nb, res, float(iso),
+                                                               counts.data_ptr(), ws.data_ptr(), ws.numel(), st))
+
+    def emit(b0, part, boxes, nb, sizes, ws, st):
+        nv, nf = int(sizes[:, 0].sum()), int(sizes[:, 1].sum())
+        verts = torch.empty((nv, 3), dtype=torch.float32, device=dev)
+        faces = torch.empty((nf, 3), dtype=torch.int32, device=dev)
+        if nv and nf:
+            check("disn_mc_emit_batch", lib().disn_mc_emit_batch(part.data_ptr(), boxes.ctypes.data, nb, res,
+                                                                 float(iso), verts.data_ptr(), faces.data_ptr(),
+                                                                 ws.data_ptr(), ws.numel(), st))
+        return (verts, 0), (faces, 1)
+
+    return _batch_rounds(sdf, sp, res, per, ws, lib().disn_mc_batch_workspace_bytes, 2, count, emit)
 
 
 def write_obj(path: str, verts, faces, normals=None, colours=None) -> None:
@@ -515,78 +537,55 @@ def dual_contour_batch(sdf: torch.Tensor, sdf_params, res: int, iso: float = 0.0
     ``sheets``: one vertex per sheet of a cell instead (include/dc/disn_amd_dc_sheets.h): every pair is bit for bit
     ``dual_contour_sheets_arrays`` of that grid, nv the grid's loops; the same points, normals, ne and nf.  A round then
     also keeps 4*B*res^3 below 2^32.  Its remaining limit is stated there."""
-    n = res + 1
-    if sdf.dim() != 2 or sdf.shape[1] != n * n * n:
-        raise ValueError("sdf must be [B, (res+1)^3 = %d], got %s" % (n * n * n, tuple(sdf.shape)))
     reg = float(reg)
     if not (0.0 < reg <= 1.0):
         raise ValueError("reg must be in (0, 1], got %r" % (reg,))
-    sdf = ops._chk(sdf, "sdf")
-    B = sdf.shape[0]
-    sp = np.ascontiguousarray(np.asarray(sdf_params, np.float64).reshape(-1, 6))
-    if sp.shape[0] != B:
-        raise ValueError("sdf_params must be [B,6] with B = %d, got %s" % (B, sp.shape))
-    per = (min(int(max_edge_slots), MC_EDGE_SLOTS) - 1) // (3 * n * n * n)      # grids per round
+    sdf, sp, per = _batch_args(sdf, sdf_params, res, max_edge_slots)
     h = lib()
     fam = "disn_dcs_" if sheets else "disn_dc_"
     ws_bytes, count_batch, points_batch, grid_normals_batch, emit_batch = (
         getattr(h, fam + k) for k in ("workspace_bytes", "count_batch", "points_batch", "grid_normals_batch", "emit_batch"))
     if sheets:
         per = min(per, (MC_EDGE_SLOTS - 1) // max(4 * res ** 3, 1))             # the loop ranks: 4*B*res^3 < 2^32
-    if B and (per < 1 or ws_bytes(1, res) == 0):
-        raise ValueError("unsupported resolution %d" % res)
     dev = sdf.device
-    out: List[Tuple[torch.Tensor, ...]] = []
-    with torch.cuda.device(dev):
-        st = ops._stream()
-        for b0 in range(0, B, max(per, 1)):
-            nb = min(per, B - b0)
-            need = ws_bytes(nb, res)
-            if ws is None or ws.numel() < need:
-                ws = torch.empty(need, dtype=torch.uint8, device=dev)
-            part, boxes = sdf[b0:b0 + nb], sp[b0:b0 + nb]
-            counts = torch.zeros((nb, 3), dtype=torch.int64, device=dev)
-            check(fam + "count_batch", count_batch(part.data_ptr(), nb, res, float(iso), counts.data_ptr(), ws.data_ptr(),
-                                                   ws.numel(), st))
-            sizes = counts.cpu().numpy()                   # the one host sync of the round: sizes are data dependent
-            ne, nv, nf = (int(sizes[:, k].sum()) for k in range(3))
-            points = torch.empty((ne, 3), dtype=torch.float32, device=dev)
-            verts = torch.empty((nv, 3), dtype=torch.float32, device=dev)
-            faces = torch.empty((nf, 3), dtype=torch.int32, device=dev)
-            e_off = np.concatenate([[0], np.cumsum(sizes[:, 0])]).astype(np.int64)
-            normals = points
-            if ne:
-                check(fam + "points_batch", points_batch(part.data_ptr(), boxes.ctypes.data, nb, res, float(iso),
-                                                         points.data_ptr(), ws.data_ptr(), ws.numel(), st))
-                if normals_fn is None:
-                    normals = torch.empty((ne, 3), dtype=torch.float32, device=dev)
-                    check(fam + "grid_normals_batch", grid_normals_batch(
-                        part.data_ptr(), boxes.ctypes.data, nb, res, float(iso), normals.data_ptr(), ws.data_ptr(),
-                        ws.numel(), st))
-                else:
-                    rows = []
-                    for k in range(nb):
-                        pk = points[e_off[k]:e_off[k + 1]]
-                        nk = normals_fn(b0 + k, pk) if len(pk) else pk
-                        if nk.shape != pk.shape or nk.dtype != torch.float32 or nk.device != pk.device:
-                            raise ValueError("normals_fn must return float32 %s on %s for grid %d, got %s %s" % (
-                                tuple(pk.shape), dev, b0 + k, nk.dtype, tuple(nk.shape)))
-                        rows.append(nk)
-                    normals = rows[0].contiguous() if nb == 1 else torch.cat(rows)
-                # a batch without a quad still has its vertices: the entry takes no NULL, so faces gets one spare row
-                fbuf = faces if nf else torch.empty((1, 3), dtype=torch.int32, device=dev)
-                check(fam + "emit_batch", emit_batch(part.data_ptr(), boxes.ctypes.data, nb, res, float(iso),
-                                                     points.data_ptr(), normals.data_ptr(), reg, verts.data_ptr(),
-                                                     fbuf.data_ptr(), ws.data_ptr(), ws.numel(), st))
-            v0 = f0 = 0
-            for k in range(nb):
-                item = (verts[v0:v0 + int(sizes[k, 1])], faces[f0:f0 + int(sizes[k, 2])])
-                if hermite:
-                    item += (points[e_off[k]:e_off[k + 1]], normals[e_off[k]:e_off[k + 1]])
-                out.append(item)
-                v0 += int(sizes[k, 1])
-                f0 += int(sizes[k, 2])
-    return out
+
+    def count(part, nb, counts, ws, st):
+        check(fam + "count_batch", count_batch(part.data_ptr(), nb, res, float(iso), counts.data_ptr(), ws.data_ptr(),
+                                               ws.numel(), st))
+
+    def emit(b0, part, boxes, nb, sizes, ws, st):
+        ne, nv, nf = (int(sizes[:, k].sum()) for k in range(3))
+        points = torch.empty((ne, 3), dtype=torch.float32, device=dev)
+        verts = torch.empty((nv, 3), dtype=torch.float32, device=dev)
+        faces = torch.empty((nf, 3), dtype=torch.int32, device=dev)
+        e_off = np.concatenate([[0], np.cumsum(sizes[:, 0])]).astype(np.int64)
+        normals = points
+        if ne:
+            check(fam + "points_batch", points_batch(part.data_ptr(), boxes.ctypes.data, nb, res, float(iso),
+                                                     points.data_ptr(), ws.data_ptr(), ws.numel(), st))
+            if normals_fn is None:
+                normals = torch.empty((ne, 3), dtype=torch.float32, device=dev)
+                check(fam + "grid_normals_batch", grid_normals_batch(
+                    part.data_ptr(), boxes.ctypes.data, nb, res, float(iso), normals.data_ptr(), ws.data_ptr(),
+                    ws.numel(), st))
+            else:
+                rows = []
+                for k in range(nb):
+                    pk = points[e_off[k]:e_off[k + 1]]
+                    nk = normals_fn(b0 + k, pk) if len(pk) else pk
+                    if nk.shape != pk.shape or nk.dtype != torch.float32 or nk.device != pk.device:
+                        raise ValueError("normals_fn must return float32 %s on %s for grid %d, got %s %s" % (
+                            tuple(pk.shape), dev, b0 + k, nk.dtype, tuple(nk.shape)))
+                    rows.append(nk)
+                normals = rows[0].contiguous() if nb == 1 else torch.cat(rows)
+            # a batch without a quad still has its vertices: the entry takes no NULL, so faces gets one spare row
+            fbuf = faces if nf else torch.empty((1, 3), dtype=torch.int32, device=dev)
+            check(fam + "emit_batch", emit_batch(part.data_ptr(), boxes.ctypes.data, nb, res, float(iso),
+                                                 points.data_ptr(), normals.data_ptr(), reg, verts.data_ptr(),
+                                                 fbuf.data_ptr(), ws.data_ptr(), ws.numel(), st))
+        return ((verts, 1), (faces, 2)) + (((points, 0), (normals, 0)) if hermite else ())
+
+    return _batch_rounds(sdf, sp, res, per, ws, ws_bytes, 3, count, emit)
 
 
 def dual_contour(sdf: torch.Tensor, sdf_params, res: int, iso: float = 0.0, normals_fn=None, reg: float = DC_REG,

@@ -318,8 +318,16 @@ def test_the_header_compiles_as_c99(tmp_path):
 
 def test_the_build_lists_the_source_without_contraction_and_the_header():
     from disn_amd.csrc import build
-    assert build.SOURCES["dual_contour.hip"] == ["-ffp-contract=off"]
-    assert any(h.endswith(os.path.join("include", "dc", "disn_amd_dc.h")) for h in build.HEADERS)
+    assert build.SOURCES["dual_contour.hip"] == ["-ffp-contract=off"] == build.SOURCES["marching_cubes.hip"]
+    assert "dual_contour_sheets.hip" not in build.SOURCES               # both vertex rules are built from the one file
+    for hdr in ("disn_amd_dc.h", "disn_amd_dc_sheets.h"):
+        assert any(h.endswith(os.path.join("include", "dc", hdr)) for h in build.HEADERS)
+    assert "grid_mesh.hpp" in build.HEADERS and "dual_contour_common.hpp" not in build.HEADERS
+    csrc = os.path.join(ROOT, "disn_amd", "csrc")
+    users = sorted(os.path.basename(f) for f in glob.glob(os.path.join(csrc, "*.hip"))
+                   if '#include "grid_mesh.hpp"' in abi_table.strip_comments(open(f).read()))
+    assert users == ["dual_contour.hip", "marching_cubes.hip"]
+    assert "atomic" not in abi_table.strip_comments(open(os.path.join(csrc, "dual_contour.hip")).read()).lower()
 
 
 # ------------------------------------------------------------------ 7. flags and paths

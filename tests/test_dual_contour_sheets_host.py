@@ -454,18 +454,35 @@ def test_the_header_compiles_as_c99(tmp_path):
 
 def test_the_build_lists_the_source_without_contraction_and_the_headers():
     from disn_amd.csrc import build
-    assert build.SOURCES["dual_contour_sheets.hip"] == ["-ffp-contract=off"] == build.SOURCES["dual_contour.hip"]
-    assert any(h.endswith(os.path.join("include", "dc", "disn_amd_dc_sheets.h")) for h in build.HEADERS)
-    assert "dual_contour_common.hpp" in build.HEADERS and "mc_loops.h" in build.HEADERS
-    # the shared bodies have one definition: both files include the common header and neither restates it
-    common = open(os.path.join(ROOT, "disn_amd", "csrc", "dual_contour_common.hpp")).read()
-    for body in ("dc_points_batch_kernel(", "dc_grid_normals_batch_kernel(", "struct DcQuadric", "dc_quad_faces("):
-        assert body in common
-    for src in ("dual_contour.hip", "dual_contour_sheets.hip"):
-        text = open(os.path.join(ROOT, "disn_amd", "csrc", src)).read()
-        assert '#include "dual_contour_common.hpp"' in text
-        assert "__global__ __launch_bounds__(256) void dc_points_batch_kernel" not in text and "struct DcQuadric" not in text
-        assert "atomic" not in abi_table.strip_comments(text).lower()
+    csrc = os.path.join(ROOT, "disn_amd", "csrc")
+    assert build.SOURCES["dual_contour.hip"] == ["-ffp-contract=off"] == build.SOURCES["marching_cubes.hip"]
+    for gone in ("dual_contour_sheets.hip", "dual_contour_common.hpp"):
+        assert gone not in build.SOURCES and gone not in build.HEADERS and not os.path.exists(os.path.join(csrc, gone))
+    for hdr in ("disn_amd_dc.h", "disn_amd_dc_sheets.h"):
+        assert any(h.endswith(os.path.join("include", "dc", hdr)) for h in build.HEADERS)
+    assert "grid_mesh.hpp" in build.HEADERS and "mc_loops.h" in build.HEADERS
+    # the bodies the meshers share have ONE definition over all of csrc (comments stripped): the axis value, the case of
+    # a cell from its eight corners, the edge-point kernel, the grid-normals kernel, the quadric, the quad's split and the
+    # 32-box kernel-argument struct
+    files = sorted(glob.glob(os.path.join(csrc, "*.hip")) + glob.glob(os.path.join(csrc, "*.hpp")))
+    text = {os.path.basename(f): abi_table.strip_comments(open(f).read()) for f in files}
+    once = {r"\bfloat\s+grid_coord\s*\(": "grid_mesh.hpp",
+            r"\bint\s+grid_cell_case\s*\(": "grid_mesh.hpp",
+            r"\?\s*128u?\s*:\s*0u?\s*;": "grid_mesh.hpp",                  # the bit of the eighth corner
+            r"\bvoid\s+grid_points_batch_kernel\s*\(": "grid_mesh.hpp",
+            r"\bvoid\s+dc_grid_normals_batch_kernel\s*\(": "dual_contour.hip",
+            r"\bstruct\s+DcQuadric\b": "dual_contour.hip",
+            r"\bvoid\s+dc_quad_faces\s*\(": "dual_contour.hip",
+            r"\bstruct\s+\w+\s*\{\s*\w+\s+\w+\[kMcBatchBoxes\]\s*;\s*\}": "grid_mesh.hpp"}
+    for pattern, home in once.items():
+        assert [name for name, t in text.items() for _ in re.findall(pattern, t)] == [home], pattern
+    for old in ("mc_verts_batch_kernel", "dc_points_batch_kernel", "mc_edge_vertex", "dc_edge(", "McBoxes", "DcBoxes"):
+        assert not [name for name, t in text.items() if old in t], old
+    assert "atomic" not in text["dual_contour.hip"].lower()
+    users = sorted(name for name, t in text.items() if name.endswith(".hip") and '#include "grid_mesh.hpp"' in t)
+    assert users == ["dual_contour.hip", "marching_cubes.hip"]
+    for rule in ("<DcPerCell>", "<DcPerSheet>"):                                  # both families in the one unit
+        assert rule in text["dual_contour.hip"]
 
 
 def test_flags_and_paths():

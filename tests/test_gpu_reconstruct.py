@@ -72,6 +72,37 @@ def test_batch_r64_b24_equals_single_grid():
     assert len(got[5][0]) == 0 and len(got[5][1]) == 0 and nonempty == B - 1
 
 
+def test_batch_of_33_grids_crosses_the_32_box_launch_in_all_three_meshers():
+    """The boxes of a batch travel as kernel arguments, 32 grids per launch: 33 grids with 33 different boxes put one
+    grid into a second launch of the edge-point, grid-normals and vertex kernels.  Every grid bit for bit the host
+    specification's, and grids 31, 32 and 0 the same grid meshed alone."""
+    import dual_contour_fixtures as F
+    from disn_amd import isosurface
+    R, B = 3, 33
+    fx = [F.noise(R, seed=b, box=F.UNIT * (0.5 + 0.01 * b)) for b in range(B)]
+    sdf, boxes = _stack([f[0] for f in fx]), np.asarray([f[1] for f in fx], np.float64)
+    mc = isosurface.marching_cubes_batch(sdf, boxes, R, 0.0)
+    dc = isosurface.dual_contour_batch(sdf, boxes, R, 0.0, None)
+    dcs = isosurface.dual_contour_batch(sdf, boxes, R, 0.0, None, sheets=True)
+    assert len(mc) == len(dc) == len(dcs) == B
+    for b, (vol, box, iso, _) in enumerate(fx):
+        nrm = isosurface.grid_normals_arrays(vol, box, iso)
+        want = {"mc": M.marching_cubes(vol.reshape((R + 1,) * 3), box, iso),
+                "dc": isosurface.dual_contour_arrays(vol, box, iso, nrm),
+                "dcs": isosurface.dual_contour_sheets_arrays(vol, box, iso, nrm)}
+        # no case can drop out silently: every grid has a surface under every mesher, and cells of several sheets
+        assert len(nrm) >= 59 and all(len(v) and len(f) for v, f in want.values()), b
+        assert len(want["mc"][0]) == len(nrm) and len(want["dc"][0]) != len(want["dcs"][0]), b
+        for name, got in (("mc", mc[b]), ("dc", dc[b]), ("dcs", dcs[b])):
+            assert _same(_host(got), want[name]), "%s: grid %d differs from the host specification" % (name, b)
+    for b in (31, 32, 0):
+        one = slice(b, b + 1)
+        assert _same(_host(isosurface.marching_cubes_batch(sdf[one], boxes[one], R, 0.0)[0]), _host(mc[b])), b
+        assert _same(_host(isosurface.marching_cubes(sdf[b], boxes[b], R, 0.0)), _host(mc[b])), b
+        assert _same(_host(isosurface.dual_contour(sdf[b], boxes[b], R, 0.0)), _host(dc[b])), b
+        assert _same(_host(isosurface.dual_contour(sdf[b], boxes[b], R, 0.0, sheets=True)), _host(dcs[b])), b
+
+
 # ------------------------------------------------------------------ 2. workspace bounds, split batches
 def test_workspace_bounds_and_split():
     from disn_amd import isosurface
