@@ -251,23 +251,29 @@ def clean_args(clean) -> Optional[Tuple[float, float, str]]:
     return dist_thresh, num_thresh, connectivity
 
 
+def _through(meshes, on: bool, call, select=None):
+    """pick, call once, scatter back: the meshes with triangles that ``select`` marks (None: all) go through ONE
+    ``call(their indices, those meshes)`` -> their new meshes in that order, None for one that stays as it is.
+    -> (meshes, left [B] bool: the picked meshes that stayed).  Not ``on``, or nothing picked: no call."""
+    meshes = list(meshes)
+    left = [False] * len(meshes)
+    picked = [b for b, m in enumerate(meshes) if (select is None or select[b]) and len(m[1])] if on else []
+    if picked:
+        for b, m in zip(picked, call(picked, [meshes[b] for b in picked])):
+            if m is None:
+                left[b] = True
+            else:
+                meshes[b] = m
+    return meshes, left
+
+
 def clean_group(meshes, clean, select=None, strict: bool = True):
     """the small-part cleanup of one group right behind its meshing: the meshes ``select`` marks (None: all) that
     have triangles go through ONE ``clean_meshes_device`` call.  -> (meshes, unclean [B] bool).  ``strict``: a mesh
     of which nothing is kept raises; otherwise it stays as it is and is marked in ``unclean``."""
-    from .postprocess import clean_meshes_device
-    meshes = list(meshes)
-    unclean = [False] * len(meshes)
-    picked = [b for b, m in enumerate(meshes) if (select is None or select[b]) and len(m[1])]
-    if clean is None or not picked:
-        return meshes, unclean
-    cleaned, _ = clean_meshes_device([meshes[b] for b in picked], clean[0], clean[1], clean[2], strict=strict)
-    for b, m in zip(picked, cleaned):
-        if m is None:
-            unclean[b] = True
-        else:
-            meshes[b] = m
-    return meshes, unclean
+    from . import postprocess
+    return _through(meshes, clean is not None, lambda picked, some: postprocess.clean_meshes_device(
+        some, clean[0], clean[1], clean[2], strict=strict)[0], select)
 
 
 def simplify_args(simplify) -> Optional[int]:
@@ -288,16 +294,9 @@ def simplify_args(simplify) -> Optional[int]:
 def simplify_group(meshes, simplify, boxes):
     """the simplification of one group behind its meshing and cleanup: the meshes that have triangles go through ONE
     ``simplify_meshes_device`` call, each on the lattice of its own box (``boxes`` [B,6]) -> the meshes"""
-    from .postprocess import simplify_meshes_device
-    meshes = list(meshes)
-    picked = [b for b, m in enumerate(meshes) if len(m[1])]
-    if simplify is None or not picked:
-        return meshes
-    boxes = np.asarray(boxes, np.float64).reshape(len(meshes), 6)
-    simplified, _ = simplify_meshes_device([meshes[b] for b in picked], boxes[picked], simplify)
-    for b, m in zip(picked, simplified):
-        meshes[b] = m
-    return meshes
+    from . import postprocess
+    return _through(meshes, simplify is not None, lambda picked, some: postprocess.simplify_meshes_device(
+        some, np.asarray(boxes, np.float64).reshape(len(meshes), 6)[picked], simplify)[0])[0]
 
 
 SMOOTH_CAP_CELLS = 0.5        # --smooth_cap: the largest move of a coordinate, in grid cells of the view's box
@@ -345,17 +344,13 @@ def smooth_cap(smooth, boxes, sdf_res: int):
 def smooth_group(meshes, smooth, boxes, sdf_res: int):
     """the smoothing of one group behind its meshing, cleanup and simplification: the meshes that have triangles go
     through ONE ``smooth_meshes_device`` call, each with the cap of its own box (``boxes`` [B,6]) -> the meshes"""
-    from .postprocess import smooth_meshes_device
-    meshes = list(meshes)
-    picked = [b for b, m in enumerate(meshes) if len(m[1])]
-    if smooth is None or not picked:
-        return meshes
-    cap = smooth_cap(smooth, np.asarray(boxes, np.float64).reshape(len(meshes), 6), sdf_res)
-    smoothed, _ = smooth_meshes_device([meshes[b] for b in picked], smooth["iters"], smooth["lam"], smooth["mu"],
-                                       smooth["pin_boundary"], None if cap is None else cap[picked])
-    for b, m in zip(picked, smoothed):
-        meshes[b] = m
-    return meshes
+    from . import postprocess
+
+    def call(picked, some):
+        cap = smooth_cap(smooth, np.asarray(boxes, np.float64).reshape(len(meshes), 6), sdf_res)
+        return postprocess.smooth_meshes_device(some, smooth["iters"], smooth["lam"], smooth["mu"],
+                                                smooth["pin_boundary"], None if cap is None else cap[picked])[0]
+    return _through(meshes, smooth is not None, call)[0]
 
 
 MIRROR_AXES = {"x": 0, "y": 1, "z": 2, "0": 0, "1": 1, "2": 2, 0: 0, 1: 1, 2: 2}
@@ -538,13 +533,39 @@ def reconstruct(engine, imgs, trans_mats, sdf_params, sdf_res: int, iso: float =
                 normals: bool = False, band=None, clean=None, simplify=None, colour=None, alpha=None, smooth=None,
                 mesher: str = "mc", dc=None):
     """``reconstruct_select`` for callers that clean every mesh or none (see there); -> the meshes"""
-    more = {} if colour is None or colour is False else {"colour": colour, "alpha": alpha}
-    if smooth is not None:
-        more["smooth"] = smooth
-    if mesher != "mc" or dc is not None:
-        more.update(mesher=mesher, dc=dc)
     return reconstruct_select(engine, imgs, trans_mats, sdf_params, sdf_res, iso, refine, normals, band, clean,
-                              simplify=simplify, **more)[0]
+                              simplify=simplify, colour=colour, alpha=alpha, smooth=smooth, mesher=mesher, dc=dc)[0]
+
+
+def _mesh_stages(engine, enc, imgs, trans_mats, grids, sp, sdf_res: int, iso: float, views_per_mesh: int, clean,
+                 simplify, smooth, colour, dc, refine: int = 0, normals: bool = False, select=None,
+                 strict: bool = True, alpha=None):
+    """THE stage chain of ``reconstruct_select`` and ``reconstruct_fused_select``: the group's grids [M,(res+1)^3] with
+    their boxes ``sp`` [M,6] -> (M meshes, unclean [M] bool).  The stage values are the CHECKED ones of the ``*_args``
+    functions (None: the stage is off and makes no device call); mesh m belongs to views m V .. (m + 1) V - 1 of
+    ``imgs`` / ``trans_mats`` / ``alpha`` (V = ``views_per_mesh``).  The order, and what every stage sees:
+      1. ``mesh_group``: the grids -> (verts, faces) per mesh, marching cubes or (``dc``) dual contouring -- with the
+         network's normals from ``enc``, with the grid's when ``enc`` is None (the fused route);
+      2. ``clean_group``: the meshes as they were meshed, so the rule sees the vertices the reference's rule sees and
+         a dropped part is never simplified, smoothed or refined; only the meshes ``select`` marks;
+      3. ``simplify_group``: the cleaned meshes, each on the lattice of its own box;
+      4. ``smooth_group``: the cleaned, simplified meshes, each with the cap of its own box;
+      5. ``isosurface.refine_mesh`` mesh by mesh, when ``refine`` > 0 or ``normals`` (needs ``enc``: V = 1): the Newton
+         steps pull the moved vertices back onto the network's level set, the normals are the gradients at the final
+         vertices;
+      6. ``colour_group``: the final meshes; vertices, faces and normals are not touched.
+    Faces change in stages 2 and 3 only."""
+    from . import isosurface
+    meshes = mesh_group(grids, sp, sdf_res, iso, dc, engine, enc, trans_mats)
+    meshes, unclean = clean_group(meshes, clean, select, strict)
+    meshes = smooth_group(simplify_group(meshes, simplify, sp), smooth, sp, sdf_res)
+    if refine > 0 or normals:
+        meshes = [tuple(isosurface.refine_mesh(engine, enc, b, trans_mats, verts, faces, sp[b], sdf_res, iso,
+                                               max(int(refine), 0))[:3 if normals else 2])
+                  for b, (verts, faces) in enumerate(meshes)]
+    if colour is not None:
+        meshes = colour_group(meshes, colour, imgs, trans_mats, views_per_mesh, alpha)
+    return meshes, unclean
 
 
 def reconstruct_select(engine, imgs, trans_mats, sdf_params, sdf_res: int, iso: float = 0.0, refine: int = 0,
@@ -554,57 +575,43 @@ def reconstruct_select(engine, imgs, trans_mats, sdf_params, sdf_res: int, iso: 
     ``create_sdf`` in one [B,(res+1)^3] tensor, ONE batched meshing (one host sync for the group).
     -> B x (verts [nv,3] float32, faces [nf,3] int32) device views; the bits are those of ``create_sdf``
     followed by ``isosurface.marching_cubes`` image by image.
-    ``refine`` > 0: behind the meshing every view's vertices take that many Newton steps onto the network's iso
-    level set (``isosurface.refine_mesh``, from the view's cached folded map); ``normals``: every mesh is a triple
+    The stages behind the meshing, all off by default, run in the order of ``_mesh_stages`` (see there for what each
+    one sees), whatever the order of the arguments:
+    ``refine`` > 0: every view's vertices take that many Newton steps onto the network's iso level set
+    (``isosurface.refine_mesh``, from the view's cached folded map); ``normals``: every mesh is a triple
     (verts, faces, normals [nv,3]) with the unit gradient at its (refined) vertices.  Faces never change.
     ``band`` = (stride, margin, dilate): the grids come from the narrow-band evaluation (one more host sync for the
     group: the band sizes); the bits are those of ``engine.query_grid_band`` and ``marching_cubes`` image by image.
-    ``clean`` = (dist_thresh, num_thresh, connectivity): right behind the meshing and BEFORE the refinement the small
-    and the far parts are dropped on the device (``clean_group``: one more host sync for the group, the cleaned
-    sizes), so the rule sees the vertices the reference's rule sees and dropped parts are never refined; the bits are
-    those of ``postprocess.clean_arrays`` on the uncleaned mesh.  ``select`` [B] bool: only those meshes are cleaned.
+    ``clean`` = (dist_thresh, num_thresh, connectivity): the small and the far parts are dropped on the device
+    (``clean_group``: one more host sync for the group, the cleaned sizes); the bits are those of
+    ``postprocess.clean_arrays`` on the uncleaned mesh.  ``select`` [B] bool: only those meshes are cleaned.
     A mesh of which nothing is kept raises ValueError (``strict``; False: it stays uncleaned).
-    ``simplify`` = CELLS: behind the cleanup and BEFORE the refinement every mesh with triangles is simplified on the
-    lattice of CELLS cells along the longest side of its view's ``sdf_params`` box (``simplify_group``: one more host
-    sync for the group, the simplified sizes); the bits are those of ``postprocess.simplify_arrays`` on the (cleaned)
-    mesh.  The refinement then pulls the moved vertices back onto the network's level set, and the normals are the
-    gradients at the final vertices.
-    ``smooth`` = ITERS or a dict (``smooth_args``): behind the simplification and BEFORE the refinement every mesh with
-    triangles is faired by Taubin smoothing (``smooth_group``: one more host sync for the group, the status words), no
-    coordinate further than ``cap`` grid cells of its view's box from where it was; the bits are those of
-    ``postprocess.smooth_arrays`` on the (cleaned, simplified) mesh.  Faces never change.
-    ``colour`` = True or a dict (``colour_args``): behind every other stage each mesh is coloured from its own view
-    (``colour_group``; ``alpha`` None or [B,137,137] uint8 masks the background) and gains ``colours`` uint8 [nv,3] as
-    its last element: (verts, faces[, normals], colours).  Vertices, faces and normals are bit for bit those of the
-    call without it; the bytes are those of ``postprocess.colour_arrays`` on the final mesh.
+    ``simplify`` = CELLS: every mesh with triangles is simplified on the lattice of CELLS cells along the longest side
+    of its view's ``sdf_params`` box (``simplify_group``: one more host sync for the group, the simplified sizes); the
+    bits are those of ``postprocess.simplify_arrays`` on the (cleaned) mesh.
+    ``smooth`` = ITERS or a dict (``smooth_args``): every mesh with triangles is faired by Taubin smoothing
+    (``smooth_group``: one more host sync for the group, the status words), no coordinate further than ``cap`` grid
+    cells of its view's box from where it was; the bits are those of ``postprocess.smooth_arrays`` on the (cleaned,
+    simplified) mesh.  Faces never change.
+    ``colour`` = True or a dict (``colour_args``): each mesh is coloured from its own view (``colour_group``; ``alpha``
+    None or [B,137,137] uint8 masks the background) and gains ``colours`` uint8 [nv,3] as its last element: (verts,
+    faces[, normals], colours).  Vertices, faces and normals are bit for bit those of the call without it; the bytes
+    are those of ``postprocess.colour_arrays`` on the final mesh.
     ``mesher`` = "dc" (``dc``: see ``dc_args``): the grids, dense or banded, go through dual contouring instead of
     marching cubes (``mesh_group``: one vertex per crossed cell placed by a quadric from the network's gradients at
     the cut edges, so creases survive; the mesh can be non-manifold where a cell holds several sheets); every later
     stage sees a (verts, faces) pair as before.  The bits are those of ``isosurface.dual_contour_batch`` on the grids.
     -> (meshes, unclean [B] bool)"""
-    from . import isosurface
     band = band_args(band, sdf_res)
-    clean = clean_args(clean)
-    simplify = simplify_args(simplify)
-    colour = colour_args(colour)
-    smooth = smooth_args(smooth)
+    clean, simplify, colour, smooth = clean_args(clean), simplify_args(simplify), colour_args(colour), smooth_args(smooth)
     dc = dc_args(mesher, dc)
     if band is None:
         enc, grids = _encode_grids(engine, imgs, trans_mats, sdf_params, sdf_res)
     else:
         enc, grids, _ = _encode_grids_band(engine, imgs, trans_mats, sdf_params, sdf_res, iso, band)
     sp = np.asarray(sdf_params, dtype=np.float64).reshape(grids.shape[0], 6)
-    meshes, unclean = clean_group(mesh_group(grids, sp, sdf_res, iso, dc, engine, enc, trans_mats), clean, select, strict)
-    meshes = simplify_group(meshes, simplify, sp)
-    if smooth is not None:
-        meshes = smooth_group(meshes, smooth, sp, sdf_res)
-    if refine <= 0 and not normals:
-        return (meshes if colour is None else colour_group(meshes, colour, imgs, trans_mats, 1, alpha)), unclean
-    out = []
-    for b, (verts, faces) in enumerate(meshes):
-        v, f, n = isosurface.refine_mesh(engine, enc, b, trans_mats, verts, faces, sp[b], sdf_res, iso, max(int(refine), 0))
-        out.append((v, f, n) if normals else (v, f))
-    return (out if colour is None else colour_group(out, colour, imgs, trans_mats, 1, alpha)), unclean
+    return _mesh_stages(engine, enc, imgs, trans_mats, grids, sp, sdf_res, iso, 1, clean, simplify, smooth, colour, dc,
+                        refine, normals, select, strict, alpha)
 
 
 def fuse_args(fuse, pool: str = "max") -> Optional[Tuple[int, str]]:
@@ -626,13 +633,9 @@ def reconstruct_fused(engine, imgs, trans_mats, sdf_params, sdf_res: int, iso: f
                       pool: str = "max", clean=None, simplify=None, colour=None, alpha=None, smooth=None,
                       mesher: str = "mc", dc=None):
     """``reconstruct_fused_select`` for callers that clean every mesh or none (see there); -> the meshes"""
-    more = {} if colour is None or colour is False else {"colour": colour, "alpha": alpha}
-    if smooth is not None:
-        more["smooth"] = smooth
-    if mesher != "mc" or dc is not None:
-        more.update(mesher=mesher, dc=dc)
     return reconstruct_fused_select(engine, imgs, trans_mats, sdf_params, sdf_res, iso, fuse, pool, clean,
-                                    simplify=simplify, **more)[0]
+                                    simplify=simplify, colour=colour, alpha=alpha, smooth=smooth, mesher=mesher,
+                                    dc=dc)[0]
 
 
 def reconstruct_fused_select(engine, imgs, trans_mats, sdf_params, sdf_res: int, iso: float = 0.0, fuse: int = 2,
@@ -642,23 +645,19 @@ def reconstruct_fused_select(engine, imgs, trans_mats, sdf_params, sdf_res: int,
     (cameras trans_mats [B,4,3] in the object's frame, the run's grid box = its first view's sdf_params).  One
     ``engine.encode`` call, one ``engine.query_grid_views`` grid per run (features pooled over the run's views,
     ``pool`` = "max" or "mean"), ONE batched meshing -> B / fuse x (verts, faces); a run's bits are those of
-    ``query_grid_views`` followed by ``isosurface.marching_cubes`` on that run alone.  ``clean``, ``select`` (one
-    entry per RUN), ``strict``, ``simplify`` (on the lattice of the run's box) and ``smooth`` (the cap in cells of the
-    run's box) as in ``reconstruct_select``;
+    ``query_grid_views`` followed by ``isosurface.marching_cubes`` on that run alone.  The stages behind the meshing
+    run in the order of ``_mesh_stages``: ``clean``, ``select`` (one entry per RUN), ``strict``, ``simplify`` (on the
+    lattice of the run's box) and ``smooth`` (the cap in cells of the run's box) as in ``reconstruct_select``;
     ``colour``: every run's mesh is coloured from ALL ``fuse`` views of the run (``alpha`` None or [B,137,137]).
-    ``mesher`` = "dc": dual contouring with the GRID normals whatever ``dc`` asks for (this route has no gradient entry).
+    ``mesher`` = "dc": dual contouring with the GRID normals whatever ``dc`` asks for (this route has no gradient entry,
+    and so no ``refine`` and no ``normals``).
     -> (meshes, unclean [B / fuse] bool)"""
     import torch
-
-    from . import isosurface
     checked = fuse_args(fuse, pool)
     if checked is None:
         raise ValueError("reconstruct_fused needs the number of views to fuse")
     V, pool = checked
-    clean = clean_args(clean)
-    simplify = simplify_args(simplify)
-    colour = colour_args(colour)
-    smooth = smooth_args(smooth)
+    clean, simplify, colour, smooth = clean_args(clean), simplify_args(simplify), colour_args(colour), smooth_args(smooth)
     dc = dc_args(mesher, dc)
     imgs = np.asarray(imgs, np.float32) if not isinstance(imgs, torch.Tensor) else imgs
     B = imgs.shape[0]
@@ -671,11 +670,8 @@ def reconstruct_fused_select(engine, imgs, trans_mats, sdf_params, sdf_res: int,
     grids = torch.empty((B // V, (sdf_res + 1) ** 3), dtype=torch.float32, device=engine.device)
     for r in range(B // V):
         engine.query_grid_views(enc, (r * V, V), tm[r * V:(r + 1) * V], sp[r], sdf_res, pool, out=grids[r])
-    meshes, unclean = clean_group(mesh_group(grids, sp, sdf_res, iso, dc), clean, select, strict)
-    meshes = simplify_group(meshes, simplify, sp)
-    if smooth is not None:
-        meshes = smooth_group(meshes, smooth, sp, sdf_res)
-    return (meshes if colour is None else colour_group(meshes, colour, imgs, tm, V, alpha)), unclean
+    return _mesh_stages(engine, None, imgs, tm, grids, sp, sdf_res, iso, V, clean, simplify, smooth, colour, dc,
+                        select=select, strict=strict, alpha=alpha)
 
 
 def fuse_runs(entries: Sequence, fuse: int) -> List[List]:
@@ -782,7 +778,6 @@ def parser():
     p.add_argument("--refine", type=int, default=0, metavar="ITERS",
                    help="Newton steps that move every vertex onto the network's iso level set [default: 0, none]")
     p.add_argument("--normals", action="store_true", help="write the unit SDF gradient at every vertex as 'vn' lines")
-    add_band_flags(p)
     p.add_argument("--fuse_views", type=int, default=0, metavar="V",
                    help="multi-view: fuse every run of V chosen views of an object into ONE mesh (features pooled "
                         "over the views); view_num and batch_size must be multiples of V [default: 0, one mesh per view]")
@@ -790,13 +785,34 @@ def parser():
     p.add_argument("--clean", default=None, metavar="CATS",
                    help="drop the small and the far parts of the meshes of these categories on the device: clean (the "
                         "reference's five), all, or names separated by commas; results go to <...>_comb")
-    add_clean_flags(p)
-    add_simplify_flag(p)
-    add_smooth_flags(p)
-    add_colour_flags(p)
+    add_stage_flags(p)
     add_score_flags(p)
-    add_dc_flags(p)
     return p
+
+
+def add_stage_flags(p) -> None:
+    """the flags of the stages that both command lines share; ``--clean`` itself stays with each parser (categories
+    here, a switch in the demo)"""
+    for add in (add_band_flags, add_clean_flags, add_simplify_flag, add_smooth_flags, add_colour_flags, add_dc_flags):
+        add(p)
+
+
+def stages_from_flags(a, clean_on: bool) -> dict:
+    """the checked stage values of a command line, as ``reconstruct_select`` takes them: every key always there, None
+    for a stage that is off (ValueError for a bad value or an option whose stage is off; no device work)"""
+    return {"band": band_from_flags(a), "clean": clean_from_flags(a, clean_on), "simplify": simplify_from_flags(a),
+            "smooth": smooth_from_flags(a), "colour": colour_from_flags(a), "mesher": a.mesher, "dc": dc_from_flags(a)}
+
+
+def write_mesh(path: str, mesh, coloured: bool) -> str:
+    """(verts, faces[, normals][, colours]) -> the .obj at ``path``; ``coloured``: the last element is the colours"""
+    from . import isosurface
+    verts, faces, *extras = mesh
+    if coloured:
+        isosurface.write_obj(path, verts, faces, *extras[:-1], colours=extras[-1])
+    else:
+        isosurface.write_obj(path, verts, faces, *extras)
+    return path
 
 
 def add_dc_flags(p) -> None:
@@ -952,13 +968,9 @@ def check_flags(a) -> Optional[Tuple[int, str]]:
         raise ValueError("--sdf_res must be positive")
     if a.refine < 0:
         raise ValueError("--refine must not be negative")
-    band_from_flags(a)
-    clean_cats_from_flags(a)
-    simplify_from_flags(a)
-    smooth_from_flags(a)
-    colour_from_flags(a)
+    stages_from_flags(a, a.clean is not None)
+    clean_cats_from_flags(a)                     # (an unknown category)
     score_from_flags(a)
-    dc_from_flags(a)
     return fuse_from_flags(a)
 
 
@@ -1000,29 +1012,19 @@ def main(argv=None, reconstruct_fn: Optional[Callable] = None) -> dict:
     from concurrent.futures import ThreadPoolExecutor
     from datetime import datetime
 
-    from . import isosurface
     from .evaluate import categories
     a = parser().parse_args(argv)
     fuse = check_flags(a)
     batch_size = a.view_num if a.batch_size is None else a.batch_size
     per_mesh = fuse[0] if fuse else 1            # views that make one mesh; a mesh is named after the first of them
-    cleaning = clean_cats_from_flags(a)
-    simplify = simplify_from_flags(a)
-    colour = colour_from_flags(a)
+    stages = stages_from_flags(a, a.clean is not None)
+    cleaning = stages["clean"] is not None
+    clean_cats = clean_cats_from_flags(a)[1] if cleaning else set()
     score = score_from_flags(a)
-    smooth = smooth_from_flags(a)
-    dc = dc_from_flags(a)
-    more = {} if simplify is None else {"simplify": simplify}     # (without the flag every call below is as it was)
-    out_dir = result_obj_path(a.log_dir, a.sdf_res, a.iso, a.cam_est, fuse, clean=cleaning is not None, **more,
-                              **({} if colour is None else {"colour": True}),
-                              **({} if smooth is None else {"smooth": smooth["iters"]}),
-                              **({} if dc is None else {"mesher": a.mesher}))
-    if dc is not None:
-        more.update(mesher=a.mesher, dc=dc)
-    if smooth is not None:
-        more["smooth"] = smooth
-    if colour is not None:
-        more["colour"] = colour
+    smooth, coloured = stages["smooth"], stages["colour"] is not None
+    out_dir = result_obj_path(a.log_dir, a.sdf_res, a.iso, a.cam_est, fuse, clean=cleaning, simplify=stages["simplify"],
+                              colour=coloured, smooth=None if smooth is None else smooth["iters"],
+                              mesher=stages["mesher"])
     entries = sample_list(categories(a.category), a.test_lst_dir, a.view_num, a.seed, a.num_shards, a.shard_id)
     if fuse:
         runs = fuse_runs(entries, per_mesh)
@@ -1040,22 +1042,15 @@ def main(argv=None, reconstruct_fn: Optional[Callable] = None) -> dict:
         engine = SdfEngine(store, torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available()
                            else None, strict=a.strict)
 
-        band = band_from_flags(a)
-
         def reconstruct_fn(imgs, trans_mats, sdf_params, select=None):
-            if cleaning is not None:
-                if fuse:
-                    return reconstruct_fused_select(engine, imgs, trans_mats, sdf_params, a.sdf_res, a.iso, fuse[0],
-                                                    fuse[1], cleaning[0], select, strict=False, **more)
-                return reconstruct_select(engine, imgs, trans_mats, sdf_params, a.sdf_res, a.iso, a.refine, a.normals,
-                                          band, cleaning[0], select, strict=False, **more)
-            if fuse:
-                return reconstruct_fused(engine, imgs, trans_mats, sdf_params, a.sdf_res, a.iso, fuse[0], fuse[1],
-                                         **more)
-            if band is None:
-                return reconstruct(engine, imgs, trans_mats, sdf_params, a.sdf_res, a.iso, a.refine, a.normals, **more)
-            return reconstruct(engine, imgs, trans_mats, sdf_params, a.sdf_res, a.iso, a.refine, a.normals, band=band,
-                               **more)
+            if fuse:                             # (no band: ``fuse_from_flags`` refuses it, the route does not take it)
+                out = reconstruct_fused_select(engine, imgs, trans_mats, sdf_params, a.sdf_res, a.iso, fuse=fuse[0],
+                                               pool=fuse[1], select=select, strict=False,
+                                               **{k: v for k, v in stages.items() if k != "band"})
+            else:
+                out = reconstruct_select(engine, imgs, trans_mats, sdf_params, a.sdf_res, a.iso, refine=a.refine,
+                                         normals=a.normals, select=select, strict=False, **stages)
+            return out if cleaning else out[0]   # the contract of an injected function: the pair only with --clean
 
     os.makedirs(out_dir, exist_ok=True)
     logf = open(os.path.join(a.log_dir, "log_test.txt"), "a")
@@ -1064,13 +1059,6 @@ def main(argv=None, reconstruct_fn: Optional[Callable] = None) -> dict:
         logf.write(s + "\n")
         logf.flush()
         print(s)
-
-    def write(path, verts, faces, *extras):
-        if colour is None:
-            isosurface.write_obj(path, verts, faces, *extras)  # device-to-host copy + file, on a writer thread
-        else:                                                  # (verts, faces[, normals], colours)
-            isosurface.write_obj(path, verts, faces, *extras[:-1], colours=extras[-1])
-        return path
 
     written = empty = unclean = scored = 0
     score_cache: dict = {}
@@ -1090,12 +1078,12 @@ def main(argv=None, reconstruct_fn: Optional[Callable] = None) -> dict:
             for gi, group in enumerate(work):
                 batch = nxt.result()
                 nxt = fetch(work[gi + 1]) if gi + 1 < len(work) else None
-                if cleaning is None:
+                if cleaning:
+                    meshes, left = reconstruct_fn(batch["img"], batch["trans_mat"], batch["sdf_params"],
+                                                  [e[0] in clean_cats for e in group[::per_mesh]])
+                else:
                     meshes = reconstruct_fn(batch["img"], batch["trans_mat"], batch["sdf_params"])
                     left = [False] * len(meshes)
-                else:
-                    meshes, left = reconstruct_fn(batch["img"], batch["trans_mat"], batch["sdf_params"],
-                                                  [e[0] in cleaning[1] for e in group[::per_mesh]])
                 if len(meshes) * per_mesh != len(group):
                     raise RuntimeError("group %d: %d meshes for %d views" % (gi, len(meshes), len(group)))
                 for f in in_flight:                         # the group before this one: a writer's exception surfaces
@@ -1107,7 +1095,8 @@ def main(argv=None, reconstruct_fn: Optional[Callable] = None) -> dict:
                         for row in rows:
                             sf.write(json.dumps(row) + "\n")
                     scored += sum(r["status"] == 0 for r in rows)
-                for (cat_id, obj, view), (verts, faces, *vn), as_it_is in zip(group[::per_mesh], meshes, left):
+                for (cat_id, obj, view), mesh, as_it_is in zip(group[::per_mesh], meshes, left):
+                    verts, faces = mesh[:2]
                     path = obj_path(out_dir, cat_id, obj, view)
                     if as_it_is:
                         unclean += 1
@@ -1117,7 +1106,7 @@ def main(argv=None, reconstruct_fn: Optional[Callable] = None) -> dict:
                         log_string("%d/%d, EMPTY mesh (no surface at iso %s): %s" % (gi, len(work), a.iso, path))
                     else:
                         log_string("%d/%d, submit create_obj %s, %s, %s" % (gi, len(work), cat_id, obj, view))
-                    in_flight.append(writers.submit(write, path, verts, faces, *vn))
+                    in_flight.append(writers.submit(write_mesh, path, mesh, coloured))     # device-to-host copy + file
                     written += 1
             for f in in_flight:
                 f.result()
@@ -1126,16 +1115,11 @@ def main(argv=None, reconstruct_fn: Optional[Callable] = None) -> dict:
     finally:
         logf.close()
     res = {"written": written, "skipped": len(entries) - len(todo), "empty": empty, "out_dir": out_dir}
-    if cleaning is not None:
-        res["unclean"] = unclean
-    if simplify is not None:
-        res["simplified"] = written - empty
-    if smooth is not None:
-        res["smoothed"] = written - empty
-    if colour is not None:
-        res["coloured"] = written - empty
-    if score is not None:
-        res["scored"] = scored
+    for key, stage, count in (("unclean", stages["clean"], unclean), ("simplified", stages["simplify"], written - empty),
+                              ("smoothed", smooth, written - empty), ("coloured", stages["colour"], written - empty),
+                              ("scored", score, scored)):
+        if stage is not None:
+            res[key] = count
     return res
 
 

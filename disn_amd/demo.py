@@ -101,16 +101,10 @@ def parser() -> argparse.ArgumentParser:
     p.add_argument("--preview", default=None, metavar="OUT.png",
                    help="also write the sphere-traced view of the predicted surface from the camera in use")
     p.add_argument("--preview_size", type=int, default=137, metavar="N", help="the preview is N x N [default: 137]")
-    from .create_sdf import add_band_flags, add_clean_flags, add_colour_flags, add_simplify_flag, add_smooth_flags
-    add_band_flags(p)
+    from .create_sdf import add_stage_flags
     p.add_argument("--clean", action="store_true",
                    help="drop the mesh's small and far parts on the device (postprocess.clean_meshes_device)")
-    add_clean_flags(p)
-    add_simplify_flag(p)
-    add_smooth_flags(p)
-    add_colour_flags(p)
-    from .create_sdf import add_dc_flags
-    add_dc_flags(p)
+    add_stage_flags(p)
     return p
 
 
@@ -146,16 +140,9 @@ def write_preview(engine, img: np.ndarray, trans_mat, path: str, size: int, iso:
 def main(argv=None) -> dict:
     """-> {"out", "verts", "faces", "trans_mat"}, with ``--colour`` also "coloured" (True) and "colours" (uint8 [nv,3])"""
     a = parser().parse_args(argv)
-    from . import isosurface
-    from .create_sdf import (band_from_flags, clean_from_flags, colour_from_flags, reconstruct, restore_weights,
-                             simplify_from_flags, smooth_from_flags)
-    band = band_from_flags(a)                                          # a bad stride / resolution: before anything else
-    clean = clean_from_flags(a, a.clean)
-    simplify = simplify_from_flags(a)
-    colour = colour_from_flags(a)
-    smooth = smooth_from_flags(a)
-    from .create_sdf import dc_from_flags
-    dc = dc_from_flags(a)
+    from .create_sdf import reconstruct, restore_weights, stages_from_flags, write_mesh
+    stages = stages_from_flags(a, a.clean)                             # a bad flag: before anything else
+    coloured = stages["colour"] is not None
     img = read_image(a.img)
     if img.shape[1:3] != (137, 137):
         raise ValueError("%s is %dx%d; the network reads 137x137 renderings" % (a.img, img.shape[2], img.shape[1]))
@@ -172,29 +159,16 @@ def main(argv=None) -> dict:
     engine = SdfEngine(store)
     if a.refine < 0:
         raise ValueError("--refine must not be negative")
-    extra = {} if band is None else {"band": band}
-    if clean is not None:
-        extra["clean"] = clean
-    if simplify is not None:
-        extra["simplify"] = simplify
-    if smooth is not None:
-        extra["smooth"] = smooth
-    if dc is not None:
-        extra.update(mesher=a.mesher, dc=dc)
-    if colour is not None:
-        alpha = read_alpha(a.img)                                      # the background of the rendering colours nothing
-        extra.update(colour=colour, alpha=None if alpha is None else alpha[None])
-    verts, faces, *vn = reconstruct(engine, img, trans_mat, DEMO_SDF_PARAMS, a.sdf_res, a.iso, a.refine, a.normals,
-                                    **extra)[0]
-    if colour is None:
-        isosurface.write_obj(a.out, verts, faces, *vn)
-    else:
-        isosurface.write_obj(a.out, verts, faces, *vn[:-1], colours=vn[-1])
+    alpha = read_alpha(a.img) if coloured else None                    # the background of the rendering colours nothing
+    mesh = reconstruct(engine, img, trans_mat, DEMO_SDF_PARAMS, a.sdf_res, a.iso, a.refine, a.normals,
+                       alpha=None if alpha is None else alpha[None], **stages)[0]
+    verts, faces = mesh[:2]
+    write_mesh(a.out, mesh, coloured)
     print("wrote %s: %d vertices, %d triangles" % (a.out, len(verts), len(faces)))
     tm = trans_mat.cpu().numpy() if hasattr(trans_mat, "cpu") else trans_mat
     res = {"out": a.out, "verts": len(verts), "faces": len(faces), "trans_mat": tm}
-    if colour is not None:
-        res["coloured"], res["colours"] = True, vn[-1].cpu().numpy()
+    if coloured:
+        res["coloured"], res["colours"] = True, mesh[-1].cpu().numpy()
     if a.preview:
         res["preview"] = write_preview(engine, img, trans_mat, a.preview, a.preview_size, a.iso, read_alpha(a.img))
     return res

@@ -161,6 +161,56 @@ def test_reconstruct_equals_create_sdf_then_marching_cubes():
     assert len(want[0][1]) > 0 and nonempty >= 3
 
 
+def _same_bits(a, b):
+    return len(a) == len(b) and all(x.dtype == y.dtype and x.shape == y.shape
+                                    and torch.equal(x.contiguous().view(torch.uint8), y.contiguous().view(torch.uint8))
+                                    for x, y in zip(a, b))
+
+
+def test_every_stage_at_once_equals_the_stage_functions_one_after_another(tmp_path):
+    """``reconstruct_select`` and ``reconstruct_fused_select`` with every stage on, bit for bit the public stage
+    functions called in the order documented at ``create_sdf._mesh_stages`` on the same grids"""
+    from disn_amd import create_sdf as cs, isosurface
+    from disn_amd.engine import SdfEngine
+    from disn_amd.weights import WeightStore
+    cats, objs = (("chair", "03001627"),), {"03001627": ["obj_a", "obj_b"]}
+    entries = RF.expected_entries(4, 2, cats, objs)
+    assert len(entries) == 4                                       # two objects, two views each: two runs of fuse=2
+    batch = cs.load_group(entries, *RF.build_dataset(str(tmp_path / "data"), entries))
+    imgs, tms, R, band = batch["img"], batch["trans_mat"], 8, (4, 0.5, 1)
+    sp = np.asarray(batch["sdf_params"], np.float64).reshape(4, 6)
+    eng = SdfEngine(WeightStore.random_init(3))
+    iso = float(cs.create_sdf(eng, imgs, tms, sp, R)[0].median())
+    on = {"clean": (3.0, 0.0, "face"), "strict": False, "simplify": 4, "smooth": 2, "colour": True, "mesher": "dcs"}
+    dc, smooth, colour = cs.dc_args("dcs"), cs.smooth_args(2), cs.colour_args(True)
+
+    def stages(meshes, boxes, refine, views_per_mesh, cams):
+        meshes, unclean = cs.clean_group(meshes, on["clean"], None, strict=False)
+        meshes = cs.smooth_group(cs.simplify_group(meshes, on["simplify"], boxes), smooth, boxes, R)
+        if refine:
+            meshes = [isosurface.refine_mesh(eng, enc, b, tms, v, f, boxes[b], R, iso, 1)
+                      for b, (v, f) in enumerate(meshes)]
+        return cs.colour_group(meshes, colour, imgs, cams, views_per_mesh), unclean
+
+    got, got_unclean = cs.reconstruct_select(eng, imgs, tms, sp, R, iso, refine=1, normals=True, band=band, **on)
+    enc = eng.encode(imgs)
+    grids = cs.create_sdf(eng, imgs, tms, sp, R, band=band, iso=iso)
+    want, want_unclean = stages(cs.mesh_group(grids, sp, R, iso, dc, eng, enc, tms), sp, True, 1, tms)
+    print("\n[pipeline] iso %.6g, triangles per view %s" % (iso, [len(m[1]) for m in want]))
+    assert len(got) == 4 and any(len(m[1]) for m in want) and got_unclean == want_unclean
+    for b in range(4):
+        assert len(got[b]) == 4 and _same_bits(got[b], want[b]), "view %d" % b
+
+    got, got_unclean = cs.reconstruct_fused_select(eng, imgs, tms, sp, R, iso, fuse=2, **on)
+    grids = torch.stack([eng.query_grid_views(enc, (2 * r, 2), tms[2 * r:2 * r + 2], sp[2 * r], R, "max")
+                         for r in range(2)])
+    want, want_unclean = stages(cs.mesh_group(grids, sp[::2], R, iso, dc), sp[::2], False, 2, tms)
+    print("[pipeline] fused: triangles per run %s" % [len(m[1]) for m in want])
+    assert len(got) == 2 and any(len(m[1]) for m in want) and got_unclean == want_unclean
+    for r in range(2):
+        assert len(got[r]) == 3 and _same_bits(got[r], want[r]), "run %d" % r
+
+
 # ------------------------------------------------------------------ 4. the command line, end to end
 def _tree(root):
     return sorted(os.path.relpath(os.path.join(d, f), root) for d, _, fs in os.walk(root) for f in fs)

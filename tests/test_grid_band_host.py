@@ -108,8 +108,10 @@ def test_band_flags_are_checked_before_any_device_work(tmp_path):
 
 
 def test_band_zero_takes_the_existing_call_path(tmp_path, monkeypatch):
-    """``--band 0``: ``reconstruct`` is called exactly as before the flag existed (no ``band`` argument) and goes
-    through ``_encode_grids``; ``--band 4``: the same call with ``band=(4, 0.5, 1)``"""
+    """``--band 0``: the driver's one call, ``reconstruct_select``, gets ``band=None`` and every other stage off, and
+    ``reconstruct`` goes through ``_encode_grids``; ``--band 4``: the same call with ``band=(4, 0.5, 1)``"""
+    import inspect
+
     import disn_amd.engine as engine_mod
     from disn_amd import isosurface
     entries = RF.expected_entries(4, 3)
@@ -124,20 +126,31 @@ def test_band_zero_takes_the_existing_call_path(tmp_path, monkeypatch):
         def __init__(self, *a, **k):
             pass
 
-    def fake_reconstruct(engine, imgs, tms, sps, *args, **kwargs):
-        calls.append((args, kwargs))
+    signature = inspect.signature(cs.reconstruct_select)
+
+    def fake_reconstruct(*args, **kwargs):
+        named = signature.bind(*args, **kwargs)
+        named.apply_defaults()
+        calls.append(named.arguments)
         t = np.array([[0, 0, 0], [1, 0, 0], [0, 1, 0], [0, 0, 1]], np.float32)
-        return [(t, np.array([[0, 2, 1], [0, 1, 3], [0, 3, 2], [1, 2, 3]], np.int32))] * imgs.shape[0]
+        B = named.arguments["imgs"].shape[0]
+        return [(t, np.array([[0, 2, 1], [0, 1, 3], [0, 3, 2], [1, 2, 3]], np.int32))] * B, [False] * B
+
+    def facts(c):
+        return [c[k] for k in ("sdf_res", "iso", "refine", "normals", "band")]
+
+    def rest_is_off(c):
+        return all(c[k] is None for k in ("clean", "simplify", "smooth", "colour", "dc")) and c["mesher"] == "mc"
 
     monkeypatch.setattr(engine_mod, "SdfEngine", FakeEngine)
     monkeypatch.setattr(cs, "restore_weights", lambda log_dir, seed: (None, "stub"))
-    monkeypatch.setattr(cs, "reconstruct", fake_reconstruct)
+    monkeypatch.setattr(cs, "reconstruct_select", fake_reconstruct)
     cs.main(argv)
     cs.main(argv + ["--band", "0", "--band_margin", "0.9"])
-    assert calls and all(c == ((8, 0.0, 0, False), {}) for c in calls)
+    assert calls and all(facts(c) == [8, 0.0, 0, False, None] and rest_is_off(c) for c in calls)
     calls.clear()
     cs.main(argv + ["--band", "4"])
-    assert calls and all(c == ((8, 0.0, 0, False), {"band": (4, 0.5, 1)}) for c in calls)
+    assert calls and all(facts(c) == [8, 0.0, 0, False, (4, 0.5, 1)] and rest_is_off(c) for c in calls)
     monkeypatch.undo()
 
     # reconstruct(band=None) itself: the dense grids, never the band's
