@@ -60,6 +60,12 @@ the whole group with one read-back (``isosurface.marching_cubes_batch``) and wri
     lines of the meshes done now are appended to those of the earlier runs).  A ground truth without area is logged
     and marked ``"gt_status": 6`` in its lines.  A mesh's samples depend on ``--seed`` and its file name alone.  Composes with every
     flag above; without it nothing changes.
+  * ``--check [--check_pairs 256]`` (not in the reference) measures every group's FINAL meshes where ``reconstruct``
+    left them, before the writers take them (``postprocess.check_meshes_device``): topology, orientation
+    and self-intersections, one JSON line per mesh in ``<out_dir>/checks.jsonl`` -- "cat", "obj", "view", "status",
+    every field of ``postprocess.CHECK_FIELDS``, "area", "volume" and the four derived booleans -- started afresh
+    by a run without ``--skip_existing``.  ``--check_pairs N``: the work cap, N candidate pairs per face (+ 4096); a
+    mesh over it has status 8 and -1 in its intersection fields.  No stage: the meshes and the tree's name stay.
   * ``--smooth ITERS [--smooth_cap CELLS] [--smooth_free_boundary]`` (1..64 iterations; not in the reference) fairs every
     mesh by Taubin's lambda|mu smoothing (``postprocess.smooth_meshes_device``) while the group still lies
     on the device: behind ``--clean`` and ``--simplify`` and BEFORE ``--refine`` and ``--normals``, so the smoothed
@@ -410,6 +416,7 @@ def colour_group(meshes, colour, imgs, trans_mats, views_per_mesh: int = 1, alph
     return out
 
 
+CHECK_PAIRS_PER_FACE = 256     # postprocess.CHECK_PAIRS_PER_FACE (imported late there: this module loads without torch)
 SCORE_POINTS = 2048
 SCORE_CACHE = 8               # ground-truth objects whose samples stay on the device between groups
 
@@ -787,6 +794,7 @@ def parser():
                         "reference's five), all, or names separated by commas; results go to <...>_comb")
     add_stage_flags(p)
     add_score_flags(p)
+    add_check_flags(p)
     return p
 
 
@@ -875,6 +883,47 @@ def score_from_flags(a) -> Optional[Tuple[str, int]]:
             raise ValueError("--score_points needs --score")
         return None
     return score_args((a.score, SCORE_POINTS if a.score_points is None else a.score_points))
+
+
+def add_check_flags(p) -> None:
+    p.add_argument("--check", action="store_true",
+                   help="check every final mesh on the device: topology, orientation, self-intersections; one JSON "
+                        "line per mesh in <out_dir>/checks.jsonl")
+    p.add_argument("--check_pairs", type=int, default=None, metavar="N",
+                   help="with --check: the work cap, candidate pairs per face [default: %d]" % CHECK_PAIRS_PER_FACE)
+
+
+def check_from_flags(a) -> Optional[int]:
+    """None without --check, else the checked pairs per face (ValueError for --check_pairs without --check or a
+    negative one)"""
+    if not a.check:
+        if a.check_pairs is not None:
+            raise ValueError("--check_pairs needs --check")
+        return None
+    n = CHECK_PAIRS_PER_FACE if a.check_pairs is None else a.check_pairs
+    if n < 0:
+        raise ValueError("--check_pairs must not be negative, got %r" % (n,))
+    return int(n)
+
+
+def check_group(meshes, keys, pairs_per_face: int, check_fn: Optional[Callable] = None) -> List[dict]:
+    """the FINAL meshes of one group, where ``reconstruct`` left them: ONE ``postprocess.check_meshes_device`` call (or
+    ``check_fn(meshes, max_pairs)`` in its place, for host-side tests of the drivers) -> one dict per mesh, ``keys``
+    [(cat_id, obj, view)] in mesh order: "cat", "obj", "view", then the dict of ``postprocess.check_arrays``.  The cap
+    of a mesh is ``pairs_per_face`` nf + 4096.  No mesh raises: its status is in its line."""
+    from . import postprocess
+    pairs = [(m[0], m[1]) for m in meshes]
+    caps = [pairs_per_face * int(m[1].shape[0]) + postprocess.CHECK_PAIRS_BASE for m in pairs]
+    if check_fn is None:
+        results = postprocess.check_meshes_device(pairs, max_pairs=caps, strict=False) if pairs else []
+    else:
+        results = check_fn(pairs, caps)
+    rows = []
+    for (c, o, v), r in zip(keys, results):
+        row = {"cat": c, "obj": o, "view": v}
+        row.update(r)
+        rows.append(row)
+    return rows
 
 
 def add_colour_flags(p) -> None:
@@ -971,6 +1020,7 @@ def check_flags(a) -> Optional[Tuple[int, str]]:
     stages_from_flags(a, a.clean is not None)
     clean_cats_from_flags(a)                     # (an unknown category)
     score_from_flags(a)
+    check_from_flags(a)
     return fuse_from_flags(a)
 
 
@@ -1000,9 +1050,10 @@ def load_group(group: Sequence, sdf_dir: str, rendered_dir: str, backcolorwhite:
     return data.get_batch(0)
 
 
-def main(argv=None, reconstruct_fn: Optional[Callable] = None) -> dict:
+def main(argv=None, reconstruct_fn: Optional[Callable] = None, check_fn: Optional[Callable] = None) -> dict:
     """-> {"written", "skipped", "empty", "out_dir"}, with ``--score`` also "scored" (the meshes with a score line of
-    status 0), with ``--clean`` also "unclean", with ``--simplify`` also "simplified" (the
+    status 0), with ``--check`` also "checked" and "watertight" (the meshes with a line in checks.jsonl, and those of
+    them that are watertight; ``check_fn``: see ``check_group``), with ``--clean`` also "unclean", with ``--simplify`` also "simplified" (the
     meshes with triangles: those that went through the stage), with ``--smooth`` also "smoothed" (likewise), with
     ``--colour`` also "coloured" (likewise; every mesh
     then ends in ``colours`` uint8 [nv,3], behind the normals when there are any).  ``reconstruct_fn(imgs, trans_mats, sdf_params)``
@@ -1021,6 +1072,7 @@ def main(argv=None, reconstruct_fn: Optional[Callable] = None) -> dict:
     cleaning = stages["clean"] is not None
     clean_cats = clean_cats_from_flags(a)[1] if cleaning else set()
     score = score_from_flags(a)
+    check = check_from_flags(a)
     smooth, coloured = stages["smooth"], stages["colour"] is not None
     out_dir = result_obj_path(a.log_dir, a.sdf_res, a.iso, a.cam_est, fuse, clean=cleaning, simplify=stages["simplify"],
                               colour=coloured, smooth=None if smooth is None else smooth["iters"],
@@ -1060,11 +1112,14 @@ def main(argv=None, reconstruct_fn: Optional[Callable] = None) -> dict:
         logf.flush()
         print(s)
 
-    written = empty = unclean = scored = 0
+    written = empty = unclean = scored = checked = watertight = 0
     score_cache: dict = {}
     scores_path = os.path.join(out_dir, "scores.jsonl")
     if score is not None and not a.skip_existing:           # every mesh is scored again: the file starts afresh
         open(scores_path, "w").close()
+    checks_path = os.path.join(out_dir, "checks.jsonl")
+    if check is not None and not a.skip_existing:           # every mesh is checked again: the file starts afresh
+        open(checks_path, "w").close()
     try:
         log_string(str(a))
         log_string("%s; %d views listed, %d to do in %d groups -> %s  (%s)"
@@ -1095,6 +1150,13 @@ def main(argv=None, reconstruct_fn: Optional[Callable] = None) -> dict:
                         for row in rows:
                             sf.write(json.dumps(row) + "\n")
                     scored += sum(r["status"] == 0 for r in rows)
+                if check is not None:                       # likewise, before the writers take them
+                    rows = check_group(meshes, group[::per_mesh], check, check_fn)
+                    with open(checks_path, "a") as cf:
+                        for row in rows:
+                            cf.write(json.dumps(row) + "\n")
+                    checked += len(rows)
+                    watertight += sum(r["watertight"] for r in rows)
                 for (cat_id, obj, view), mesh, as_it_is in zip(group[::per_mesh], meshes, left):
                     verts, faces = mesh[:2]
                     path = obj_path(out_dir, cat_id, obj, view)
@@ -1117,7 +1179,8 @@ def main(argv=None, reconstruct_fn: Optional[Callable] = None) -> dict:
     res = {"written": written, "skipped": len(entries) - len(todo), "empty": empty, "out_dir": out_dir}
     for key, stage, count in (("unclean", stages["clean"], unclean), ("simplified", stages["simplify"], written - empty),
                               ("smoothed", smooth, written - empty), ("coloured", stages["colour"], written - empty),
-                              ("scored", score, scored)):
+                              ("scored", score, scored), ("checked", check, checked),
+                              ("watertight", check, watertight)):
         if stage is not None:
             res[key] = count
     return res

@@ -1,5 +1,5 @@
 // The building blocks of the stages that work on "B meshes back to back, with host offsets" (mesh_clean.hip,
-// mesh_simplify.hip, mesh_colour.hip, mesh_sample.hip, mesh_smooth.hip; DESIGN 4z states each block's contract).  Everything has internal linkage: each
+// mesh_simplify.hip, mesh_colour.hip, mesh_sample.hip, mesh_smooth.hip, mesh_check.hip; DESIGN 4z states each block's contract).  Everything has internal linkage: each
 // translation unit that includes this keeps its own copy, and no kernel is launched across translation units.  FOR
 // THOSE FILES ONLY: the compiler emits a __global__ function whether or not the file launches it, so the workspace
 // cursor (WsCursor, scan_bsum_items), which marching_cubes.hip and grid_band.hip use as well, lives in kernels.hpp.
@@ -63,6 +63,31 @@ __device__ __forceinline__ long long table_find(const unsigned long long* __rest
     h = (h + 1) & mask;
   }
   return -1;
+}
+
+// a union-find whose parents only decrease (parent[x] <= x, set to x by init_parent_kernel).  find_root follows
+// parent[x] < x strictly downwards: at most x steps.  unite retries only when its CAS found parent[a] already lowered by
+// someone else, and goes on from that lower value, so the retries of all threads together are bounded.
+__device__ __forceinline__ int find_root(int* parent, int x) {
+  int p;
+  while ((p = __atomic_load_n(&parent[x], __ATOMIC_RELAXED)) != x) x = p;   // p < x
+  return x;
+}
+
+__device__ __forceinline__ void unite(int* parent, int a, int b) {
+  for (;;) {
+    a = find_root(parent, a);
+    b = find_root(parent, b);
+    if (a == b) return;
+    if (a < b) { const int t = a; a = b; b = t; }
+    const int old = atomicCAS(&parent[a], a, b);   // hook the larger root under the smaller
+    if (old == a) return;
+    a = old;                                       // someone lowered parent[a] first: go on from there
+  }
+}
+
+__global__ __launch_bounds__(kThreads) void init_parent_kernel(int* __restrict__ parent, long long nf) {
+  GRID_STRIDE(f, nf) parent[f] = (int)f;
 }
 
 // status 2 for a mesh with an index outside [0, nv_b): the ONLY kernel that looks at an index before it is checked

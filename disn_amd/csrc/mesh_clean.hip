@@ -26,27 +26,7 @@ namespace {
 
 enum { ST_NOTHING_KEPT = 1 };
 
-__device__ __forceinline__ int find_root(int* parent, int x) {
-  int p;
-  while ((p = __atomic_load_n(&parent[x], __ATOMIC_RELAXED)) != x) x = p;   // p < x
-  return x;
-}
-
-__device__ __forceinline__ void unite(int* parent, int a, int b) {
-  for (;;) {
-    a = find_root(parent, a);
-    b = find_root(parent, b);
-    if (a == b) return;
-    if (a < b) { const int t = a; a = b; b = t; }
-    const int old = atomicCAS(&parent[a], a, b);   // hook the larger root under the smaller
-    if (old == a) return;
-    a = old;                                       // someone lowered parent[a] first: go on from there
-  }
-}
-
-__global__ __launch_bounds__(kThreads) void init_parent_kernel(int* __restrict__ parent, long long nf) {
-  GRID_STRIDE(f, nf) parent[f] = (int)f;
-}
+// (find_root, unite and init_parent_kernel are those of mesh_batch.hpp: mesh_check.hip runs the same union-find)
 
 __device__ __forceinline__ unsigned long long edge_key(const int* __restrict__ faces, long long f, int k,
                                                        long long vbase) {

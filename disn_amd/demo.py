@@ -7,6 +7,7 @@
                             [--simplify CELLS]
                             [--smooth ITERS --smooth_cap 0.5 --smooth_free_boundary]
                             [--preview OUT.png [--preview_size 137]]
+                            [--check [--check_pairs 256]]
 
 The image is read as demo/demo.py:261-279 reads it (``cv2.imread(IMREAD_UNCHANGED)[:, :, :3] / 255``: the
 channels in B, G, R order, alpha dropped) -- through PIL, which is what this project has.  Without ``--cam_est``
@@ -27,6 +28,10 @@ before ``--refine`` / ``--normals``.
 ``--smooth ITERS`` fairs the mesh on the device by Taubin's lambda|mu smoothing (``postprocess.smooth_meshes_device``,
 DESIGN §4zd) behind ``--simplify`` and before ``--refine`` / ``--normals``: the faces stay, no coordinate moves further
 than ``--smooth_cap`` grid cells (default 0.5), boundary vertices stay unless ``--smooth_free_boundary`` is given.
+
+``--check`` measures the final mesh on the device before it is written (``postprocess.check_meshes_device``, DESIGN
+§4zh): topology, orientation and self-intersections, printed and written as one JSON line to ``checks.jsonl`` beside
+``--out`` (started afresh).  It changes nothing of the mesh.
 """
 from __future__ import annotations
 
@@ -101,10 +106,11 @@ def parser() -> argparse.ArgumentParser:
     p.add_argument("--preview", default=None, metavar="OUT.png",
                    help="also write the sphere-traced view of the predicted surface from the camera in use")
     p.add_argument("--preview_size", type=int, default=137, metavar="N", help="the preview is N x N [default: 137]")
-    from .create_sdf import add_stage_flags
+    from .create_sdf import add_check_flags, add_stage_flags
     p.add_argument("--clean", action="store_true",
                    help="drop the mesh's small and far parts on the device (postprocess.clean_meshes_device)")
     add_stage_flags(p)
+    add_check_flags(p)
     return p
 
 
@@ -138,10 +144,13 @@ def write_preview(engine, img: np.ndarray, trans_mat, path: str, size: int, iso:
 
 
 def main(argv=None) -> dict:
-    """-> {"out", "verts", "faces", "trans_mat"}, with ``--colour`` also "coloured" (True) and "colours" (uint8 [nv,3])"""
+    """-> {"out", "verts", "faces", "trans_mat"}, with ``--colour`` also "coloured" (True) and "colours" (uint8 [nv,3]),
+    with ``--check`` also "checked" (1), "watertight" (0 or 1) and "check" (the mesh's line of checks.jsonl)"""
     a = parser().parse_args(argv)
-    from .create_sdf import reconstruct, restore_weights, stages_from_flags, write_mesh
+    from .create_sdf import (check_from_flags, check_group, reconstruct, restore_weights, stages_from_flags,
+                             write_mesh)
     stages = stages_from_flags(a, a.clean)                             # a bad flag: before anything else
+    check = check_from_flags(a)
     coloured = stages["colour"] is not None
     img = read_image(a.img)
     if img.shape[1:3] != (137, 137):
@@ -163,12 +172,22 @@ def main(argv=None) -> dict:
     mesh = reconstruct(engine, img, trans_mat, DEMO_SDF_PARAMS, a.sdf_res, a.iso, a.refine, a.normals,
                        alpha=None if alpha is None else alpha[None], **stages)[0]
     verts, faces = mesh[:2]
+    row = None
+    if check is not None:                                              # the final mesh, before it is written
+        import json
+        row = check_group([mesh], [("", os.path.basename(a.out), 0)], check)[0]
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(os.path.join(os.path.dirname(os.path.abspath(a.out)), "checks.jsonl"), "w") as cf:
+            cf.write(json.dumps(row) + "\n")
+        print("check: %s" % row)
     write_mesh(a.out, mesh, coloured)
     print("wrote %s: %d vertices, %d triangles" % (a.out, len(verts), len(faces)))
     tm = trans_mat.cpu().numpy() if hasattr(trans_mat, "cpu") else trans_mat
     res = {"out": a.out, "verts": len(verts), "faces": len(faces), "trans_mat": tm}
     if coloured:
         res["coloured"], res["colours"] = True, mesh[-1].cpu().numpy()
+    if row is not None:
+        res["checked"], res["watertight"], res["check"] = 1, int(row["watertight"]), row
     if a.preview:
         res["preview"] = write_preview(engine, img, trans_mat, a.preview, a.preview_size, a.iso, read_alpha(a.img))
     return res

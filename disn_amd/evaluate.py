@@ -44,6 +44,7 @@ drawn from ``numpy.random.default_rng(seed + batch index)``; a missing checkpoin
 from __future__ import annotations
 
 import argparse
+import glob
 import os
 import random
 import sys
@@ -385,6 +386,72 @@ SDF_ACC_NAMES = ("accuracy", "sdf_loss_realvalue", "sdf_loss", "regularization",
 SDF_WEIGHT = 10.0            # test/test_sdf_acc.py:61
 
 
+MESH_CHECK_SHARES = ("closed", "manifold", "oriented", "no_self_intersection", "watertight")
+
+
+def mesh_check_summary(rows) -> dict:
+    """the lines of one category -> {"meshes", "share": {closed, manifold, oriented, no_self_intersection, watertight},
+    "mean": {every count of postprocess.CHECK_FIELDS, over the meshes where it is valid (>= 0)}, "status": {status:
+    meshes}}"""
+    from .postprocess import CHECK_FIELDS
+    n = len(rows)
+    flag = lambda r, k: r["intersecting_pairs"] == 0 if k == "no_self_intersection" else bool(r[k])
+    share = {k: (sum(flag(r, k) for r in rows) / n if n else 0.0) for k in MESH_CHECK_SHARES}
+    mean = {}
+    for k in CHECK_FIELDS:
+        valid = [r[k] for r in rows if r[k] >= 0]
+        mean[k] = float(np.mean(valid)) if valid else None
+    status: Dict[str, int] = {}
+    for r in rows:
+        status[str(r["status"])] = status.get(str(r["status"]), 0) + 1
+    return {"meshes": n, "share": share, "mean": mean, "status": status}
+
+
+def mesh_check_all(cats: Dict[str, str], obj_dir: str, group: int = 16, pairs_per_face: Optional[int] = None,
+                   out=sys.stdout, check_fn=None) -> dict:
+    """``mesh_check OBJ_DIR``: every ``<obj_dir>/<cat_id>/*.obj`` of the listed categories through
+    ``postprocess.check_meshes_device`` in groups of ``group`` files (``check_fn``: see ``create_sdf.check_group``);
+    one JSON line per mesh in ``<obj_dir>/checks.jsonl`` (the lines of ``create_sdf --check``: "view" is the file's
+    name), started afresh, and a summary per category -> {"categories": {name: mesh_check_summary}, "checked",
+    "watertight", "out"}.  An empty file is a mesh without triangles.  No mesh raises: a bad file's status is in its
+    line."""
+    import json
+
+    from . import mesh_sdf
+    from .create_sdf import CHECK_PAIRS_PER_FACE, check_group
+    if group < 1:
+        raise ValueError("--group must be positive")
+    pairs = CHECK_PAIRS_PER_FACE if pairs_per_face is None else pairs_per_face
+    if pairs < 0:
+        raise ValueError("--check_pairs must not be negative")
+    path = os.path.join(obj_dir, "checks.jsonl")
+    per, checked, watertight = {}, 0, 0
+    with open(path, "w") as lines:
+        for name, cat_id in cats.items():
+            files = sorted(glob.glob(os.path.join(obj_dir, cat_id, "*.obj")))
+            rows = []
+            for at in range(0, len(files), group):
+                part = files[at:at + group]
+                host = [mesh_sdf.read_obj_mesh(f) if os.path.getsize(f) else
+                        (np.zeros((0, 3), np.float32), np.zeros((0, 3), np.int32)) for f in part]
+                if check_fn is None:
+                    import torch
+                    host = [(torch.from_numpy(v).cuda(), torch.from_numpy(f).cuda()) for v, f in host]
+                keys = [(cat_id, os.path.splitext(os.path.basename(f))[0], os.path.basename(f)) for f in part]
+                rows += check_group(host, keys, pairs, check_fn)
+            for r in rows:
+                lines.write(json.dumps(r) + "\n")
+            per[name] = mesh_check_summary(rows)
+            checked += len(rows)
+            watertight += sum(r["watertight"] for r in rows)
+            s = per[name]
+            print("%s (%s): %d meshes; %s" % (name, cat_id, s["meshes"], ", ".join(
+                "%s %.1f%%" % (k, 100.0 * s["share"][k]) for k in MESH_CHECK_SHARES)), file=out)
+            print("  mean " + ", ".join("%s %s" % (k, "-" if v is None else "%.4g" % v) for k, v in s["mean"].items()),
+                  file=out)
+    return {"categories": per, "checked": checked, "watertight": watertight, "out": path}
+
+
 def regularization_of(store, wd: float = 1e-5) -> float:
     """wd * sum(w^2) / 2 over every '/weights' variable: the scalar the trainer adds to its loss, a function of the
     weights alone (float64 on the host, once per weight set)"""
@@ -464,6 +531,13 @@ def parser() -> argparse.ArgumentParser:
     s.add_argument("--mode", default="reference", choices=("reference", "solid"),
                    help="reference: the shell IoU of test_iou.py; solid: filled voxels [default: reference]")
     s.add_argument("--seed", type=int, default=0, help="seed of the view sampling [default: 0]")
+    s = sub.add_parser("mesh_check", help="topology, orientation and self-intersections of every mesh of a tree, on "
+                                          "the device (not in the reference)")
+    s.add_argument("obj_dir", metavar="OBJ_DIR", help="directory of the meshes (<cat_id>/*.obj)")
+    s.add_argument("--category", default="all", help="all, clean or one category name [default: all]")
+    s.add_argument("--group", type=int, default=16, help="meshes per device call [default: 16]")
+    s.add_argument("--check_pairs", type=int, default=None, metavar="N",
+                   help="the work cap, candidate pairs per face [default: 256]")
     s = sub.add_parser("sdf_acc", help="accuracy and losses of the predicted SDF on sampled points of the test views")
     s.add_argument("--log_dir", required=True, help="checkpoint directory of the SDF network")
     s.add_argument("--test_lst_dir", required=True, help="object lists (<cat_id>_test.lst)")
@@ -489,6 +563,8 @@ def main(argv=None) -> dict:
         return sdf_acc(cats, a.log_dir, a.test_lst_dir, a.sdf_dir, a.rendered_dir, batch_size=a.batch_size,
                        num_sample_points=a.num_sample_points, mask_weight=a.mask_weight, view_num=a.view_num,
                        seed=a.seed, random_init=a.random_init, rot=a.rot, backcolorwhite=a.backcolorwhite)
+    if a.command == "mesh_check":
+        return mesh_check_all(cats, a.obj_dir, group=a.group, pairs_per_face=a.check_pairs)
     if a.command == "surface":
         return surface_all(cats, a.pred_dir, a.gt_dir, a.test_lst_dir, truethreshold=a.truethreshold,
                            view_num=a.view_num, num_sample_points=a.num_sample_points, seed=a.seed)

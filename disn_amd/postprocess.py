@@ -29,6 +29,11 @@ meshes that lie on the device.
 Not in the reference either: fairing by Taubin's lambda|mu smoothing (``--smooth ITERS`` of ``create_sdf`` and ``demo``,
 DESIGN 4zd).  ``smooth_arrays`` is the rule, on the host; ``smooth_meshes_device`` / ``smooth_arrays_device``
 (mesh_smooth.hip) give its position bits for meshes that lie on the device.
+
+Not in the reference either: checks of a mesh's topology, orientation and self-intersections (``--check`` of
+``create_sdf`` and ``demo``, ``evaluate mesh_check``, DESIGN 4zh).  ``check_arrays`` is the rule, on the host;
+``check_meshes_device`` / ``check_arrays_device`` (mesh_check.hip) give its integers for meshes that lie on the device.
+They measure and repair nothing.
 """
 from __future__ import annotations
 
@@ -371,6 +376,220 @@ def smooth_arrays(verts, faces, iters=10, lam=0.5, mu=-0.53, pin_boundary=True, 
                          % SMOOTH_RANGE)
     _one_mesh(_raise_status, 0, status, [0, out.shape[0]], "smooth_arrays")
     return out
+
+
+# ---- mesh checks: the rule (the device restates it, mesh_check.hip) ------------------------------------
+CHECK_FIELDS = ("nv", "nf", "unreferenced_vertices", "index_degenerate_faces", "edges", "boundary_edges",
+                "nonmanifold_edges", "misoriented_edges", "nonmanifold_vertices", "euler", "zero_area_faces",
+                "candidate_pairs", "intersecting_pairs", "intersecting_faces")      # DISN_CHECK_NV .. in this order
+CHECK_PAIRS_PER_FACE = 256     # the default work cap of a mesh: CHECK_PAIRS_PER_FACE nf + CHECK_PAIRS_BASE candidate pairs
+CHECK_PAIRS_BASE = 4096
+STATUS_CHECK_PAIRS = 8
+FLAG_INTERSECTS, FLAG_DEGENERATE, FLAG_BOUNDARY, FLAG_NONMANIFOLD, FLAG_MISORIENTED = 1, 2, 4, 8, 16
+_CHECK_TOPOLOGY, _CHECK_GEOMETRY = CHECK_FIELDS[2:10], CHECK_FIELDS[10:]
+
+
+def check_max_pairs(max_pairs, nf: int) -> int:
+    """the work cap of one mesh: ``max_pairs`` candidate pairs, by default CHECK_PAIRS_PER_FACE nf + CHECK_PAIRS_BASE"""
+    cap = CHECK_PAIRS_PER_FACE * int(nf) + CHECK_PAIRS_BASE if max_pairs is None else int(max_pairs)
+    if cap < 0:
+        raise ValueError("check: max_pairs must be >= 0 (got %r)" % (max_pairs,))
+    return cap
+
+
+def check_orient(a, b, c, d):
+    """the float64 determinant of [b - a, c - a, d - a], expanded along its first row:
+    (u0 (v1 w2 - v2 w1) - u1 (v0 w2 - v2 w0)) + u2 (v0 w1 - v1 w0), every product and difference rounded once"""
+    u, v, w = b - a, c - a, d - a
+    return ((u[..., 0] * (v[..., 1] * w[..., 2] - v[..., 2] * w[..., 1])
+             - u[..., 1] * (v[..., 0] * w[..., 2] - v[..., 2] * w[..., 0]))
+            + u[..., 2] * (v[..., 0] * w[..., 1] - v[..., 1] * w[..., 0]))
+
+
+def _check_pierces(P, T):
+    """[n] bool: an edge (p, q) of triangle P[n] goes through the inside of triangle T[n] (float64 [n,3,3])"""
+    a, b, c = T[:, 0], T[:, 1], T[:, 2]
+    hit = np.zeros(P.shape[0], bool)
+    for k in range(3):
+        p, q = P[:, k], P[:, (k + 1) % 3]
+        across = check_orient(a, b, c, p) * check_orient(a, b, c, q) < 0
+        s1, s2, s3 = check_orient(p, q, a, b), check_orient(p, q, b, c), check_orient(p, q, c, a)
+        hit |= across & (((s1 > 0) & (s2 > 0) & (s3 > 0)) | ((s1 < 0) & (s2 < 0) & (s3 < 0)))
+    return hit
+
+
+def _check_candidates(lo, hi):
+    """the pairs i < j of boxes [lo, hi] (float32 [n,3]) that overlap, closed -> (i, j), int64 each; a sweep along x"""
+    order = np.argsort(lo[:, 0], kind="stable")
+    I, J = [np.zeros(0, np.int64)], [np.zeros(0, np.int64)]
+    for n, i in enumerate(order):
+        j = order[n + 1:]
+        j = j[:np.searchsorted(lo[j, 0], hi[i, 0], side="right")]
+        j = j[np.all((lo[j] <= hi[i]) & (lo[i] <= hi[j]), axis=1)]
+        I.append(np.minimum(i, j))
+        J.append(np.maximum(i, j))
+    return np.concatenate(I), np.concatenate(J)
+
+
+def _check_fans(f: np.ndarray, key: np.ndarray, lo_first: np.ndarray, nv: int) -> int:
+    """the vertices with two or more fans.  f [n,3] the faces that take part, key [3n] the undirected edge of corner pair
+    (face, k) -> (k+1)%3 in face-major order, lo_first [3n]: that pair runs from its smaller index"""
+    n3 = key.size
+    parent = np.arange(n3)
+
+    def root(x):
+        while parent[x] != x:
+            parent[x] = parent[parent[x]]
+            x = parent[x]
+        return x
+
+    corner = np.arange(n3)
+    nxt = corner - corner % 3 + (corner % 3 + 1) % 3             # the corner of the pair's second index, same face
+    at_lo, at_hi = np.where(lo_first, corner, nxt), np.where(lo_first, nxt, corner)
+    order = np.argsort(key, kind="stable")
+    same = np.nonzero(key[order][1:] == key[order][:-1])[0]
+    for k in same:                                               # two corner pairs of one edge: their faces share it
+        for at in (at_lo, at_hi):
+            a, b = root(at[order[k]]), root(at[order[k + 1]])
+            if a != b:
+                parent[max(a, b)] = min(a, b)
+    roots = np.array([root(x) for x in range(n3)], np.int64)
+    fans = np.bincount(f.reshape(-1)[np.unique(roots)], minlength=nv)
+    return int((fans >= 2).sum())
+
+
+def _check_derive(out: dict) -> dict:
+    """the four derived booleans; an invalid field (-1) makes its boolean False"""
+    out["closed"] = out["boundary_edges"] == 0
+    out["manifold"] = out["nonmanifold_edges"] == 0 and out["nonmanifold_vertices"] == 0
+    out["oriented"] = out["misoriented_edges"] == 0
+    out["watertight"] = (out["closed"] and out["manifold"] and out["oriented"] and out["intersecting_pairs"] == 0
+                         and out["status"] == 0)
+    return out
+
+
+def _check(verts, faces, max_pairs=None) -> Tuple[dict, np.ndarray]:
+    v32 = np.ascontiguousarray(verts.detach().cpu().numpy() if hasattr(verts, "detach") else verts,
+                               np.float32).reshape(-1, 3)
+    f = np.ascontiguousarray(faces.detach().cpu().numpy() if hasattr(faces, "detach") else faces).reshape(-1, 3)
+    f = f.astype(np.int64)
+    nv, nf = v32.shape[0], f.shape[0]
+    cap = check_max_pairs(max_pairs, nf)
+    out = {"status": 0}
+    out.update((k, 0) for k in CHECK_FIELDS)
+    out.update(nv=nv, nf=nf, area=0.0, volume=0.0)
+    flags = np.zeros(nf, np.uint8)
+
+    def done():
+        return _check_derive(out), flags
+
+    if nf and (f.min() < 0 or f.max() >= nv):
+        out["status"] = STATUS_INDEX
+        out.update((k, -1) for k in _CHECK_TOPOLOGY + _CHECK_GEOMETRY)
+        return done()
+    finite = bool(np.isfinite(v32).all())
+    # -- topology: the indices alone
+    part = (f[:, 0] != f[:, 1]) & (f[:, 1] != f[:, 2]) & (f[:, 2] != f[:, 0])
+    ids = np.nonzero(part)[0]
+    g = f[part]
+    flags[~part] |= FLAG_DEGENERATE
+    referenced = np.zeros(nv, bool)
+    referenced[g.reshape(-1)] = True
+    a, b = g.reshape(-1), g[:, (1, 2, 0)].reshape(-1)             # corner pair 3 n + k: index k -> index (k+1)%3
+    key = np.minimum(a, b) * np.int64(max(nv, 1)) + np.maximum(a, b)
+    uniq, inv, held = np.unique(key, return_inverse=True, return_counts=True)
+    forward = np.bincount(inv.reshape(-1), weights=(a < b), minlength=uniq.size).astype(np.int64)
+    boundary, nonmanifold = held == 1, held >= 3
+    misoriented = (held == 2) & (forward != 1)
+    for mark, bit in ((boundary, FLAG_BOUNDARY), (nonmanifold, FLAG_NONMANIFOLD), (misoriented, FLAG_MISORIENTED)):
+        on = mark[inv.reshape(-1)].reshape(-1, 3).any(axis=1)
+        flags[ids[on]] |= bit
+    out.update(unreferenced_vertices=int(nv - referenced.sum()), index_degenerate_faces=int(nf - g.shape[0]),
+               edges=int(uniq.size), boundary_edges=int(boundary.sum()), nonmanifold_edges=int(nonmanifold.sum()),
+               misoriented_edges=int(misoriented.sum()), nonmanifold_vertices=_check_fans(g, key, a < b, nv),
+               euler=int(referenced.sum()) - int(uniq.size) + int(g.shape[0]))
+    if not finite:
+        out["status"] = STATUS_FINITE
+        out.update((k, -1) for k in _CHECK_GEOMETRY)
+        return done()
+    # -- geometry: float64 arithmetic on the float32 coordinates
+    p = v32.astype(np.float64)[g]                                 # [n,3,3]
+    u, w = p[:, 1] - p[:, 0], p[:, 2] - p[:, 0]
+    cross = np.stack([u[:, 1] * w[:, 2] - u[:, 2] * w[:, 1], u[:, 2] * w[:, 0] - u[:, 0] * w[:, 2],
+                      u[:, 0] * w[:, 1] - u[:, 1] * w[:, 0]], axis=1)
+    flat = (cross == 0).all(axis=1)
+    flags[ids[flat]] |= FLAG_DEGENERATE
+    out["zero_area_faces"] = int(flat.sum())
+    out["area"] = float(np.sum(0.5 * np.sqrt((cross[:, 0] * cross[:, 0] + cross[:, 1] * cross[:, 1])
+                                             + cross[:, 2] * cross[:, 2])))
+    out["volume"] = float(np.sum(_check_volume_terms(p)))
+    # -- self-intersections
+    t32 = v32[g]
+    I, J = _check_candidates(t32.min(axis=1), t32.max(axis=1))
+    out["candidate_pairs"] = int(I.size)
+    if I.size > cap:
+        out["status"] = STATUS_CHECK_PAIRS
+        out["intersecting_pairs"] = out["intersecting_faces"] = -1
+        return done()
+    hit = _check_pierces(p[I], p[J]) | _check_pierces(p[J], p[I])
+    out["intersecting_pairs"] = int(hit.sum())
+    faces_hit = np.unique(np.concatenate([I[hit], J[hit]]))
+    out["intersecting_faces"] = int(faces_hit.size)
+    flags[ids[faces_hit]] |= FLAG_INTERSECTS
+    return done()
+
+
+def _check_volume_terms(p: np.ndarray) -> np.ndarray:
+    """p0 . (p1 x p2) / 6 of every triangle p [n,3,3] float64: ((x0 c0 + y0 c1) + z0 c2) / 6, c = p1 x p2"""
+    a, b, c = p[:, 0], p[:, 1], p[:, 2]
+    c0 = b[:, 1] * c[:, 2] - b[:, 2] * c[:, 1]
+    c1 = b[:, 2] * c[:, 0] - b[:, 0] * c[:, 2]
+    c2 = b[:, 0] * c[:, 1] - b[:, 1] * c[:, 0]
+    return ((a[:, 0] * c0 + a[:, 1] * c1) + a[:, 2] * c2) / 6.0
+
+
+def check_arrays(verts, faces, max_pairs=None) -> dict:
+    """Topology, orientation and self-intersections of one mesh on the host: THE SPECIFICATION of
+    ``check_meshes_device`` (same integers; ``area`` and ``volume`` up to the order of their sums).  -> a dict of
+    ``status``, the CHECK_FIELDS, ``area``, ``volume`` and four derived booleans.  It repairs nothing.
+
+    Status: 0; 2 a face index outside [0, nv): only nv and nf are valid; 4 a coordinate that is not finite: the
+    topological fields are valid, the geometric ones not; 8 (STATUS_CHECK_PAIRS) more than ``max_pairs`` candidate
+    pairs: ``intersecting_pairs`` and ``intersecting_faces`` are invalid.  Of several the largest; an invalid count is
+    -1, an invalid sum 0.0.  An empty mesh has status 0 and zeros.
+
+    Topology (the indices alone).  A face with a repeated index counts in ``index_degenerate_faces`` and takes no
+    further part.  Every other face gives three corner pairs (a, b), (b, c), (c, a).  ``unreferenced_vertices``: named
+    by no face that takes part.  ``edges``: distinct undirected {i, j}; ``boundary_edges``: held by exactly one corner
+    pair; ``nonmanifold_edges``: by three or more; ``misoriented_edges``: by exactly two that run the same way.
+    ``nonmanifold_vertices``: two corners (f, i), (g, i) of vertex i are related when f and g share an undirected edge
+    {i, j}, however many faces it has; a fan is a class of the transitive closure; the field counts the vertices with
+    two or more fans.  ``euler`` = referenced vertices - edges + faces that take part.
+
+    Geometry, in float64 on the float32 coordinates, + - * and sqrt only, each rounded once, in the order written.
+    cross = (p1 - p0) x (p2 - p0) = (u1 w2 - u2 w1, u2 w0 - u0 w2, u0 w1 - u1 w0); ``zero_area_faces``: faces that take
+    part whose cross is (0, 0, 0), either sign; ``area`` = sum of 0.5 sqrt((c0 c0 + c1 c1) + c2 c2); ``volume`` = sum
+    of ((x0 c0 + y0 c1) + z0 c2) / 6 with c = p1 x p2 written the same way.  The order of the two sums is the
+    implementation's (here numpy's pairwise sum).
+
+    Self-intersections among the faces that take part.  ``candidate_pairs``: the pairs f < g whose float32 bounding
+    boxes overlap, closed.  orient(a, b, c, d) is ``check_orient``.  An edge (p, q) pierces a triangle (a, b, c) when
+    orient(a,b,c,p) orient(a,b,c,q) < 0 (the float64 product) and orient(p,q,a,b), orient(p,q,b,c), orient(p,q,c,a) are
+    all > 0 or all < 0.  A pair intersects when one of the three edges (p0,p1), (p1,p2), (p2,p0) of either face
+    pierces the other.  Every zero is a no: touching and coplanar overlaps do not count.  ``intersecting_pairs``,
+    ``intersecting_faces`` (faces in at least one such pair).
+
+    Derived: ``closed`` (no boundary edge), ``manifold`` (no non-manifold edge or vertex), ``oriented`` (no
+    misoriented edge), ``watertight`` (all three, no intersecting pair, status 0); False where a field is invalid.
+    Not covered: connected components (``separate_mesh`` reports them), duplicate faces (they show as non-manifold
+    edges), coplanar overlaps."""
+    return _check(verts, faces, max_pairs)[0]
+
+
+def check_face_flags(verts, faces, max_pairs=None) -> np.ndarray:
+    """uint8 [nf] beside ``check_arrays``: 1 in an intersecting pair, 2 zero area or a repeated index, 4 on a boundary
+    edge, 8 on a non-manifold edge, 16 on a misoriented edge; a bit whose field is invalid stays 0"""
+    return _check(verts, faces, max_pairs)[1]
 
 
 # ---- vertex colours from the input views: the rule (DESIGN 4zb; the device restates it, mesh_colour.hip) ----------
@@ -917,6 +1136,70 @@ def smooth_arrays_device(verts, faces, **kw):
     """``smooth_arrays`` for one mesh on the device -> verts' (a device tensor with the bits of ``smooth_arrays``); the
     same ValueErrors"""
     return _one_mesh(smooth_meshes_device, [(verts, faces)], **kw)[0][0][0]
+
+
+# ---- mesh checks on the device (mesh_check.hip) -------------------------------------------------------------------
+def check_result(status: int, counts, area: float, volume: float) -> dict:
+    """one mesh's status word, its DISN_CHECK_FIELDS counts and its two sums -> the dict of ``check_arrays``"""
+    out = {"status": int(status)}
+    out.update((k, int(c)) for k, c in zip(CHECK_FIELDS, counts))
+    out.update(area=float(area), volume=float(volume))
+    return _check_derive(out)
+
+
+def check_meshes_device(meshes, max_pairs=None, face_flags: bool = False, strict: bool = True):
+    """``check_arrays`` for a group of meshes that lie on the device.  ``meshes``: B x (verts [nv,3] float32, faces
+    [nf,3] int32[, further arrays]) device tensors, used in place; ``max_pairs`` None (the default cap of every mesh),
+    one number or B numbers.  ONE call and ONE device-to-host copy for the group: the status words, the counts and the
+    sums travel in one buffer.
+    -> B dicts with the integers of ``check_arrays`` (``area`` and ``volume`` up to the order of their sums, which is
+    fixed: the same bits from run to run and in any batch); with ``face_flags`` -> (dicts, B uint8 [nf] device tensors
+    with the bits of ``check_face_flags``).  A mesh with status 2 (a face index out of range) or 4 (a coordinate that is
+    not finite) raises ValueError naming the mesh -- with ``strict=False`` its dict carries the status and -1 in the
+    fields that status makes invalid.  Status 8 (more candidate pairs than the cap) never raises: the dict carries it."""
+    import torch
+
+    from . import ops
+    from ._lib import check
+    meshes = [tuple(m) for m in meshes]
+    if not meshes:
+        return ([], []) if face_flags else []
+    B, h = len(meshes), lib()
+    if max_pairs is not None and np.ndim(max_pairs) and np.shape(max_pairs) != (B,):
+        raise ValueError("check: %d values of max_pairs for %d meshes" % (np.size(max_pairs), B))
+    caps = np.ascontiguousarray([check_max_pairs(None if max_pairs is None else np.broadcast_to(max_pairs, (B,))[b],
+                                                 m[1].shape[0]) for b, m in enumerate(meshes)], np.int64)
+    v, v_off, f, f_off, ws = _pack_meshes(
+        meshes, lambda nv, nf: h.disn_mesh_check_workspace_bytes(B, nv, nf, int(min(caps.sum(), 2 ** 62))))
+    nf, dev = int(f_off[-1]), v.device
+    words = 1 + len(CHECK_FIELDS) + 2                              # per mesh: status, the counts, the two sums
+    with torch.cuda.device(dev):
+        out = torch.empty(B * words, dtype=torch.int64, device=dev)
+        status, counts, sums = out[:B].view(torch.int32), out[B:B * (1 + len(CHECK_FIELDS))], out[B * (words - 2):]
+        flags = torch.empty(nf, dtype=torch.uint8, device=dev) if face_flags else None
+        check("disn_mesh_check_batch", h.disn_mesh_check_batch(
+            v.data_ptr(), f.data_ptr(), v_off.ctypes.data, f_off.ctypes.data, B, caps.ctypes.data, counts.data_ptr(),
+            sums.view(torch.float64).data_ptr(), None if flags is None else flags.data_ptr(), status.data_ptr(),
+            ws.data_ptr(), ws.numel(), ops._stream()))
+        host = out.cpu().numpy()                                # the one copy (and host sync) of the group
+    st = host[:B].view(np.int32)[:B]
+    cnt = host[B:B * (1 + len(CHECK_FIELDS))].reshape(B, len(CHECK_FIELDS))
+    sm = host[B * (words - 2):].view(np.float64).reshape(B, 2)
+    for b in np.nonzero(st)[0] if strict else ():
+        _raise_status(b, st[b], v_off, "disn_mesh_check_batch")
+        if st[b] != STATUS_CHECK_PAIRS:
+            raise RuntimeError("mesh %d: disn_mesh_check_batch gave status %d" % (b, st[b]))
+    results = [check_result(st[b], cnt[b], sm[b, 0], sm[b, 1]) for b in range(B)]
+    if not face_flags:
+        return results
+    return results, [flags[int(f_off[b]):int(f_off[b + 1])] for b in range(B)]
+
+
+def check_arrays_device(verts, faces, max_pairs=None, face_flags: bool = False, strict: bool = True):
+    """``check_arrays`` for one mesh on the device -> its dict (with ``face_flags``: (dict, uint8 [nf] device tensor));
+    the ValueErrors of ``check_meshes_device``"""
+    r = _one_mesh(check_meshes_device, [(verts, faces)], max_pairs=max_pairs, face_flags=face_flags, strict=strict)
+    return (r[0][0], r[1][0]) if face_flags else r[0]
 
 
 # ---- vertex colours on the device (mesh_colour.hip) -------------------------------------------------------------
