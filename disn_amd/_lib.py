@@ -1,7 +1,8 @@
 """ctypes binding of libdisn_amd.so (include/disn_amd.h and, for the mesh simplification and the vertex colours,
 include/disn_amd_simplify.h and include/disn_amd_colour.h; for the surface samples, include/disn_amd_sample.h; for
 the Taubin smoothing, include/disn_amd_smooth.h; for dual contouring, include/dc/disn_amd_dc.h and
-include/dc/disn_amd_dc_sheets.h; for the mesh checks, include/check/disn_amd_check.h).
+include/dc/disn_amd_dc_sheets.h; for the mesh checks, include/check/disn_amd_check.h; for the mesh repair,
+include/repair/disn_amd_repair.h).
 
 The HIP library is the product: there is NO CPU fallback.  ``lib()`` raises
 ``DisnLibraryError`` when the shared object is missing or does not export the
@@ -301,6 +302,14 @@ SIGNATURES_CHECK = {
     "disn_mesh_check_batch": (I, [P, P, P, P, I, P, P, P, P, P, P, Z, P]),
 }
 
+# name -> (restype, argtypes); every symbol declared in include/repair/disn_amd_repair.h (the ninth header, in a
+# directory of its own: the mesh repair)
+SIGNATURES_REPAIR = {
+    "disn_mesh_repair_workspace_bytes": (Z, [I, L, L]),
+    "disn_mesh_repair_count_batch": (I, [P, P, P, P, I, I, P, P, Z, P]),
+    "disn_mesh_repair_emit_batch": (I, [P, P, P, P, I, I, P, P, P, P, P, P, Z, P]),
+}
+
 _LIB: Optional[C.CDLL] = None
 
 
@@ -318,7 +327,8 @@ def lib() -> C.CDLL:
     except OSError as e:  # pragma: no cover - depends on the box
         raise DisnLibraryError("cannot load %s: %s" % (LIB_PATH, e)) from e
     for name, (res, args) in [kv for t in (SIGNATURES, SIGNATURES_SIMPLIFY, SIGNATURES_COLOUR, SIGNATURES_SAMPLE,
-                                                     SIGNATURES_SMOOTH, SIGNATURES_DC, SIGNATURES_DCS, SIGNATURES_CHECK) for kv in t.items()]:
+                                                     SIGNATURES_SMOOTH, SIGNATURES_DC, SIGNATURES_DCS, SIGNATURES_CHECK,
+                                                     SIGNATURES_REPAIR) for kv in t.items()]:
         try:
             fn = getattr(h, name)
         except AttributeError as e:

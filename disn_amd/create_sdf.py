@@ -66,6 +66,12 @@ the whole group with one read-back (``isosurface.marching_cubes_batch``) and wri
     every field of ``postprocess.CHECK_FIELDS``, "area", "volume" and the four derived booleans -- started afresh
     by a run without ``--skip_existing``.  ``--check_pairs N``: the work cap, N candidate pairs per face (+ 4096); a
     mesh over it has status 8 and -1 in its intersection fields.  No stage: the meshes and the tree's name stay.
+  * ``--repair [--repair_no_weld] [--repair_no_stitch]`` (not in the reference) welds, stitches and splits every mesh to
+    a manifold while the group still lies on the device (``postprocess.repair_meshes_device``): behind
+    ``--smooth``, ``--refine`` and ``--normals`` (the normals follow their vertices) and before ``--colour``, ``--score``
+    and ``--check``, which see the repaired mesh.  Results go to <...>_rep[_col]; one JSON line per mesh -- "cat", "obj",
+    "view" and the report of ``postprocess.repair_arrays`` -- to ``<out_dir>/repairs.jsonl``, started afresh by a run
+    without ``--skip_existing``.  Without the flag nothing changes.
   * ``--smooth ITERS [--smooth_cap CELLS] [--smooth_free_boundary]`` (1..64 iterations; not in the reference) fairs every
     mesh by Taubin's lambda|mu smoothing (``postprocess.smooth_meshes_device``) while the group still lies
     on the device: behind ``--clean`` and ``--simplify`` and BEFORE ``--refine`` and ``--normals``, so the smoothed
@@ -359,6 +365,47 @@ def smooth_group(meshes, smooth, boxes, sdf_res: int):
     return _through(meshes, smooth is not None, call)[0]
 
 
+def repair_args(repair) -> Optional[dict]:
+    """``repair`` = None / False (off), True (weld and stitch) or a dict with some of ``weld``, ``stitch`` -> None or the
+    checked, complete dict (ValueError; no device work): what ``reconstruct`` / ``reconstruct_fused`` hand to
+    ``repair_group``"""
+    if repair is None or repair is False:
+        return None
+    given = {} if repair is True else repair
+    if not isinstance(given, dict):
+        raise ValueError("--repair takes True or a dict of weld and stitch, got %r" % (repair,))
+    unknown = sorted(set(given) - {"weld", "stitch"})
+    if unknown:
+        raise ValueError("--repair takes weld and stitch, not %s" % ", ".join(unknown))
+    c = dict({"weld": True, "stitch": True}, **given)
+    for k in ("weld", "stitch"):
+        if not isinstance(c[k], (bool, np.bool_)):
+            raise ValueError("--repair: %s must be True or False, got %r" % (k, c[k]))
+        c[k] = bool(c[k])
+    return c
+
+
+def repair_group(meshes, repair, log: Optional[list] = None):
+    """the repair of one group behind its smoothing and refinement: the meshes that have triangles go through ONE
+    ``repair_meshes_device`` call; every further per-vertex array (the normals) follows its vertex -> the meshes.
+    ``log``: a list that takes one report per mesh of the group, in mesh order (``postprocess.repair_arrays``; a mesh
+    without triangles stays as it is and reports zeros)"""
+    from . import postprocess
+    reports: dict = {}
+
+    def call(picked, some):
+        repaired, reps = postprocess.repair_meshes_device(some, repair["weld"], repair["stitch"])
+        reports.update(zip(picked, reps))
+        return [m[:-2] for m in repaired]                     # without vmap and kept
+    out = _through(meshes, repair is not None, call)[0]
+    if log is not None and repair is not None:
+        for b, m in enumerate(meshes):
+            zeros = np.zeros(len(postprocess.REPAIR_FIELDS), np.int64)
+            zeros[0] = len(m[0])
+            log.append(reports.get(b) or postprocess.repair_report(zeros, len(m[0]), len(m[1])))
+    return out
+
+
 MIRROR_AXES = {"x": 0, "y": 1, "z": 2, "0": 0, "1": 1, "2": 2, 0: 0, 1: 1, 2: 2}
 COLOUR_DEFAULTS = {"S": 2, "rel_tol": 1e-3, "mirror_axis": None, "fill_iters": 32, "bgr": True}
 
@@ -538,15 +585,16 @@ def mesh_group(grids, sp, sdf_res: int, iso: float, dc=None, engine=None, enc=No
 
 def reconstruct(engine, imgs, trans_mats, sdf_params, sdf_res: int, iso: float = 0.0, refine: int = 0,
                 normals: bool = False, band=None, clean=None, simplify=None, colour=None, alpha=None, smooth=None,
-                mesher: str = "mc", dc=None):
+                mesher: str = "mc", dc=None, repair=None, repair_log=None):
     """``reconstruct_select`` for callers that clean every mesh or none (see there); -> the meshes"""
     return reconstruct_select(engine, imgs, trans_mats, sdf_params, sdf_res, iso, refine, normals, band, clean,
-                              simplify=simplify, colour=colour, alpha=alpha, smooth=smooth, mesher=mesher, dc=dc)[0]
+                              simplify=simplify, colour=colour, alpha=alpha, smooth=smooth, mesher=mesher, dc=dc,
+                              repair=repair, repair_log=repair_log)[0]
 
 
 def _mesh_stages(engine, enc, imgs, trans_mats, grids, sp, sdf_res: int, iso: float, views_per_mesh: int, clean,
                  simplify, smooth, colour, dc, refine: int = 0, normals: bool = False, select=None,
-                 strict: bool = True, alpha=None):
+                 strict: bool = True, alpha=None, repair=None, repair_log=None):
     """THE stage chain of ``reconstruct_select`` and ``reconstruct_fused_select``: the group's grids [M,(res+1)^3] with
     their boxes ``sp`` [M,6] -> (M meshes, unclean [M] bool).  The stage values are the CHECKED ones of the ``*_args``
     functions (None: the stage is off and makes no device call); mesh m belongs to views m V .. (m + 1) V - 1 of
@@ -560,8 +608,12 @@ def _mesh_stages(engine, enc, imgs, trans_mats, grids, sp, sdf_res: int, iso: fl
       5. ``isosurface.refine_mesh`` mesh by mesh, when ``refine`` > 0 or ``normals`` (needs ``enc``: V = 1): the Newton
          steps pull the moved vertices back onto the network's level set, the normals are the gradients at the final
          vertices;
+      5b. ``repair_group``: the smoothed, refined meshes are welded, stitched and split to a manifold.  It stands HERE
+         because smoothing or refining the copies of one position could pull them apart: behind those stages the copies
+         stay coincident, the normals follow their vertices, and the colours and a driver's ``--check`` see the repaired
+         mesh (``repair_log``: see ``repair_group``);
       6. ``colour_group``: the final meshes; vertices, faces and normals are not touched.
-    Faces change in stages 2 and 3 only."""
+    Faces change in stages 2, 3 and 5b only."""
     from . import isosurface
     meshes = mesh_group(grids, sp, sdf_res, iso, dc, engine, enc, trans_mats)
     meshes, unclean = clean_group(meshes, clean, select, strict)
@@ -570,6 +622,7 @@ def _mesh_stages(engine, enc, imgs, trans_mats, grids, sp, sdf_res: int, iso: fl
         meshes = [tuple(isosurface.refine_mesh(engine, enc, b, trans_mats, verts, faces, sp[b], sdf_res, iso,
                                                max(int(refine), 0))[:3 if normals else 2])
                   for b, (verts, faces) in enumerate(meshes)]
+    meshes = repair_group(meshes, repair, repair_log)
     if colour is not None:
         meshes = colour_group(meshes, colour, imgs, trans_mats, views_per_mesh, alpha)
     return meshes, unclean
@@ -577,7 +630,8 @@ def _mesh_stages(engine, enc, imgs, trans_mats, grids, sp, sdf_res: int, iso: fl
 
 def reconstruct_select(engine, imgs, trans_mats, sdf_params, sdf_res: int, iso: float = 0.0, refine: int = 0,
                        normals: bool = False, band=None, clean=None, select=None, strict: bool = True,
-                       simplify=None, colour=None, alpha=None, smooth=None, mesher: str = "mc", dc=None):
+                       simplify=None, colour=None, alpha=None, smooth=None, mesher: str = "mc", dc=None, repair=None,
+                       repair_log=None):
     """images -> meshes for one group of views: one ``engine.encode`` call, the per-image grids of
     ``create_sdf`` in one [B,(res+1)^3] tensor, ONE batched meshing (one host sync for the group).
     -> B x (verts [nv,3] float32, faces [nf,3] int32) device views; the bits are those of ``create_sdf``
@@ -608,17 +662,22 @@ def reconstruct_select(engine, imgs, trans_mats, sdf_params, sdf_res: int, iso: 
     marching cubes (``mesh_group``: one vertex per crossed cell placed by a quadric from the network's gradients at
     the cut edges, so creases survive; the mesh can be non-manifold where a cell holds several sheets); every later
     stage sees a (verts, faces) pair as before.  The bits are those of ``isosurface.dual_contour_batch`` on the grids.
+    ``repair`` = True or a dict (``repair_args``): every mesh with triangles is welded, stitched and split to a manifold
+    behind the smoothing and the refinement (``repair_group``: one more host sync for the group, the repaired sizes); the
+    integers and the position bits are those of ``postprocess.repair_arrays`` on the mesh of the call without it, the
+    normals follow their vertices, the colours are those of the repaired mesh.  ``repair_log``: a list that takes one
+    report per mesh.
     -> (meshes, unclean [B] bool)"""
     band = band_args(band, sdf_res)
     clean, simplify, colour, smooth = clean_args(clean), simplify_args(simplify), colour_args(colour), smooth_args(smooth)
-    dc = dc_args(mesher, dc)
+    dc, repair = dc_args(mesher, dc), repair_args(repair)
     if band is None:
         enc, grids = _encode_grids(engine, imgs, trans_mats, sdf_params, sdf_res)
     else:
         enc, grids, _ = _encode_grids_band(engine, imgs, trans_mats, sdf_params, sdf_res, iso, band)
     sp = np.asarray(sdf_params, dtype=np.float64).reshape(grids.shape[0], 6)
     return _mesh_stages(engine, enc, imgs, trans_mats, grids, sp, sdf_res, iso, 1, clean, simplify, smooth, colour, dc,
-                        refine, normals, select, strict, alpha)
+                        refine, normals, select, strict, alpha, repair, repair_log)
 
 
 def fuse_args(fuse, pool: str = "max") -> Optional[Tuple[int, str]]:
@@ -638,16 +697,17 @@ def fuse_args(fuse, pool: str = "max") -> Optional[Tuple[int, str]]:
 
 def reconstruct_fused(engine, imgs, trans_mats, sdf_params, sdf_res: int, iso: float = 0.0, fuse: int = 2,
                       pool: str = "max", clean=None, simplify=None, colour=None, alpha=None, smooth=None,
-                      mesher: str = "mc", dc=None):
+                      mesher: str = "mc", dc=None, repair=None, repair_log=None):
     """``reconstruct_fused_select`` for callers that clean every mesh or none (see there); -> the meshes"""
     return reconstruct_fused_select(engine, imgs, trans_mats, sdf_params, sdf_res, iso, fuse, pool, clean,
                                     simplify=simplify, colour=colour, alpha=alpha, smooth=smooth, mesher=mesher,
-                                    dc=dc)[0]
+                                    dc=dc, repair=repair, repair_log=repair_log)[0]
 
 
 def reconstruct_fused_select(engine, imgs, trans_mats, sdf_params, sdf_res: int, iso: float = 0.0, fuse: int = 2,
                              pool: str = "max", clean=None, select=None, strict: bool = True, simplify=None,
-                             colour=None, alpha=None, smooth=None, mesher: str = "mc", dc=None):
+                             colour=None, alpha=None, smooth=None, mesher: str = "mc", dc=None, repair=None,
+                             repair_log=None):
     """multi-view ``reconstruct``: the B images are B / ``fuse`` runs of ``fuse`` consecutive views of one object each
     (cameras trans_mats [B,4,3] in the object's frame, the run's grid box = its first view's sdf_params).  One
     ``engine.encode`` call, one ``engine.query_grid_views`` grid per run (features pooled over the run's views,
@@ -657,7 +717,7 @@ def reconstruct_fused_select(engine, imgs, trans_mats, sdf_params, sdf_res: int,
     lattice of the run's box) and ``smooth`` (the cap in cells of the run's box) as in ``reconstruct_select``;
     ``colour``: every run's mesh is coloured from ALL ``fuse`` views of the run (``alpha`` None or [B,137,137]).
     ``mesher`` = "dc": dual contouring with the GRID normals whatever ``dc`` asks for (this route has no gradient entry,
-    and so no ``refine`` and no ``normals``).
+    and so no ``refine`` and no ``normals``).  ``repair``, ``repair_log``: as in ``reconstruct_select``.
     -> (meshes, unclean [B / fuse] bool)"""
     import torch
     checked = fuse_args(fuse, pool)
@@ -665,7 +725,7 @@ def reconstruct_fused_select(engine, imgs, trans_mats, sdf_params, sdf_res: int,
         raise ValueError("reconstruct_fused needs the number of views to fuse")
     V, pool = checked
     clean, simplify, colour, smooth = clean_args(clean), simplify_args(simplify), colour_args(colour), smooth_args(smooth)
-    dc = dc_args(mesher, dc)
+    dc, repair = dc_args(mesher, dc), repair_args(repair)
     imgs = np.asarray(imgs, np.float32) if not isinstance(imgs, torch.Tensor) else imgs
     B = imgs.shape[0]
     if B % V:
@@ -678,7 +738,7 @@ def reconstruct_fused_select(engine, imgs, trans_mats, sdf_params, sdf_res: int,
     for r in range(B // V):
         engine.query_grid_views(enc, (r * V, V), tm[r * V:(r + 1) * V], sp[r], sdf_res, pool, out=grids[r])
     return _mesh_stages(engine, None, imgs, tm, grids, sp, sdf_res, iso, V, clean, simplify, smooth, colour, dc,
-                        select=select, strict=strict, alpha=alpha)
+                        select=select, strict=strict, alpha=alpha, repair=repair, repair_log=repair_log)
 
 
 def fuse_runs(entries: Sequence, fuse: int) -> List[List]:
@@ -727,18 +787,21 @@ def groups(entries: Sequence, batch_size: int) -> List[List]:
 
 
 def result_obj_path(log_dir: str, sdf_res: int, iso: float, cam_est: bool = False, fuse=None,
-                    clean: bool = False, simplify=None, colour: bool = False, smooth=None, mesher: str = "mc") -> str:
+                    clean: bool = False, simplify=None, colour: bool = False, smooth=None, mesher: str = "mc",
+                    repair: bool = False) -> str:
     """test/create_sdf.py:88-93: <log_dir>/test_objs/[camest_]<res+1>_<str(iso)>; ``fuse`` = (V, pool): the fused
     meshes' own directory [camest_]fuse<V><pool>_<res+1>_<str(iso)>; ``clean``: the tree with the cleaned categories,
     <...>_comb (the name INTEGRATION 3e gives the combined tree); ``simplify`` = CELLS: the simplified meshes' tree,
     <...>[_comb]_s<CELLS>; ``colour``: the coloured meshes' tree, <...>[_comb][_s<CELLS>]_col; ``smooth`` = ITERS: the
     smoothed meshes' tree, _t<ITERS> between _comb and _s<CELLS>: <...>[_comb]_t<ITERS>[_s<CELLS>][_col];
-    ``mesher`` = "dc" / "dcs": the dual-contoured meshes' tree, _dc / _dcs directly behind <res+1>_<str(iso)>"""
+    ``mesher`` = "dc" / "dcs": the dual-contoured meshes' tree, _dc / _dcs directly behind <res+1>_<str(iso)>;
+    ``repair``: the repaired meshes' tree, _rep in front of _col: <...>[_s<CELLS>]_rep[_col]"""
     prefix = ("camest_" if cam_est else "") + ("fuse%d%s_" % tuple(fuse) if fuse else "")
     return os.path.join(log_dir, "test_objs", prefix + str(sdf_res + 1) + "_" + str(iso)
                         + ("_" + mesher if mesher in ("dc", "dcs") else "") + ("_comb" if clean else "")
                         + ("_t%d" % smooth if smooth is not None else "")
-                        + ("_s%d" % simplify if simplify is not None else "") + ("_col" if colour else ""))
+                        + ("_s%d" % simplify if simplify is not None else "") + ("_rep" if repair else "")
+                        + ("_col" if colour else ""))
 
 
 def obj_path(out_dir: str, cat_id: str, obj: str, view: int) -> str:
@@ -795,6 +858,7 @@ def parser():
     add_stage_flags(p)
     add_score_flags(p)
     add_check_flags(p)
+    add_repair_flags(p)
     return p
 
 
@@ -883,6 +947,26 @@ def score_from_flags(a) -> Optional[Tuple[str, int]]:
             raise ValueError("--score_points needs --score")
         return None
     return score_args((a.score, SCORE_POINTS if a.score_points is None else a.score_points))
+
+
+def add_repair_flags(p) -> None:
+    p.add_argument("--repair", action="store_true",
+                   help="weld, stitch and split every mesh to a manifold on the device, behind the smoothing and the "
+                        "refinement; results go to <...>_rep, one JSON line per mesh to <out_dir>/repairs.jsonl")
+    p.add_argument("--repair_no_weld", action="store_true", help="with --repair: do not merge coincident vertices")
+    p.add_argument("--repair_no_stitch", action="store_true",
+                   help="with --repair: cut every singular edge instead of pairing its faces by angle")
+
+
+def repair_from_flags(a) -> Optional[dict]:
+    """None without --repair, else the checked dict of ``repair_args`` (ValueError for --repair_no_weld or
+    --repair_no_stitch without --repair)"""
+    if not a.repair:
+        for flag in ("repair_no_weld", "repair_no_stitch"):
+            if getattr(a, flag):
+                raise ValueError("--%s needs --repair" % flag)
+        return None
+    return repair_args({"weld": not a.repair_no_weld, "stitch": not a.repair_no_stitch})
 
 
 def add_check_flags(p) -> None:
@@ -1021,6 +1105,7 @@ def check_flags(a) -> Optional[Tuple[int, str]]:
     clean_cats_from_flags(a)                     # (an unknown category)
     score_from_flags(a)
     check_from_flags(a)
+    repair_from_flags(a)
     return fuse_from_flags(a)
 
 
@@ -1050,7 +1135,8 @@ def load_group(group: Sequence, sdf_dir: str, rendered_dir: str, backcolorwhite:
     return data.get_batch(0)
 
 
-def main(argv=None, reconstruct_fn: Optional[Callable] = None, check_fn: Optional[Callable] = None) -> dict:
+def main(argv=None, reconstruct_fn: Optional[Callable] = None, check_fn: Optional[Callable] = None,
+         repair_log: Optional[list] = None) -> dict:
     """-> {"written", "skipped", "empty", "out_dir"}, with ``--score`` also "scored" (the meshes with a score line of
     status 0), with ``--check`` also "checked" and "watertight" (the meshes with a line in checks.jsonl, and those of
     them that are watertight; ``check_fn``: see ``check_group``), with ``--clean`` also "unclean", with ``--simplify`` also "simplified" (the
@@ -1059,7 +1145,10 @@ def main(argv=None, reconstruct_fn: Optional[Callable] = None, check_fn: Optiona
     then ends in ``colours`` uint8 [nv,3], behind the normals when there are any).  ``reconstruct_fn(imgs, trans_mats, sdf_params)``
     replaces the device work (engine + ``reconstruct``) -- for host-side tests of the driver.  With ``--clean`` it is
     called as ``reconstruct_fn(imgs, trans_mats, sdf_params, select)`` -- ``select``: one bool per mesh, True for the
-    listed categories -- and returns (meshes, unclean): ``unclean`` marks the meshes of which nothing was kept."""
+    listed categories -- and returns (meshes, unclean): ``unclean`` marks the meshes of which nothing was kept.
+    With ``--repair`` also "repaired" (the meshes with a line in repairs.jsonl: "cat", "obj", "view", then the report of
+    ``postprocess.repair_arrays``); ``repair_log``: the list an injected ``reconstruct_fn`` appends one report per mesh
+    to (the device route fills its own)."""
     from concurrent.futures import ThreadPoolExecutor
     from datetime import datetime
 
@@ -1073,10 +1162,12 @@ def main(argv=None, reconstruct_fn: Optional[Callable] = None, check_fn: Optiona
     clean_cats = clean_cats_from_flags(a)[1] if cleaning else set()
     score = score_from_flags(a)
     check = check_from_flags(a)
+    repair = repair_from_flags(a)
+    repair_log = [] if repair_log is None else repair_log
     smooth, coloured = stages["smooth"], stages["colour"] is not None
     out_dir = result_obj_path(a.log_dir, a.sdf_res, a.iso, a.cam_est, fuse, clean=cleaning, simplify=stages["simplify"],
                               colour=coloured, smooth=None if smooth is None else smooth["iters"],
-                              mesher=stages["mesher"])
+                              mesher=stages["mesher"], repair=repair is not None)
     entries = sample_list(categories(a.category), a.test_lst_dir, a.view_num, a.seed, a.num_shards, a.shard_id)
     if fuse:
         runs = fuse_runs(entries, per_mesh)
@@ -1097,11 +1188,13 @@ def main(argv=None, reconstruct_fn: Optional[Callable] = None, check_fn: Optiona
         def reconstruct_fn(imgs, trans_mats, sdf_params, select=None):
             if fuse:                             # (no band: ``fuse_from_flags`` refuses it, the route does not take it)
                 out = reconstruct_fused_select(engine, imgs, trans_mats, sdf_params, a.sdf_res, a.iso, fuse=fuse[0],
-                                               pool=fuse[1], select=select, strict=False,
+                                               pool=fuse[1], select=select, strict=False, repair=repair,
+                                               repair_log=repair_log,
                                                **{k: v for k, v in stages.items() if k != "band"})
             else:
                 out = reconstruct_select(engine, imgs, trans_mats, sdf_params, a.sdf_res, a.iso, refine=a.refine,
-                                         normals=a.normals, select=select, strict=False, **stages)
+                                         normals=a.normals, select=select, strict=False, repair=repair,
+                                         repair_log=repair_log, **stages)
             return out if cleaning else out[0]   # the contract of an injected function: the pair only with --clean
 
     os.makedirs(out_dir, exist_ok=True)
@@ -1112,7 +1205,7 @@ def main(argv=None, reconstruct_fn: Optional[Callable] = None, check_fn: Optiona
         logf.flush()
         print(s)
 
-    written = empty = unclean = scored = checked = watertight = 0
+    written = empty = unclean = scored = checked = watertight = repaired = 0
     score_cache: dict = {}
     scores_path = os.path.join(out_dir, "scores.jsonl")
     if score is not None and not a.skip_existing:           # every mesh is scored again: the file starts afresh
@@ -1120,6 +1213,9 @@ def main(argv=None, reconstruct_fn: Optional[Callable] = None, check_fn: Optiona
     checks_path = os.path.join(out_dir, "checks.jsonl")
     if check is not None and not a.skip_existing:           # every mesh is checked again: the file starts afresh
         open(checks_path, "w").close()
+    repairs_path = os.path.join(out_dir, "repairs.jsonl")
+    if repair is not None and not a.skip_existing:          # every mesh is repaired again: the file starts afresh
+        open(repairs_path, "w").close()
     try:
         log_string(str(a))
         log_string("%s; %d views listed, %d to do in %d groups -> %s  (%s)"
@@ -1144,6 +1240,12 @@ def main(argv=None, reconstruct_fn: Optional[Callable] = None, check_fn: Optiona
                 for f in in_flight:                         # the group before this one: a writer's exception surfaces
                     f.result()
                 in_flight = []
+                if repair is not None:                      # the reports the group's reconstruction left
+                    with open(repairs_path, "a") as rf:
+                        for (cat_id, obj, view), report in zip(group[::per_mesh], repair_log):
+                            rf.write(json.dumps(dict({"cat": cat_id, "obj": obj, "view": view}, **report)) + "\n")
+                            repaired += 1
+                    del repair_log[:]
                 if score is not None:                       # the final meshes, still where reconstruct left them
                     rows = score_group(meshes, group[::per_mesh], score, a.seed, score_cache, log=log_string)
                     with open(scores_path, "a") as sf:
@@ -1180,7 +1282,7 @@ def main(argv=None, reconstruct_fn: Optional[Callable] = None, check_fn: Optiona
     for key, stage, count in (("unclean", stages["clean"], unclean), ("simplified", stages["simplify"], written - empty),
                               ("smoothed", smooth, written - empty), ("coloured", stages["colour"], written - empty),
                               ("scored", score, scored), ("checked", check, checked),
-                              ("watertight", check, watertight)):
+                              ("watertight", check, watertight), ("repaired", repair, repaired)):
         if stage is not None:
             res[key] = count
     return res

@@ -1,5 +1,5 @@
 // The building blocks of the stages that work on "B meshes back to back, with host offsets" (mesh_clean.hip,
-// mesh_simplify.hip, mesh_colour.hip, mesh_sample.hip, mesh_smooth.hip, mesh_check.hip; DESIGN 4z states each block's contract).  Everything has internal linkage: each
+// mesh_simplify.hip, mesh_colour.hip, mesh_sample.hip, mesh_smooth.hip, mesh_check.hip, mesh_repair.hip; DESIGN 4z states each block's contract).  Everything has internal linkage: each
 // translation unit that includes this keeps its own copy, and no kernel is launched across translation units.  FOR
 // THOSE FILES ONLY: the compiler emits a __global__ function whether or not the file launches it, so the workspace
 // cursor (WsCursor, scan_bsum_items), which marching_cubes.hip and grid_band.hip use as well, lives in kernels.hpp.

@@ -34,6 +34,10 @@ Not in the reference either: checks of a mesh's topology, orientation and self-i
 ``create_sdf`` and ``demo``, ``evaluate mesh_check``, DESIGN 4zh).  ``check_arrays`` is the rule, on the host;
 ``check_meshes_device`` / ``check_arrays_device`` (mesh_check.hip) give its integers for meshes that lie on the device.
 They measure and repair nothing.
+
+Not in the reference either: repair of a mesh to a manifold -- weld, drop, stitch and split (``--repair`` of
+``create_sdf`` and ``demo``).  ``repair_arrays`` is the rule, on the host; ``repair_meshes_device`` /
+``repair_arrays_device`` (mesh_repair.hip) give its integers and its position bits for meshes that lie on the device.
 """
 from __future__ import annotations
 
@@ -590,6 +594,234 @@ def check_face_flags(verts, faces, max_pairs=None) -> np.ndarray:
     """uint8 [nf] beside ``check_arrays``: 1 in an intersecting pair, 2 zero area or a repeated index, 4 on a boundary
     edge, 8 on a non-manifold edge, 16 on a misoriented edge; a bit whose field is invalid stays 0"""
     return _check(verts, faces, max_pairs)[1]
+
+
+# ---- mesh repair: the rule (DESIGN 4zi; the device restates it, mesh_repair.hip) -----------------------------------
+REPAIR_FIELDS = ("nv_out", "nf_out", "status", "welded_vertices", "repeated_faces", "duplicate_faces", "pillow_faces",
+                 "singular_edges", "stitched_edges", "pinched_edges", "added_vertices",
+                 "dropped_vertices")                              # DISN_REPAIR_NV_OUT .. in this order
+REPAIR_WELD, REPAIR_STITCH = 1, 2                                 # the flag bits of disn_mesh_repair_count_batch
+REPAIR_MAX_FAN = 16                                               # the most faces of an edge the stitch orders
+
+
+def _repair_cross(a, b):
+    return np.array([a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0]])
+
+
+def _repair_dot(a, b):
+    return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]
+
+
+def _repair_det(a, b, c):
+    """the determinant of the rows a, b, c, written as ``check_orient`` writes it"""
+    return (a[0] * (b[1] * c[2] - b[2] * c[1]) - a[1] * (b[0] * c[2] - b[2] * c[0])) + a[2] * (b[0] * c[1] - b[1] * c[0])
+
+
+def repair_stitch_edge(e, d, forward):
+    """the angular rule of ``repair_arrays`` on ONE singular edge: e = p_hi - p_lo, d [k,3] = p_opp - p_lo of the edge's
+    faces in ascending face order (float64), forward [k]: the face's corner pair runs lo -> hi.  -> the partners
+    [(m, n)] as positions in that order, or None when the rule fails (a tie, a rounding inconsistency, or directions that
+    do not alternate)"""
+    k = len(d)
+    r = d[0]
+    er = _repair_cross(e, r)
+    half = [0] * k
+    for m in range(1, k):
+        s, c = _repair_det(e, r, d[m]), _repair_dot(er, _repair_cross(e, d[m]))
+        if s > 0 or (s == 0 and c > 0):
+            half[m] = 0
+        elif s < 0 or (s == 0 and c < 0):
+            half[m] = 1
+        else:
+            return None
+    rank = [0] * k
+    for m in range(1, k):
+        n_before = 1                                              # the reference is before everyone
+        for n in range(1, k):
+            if n != m and (half[n] < half[m] or (half[n] == half[m] and _repair_det(e, d[n], d[m]) > 0)):
+                n_before += 1
+        rank[m] = n_before
+    at = [-1] * k
+    for m in range(k):
+        if at[rank[m]] >= 0:
+            return None                                           # two faces of one rank: no permutation
+        at[rank[m]] = m
+    if any(forward[at[q]] == forward[at[(q + 1) % k]] for q in range(k)):
+        return None
+    return [(at[q], at[(q + 1) % k]) for q in range(k) if not forward[at[q]]]
+
+
+def _repair_identity(v32, f, status: int):
+    nv, nf = v32.shape[0], f.shape[0]
+    report = {"status": status, "nv": nv, "nf": nf}
+    report.update((k, 0) for k in REPAIR_FIELDS if k != "status")
+    report.update(nv_out=nv, nf_out=nf)
+    return v32.copy(), f.astype(np.int32), np.arange(nv, dtype=np.int32), np.arange(nf, dtype=np.int32), report
+
+
+def repair_arrays(verts, faces, weld: bool = True, stitch: bool = True):
+    """Repair of one mesh to a manifold on the host: THE SPECIFICATION of ``repair_meshes_device`` (every integer; the
+    positions are a gather, so their bits follow).  -> (verts' float32 [nv',3], faces' int32 [nf',3], vmap int32 [nv']:
+    the ORIGINAL vertex a new one copies, kept int32 [nf']: the original face of a new one, report: ``status``, ``nv``,
+    ``nf`` and the REPAIR_FIELDS).  All geometry is float64 on the float32 coordinates, + - x only, each operation
+    rounded once, no contraction (as ``check_orient``).
+
+    Status: 2 a face index outside [0, nv); 4 a coordinate that is not finite; of both the larger.  The mesh then comes
+    back unchanged, ``vmap`` and ``kept`` the identity, every other count zero.  An empty mesh has status 0 and zeros.
+
+    Weld (``weld``): vertices whose three float32 coordinates are equal (after adding float32(0): -0 equals +0) merge
+    into the smallest index of the group (``welded_vertices``: the vertices merged away); otherwise every vertex stands
+    for itself.  Drop, on the welded indices: a face with a repeated index (``repeated_faces``); of several faces with
+    the same unordered triple, all of one cyclic orientation, all but the smallest face index (``duplicate_faces``); a
+    triple held in BOTH orientations is a pillow and loses all its faces (``pillow_faces``).  Zero-area faces on three
+    distinct positions stay (dropping one opens a hole).  The survivors keep their order and orientation.
+
+    Edges of the survivors: an undirected edge held by exactly two corner pairs is regular and its two faces are
+    PARTNERS there; one held by three or more is singular (``singular_edges``).  Stitch (``stitch``), on a singular edge
+    of k faces, k even and k <= REPAIR_MAX_FAN: lo < hi its ends, e = p_hi - p_lo, d_m = p_opp(m) - p_lo, r the d of the
+    edge's smallest face; cross(a, b) = (a1 b2 - a2 b1, a2 b0 - a0 b2, a0 b1 - a1 b0), dot(a, b) = (a0 b0 + a1 b1) +
+    a2 b2, det(a, b, c) = (a0 (b1 c2 - b2 c1) - a1 (b0 c2 - b2 c0)) + a2 (b0 c1 - b1 c0).  For every other face s_m =
+    det(e, r, d_m), c_m = dot(cross(e, r), cross(e, d_m)); half 0 when s_m > 0 or (s_m = 0 and c_m > 0), half 1 when
+    s_m < 0 or (s_m = 0 and c_m < 0), both zero: the edge fails.  Face m is before n when half_m < half_n, or the halves
+    are equal and det(e, d_m, d_n) > 0; the reference is before everyone; rank_m = the number of faces before m.  The
+    ranks must be a permutation of 0 .. k-1 (any tie or inconsistency of rounding fails the edge: no sort is involved),
+    and the direction of the corner pair (lo -> hi or not) must alternate around the cycle of ranks.  Then each face that
+    runs hi -> lo, at rank q, is the partner of the face at rank (q + 1) mod k: the wedge between them is the inside of
+    both (``stitched_edges``).  An edge the rule does not apply to, or fails on, is CUT: no face has a partner there.
+
+    Split: the corners (f, i), (g, i) of partners f, g at an edge {i, j} are related, and so are their corners at j; the
+    classes are the transitive closure.  A stitched edge two of whose pairs have the same (class at lo, class at hi) is
+    pinched (``pinched_edges``, counted among the stitched ones too); the classes are computed AGAIN with every pinched
+    edge cut, and that result is final.  Numbering: first the referenced welded vertices in ascending order, each for
+    the class of its smallest corner (corner 3 f + k of original face f), then one new vertex per further class in the
+    order of the classes' smallest corners (``added_vertices``); unreferenced and welded-away vertices disappear
+    (``dropped_vertices``).  Normals and colours ride along through ``vmap``.
+
+    Why the result is manifold: every face has at most one partner per edge, so the corners of a vertex form paths and
+    cycles under the partner relation, and a class touches a cut edge with at most its two path ends.  The second pass
+    only refines the classes of the first, so distinct pairs of an unpinched stitched edge keep distinct (class at lo,
+    class at hi).  Hence every output edge has at most two faces and every output vertex one fan: for status 0,
+    ``check_arrays`` of the result gives nonmanifold_edges = nonmanifold_vertices = index_degenerate_faces =
+    unreferenced_vertices = 0, and with ``weld=False`` the repair of the result is the identity.
+
+    Not in scope: orientation repair (the meshers report no misoriented edge), hole filling (a cut edge becomes
+    boundary), self-intersections, and the other pairing choice at a pinched edge."""
+    v32 = np.ascontiguousarray(verts.detach().cpu().numpy() if hasattr(verts, "detach") else verts,
+                               np.float32).reshape(-1, 3)
+    f = np.ascontiguousarray(faces.detach().cpu().numpy() if hasattr(faces, "detach") else faces).reshape(-1, 3)
+    f = f.astype(np.int64)
+    nv, nf = v32.shape[0], f.shape[0]
+    status = 0
+    if nf and (f.min() < 0 or f.max() >= nv):
+        status = STATUS_INDEX
+    if not np.isfinite(v32).all():
+        status = STATUS_FINITE
+    if status:
+        return _repair_identity(v32, f, status)
+    # -- weld
+    rep = np.arange(nv, dtype=np.int64)
+    if weld and nv:
+        bits = (v32 + np.float32(0)).view(np.uint32)
+        _, inv = np.unique(bits, axis=0, return_inverse=True)
+        inv = inv.reshape(-1)
+        smallest = np.full(int(inv.max()) + 1, nv, np.int64)
+        np.minimum.at(smallest, inv, np.arange(nv))
+        rep = smallest[inv]
+    g = rep[f] if nf else f
+    # -- drop
+    repeated = (g[:, 0] == g[:, 1]) | (g[:, 1] == g[:, 2]) | (g[:, 2] == g[:, 0])
+    keep = ~repeated
+    even = ((g[:, 0] < g[:, 1]).astype(np.int64) + (g[:, 1] < g[:, 2]) + (g[:, 2] < g[:, 0])) == 2
+    duplicate = pillow = 0
+    ids = np.nonzero(keep)[0]
+    if ids.size:
+        _, tinv = np.unique(np.sort(g[ids], axis=1), axis=0, return_inverse=True)
+        tinv = tinv.reshape(-1)
+        n_even = np.bincount(tinv, weights=even[ids]).astype(np.int64)
+        n_all = np.bincount(tinv)
+        both = (n_even > 0) & (n_even < n_all)
+        first = np.full(n_all.size, nf, np.int64)
+        np.minimum.at(first, tinv, ids)
+        in_pillow = both[tinv]
+        is_dup = ~in_pillow & (first[tinv] != ids)
+        pillow, duplicate = int(in_pillow.sum()), int(is_dup.sum())
+        keep[ids[in_pillow | is_dup]] = False
+    kept = np.nonzero(keep)[0]
+    g = g[kept]
+    n = g.shape[0]
+    # -- edges and partners; corner pair 3 j + k of survivor j runs from its index k to its index (k+1)%3
+    a, b = g.reshape(-1), g[:, (1, 2, 0)].reshape(-1)
+    forward = a < b
+    pair = np.arange(3 * n)
+    nxt = pair - pair % 3 + (pair % 3 + 1) % 3
+    at_lo, at_hi = np.where(forward, pair, nxt), np.where(forward, nxt, pair)
+    ekey = np.minimum(a, b) * np.int64(max(nv, 1)) + np.maximum(a, b)
+    order = np.argsort(ekey, kind="stable")                      # the pairs of an edge in ascending face order
+    starts = np.nonzero(np.r_[True, ekey[order][1:] != ekey[order][:-1]])[0] if n else np.zeros(0, np.int64)
+    ends = np.r_[starts[1:], 3 * n] if n else starts
+    partner = np.full(3 * n, -1, np.int64)
+    p64 = v32.astype(np.float64)
+    singular, stitched = 0, []
+    for s0, s1 in zip(starts, ends):
+        k = s1 - s0
+        row = order[s0:s1]
+        if k == 2:
+            partner[row[0]], partner[row[1]] = row[1], row[0]
+        elif k >= 3:
+            singular += 1
+            if not (stitch and k % 2 == 0 and k <= REPAIR_MAX_FAN):
+                continue
+            lo, hi = min(a[row[0]], b[row[0]]), max(a[row[0]], b[row[0]])
+            d = [p64[g[c // 3, (c % 3 + 2) % 3]] - p64[lo] for c in row]
+            pairs = repair_stitch_edge(p64[hi] - p64[lo], d, [bool(forward[c]) for c in row])
+            if pairs is None:
+                continue
+            for m, q in pairs:
+                partner[row[m]], partner[row[q]] = row[q], row[m]
+            stitched.append(row)
+
+    def classes():
+        parent = np.arange(3 * n)
+
+        def root(x):
+            while parent[x] != x:
+                parent[x] = parent[parent[x]]
+                x = parent[x]
+            return x
+
+        for c in np.nonzero(partner > pair)[0]:
+            for at in (at_lo, at_hi):
+                x, y = root(at[c]), root(at[partner[c]])
+                if x != y:
+                    parent[max(x, y)] = min(x, y)
+        return np.array([root(x) for x in range(3 * n)], np.int64)
+
+    roots = classes()
+    pinched = 0
+    for row in stitched:
+        sig = [(roots[at_lo[c]], roots[at_hi[c]]) for c in row if not forward[c]]
+        if len(set(sig)) < len(sig):
+            pinched += 1
+            partner[row] = -1
+    if pinched:
+        roots = classes()
+    # -- numbering
+    first_corner = np.full(nv, 3 * n, np.int64)
+    np.minimum.at(first_corner, a, pair)
+    ref = first_corner < 3 * n
+    main_root = np.full(nv, -1, np.int64)
+    main_root[ref] = roots[first_corner[ref]]
+    extra = (roots == pair) & (main_root[a] != pair)
+    n_main = int(ref.sum())
+    new_of_root = np.where(extra, n_main + np.cumsum(extra) - 1, (np.cumsum(ref) - 1)[a])
+    faces_out = new_of_root[roots].reshape(-1, 3).astype(np.int32)
+    vmap = np.r_[np.nonzero(ref)[0], a[extra]].astype(np.int32)
+    report = {"status": 0, "nv": nv, "nf": nf, "nv_out": int(vmap.size), "nf_out": int(n),
+              "welded_vertices": int((rep != np.arange(nv)).sum()), "repeated_faces": int(repeated.sum()),
+              "duplicate_faces": duplicate, "pillow_faces": pillow, "singular_edges": singular,
+              "stitched_edges": len(stitched), "pinched_edges": pinched, "added_vertices": int(extra.sum()),
+              "dropped_vertices": nv - n_main}
+    return v32[vmap], faces_out, vmap, kept.astype(np.int32), report
 
 
 # ---- vertex colours from the input views: the rule (DESIGN 4zb; the device restates it, mesh_colour.hip) ----------
@@ -1203,6 +1435,73 @@ def check_arrays_device(verts, faces, max_pairs=None, face_flags: bool = False, 
 
 
 # ---- vertex colours on the device (mesh_colour.hip) -------------------------------------------------------------
+# ---- mesh repair on the device (mesh_repair.hip) ------------------------------------------------------------------
+def repair_report(counts, nv: int, nf: int) -> dict:
+    """one mesh's DISN_REPAIR_FIELDS counts and its input sizes -> the report of ``repair_arrays``"""
+    out = {"status": int(counts[REPAIR_FIELDS.index("status")]), "nv": int(nv), "nf": int(nf)}
+    out.update((k, int(c)) for k, c in zip(REPAIR_FIELDS, counts) if k != "status")
+    return out
+
+
+def repair_meshes_device(meshes, weld: bool = True, stitch: bool = True, strict: bool = True):
+    """``repair_arrays`` for a group of meshes that lie on the device.  ``meshes``: B x (verts [nv,3] float32, faces
+    [nf,3] int32[, further per-vertex arrays]) device tensors (the views the earlier stages return are used in place).
+    ONE count call, ONE read-back of the [B,12] sizes, ONE emit call.
+    -> (repaired, reports): B x (verts', faces'[, arrays'], vmap int32 [nv'], kept int32 [nf']) views of the outputs --
+    the integers and the position bits of ``repair_arrays``; a further array takes, for every output vertex, the row of
+    the vertex it copies (``vmap``) -- and B reports, the dicts of ``repair_arrays``.  An empty mesh stays empty.  A mesh
+    with status 2 (a face index out of range) or 4 (a coordinate that is not finite) raises ValueError naming the mesh --
+    with ``strict=False`` it comes back unchanged and its report carries the status."""
+    import torch
+
+    from . import ops
+    from ._lib import check
+    meshes = [tuple(m) for m in meshes]
+    if not meshes:
+        return [], []
+    B, h = len(meshes), lib()
+    flags = (REPAIR_WELD if weld else 0) | (REPAIR_STITCH if stitch else 0)
+    v, v_off, f, f_off, ws = _pack_meshes(meshes, lambda nv, nf: h.disn_mesh_repair_workspace_bytes(B, nv, nf))
+    dev, K = v.device, len(REPAIR_FIELDS)
+    with torch.cuda.device(dev):
+        counts = torch.zeros((B, K), dtype=torch.int64, device=dev)
+        st = ops._stream()
+        check("disn_mesh_repair_count_batch", h.disn_mesh_repair_count_batch(
+            v.data_ptr(), f.data_ptr(), v_off.ctypes.data, f_off.ctypes.data, B, flags, counts.data_ptr(), ws.data_ptr(),
+            ws.numel(), st))
+        sizes = np.ascontiguousarray(counts.cpu().numpy())      # the one host sync of the group
+        status = sizes[:, REPAIR_FIELDS.index("status")]
+        for b in np.nonzero(status)[0]:
+            if strict or status[b] not in (STATUS_INDEX, STATUS_FINITE):
+                _raise_status(b, status[b], v_off, "disn_mesh_repair_count_batch")
+                raise RuntimeError("mesh %d: disn_mesh_repair_count_batch gave status %d" % (b, status[b]))
+        nvo, nfo = int(sizes[:, 0].sum()), int(sizes[:, 1].sum())
+        out_v = torch.empty((nvo, 3), dtype=torch.float32, device=dev)
+        out_f = torch.empty((nfo, 3), dtype=torch.int32, device=dev)
+        vmap = torch.empty(nvo, dtype=torch.int32, device=dev)
+        kept = torch.empty(nfo, dtype=torch.int32, device=dev)
+        if nvo or nfo:
+            check("disn_mesh_repair_emit_batch", h.disn_mesh_repair_emit_batch(
+                v.data_ptr(), f.data_ptr(), v_off.ctypes.data, f_off.ctypes.data, B, flags, sizes.ctypes.data,
+                out_v.data_ptr(), out_f.data_ptr(), vmap.data_ptr(), kept.data_ptr(), ws.data_ptr(), ws.numel(), st))
+    repaired, reports, v0, f0 = [], [], 0, 0
+    for b, m in enumerate(meshes):
+        nvb, nfb = int(sizes[b, 0]), int(sizes[b, 1])
+        vm = vmap[v0:v0 + nvb]
+        rest = tuple(x.index_select(0, vm.long()) for x in m[2:])
+        repaired.append((out_v[v0:v0 + nvb], out_f[f0:f0 + nfb]) + rest + (vm, kept[f0:f0 + nfb]))
+        reports.append(repair_report(sizes[b], v_off[b + 1] - v_off[b], f_off[b + 1] - f_off[b]))
+        v0, f0 = v0 + nvb, f0 + nfb
+    return repaired, reports
+
+
+def repair_arrays_device(verts, faces, weld: bool = True, stitch: bool = True, strict: bool = True):
+    """``repair_arrays`` for one mesh on the device -> (verts', faces', vmap, kept, report): device tensors with the
+    integers and the position bits of ``repair_arrays``, and its report; the ValueErrors of ``repair_meshes_device``"""
+    repaired, reports = _one_mesh(repair_meshes_device, [(verts, faces)], weld=weld, stitch=stitch, strict=strict)
+    return repaired[0] + (reports[0],)
+
+
 def _colour_inputs(meshes, trans_mats, views_per_mesh: int, S: int):
     """-> (B, V, verts, v_off, faces, f_off, trans_mat [B,V,4,3] device, workspace)"""
     import torch
