@@ -2,7 +2,7 @@
 include/disn_amd_simplify.h and include/disn_amd_colour.h; for the surface samples, include/disn_amd_sample.h; for
 the Taubin smoothing, include/disn_amd_smooth.h; for dual contouring, include/dc/disn_amd_dc.h and
 include/dc/disn_amd_dc_sheets.h; for the mesh checks, include/check/disn_amd_check.h; for the mesh repair,
-include/repair/disn_amd_repair.h).
+include/repair/disn_amd_repair.h; for the mesh closing, include/close/disn_amd_close.h).
 
 The HIP library is the product: there is NO CPU fallback.  ``lib()`` raises
 ``DisnLibraryError`` when the shared object is missing or does not export the
@@ -310,6 +310,14 @@ SIGNATURES_REPAIR = {
     "disn_mesh_repair_emit_batch": (I, [P, P, P, P, I, I, P, P, P, P, P, P, Z, P]),
 }
 
+# name -> (restype, argtypes); every symbol declared in include/close/disn_amd_close.h (the tenth header: the mesh
+# closing)
+SIGNATURES_CLOSE = {
+    "disn_mesh_close_workspace_bytes": (Z, [I, L, L]),
+    "disn_mesh_close_count_batch": (I, [P, P, P, P, I, I, L, P, P, Z, P]),
+    "disn_mesh_close_emit_batch": (I, [P, P, P, P, I, I, L, P, P, P, P, P, P, Z, P]),
+}
+
 _LIB: Optional[C.CDLL] = None
 
 
@@ -328,7 +336,7 @@ def lib() -> C.CDLL:
         raise DisnLibraryError("cannot load %s: %s" % (LIB_PATH, e)) from e
     for name, (res, args) in [kv for t in (SIGNATURES, SIGNATURES_SIMPLIFY, SIGNATURES_COLOUR, SIGNATURES_SAMPLE,
                                                      SIGNATURES_SMOOTH, SIGNATURES_DC, SIGNATURES_DCS, SIGNATURES_CHECK,
-                                                     SIGNATURES_REPAIR) for kv in t.items()]:
+                                                     SIGNATURES_REPAIR, SIGNATURES_CLOSE) for kv in t.items()]:
         try:
             fn = getattr(h, name)
         except AttributeError as e:

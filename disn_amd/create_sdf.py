@@ -72,6 +72,13 @@ the whole group with one read-back (``isosurface.marching_cubes_batch``) and wri
     and ``--check``, which see the repaired mesh.  Results go to <...>_rep[_col]; one JSON line per mesh -- "cat", "obj",
     "view" and the report of ``postprocess.repair_arrays`` -- to ``<out_dir>/repairs.jsonl``, started afresh by a run
     without ``--skip_existing``.  Without the flag nothing changes.
+  * ``--close [--close_no_orient] [--close_no_fill] [--close_outward] [--close_max_hole N]`` (not in the reference)
+    orients every mesh consistently and fills its holes while the group still lies on the device
+    (``postprocess.close_meshes_device``): directly behind ``--repair`` (a mesh that is not manifold is
+    refused: give ``--repair``) and before ``--colour``, ``--score`` and ``--check``, which see the closed mesh.  Results
+    go to <...>[_rep]_cls[_col]; one JSON line per mesh -- "cat", "obj", "view" and the report of
+    ``postprocess.close_arrays`` -- to ``<out_dir>/closes.jsonl``, started afresh by a run without ``--skip_existing``.
+    Without the flag nothing changes.
   * ``--smooth ITERS [--smooth_cap CELLS] [--smooth_free_boundary]`` (1..64 iterations; not in the reference) fairs every
     mesh by Taubin's lambda|mu smoothing (``postprocess.smooth_meshes_device``) while the group still lies
     on the device: behind ``--clean`` and ``--simplify`` and BEFORE ``--refine`` and ``--normals``, so the smoothed
@@ -406,6 +413,49 @@ def repair_group(meshes, repair, log: Optional[list] = None):
     return out
 
 
+def close_args(close) -> Optional[dict]:
+    """``close`` = None / False (off), True (orient and fill) or a dict with some of ``orient``, ``fill``, ``outward``,
+    ``max_hole`` -> None or the checked, complete dict (ValueError; no device work): what ``reconstruct`` /
+    ``reconstruct_fused`` hand to ``close_group``"""
+    if close is None or close is False:
+        return None
+    given = {} if close is True else close
+    if not isinstance(given, dict):
+        raise ValueError("--close takes True or a dict of orient, fill, outward and max_hole, got %r" % (close,))
+    unknown = sorted(set(given) - {"orient", "fill", "outward", "max_hole"})
+    if unknown:
+        raise ValueError("--close takes orient, fill, outward and max_hole, not %s" % ", ".join(unknown))
+    from .postprocess import close_flags
+    c = dict({"orient": True, "fill": True, "outward": False, "max_hole": None}, **given)
+    try:
+        _, cap = close_flags(c["orient"], c["fill"], c["outward"], c["max_hole"])
+    except ValueError as e:
+        raise ValueError("--" + str(e)) from e                 # "--close: outward needs orient"
+    return {"orient": bool(c["orient"]), "fill": bool(c["fill"]), "outward": bool(c["outward"]), "max_hole": cap}
+
+
+def close_group(meshes, close, log: Optional[list] = None):
+    """the closing of one group directly behind its repair: the meshes that have triangles go through ONE
+    ``close_meshes_device`` call; every further per-vertex array (the normals) follows ``vmap`` -> the meshes.
+    ``log``: a list that takes one report per mesh of the group, in mesh order (``postprocess.close_arrays``; a mesh
+    without triangles stays as it is and reports zeros)"""
+    from . import postprocess
+    reports: dict = {}
+
+    def call(picked, some):
+        closed, reps = postprocess.close_meshes_device(some, close["orient"], close["fill"], close["outward"],
+                                                       close["max_hole"])
+        reports.update(zip(picked, reps))
+        return [m[:-2] for m in closed]                       # without vmap and kept
+    out = _through(meshes, close is not None, call)[0]
+    if log is not None and close is not None:
+        for b, m in enumerate(meshes):
+            zeros = np.zeros(len(postprocess.CLOSE_FIELDS), np.int64)
+            zeros[0] = len(m[0])
+            log.append(reports.get(b) or postprocess.close_report(zeros, len(m[0]), len(m[1])))
+    return out
+
+
 MIRROR_AXES = {"x": 0, "y": 1, "z": 2, "0": 0, "1": 1, "2": 2, 0: 0, 1: 1, 2: 2}
 COLOUR_DEFAULTS = {"S": 2, "rel_tol": 1e-3, "mirror_axis": None, "fill_iters": 32, "bgr": True}
 
@@ -585,16 +635,16 @@ def mesh_group(grids, sp, sdf_res: int, iso: float, dc=None, engine=None, enc=No
 
 def reconstruct(engine, imgs, trans_mats, sdf_params, sdf_res: int, iso: float = 0.0, refine: int = 0,
                 normals: bool = False, band=None, clean=None, simplify=None, colour=None, alpha=None, smooth=None,
-                mesher: str = "mc", dc=None, repair=None, repair_log=None):
+                mesher: str = "mc", dc=None, repair=None, repair_log=None, close=None, close_log=None):
     """``reconstruct_select`` for callers that clean every mesh or none (see there); -> the meshes"""
     return reconstruct_select(engine, imgs, trans_mats, sdf_params, sdf_res, iso, refine, normals, band, clean,
                               simplify=simplify, colour=colour, alpha=alpha, smooth=smooth, mesher=mesher, dc=dc,
-                              repair=repair, repair_log=repair_log)[0]
+                              repair=repair, repair_log=repair_log, close=close, close_log=close_log)[0]
 
 
 def _mesh_stages(engine, enc, imgs, trans_mats, grids, sp, sdf_res: int, iso: float, views_per_mesh: int, clean,
                  simplify, smooth, colour, dc, refine: int = 0, normals: bool = False, select=None,
-                 strict: bool = True, alpha=None, repair=None, repair_log=None):
+                 strict: bool = True, alpha=None, repair=None, repair_log=None, close=None, close_log=None):
     """THE stage chain of ``reconstruct_select`` and ``reconstruct_fused_select``: the group's grids [M,(res+1)^3] with
     their boxes ``sp`` [M,6] -> (M meshes, unclean [M] bool).  The stage values are the CHECKED ones of the ``*_args``
     functions (None: the stage is off and makes no device call); mesh m belongs to views m V .. (m + 1) V - 1 of
@@ -612,8 +662,12 @@ def _mesh_stages(engine, enc, imgs, trans_mats, grids, sp, sdf_res: int, iso: fl
          because smoothing or refining the copies of one position could pull them apart: behind those stages the copies
          stay coincident, the normals follow their vertices, and the colours and a driver's ``--check`` see the repaired
          mesh (``repair_log``: see ``repair_group``);
+      5c. ``close_group``: the repaired meshes are oriented consistently and their holes filled, directly behind the
+         repair (whose output is what the closing's rule asks for) and before the colours, so that a centre is coloured
+         like any vertex and a driver's ``--check`` sees the closed mesh; a centre's normal is that of its loop's
+         smallest vertex (``close_log``: see ``close_group``);
       6. ``colour_group``: the final meshes; vertices, faces and normals are not touched.
-    Faces change in stages 2, 3 and 5b only."""
+    Faces change in stages 2, 3 and 5b, and 5c flips faces and adds new ones behind them."""
     from . import isosurface
     meshes = mesh_group(grids, sp, sdf_res, iso, dc, engine, enc, trans_mats)
     meshes, unclean = clean_group(meshes, clean, select, strict)
@@ -622,7 +676,7 @@ def _mesh_stages(engine, enc, imgs, trans_mats, grids, sp, sdf_res: int, iso: fl
         meshes = [tuple(isosurface.refine_mesh(engine, enc, b, trans_mats, verts, faces, sp[b], sdf_res, iso,
                                                max(int(refine), 0))[:3 if normals else 2])
                   for b, (verts, faces) in enumerate(meshes)]
-    meshes = repair_group(meshes, repair, repair_log)
+    meshes = close_group(repair_group(meshes, repair, repair_log), close, close_log)
     if colour is not None:
         meshes = colour_group(meshes, colour, imgs, trans_mats, views_per_mesh, alpha)
     return meshes, unclean
@@ -631,7 +685,7 @@ def _mesh_stages(engine, enc, imgs, trans_mats, grids, sp, sdf_res: int, iso: fl
 def reconstruct_select(engine, imgs, trans_mats, sdf_params, sdf_res: int, iso: float = 0.0, refine: int = 0,
                        normals: bool = False, band=None, clean=None, select=None, strict: bool = True,
                        simplify=None, colour=None, alpha=None, smooth=None, mesher: str = "mc", dc=None, repair=None,
-                       repair_log=None):
+                       repair_log=None, close=None, close_log=None):
     """images -> meshes for one group of views: one ``engine.encode`` call, the per-image grids of
     ``create_sdf`` in one [B,(res+1)^3] tensor, ONE batched meshing (one host sync for the group).
     -> B x (verts [nv,3] float32, faces [nf,3] int32) device views; the bits are those of ``create_sdf``
@@ -667,17 +721,21 @@ def reconstruct_select(engine, imgs, trans_mats, sdf_params, sdf_res: int, iso: 
     integers and the position bits are those of ``postprocess.repair_arrays`` on the mesh of the call without it, the
     normals follow their vertices, the colours are those of the repaired mesh.  ``repair_log``: a list that takes one
     report per mesh.
+    ``close`` = True or a dict (``close_args``): every mesh with triangles is oriented consistently and its holes are
+    filled directly behind the repair (``close_group``: one more host sync for the group, the closed sizes); the integers
+    and the position bits are those of ``postprocess.close_arrays`` on the mesh of the call without it; a mesh that is
+    not manifold raises ValueError (``repair`` comes first).  ``close_log``: a list that takes one report per mesh.
     -> (meshes, unclean [B] bool)"""
     band = band_args(band, sdf_res)
     clean, simplify, colour, smooth = clean_args(clean), simplify_args(simplify), colour_args(colour), smooth_args(smooth)
-    dc, repair = dc_args(mesher, dc), repair_args(repair)
+    dc, repair, close = dc_args(mesher, dc), repair_args(repair), close_args(close)
     if band is None:
         enc, grids = _encode_grids(engine, imgs, trans_mats, sdf_params, sdf_res)
     else:
         enc, grids, _ = _encode_grids_band(engine, imgs, trans_mats, sdf_params, sdf_res, iso, band)
     sp = np.asarray(sdf_params, dtype=np.float64).reshape(grids.shape[0], 6)
     return _mesh_stages(engine, enc, imgs, trans_mats, grids, sp, sdf_res, iso, 1, clean, simplify, smooth, colour, dc,
-                        refine, normals, select, strict, alpha, repair, repair_log)
+                        refine, normals, select, strict, alpha, repair, repair_log, close, close_log)
 
 
 def fuse_args(fuse, pool: str = "max") -> Optional[Tuple[int, str]]:
@@ -697,17 +755,18 @@ def fuse_args(fuse, pool: str = "max") -> Optional[Tuple[int, str]]:
 
 def reconstruct_fused(engine, imgs, trans_mats, sdf_params, sdf_res: int, iso: float = 0.0, fuse: int = 2,
                       pool: str = "max", clean=None, simplify=None, colour=None, alpha=None, smooth=None,
-                      mesher: str = "mc", dc=None, repair=None, repair_log=None):
+                      mesher: str = "mc", dc=None, repair=None, repair_log=None, close=None, close_log=None):
     """``reconstruct_fused_select`` for callers that clean every mesh or none (see there); -> the meshes"""
     return reconstruct_fused_select(engine, imgs, trans_mats, sdf_params, sdf_res, iso, fuse, pool, clean,
                                     simplify=simplify, colour=colour, alpha=alpha, smooth=smooth, mesher=mesher,
-                                    dc=dc, repair=repair, repair_log=repair_log)[0]
+                                    dc=dc, repair=repair, repair_log=repair_log, close=close,
+                                    close_log=close_log)[0]
 
 
 def reconstruct_fused_select(engine, imgs, trans_mats, sdf_params, sdf_res: int, iso: float = 0.0, fuse: int = 2,
                              pool: str = "max", clean=None, select=None, strict: bool = True, simplify=None,
                              colour=None, alpha=None, smooth=None, mesher: str = "mc", dc=None, repair=None,
-                             repair_log=None):
+                             repair_log=None, close=None, close_log=None):
     """multi-view ``reconstruct``: the B images are B / ``fuse`` runs of ``fuse`` consecutive views of one object each
     (cameras trans_mats [B,4,3] in the object's frame, the run's grid box = its first view's sdf_params).  One
     ``engine.encode`` call, one ``engine.query_grid_views`` grid per run (features pooled over the run's views,
@@ -717,7 +776,8 @@ def reconstruct_fused_select(engine, imgs, trans_mats, sdf_params, sdf_res: int,
     lattice of the run's box) and ``smooth`` (the cap in cells of the run's box) as in ``reconstruct_select``;
     ``colour``: every run's mesh is coloured from ALL ``fuse`` views of the run (``alpha`` None or [B,137,137]).
     ``mesher`` = "dc": dual contouring with the GRID normals whatever ``dc`` asks for (this route has no gradient entry,
-    and so no ``refine`` and no ``normals``).  ``repair``, ``repair_log``: as in ``reconstruct_select``.
+    and so no ``refine`` and no ``normals``).  ``repair``, ``repair_log``, ``close``, ``close_log``: as in
+    ``reconstruct_select``.
     -> (meshes, unclean [B / fuse] bool)"""
     import torch
     checked = fuse_args(fuse, pool)
@@ -725,7 +785,7 @@ def reconstruct_fused_select(engine, imgs, trans_mats, sdf_params, sdf_res: int,
         raise ValueError("reconstruct_fused needs the number of views to fuse")
     V, pool = checked
     clean, simplify, colour, smooth = clean_args(clean), simplify_args(simplify), colour_args(colour), smooth_args(smooth)
-    dc, repair = dc_args(mesher, dc), repair_args(repair)
+    dc, repair, close = dc_args(mesher, dc), repair_args(repair), close_args(close)
     imgs = np.asarray(imgs, np.float32) if not isinstance(imgs, torch.Tensor) else imgs
     B = imgs.shape[0]
     if B % V:
@@ -738,7 +798,8 @@ def reconstruct_fused_select(engine, imgs, trans_mats, sdf_params, sdf_res: int,
     for r in range(B // V):
         engine.query_grid_views(enc, (r * V, V), tm[r * V:(r + 1) * V], sp[r], sdf_res, pool, out=grids[r])
     return _mesh_stages(engine, None, imgs, tm, grids, sp, sdf_res, iso, V, clean, simplify, smooth, colour, dc,
-                        select=select, strict=strict, alpha=alpha, repair=repair, repair_log=repair_log)
+                        select=select, strict=strict, alpha=alpha, repair=repair, repair_log=repair_log, close=close,
+                        close_log=close_log)
 
 
 def fuse_runs(entries: Sequence, fuse: int) -> List[List]:
@@ -788,20 +849,21 @@ def groups(entries: Sequence, batch_size: int) -> List[List]:
 
 def result_obj_path(log_dir: str, sdf_res: int, iso: float, cam_est: bool = False, fuse=None,
                     clean: bool = False, simplify=None, colour: bool = False, smooth=None, mesher: str = "mc",
-                    repair: bool = False) -> str:
+                    repair: bool = False, close: bool = False) -> str:
     """test/create_sdf.py:88-93: <log_dir>/test_objs/[camest_]<res+1>_<str(iso)>; ``fuse`` = (V, pool): the fused
     meshes' own directory [camest_]fuse<V><pool>_<res+1>_<str(iso)>; ``clean``: the tree with the cleaned categories,
     <...>_comb (the name INTEGRATION 3e gives the combined tree); ``simplify`` = CELLS: the simplified meshes' tree,
     <...>[_comb]_s<CELLS>; ``colour``: the coloured meshes' tree, <...>[_comb][_s<CELLS>]_col; ``smooth`` = ITERS: the
     smoothed meshes' tree, _t<ITERS> between _comb and _s<CELLS>: <...>[_comb]_t<ITERS>[_s<CELLS>][_col];
     ``mesher`` = "dc" / "dcs": the dual-contoured meshes' tree, _dc / _dcs directly behind <res+1>_<str(iso)>;
-    ``repair``: the repaired meshes' tree, _rep in front of _col: <...>[_s<CELLS>]_rep[_col]"""
+    ``repair``: the repaired meshes' tree, _rep in front of _col: <...>[_s<CELLS>]_rep[_col]; ``close``: the closed
+    meshes' tree, _cls behind _rep: <...>[_rep]_cls[_col]"""
     prefix = ("camest_" if cam_est else "") + ("fuse%d%s_" % tuple(fuse) if fuse else "")
     return os.path.join(log_dir, "test_objs", prefix + str(sdf_res + 1) + "_" + str(iso)
                         + ("_" + mesher if mesher in ("dc", "dcs") else "") + ("_comb" if clean else "")
                         + ("_t%d" % smooth if smooth is not None else "")
                         + ("_s%d" % simplify if simplify is not None else "") + ("_rep" if repair else "")
-                        + ("_col" if colour else ""))
+                        + ("_cls" if close else "") + ("_col" if colour else ""))
 
 
 def obj_path(out_dir: str, cat_id: str, obj: str, view: int) -> str:
@@ -859,6 +921,7 @@ def parser():
     add_score_flags(p)
     add_check_flags(p)
     add_repair_flags(p)
+    add_close_flags(p)
     return p
 
 
@@ -967,6 +1030,31 @@ def repair_from_flags(a) -> Optional[dict]:
                 raise ValueError("--%s needs --repair" % flag)
         return None
     return repair_args({"weld": not a.repair_no_weld, "stitch": not a.repair_no_stitch})
+
+
+def add_close_flags(p) -> None:
+    p.add_argument("--close", action="store_true",
+                   help="orient every mesh consistently and fill its holes on the device, directly behind --repair; "
+                        "results go to <...>_cls, one JSON line per mesh to <out_dir>/closes.jsonl")
+    p.add_argument("--close_no_orient", action="store_true", help="with --close: leave every face's orientation")
+    p.add_argument("--close_no_fill", action="store_true", help="with --close: fill no hole")
+    p.add_argument("--close_outward", action="store_true",
+                   help="with --close: turn every closed component so that its volume is positive (wrong for cavities)")
+    p.add_argument("--close_max_hole", type=int, default=None, metavar="N",
+                   help="with --close: fill only the holes of at most N boundary edges (default and limit 2^22)")
+
+
+def close_from_flags(a) -> Optional[dict]:
+    """None without --close, else the checked dict of ``close_args`` (ValueError for a --close_* flag without --close)"""
+    if not a.close:
+        for flag in ("close_no_orient", "close_no_fill", "close_outward"):
+            if getattr(a, flag):
+                raise ValueError("--%s needs --close" % flag)
+        if a.close_max_hole is not None:
+            raise ValueError("--close_max_hole needs --close")
+        return None
+    return close_args({"orient": not a.close_no_orient, "fill": not a.close_no_fill, "outward": a.close_outward,
+                       "max_hole": a.close_max_hole})
 
 
 def add_check_flags(p) -> None:
@@ -1106,6 +1194,7 @@ def check_flags(a) -> Optional[Tuple[int, str]]:
     score_from_flags(a)
     check_from_flags(a)
     repair_from_flags(a)
+    close_from_flags(a)
     return fuse_from_flags(a)
 
 
@@ -1136,7 +1225,7 @@ def load_group(group: Sequence, sdf_dir: str, rendered_dir: str, backcolorwhite:
 
 
 def main(argv=None, reconstruct_fn: Optional[Callable] = None, check_fn: Optional[Callable] = None,
-         repair_log: Optional[list] = None) -> dict:
+         repair_log: Optional[list] = None, close_log: Optional[list] = None) -> dict:
     """-> {"written", "skipped", "empty", "out_dir"}, with ``--score`` also "scored" (the meshes with a score line of
     status 0), with ``--check`` also "checked" and "watertight" (the meshes with a line in checks.jsonl, and those of
     them that are watertight; ``check_fn``: see ``check_group``), with ``--clean`` also "unclean", with ``--simplify`` also "simplified" (the
@@ -1148,7 +1237,8 @@ def main(argv=None, reconstruct_fn: Optional[Callable] = None, check_fn: Optiona
     listed categories -- and returns (meshes, unclean): ``unclean`` marks the meshes of which nothing was kept.
     With ``--repair`` also "repaired" (the meshes with a line in repairs.jsonl: "cat", "obj", "view", then the report of
     ``postprocess.repair_arrays``); ``repair_log``: the list an injected ``reconstruct_fn`` appends one report per mesh
-    to (the device route fills its own)."""
+    to (the device route fills its own).  With ``--close`` also "closed" (the meshes with a line in closes.jsonl: "cat",
+    "obj", "view", then the report of ``postprocess.close_arrays``); ``close_log``: as ``repair_log``."""
     from concurrent.futures import ThreadPoolExecutor
     from datetime import datetime
 
@@ -1164,10 +1254,12 @@ def main(argv=None, reconstruct_fn: Optional[Callable] = None, check_fn: Optiona
     check = check_from_flags(a)
     repair = repair_from_flags(a)
     repair_log = [] if repair_log is None else repair_log
+    close = close_from_flags(a)
+    close_log = [] if close_log is None else close_log
     smooth, coloured = stages["smooth"], stages["colour"] is not None
     out_dir = result_obj_path(a.log_dir, a.sdf_res, a.iso, a.cam_est, fuse, clean=cleaning, simplify=stages["simplify"],
                               colour=coloured, smooth=None if smooth is None else smooth["iters"],
-                              mesher=stages["mesher"], repair=repair is not None)
+                              mesher=stages["mesher"], repair=repair is not None, close=close is not None)
     entries = sample_list(categories(a.category), a.test_lst_dir, a.view_num, a.seed, a.num_shards, a.shard_id)
     if fuse:
         runs = fuse_runs(entries, per_mesh)
@@ -1189,12 +1281,12 @@ def main(argv=None, reconstruct_fn: Optional[Callable] = None, check_fn: Optiona
             if fuse:                             # (no band: ``fuse_from_flags`` refuses it, the route does not take it)
                 out = reconstruct_fused_select(engine, imgs, trans_mats, sdf_params, a.sdf_res, a.iso, fuse=fuse[0],
                                                pool=fuse[1], select=select, strict=False, repair=repair,
-                                               repair_log=repair_log,
+                                               repair_log=repair_log, close=close, close_log=close_log,
                                                **{k: v for k, v in stages.items() if k != "band"})
             else:
                 out = reconstruct_select(engine, imgs, trans_mats, sdf_params, a.sdf_res, a.iso, refine=a.refine,
                                          normals=a.normals, select=select, strict=False, repair=repair,
-                                         repair_log=repair_log, **stages)
+                                         repair_log=repair_log, close=close, close_log=close_log, **stages)
             return out if cleaning else out[0]   # the contract of an injected function: the pair only with --clean
 
     os.makedirs(out_dir, exist_ok=True)
@@ -1205,7 +1297,7 @@ def main(argv=None, reconstruct_fn: Optional[Callable] = None, check_fn: Optiona
         logf.flush()
         print(s)
 
-    written = empty = unclean = scored = checked = watertight = repaired = 0
+    written = empty = unclean = scored = checked = watertight = repaired = closed = 0
     score_cache: dict = {}
     scores_path = os.path.join(out_dir, "scores.jsonl")
     if score is not None and not a.skip_existing:           # every mesh is scored again: the file starts afresh
@@ -1216,6 +1308,9 @@ def main(argv=None, reconstruct_fn: Optional[Callable] = None, check_fn: Optiona
     repairs_path = os.path.join(out_dir, "repairs.jsonl")
     if repair is not None and not a.skip_existing:          # every mesh is repaired again: the file starts afresh
         open(repairs_path, "w").close()
+    closes_path = os.path.join(out_dir, "closes.jsonl")
+    if close is not None and not a.skip_existing:           # every mesh is closed again: the file starts afresh
+        open(closes_path, "w").close()
     try:
         log_string(str(a))
         log_string("%s; %d views listed, %d to do in %d groups -> %s  (%s)"
@@ -1246,6 +1341,12 @@ def main(argv=None, reconstruct_fn: Optional[Callable] = None, check_fn: Optiona
                             rf.write(json.dumps(dict({"cat": cat_id, "obj": obj, "view": view}, **report)) + "\n")
                             repaired += 1
                     del repair_log[:]
+                if close is not None:                       # likewise
+                    with open(closes_path, "a") as cf:
+                        for (cat_id, obj, view), report in zip(group[::per_mesh], close_log):
+                            cf.write(json.dumps(dict({"cat": cat_id, "obj": obj, "view": view}, **report)) + "\n")
+                            closed += 1
+                    del close_log[:]
                 if score is not None:                       # the final meshes, still where reconstruct left them
                     rows = score_group(meshes, group[::per_mesh], score, a.seed, score_cache, log=log_string)
                     with open(scores_path, "a") as sf:
@@ -1282,7 +1383,8 @@ def main(argv=None, reconstruct_fn: Optional[Callable] = None, check_fn: Optiona
     for key, stage, count in (("unclean", stages["clean"], unclean), ("simplified", stages["simplify"], written - empty),
                               ("smoothed", smooth, written - empty), ("coloured", stages["colour"], written - empty),
                               ("scored", score, scored), ("checked", check, checked),
-                              ("watertight", check, watertight), ("repaired", repair, repaired)):
+                              ("watertight", check, watertight), ("repaired", repair, repaired),
+                              ("closed", close, closed)):
         if stage is not None:
             res[key] = count
     return res

@@ -53,6 +53,7 @@ SOURCES = {
     "mesh_smooth.hip": ["-ffp-contract=off"],     # the steps' float64 arithmetic rounds as smooth_arrays states it
     "mesh_check.hip": ["-ffp-contract=off"],      # the determinants, the areas and the volumes round as check_arrays states them
     "mesh_repair.hip": ["-ffp-contract=off"],     # the determinants of the angular rule round as repair_arrays states them
+    "mesh_close.hip": ["-ffp-contract=off"],      # the centres and the volume terms round as close_arrays states them
     "dual_contour.hip": ["-ffp-contract=off"],    # the points, the quadric and the solve round as dual_contour_arrays states them
     "batch_assemble.hip": ["-ffp-contract=off"],  # sample_pc_rot in the order its bound is derived for
     "api.hip": [],
@@ -68,7 +69,8 @@ HEADERS = ["kernels.hpp", "tuning.hpp", "h2_common.hpp", "mc_tables.h", "mesh_bv
            os.path.join(ROOT, "include", "dc", "disn_amd_dc.h"),
            os.path.join(ROOT, "include", "dc", "disn_amd_dc_sheets.h"),
            os.path.join(ROOT, "include", "check", "disn_amd_check.h"),
-           os.path.join(ROOT, "include", "repair", "disn_amd_repair.h")]
+           os.path.join(ROOT, "include", "repair", "disn_amd_repair.h"),
+           os.path.join(ROOT, "include", "close", "disn_amd_close.h")]
 
 
 def _digest(paths, extra=""):

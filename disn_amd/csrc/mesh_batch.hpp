@@ -1,5 +1,5 @@
 // The building blocks of the stages that work on "B meshes back to back, with host offsets" (mesh_clean.hip,
-// mesh_simplify.hip, mesh_colour.hip, mesh_sample.hip, mesh_smooth.hip, mesh_check.hip, mesh_repair.hip; DESIGN 4z states each block's contract).  Everything has internal linkage: each
+// mesh_simplify.hip, mesh_colour.hip, mesh_sample.hip, mesh_smooth.hip, mesh_check.hip, mesh_repair.hip, mesh_close.hip; DESIGN 4z states each block's contract).  Everything has internal linkage: each
 // translation unit that includes this keeps its own copy, and no kernel is launched across translation units.  FOR
 // THOSE FILES ONLY: the compiler emits a __global__ function whether or not the file launches it, so the workspace
 // cursor (WsCursor, scan_bsum_items), which marching_cubes.hip and grid_band.hip use as well, lives in kernels.hpp.
@@ -123,6 +123,13 @@ inline int blocks_for(long long n) {
   long long b = (n + kThreads - 1) / kThreads;
   if (b > 16384) b = 16384;
   return (int)(b < 1 ? 1 : b);
+}
+
+// the slots of a table of `entries` keys or elements: a power of two, at most half full
+inline unsigned long long table_size(size_t entries) {
+  unsigned long long T = 16;
+  while (T < 2ull * entries) T <<= 1;
+  return T;
 }
 
 // inside a function that returns the hipError_t as an int and has the stream in `st`

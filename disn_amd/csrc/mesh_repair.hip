@@ -568,12 +568,6 @@ struct RepairWs {
   size_t total;
 };
 
-unsigned long long table_size(size_t entries) {
-  unsigned long long T = 16;
-  while (T < 2ull * entries) T <<= 1;              // at most half full
-  return T;
-}
-
 RepairWs repair_layout(void* ws, int B, long long nv, long long nf) {
   WsCursor c(ws);
   const size_t b1 = (size_t)B + 1, f = (size_t)(nf > 0 ? nf : 1), v = (size_t)(nv > 0 ? nv : 1);

@@ -106,12 +106,13 @@ def parser() -> argparse.ArgumentParser:
     p.add_argument("--preview", default=None, metavar="OUT.png",
                    help="also write the sphere-traced view of the predicted surface from the camera in use")
     p.add_argument("--preview_size", type=int, default=137, metavar="N", help="the preview is N x N [default: 137]")
-    from .create_sdf import add_check_flags, add_repair_flags, add_stage_flags
+    from .create_sdf import add_check_flags, add_close_flags, add_repair_flags, add_stage_flags
     p.add_argument("--clean", action="store_true",
                    help="drop the mesh's small and far parts on the device (postprocess.clean_meshes_device)")
     add_stage_flags(p)
     add_check_flags(p)
     add_repair_flags(p)
+    add_close_flags(p)
     return p
 
 
@@ -147,13 +148,15 @@ def write_preview(engine, img: np.ndarray, trans_mat, path: str, size: int, iso:
 def main(argv=None) -> dict:
     """-> {"out", "verts", "faces", "trans_mat"}, with ``--colour`` also "coloured" (True) and "colours" (uint8 [nv,3]),
     with ``--check`` also "checked" (1), "watertight" (0 or 1) and "check" (the mesh's line of checks.jsonl), with
-    ``--repair`` also "repair" (the mesh's line of repairs.jsonl, written beside ``--out``)"""
+    ``--repair`` also "repair" (the mesh's line of repairs.jsonl, written beside ``--out``), with ``--close`` also
+    "close" (likewise, closes.jsonl)"""
     a = parser().parse_args(argv)
-    from .create_sdf import (check_from_flags, check_group, reconstruct, repair_from_flags, restore_weights,
-                             stages_from_flags, write_mesh)
+    from .create_sdf import (check_from_flags, check_group, close_from_flags, reconstruct, repair_from_flags,
+                             restore_weights, stages_from_flags, write_mesh)
     stages = stages_from_flags(a, a.clean)                             # a bad flag: before anything else
     check = check_from_flags(a)
     repair, repair_log = repair_from_flags(a), []
+    close, close_log = close_from_flags(a), []
     coloured = stages["colour"] is not None
     img = read_image(a.img)
     if img.shape[1:3] != (137, 137):
@@ -174,7 +177,7 @@ def main(argv=None) -> dict:
     alpha = read_alpha(a.img) if coloured else None                    # the background of the rendering colours nothing
     mesh = reconstruct(engine, img, trans_mat, DEMO_SDF_PARAMS, a.sdf_res, a.iso, a.refine, a.normals,
                        alpha=None if alpha is None else alpha[None], repair=repair, repair_log=repair_log,
-                       **stages)[0]
+                       close=close, close_log=close_log, **stages)[0]
     verts, faces = mesh[:2]
     if repair_log:                                                     # the report of --repair, beside the mesh
         import json
@@ -182,6 +185,12 @@ def main(argv=None) -> dict:
         with open(os.path.join(os.path.dirname(os.path.abspath(a.out)), "repairs.jsonl"), "w") as rf:
             rf.write(json.dumps(dict({"cat": "", "obj": os.path.basename(a.out), "view": 0}, **repair_log[0])) + "\n")
         print("repair: %s" % repair_log[0])
+    if close_log:                                                      # likewise, the report of --close
+        import json
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(os.path.join(os.path.dirname(os.path.abspath(a.out)), "closes.jsonl"), "w") as cf:
+            cf.write(json.dumps(dict({"cat": "", "obj": os.path.basename(a.out), "view": 0}, **close_log[0])) + "\n")
+        print("close: %s" % close_log[0])
     row = None
     if check is not None:                                              # the final mesh, before it is written
         import json
@@ -200,6 +209,8 @@ def main(argv=None) -> dict:
         res["checked"], res["watertight"], res["check"] = 1, int(row["watertight"]), row
     if repair_log:
         res["repair"] = repair_log[0]
+    if close_log:
+        res["close"] = close_log[0]
     if a.preview:
         res["preview"] = write_preview(engine, img, trans_mat, a.preview, a.preview_size, a.iso, read_alpha(a.img))
     return res

@@ -704,8 +704,8 @@ def repair_arrays(verts, faces, weld: bool = True, stitch: bool = True):
     ``check_arrays`` of the result gives nonmanifold_edges = nonmanifold_vertices = index_degenerate_faces =
     unreferenced_vertices = 0, and with ``weld=False`` the repair of the result is the identity.
 
-    Not in scope: orientation repair (the meshers report no misoriented edge), hole filling (a cut edge becomes
-    boundary), self-intersections, and the other pairing choice at a pinched edge."""
+    Not in scope: self-intersections and the other pairing choice at a pinched edge.  Faces keep their orientation
+    and a cut edge becomes boundary: ``close_arrays`` orients and closes what this leaves."""
     v32 = np.ascontiguousarray(verts.detach().cpu().numpy() if hasattr(verts, "detach") else verts,
                                np.float32).reshape(-1, 3)
     f = np.ascontiguousarray(faces.detach().cpu().numpy() if hasattr(faces, "detach") else faces).reshape(-1, 3)
@@ -822,6 +822,211 @@ def repair_arrays(verts, faces, weld: bool = True, stitch: bool = True):
               "stitched_edges": len(stitched), "pinched_edges": pinched, "added_vertices": int(extra.sum()),
               "dropped_vertices": nv - n_main}
     return v32[vmap], faces_out, vmap, kept.astype(np.int32), report
+
+
+# ---- mesh closing: the rule (the device restates it, mesh_close.hip) -----------------------------------
+CLOSE_FIELDS = ("nv_out", "nf_out", "status", "components", "unorientable_components", "flipped_faces", "loops",
+                "filled_loops", "fill_faces")                     # DISN_CLOSE_NV_OUT .. in this order
+CLOSE_ORIENT, CLOSE_FILL, CLOSE_OUTWARD = 1, 2, 4                 # the flag bits of disn_mesh_close_count_batch
+CLOSE_MAX_HOLE = 1 << 22                                          # the longest loop that is filled: 2^22 2^40 = 2^62
+STATUS_NOT_MANIFOLD = 16
+
+
+def close_flags(orient=True, fill=True, outward=False, max_hole=None) -> Tuple[int, int]:
+    """the checked (flag bits, max_hole) of ``close_arrays`` and ``close_meshes_device``; ValueError otherwise"""
+    for name, x in (("orient", orient), ("fill", fill), ("outward", outward)):
+        if not isinstance(x, (bool, np.bool_)):
+            raise ValueError("close: %s must be True or False, got %r" % (name, x))
+    if outward and not orient:
+        raise ValueError("close: outward needs orient")
+    cap = CLOSE_MAX_HOLE if max_hole is None else max_hole
+    if isinstance(cap, (bool, np.bool_)) or not isinstance(cap, (int, np.integer)) or not 0 <= cap <= CLOSE_MAX_HOLE:
+        raise ValueError("close: max_hole must be an integer in 0..%d, got %r" % (CLOSE_MAX_HOLE, max_hole))
+    return ((CLOSE_ORIENT if orient else 0) | (CLOSE_FILL if fill else 0) | (CLOSE_OUTWARD if outward else 0)), int(cap)
+
+
+def close_exponent(v32: np.ndarray) -> int:
+    """E: the ``frexp`` exponent of the largest |coordinate| (largest = 2^E m, 0.5 <= m < 1), 0 when that is 0"""
+    largest = float(np.abs(v32).max()) if v32.size else 0.0
+    return int(np.frexp(largest)[1]) if largest != 0.0 else 0
+
+
+def _close_identity(v32, f, status: int):
+    nv, nf = v32.shape[0], f.shape[0]
+    report = {"status": status, "nv": nv, "nf": nf}
+    report.update((k, 0) for k in CLOSE_FIELDS if k != "status")
+    report.update(nv_out=nv, nf_out=nf)
+    return v32.copy(), f.astype(np.int32), np.arange(nv, dtype=np.int32), np.arange(nf, dtype=np.int32), report
+
+
+def close_arrays(verts, faces, orient: bool = True, fill: bool = True, outward: bool = False, max_hole=None):
+    """Closing of one manifold mesh on the host: consistent orientation and hole filling.  THE SPECIFICATION of
+    ``close_meshes_device`` (every integer and every position bit).  -> (verts' float32 [nv',3], faces' int32 [nf',3],
+    vmap int32 [nv'], kept int32 [nf'], report: ``status``, ``nv``, ``nf`` and the CLOSE_FIELDS).  It stands behind
+    ``repair_arrays``, whose output never has status 16.
+
+    Status, of several the largest: 0; 2 a face index outside [0, nv); 4 a coordinate that is not finite; 16
+    (STATUS_NOT_MANIFOLD) a face with a repeated index, an undirected edge held by three or more corner pairs, or a
+    vertex on more than two boundary edges -- tests on integers alone, made where every index is valid (a mesh with a
+    bad index is not looked at through its indices: it has status 2, or 4).  A mesh with a status comes back unchanged,
+    ``vmap`` and ``kept`` the identity, every counter 0.  An empty mesh has status 0 and zeros.
+
+    Edges as in ``repair_arrays``: face (a, b, c) gives the corner pairs (a, b), (b, c), (c, a), corner 3 f + k is pair
+    k of face f; an undirected edge held by two pairs makes its faces PARTNERS, one held by one pair is boundary.
+
+    Orient (``orient``; without it ``components``, ``unorientable_components`` and ``flipped_faces`` are 0).  The
+    components are the classes of faces under "partners" (``components``); a component's root is its smallest face.
+    Two partners are related by 1 when their corner pairs at the shared edge run the same way (``check_arrays`` calls
+    that edge misoriented), else by 0.  A component is orientable when every face can be given a parity, the root 0,
+    such that every relation holds; the parity is then unique.  A non-orientable component
+    (``unorientable_components``) keeps the orientation of its faces; it is still filled.  Of an orientable one, n0 and
+    n1 are the faces of parity 0 and 1 and K = 1 if n1 > n0 else 0: the majority stays, a tie keeps the root's
+    orientation.  Every face of parity != K is written as (a, c, b) (``flipped_faces``).  A consistent component
+    (n1 = 0) is never touched without ``outward``: an inward-facing cavity is legitimate.
+
+    Fill (``fill``; without it ``loops``, ``filled_loops`` and ``fill_faces`` are 0).  Boundary vertices joined by a
+    boundary corner pair belong to one loop, whose id is its smallest vertex and whose length L its number of boundary
+    pairs (``loops``); under status 0 the loops are simple and vertex-disjoint.  A loop with L <= ``max_hole`` (default
+    and limit CLOSE_MAX_HOLE = 2^22) is filled (``filled_loops``): one new vertex c, and for every boundary pair
+    (a -> b) of the loop one face (c, b, a) -- (c, a, b) when the pair's face is flipped -- (``fill_faces``).  A fan
+    from a centre never names an edge the mesh already has; a fan from a rim vertex can.  The centre, in integers and
+    single roundings: E = ``close_exponent`` of all nv vertices; q(x) = rint(float64(x) 2^(40-E)) as int64 of every
+    coordinate of the tail a of every boundary pair of the loop (in the input's orientation); S = their exact sum;
+    centre = float32(float64(S) / float64(L) * 2^(E-40)) per axis.
+
+    Outward (``outward``, needs ``orient``; wrong for cavities, hence off by default), on the orientable components
+    with no unfilled boundary pair: t_f = ``_check_volume_terms`` of face f, an input face as it came, a fill face as
+    (c, b, a); tq_f = rint(t_f 2^(30-3E)) as int64 (|tq| <= 2^30); V = the sum of tq_f over the component's faces,
+    fill faces included, + for a face of parity K and - otherwise, a fill face having the parity of the face of its
+    pair.  V < 0: K becomes 1 - K.  V is an integer, so its sign does not depend on the order of the sum.
+
+    Numbering: verts' = the nv input vertices untouched and in place (closing drops nothing, unreferenced vertices
+    stay), then one centre per filled loop in ascending loop id; faces' = the nf input faces in order, then the fill
+    faces in ascending corner 3 f + k of their pairs.  vmap[i] = i for i < nv and the loop id for a centre: the vertex
+    whose rows of any further per-vertex array (the normals) the centre inherits.  kept[f] = f for an input face, the
+    face of its pair for a fill face.
+
+    Guarantee: for status 0 with ``orient`` and ``fill`` and no loop over ``max_hole``, ``check_arrays`` of the result
+    has boundary_edges = 0, nonmanifold_edges = 0, nonmanifold_vertices as the input's, and misoriented_edges = 0 when
+    ``unorientable_components`` = 0; closing the result again changes nothing.  Limits: a fan over a non-planar loop
+    may intersect itself or the mesh, caps are flat, non-orientable components stay as they are, the centre inherits a
+    rim vertex's normal."""
+    v32 = np.ascontiguousarray(verts.detach().cpu().numpy() if hasattr(verts, "detach") else verts,
+                               np.float32).reshape(-1, 3)
+    f = np.ascontiguousarray(faces.detach().cpu().numpy() if hasattr(faces, "detach") else faces).reshape(-1, 3)
+    f = f.astype(np.int64)
+    nv, nf = v32.shape[0], f.shape[0]
+    flags, cap = close_flags(orient, fill, outward, max_hole)
+    valid = not (nf and (f.min() < 0 or f.max() >= nv))
+    status = 0 if valid else STATUS_INDEX
+    if not np.isfinite(v32).all():
+        status = STATUS_FINITE
+    a, b = f.reshape(-1), f[:, (1, 2, 0)].reshape(-1)            # corner pair 3 f + k: index k -> index (k+1)%3
+    if valid and nf:
+        key = np.minimum(a, b) * np.int64(nv) + np.maximum(a, b)
+        _, inv, held = np.unique(key, return_inverse=True, return_counts=True)
+        inv = inv.reshape(-1)
+        boundary = held[inv] == 1
+        degree = np.bincount(a[boundary], minlength=nv) + np.bincount(b[boundary], minlength=nv)
+        if (a == b).any() or (held >= 3).any() or (degree > 2).any():
+            status = STATUS_NOT_MANIFOLD
+    if status or not nf:
+        return _close_identity(v32, f, status)
+    forward = a < b
+    order = np.argsort(inv, kind="stable")
+    first = (np.cumsum(held) - held)[held == 2]
+    c0, c1 = order[first], order[first + 1]                      # the two pairs of every regular edge
+    rel = (forward[c0] == forward[c1]).astype(np.int64)
+    p64 = v32.astype(np.float64)
+    E = close_exponent(v32)
+    # -- orient: a union-find of faces that carries each face's parity against its parent; roots only decrease
+    root, parity = np.arange(nf), np.zeros(nf, np.int64)
+    orientable = np.ones(nf, bool)                               # read at the roots
+    if orient:
+        parent, par = list(range(nf)), [0] * nf
+
+        def find(x):
+            path = []
+            while parent[x] != x:
+                path.append(x)
+                x = parent[x]
+            p = 0
+            for y in reversed(path):
+                p ^= par[y]
+                parent[y], par[y] = x, p
+            return x, p
+
+        clash = []
+        for x, y, r in zip((c0 // 3).tolist(), (c1 // 3).tolist(), rel.tolist()):
+            (rx, px), (ry, py) = find(x), find(y)
+            if rx == ry:
+                if px ^ py != r:
+                    clash.append(x)
+            else:
+                hi, lo = max(rx, ry), min(rx, ry)
+                parent[hi], par[hi] = lo, px ^ py ^ r
+        found = [find(x) for x in range(nf)]
+        root, parity = np.array([r for r, _ in found], np.int64), np.array([p for _, p in found], np.int64)
+        orientable[root[np.array(clash, np.int64)]] = False
+    n1 = np.bincount(root, weights=parity, minlength=nf).astype(np.int64)
+    K = (n1 > np.bincount(root, minlength=nf) - n1).astype(np.int64)
+    # -- fill: a union-find of vertices over the boundary pairs
+    bc = np.nonzero(boundary)[0]
+    filled_pair = np.zeros(3 * nf, bool)
+    ids = np.zeros(0, np.int64)
+    loops = 0
+    centres = np.zeros((0, 3), np.float32)
+    if fill and bc.size:
+        vparent = list(range(nv))
+
+        def vroot(x):
+            while vparent[x] != x:
+                vparent[x] = vparent[vparent[x]]
+                x = vparent[x]
+            return x
+
+        for x, y in zip(a[bc].tolist(), b[bc].tolist()):
+            rx, ry = vroot(x), vroot(y)
+            if rx != ry:
+                vparent[max(rx, ry)] = min(rx, ry)
+        loop = np.array([vroot(x) for x in a[bc].tolist()], np.int64)
+        L = np.bincount(loop, minlength=nv)
+        loops = int((L > 0).sum())
+        ids = np.nonzero((L > 0) & (L <= cap))[0]                # the filled loops, ascending
+        filled_pair[bc] = L[loop] <= cap
+        S = np.zeros((nv, 3), np.int64)
+        np.add.at(S, loop, np.rint(p64[a[bc]] * np.ldexp(1.0, 40 - E)).astype(np.int64))
+        centres = (S[ids].astype(np.float64) / L[ids].astype(np.float64)[:, None]
+                   * np.ldexp(1.0, E - 40)).astype(np.float32)
+    fc = np.nonzero(filled_pair)[0]                              # the pairs that get a face, ascending
+    rank = np.zeros(nv, np.int64)
+    rank[ids] = np.arange(ids.size)
+    centre_of = nv + rank[np.array([vroot(x) for x in a[fc].tolist()], np.int64)] if fc.size else fc
+    verts_out = np.concatenate([v32, centres])
+    caps = np.stack([centre_of, b[fc], a[fc]], axis=1)
+    # -- outward
+    if outward:
+        still_open = np.zeros(nf, bool)
+        still_open[root[bc[~filled_pair[bc]] // 3]] = True
+        scale = np.ldexp(1.0, 30 - 3 * E)
+        tq = np.rint(_check_volume_terms(p64[f]) * scale).astype(np.int64)
+        tq_caps = np.rint(_check_volume_terms(verts_out.astype(np.float64)[caps]) * scale).astype(np.int64)
+        V = np.zeros(nf, np.int64)
+        np.add.at(V, root, np.where(parity == K[root], tq, -tq))
+        np.add.at(V, root[fc // 3], np.where(parity[fc // 3] == K[root[fc // 3]], tq_caps, -tq_caps))
+        K = np.where(orientable & ~still_open & (V < 0), 1 - K, K)
+    flip = orientable[root] & (parity != K[root]) if orient else np.zeros(nf, bool)
+    faces_out = f.copy()
+    faces_out[flip] = faces_out[flip][:, (0, 2, 1)]
+    caps[flip[fc // 3]] = caps[flip[fc // 3]][:, (0, 2, 1)]
+    is_root = root == np.arange(nf)
+    report = {"status": 0, "nv": nv, "nf": nf, "nv_out": nv + int(ids.size), "nf_out": nf + int(fc.size),
+              "components": int(is_root.sum()) if orient else 0,
+              "unorientable_components": int((is_root & ~orientable).sum()) if orient else 0,
+              "flipped_faces": int(flip.sum()), "loops": loops, "filled_loops": int(ids.size),
+              "fill_faces": int(fc.size)}
+    return (verts_out, np.concatenate([faces_out, caps]).astype(np.int32),
+            np.r_[np.arange(nv), ids].astype(np.int32), np.r_[np.arange(nf), fc // 3].astype(np.int32), report)
 
 
 # ---- vertex colours from the input views: the rule (DESIGN 4zb; the device restates it, mesh_colour.hip) ----------
@@ -1500,6 +1705,80 @@ def repair_arrays_device(verts, faces, weld: bool = True, stitch: bool = True, s
     integers and the position bits of ``repair_arrays``, and its report; the ValueErrors of ``repair_meshes_device``"""
     repaired, reports = _one_mesh(repair_meshes_device, [(verts, faces)], weld=weld, stitch=stitch, strict=strict)
     return repaired[0] + (reports[0],)
+
+
+# ---- mesh closing on the device (mesh_close.hip) ------------------------------------------------------------------
+def close_report(counts, nv: int, nf: int) -> dict:
+    """one mesh's DISN_CLOSE_FIELDS counts and its input sizes -> the report of ``close_arrays``"""
+    out = {"status": int(counts[CLOSE_FIELDS.index("status")]), "nv": int(nv), "nf": int(nf)}
+    out.update((k, int(c)) for k, c in zip(CLOSE_FIELDS, counts) if k != "status")
+    return out
+
+
+def close_meshes_device(meshes, orient: bool = True, fill: bool = True, outward: bool = False, max_hole=None,
+                        strict: bool = True):
+    """``close_arrays`` for a group of meshes that lie on the device.  ``meshes``: B x (verts [nv,3] float32, faces
+    [nf,3] int32[, further per-vertex arrays]) device tensors (the views the earlier stages return are used in place).
+    ONE count call, ONE read-back of the [B,9] sizes, ONE emit call.
+    -> (closed, reports): B x (verts', faces'[, arrays'], vmap int32 [nv'], kept int32 [nf']) views of the outputs --
+    the integers and the position bits of ``close_arrays``; a further array takes, for every output vertex, the row of
+    ``vmap``: its own for an input vertex, that of its loop's smallest vertex for a centre -- and B reports, the dicts
+    of ``close_arrays``.  An empty mesh stays empty.  A mesh with status 2 (a face index out of range), 4 (a coordinate
+    that is not finite) or 16 (not manifold: ``repair_meshes_device`` comes first) raises ValueError naming the mesh --
+    with ``strict=False`` it comes back unchanged and its report carries the status."""
+    import torch
+
+    from . import ops
+    from ._lib import check
+    flags, cap = close_flags(orient, fill, outward, max_hole)
+    meshes = [tuple(m) for m in meshes]
+    if not meshes:
+        return [], []
+    B, h = len(meshes), lib()
+    v, v_off, f, f_off, ws = _pack_meshes(meshes, lambda nv, nf: h.disn_mesh_close_workspace_bytes(B, nv, nf))
+    dev, K = v.device, len(CLOSE_FIELDS)
+    with torch.cuda.device(dev):
+        counts = torch.zeros((B, K), dtype=torch.int64, device=dev)
+        st = ops._stream()
+        check("disn_mesh_close_count_batch", h.disn_mesh_close_count_batch(
+            v.data_ptr(), f.data_ptr(), v_off.ctypes.data, f_off.ctypes.data, B, flags, cap, counts.data_ptr(),
+            ws.data_ptr(), ws.numel(), st))
+        sizes = np.ascontiguousarray(counts.cpu().numpy())      # the one host sync of the group
+        status = sizes[:, CLOSE_FIELDS.index("status")]
+        for b in np.nonzero(status)[0]:
+            if strict or status[b] not in (STATUS_INDEX, STATUS_FINITE, STATUS_NOT_MANIFOLD):
+                _raise_status(b, status[b], v_off, "disn_mesh_close_count_batch")
+                if status[b] == STATUS_NOT_MANIFOLD:
+                    raise ValueError("mesh %d: not manifold (a repeated index, an edge of three faces or a vertex on "
+                                     "more than two boundary edges): repair it first" % b)
+                raise RuntimeError("mesh %d: disn_mesh_close_count_batch gave status %d" % (b, status[b]))
+        nvo, nfo = int(sizes[:, 0].sum()), int(sizes[:, 1].sum())
+        out_v = torch.empty((nvo, 3), dtype=torch.float32, device=dev)
+        out_f = torch.empty((nfo, 3), dtype=torch.int32, device=dev)
+        vmap = torch.empty(nvo, dtype=torch.int32, device=dev)
+        kept = torch.empty(nfo, dtype=torch.int32, device=dev)
+        if nvo or nfo:
+            check("disn_mesh_close_emit_batch", h.disn_mesh_close_emit_batch(
+                v.data_ptr(), f.data_ptr(), v_off.ctypes.data, f_off.ctypes.data, B, flags, cap, sizes.ctypes.data,
+                out_v.data_ptr(), out_f.data_ptr(), vmap.data_ptr(), kept.data_ptr(), ws.data_ptr(), ws.numel(), st))
+    closed, reports, v0, f0 = [], [], 0, 0
+    for b, m in enumerate(meshes):
+        nvb, nfb = int(sizes[b, 0]), int(sizes[b, 1])
+        vm = vmap[v0:v0 + nvb]
+        rest = tuple(x.index_select(0, vm.long()) for x in m[2:])
+        closed.append((out_v[v0:v0 + nvb], out_f[f0:f0 + nfb]) + rest + (vm, kept[f0:f0 + nfb]))
+        reports.append(close_report(sizes[b], v_off[b + 1] - v_off[b], f_off[b + 1] - f_off[b]))
+        v0, f0 = v0 + nvb, f0 + nfb
+    return closed, reports
+
+
+def close_arrays_device(verts, faces, orient: bool = True, fill: bool = True, outward: bool = False, max_hole=None,
+                        strict: bool = True):
+    """``close_arrays`` for one mesh on the device -> (verts', faces', vmap, kept, report): device tensors with the
+    integers and the position bits of ``close_arrays``, and its report; the ValueErrors of ``close_meshes_device``"""
+    closed, reports = _one_mesh(close_meshes_device, [(verts, faces)], orient=orient, fill=fill, outward=outward,
+                                max_hole=max_hole, strict=strict)
+    return closed[0] + (reports[0],)
 
 
 def _colour_inputs(meshes, trans_mats, views_per_mesh: int, S: int):

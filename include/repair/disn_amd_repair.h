@@ -52,7 +52,8 @@
  * The result is manifold: every face has at most one partner per edge, so the corners of a vertex form paths and cycles
  * and a class touches a cut edge with at most its two path ends; the second pass only refines the classes, so distinct
  * pairs of an unpinched stitched edge keep distinct signatures.  Every output edge has at most two faces, every output
- * vertex one fan.  Not in scope: orientation repair, hole filling, self-intersections, the other pairing at a pinched edge.
+ * vertex one fan.  Not in scope: self-intersections, the other pairing at a pinched edge; orientation and the holes a cut
+ * edge opens are disn_mesh_close_*'s (include/close/disn_amd_close.h).
  *
  *   disn_mesh_repair_count_batch  counts [B][DISN_REPAIR_FIELDS] int64: device.  Leaves in ws what the emit reads.
  *   disn_mesh_repair_emit_batch   the same inputs and ws, untouched in between; counts_host: the counts read back.
